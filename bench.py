@@ -22,7 +22,16 @@ Timing: W warm-up steps, then R windows of EXACTLY K steps each, every window br
 + torch.cuda.synchronize() on both sides, MAX over ranks.  `value` / `ms_per_step` are the FIRST
 window (iterations W+1 … W+K, the contract); `value_median/min/max` summarise all R windows.
 
-Prints ONE JSON line on rank 0 (contract + `roofline` + `cpu_baseline`).
+A plain run does only what the headline needs: one window (R = 1, so exactly K timed steps), no CPU
+baseline, no stand-alone stream-mix run.  `--full` adds them: R = 5 windows by default, `cpu_baseline`
+(the oracle on the same workload, one thread and all cores) and, where the placement search did not
+time the solver's own buffers, `roofline.measured_mix_ceiling_gbps` from a run of its own.
+
+`--dump-outputs DIR` (one GPU): after the timed steps, what a caller of minimizeobjective would receive
+at the last one (minimizer, gradient, objective, trace) as float64 .npy files under DIR; vectors longer
+than DUMP_SAMPLE entries at a fixed, seeded set of positions (DIR/sample_index.npy).
+
+Prints ONE JSON line on rank 0 (contract + `roofline`, + `cpu_baseline` with --full).
 """
 import argparse
 import json
@@ -204,6 +213,24 @@ WORKLOADS = {  # workload → (default n, default β, description)
 }
 
 
+DUMP_SAMPLE = 1 << 21   # entries per long vector that --dump-outputs writes: 2 vectors × 16 MB in float64, within 64 MB
+
+
+def dump_outputs(out_dir: str, r, sample: int = DUMP_SAMPLE, seed: int = 24) -> None:
+    """Results `r` (with vectors) as float64 .npy files under out_dir.  The positions of a vector longer than `sample` are
+    drawn once from a fixed seed (sorted, duplicates dropped), so two builds run with the same arguments write the same ones."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = r.minimizer.size
+    idx = np.arange(n) if n <= sample else np.unique(np.random.default_rng(seed).integers(0, n, sample))
+    arrays = {"minimizer": r.minimizer[idx], "gradient": r.gradient[idx], "sample_index": idx,
+              "objective": [r.objective], "iters_ran": [r.iters_ran],
+              "trace_objective": r.trace.objective, "trace_grad_norm": r.trace.grad_norm,
+              "trace_step_size": r.trace.step_size, "trace_objective_evals": r.trace.objective_evals}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def git_head() -> str:
     try:
         return subprocess.run(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], capture_output=True, text=True, timeout=5).stdout.strip()
@@ -239,7 +266,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=5, help="R: timed windows of --steps steps each (value = the first)")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="R: timed windows of --steps steps each (value = the first); default 1, or 5 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: 5 windows by default, the CPU baselines, the stand-alone "
+                         "stream-mix ceiling")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the solver's results at the last one to DIR/<name>.npy (one GPU only)")
     ap.add_argument("--size", dest="n", type=float, default=None, help="global problem size (default: the workload's)")
     ap.add_argument("--workload", default="c5", choices=sorted(WORKLOADS),
                     help="BASELINE.json config: c5 (default, headline) quadratic n=1e8 PR-CG; c1 / c1c Rosenbrock n=1000 PR-CG (paired / "
@@ -258,6 +291,8 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for rendezvous/barriers (gloo: rehearsal with several ranks on one GPU)")
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs: single-GPU runs only")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args))   # nothing has touched the GPU yet: torch is imported below
@@ -305,7 +340,7 @@ def main():
     n = int(args.n if args.n else W[0])
     bname = args.beta or W[1]
     c1, c2 = 1e-5, 0.1
-    R = max(1, args.windows)
+    R = max(1, args.windows if args.windows is not None else (5 if args.full else 1))
     beta = {"PolakRibiere": cgo.PolakRibiere(), "HagerZhang": cgo.HagerZhang(), "DaiYuan": cgo.DaiYuan(),
             "LBFGS": cgo.LBFGS(10)}[bname]
     cfg = cgo.setupCGConfig(1e-200, beta, cgo.EnableTrace(), max_iters=args.warmup + R * args.steps + 8)
@@ -477,6 +512,8 @@ def main():
                        profile="off" if no_prof else "on", dominant=dom, device_mailboxes=devmail.get(label),
                        dominant_symbol=s.kernel_symbol(dom) if dom else "")
             xw = [xpw / max(xn, 1), xdev]
+            if args.dump_outputs:    # after profile_get: fetching the gradient must not enter the kernel table
+                dump_outputs(args.dump_outputs, s.results(vectors=True))
             pf, pb, pc = s.placement_info()
             if pc:      # the placement search of DESIGN.md §2.5 ran: what it found, and at which of the measured LEVELS the launch now runs
                 tb = 40.0 * obj.n_local / pb / 1e6 if pb > 0 else 0.0   # TB/s of the bare 5-stream mix on the buffers in use
@@ -489,7 +526,7 @@ def main():
             if rank == 0 and world == 1 and dom == "accept_dir_trial" and args.workload in ("c5", "c2") and obj.n_local >= 3 * 10**7:
                 if pc:     # the bare mix on the very buffers the solver runs on (timed during its placement search)
                     res["mix_ceiling_us"] = pb
-                else:
+                elif args.full:
                     s.close(); obj.close(); s = None      # free the solver's vectors first: the harness allocates three of its own
                     res["mix_ceiling_us"] = cgo.bench_stream_mix(res["n_per_gpu"], 9, ctx)[0]
         except Exception as e:
@@ -597,7 +634,7 @@ def main():
                     # the curve per transport at a glance (north_star names RCCL; `value` is the faster of the two)
                     out["value_rccl"] = good["rccl"]["value"] if "rccl" in good else None
                     out["value_shm"] = good["shm"]["value"] if "shm" in good else None
-                if world == 1 and not args.no_cpu_baseline:      # the oracle on the SAME workload, beside every line (≈ 5–30 s of CPU work per leg)
+                if world == 1 and args.full and not args.no_cpu_baseline:   # the oracle on the SAME workload (≈ 5–30 s of CPU work per leg)
                     for key, allc in (("cpu_baseline", False), ("cpu_baseline_all_cores", True)):
                         try:
                             out[key] = cpu_baseline_child(args.workload, n, allc)

@@ -31,24 +31,24 @@ done
 fi
 if [[ " $STAGES " == *" 2 "* ]]; then
 cd $R
-python3 bench.py > $OUT/bench_c5.json 2> $OUT/bench_c5.err; echo "bench c5 rc=$?"; tail -c 400 $OUT/bench_c5.json
-python3 bench.py --no-placement-search --no-cpu-baseline > $OUT/bench_c5_nosearch.json 2> $OUT/bench_c5_nosearch.err; echo "bench c5 (no placement search) rc=$?"
-python3 bench.py --workload c1 --steps 15 --warmup 3 --windows 1 > $OUT/bench_c1.json 2> $OUT/bench_c1.err; echo "bench c1 rc=$?"
-python3 bench.py --workload c1c --steps 15 --warmup 3 --windows 1 > $OUT/bench_c1c.json 2> $OUT/bench_c1c.err; echo "bench c1c rc=$?"
-python3 bench.py --workload c2 --steps 200 --warmup 10 > $OUT/bench_c2.json 2> $OUT/bench_c2.err; echo "bench c2 rc=$?"
-CGO_RESIDENT=0 python3 bench.py --workload c2 --steps 200 --warmup 10 --no-cpu-baseline > $OUT/bench_c2_hostdriven.json 2> $OUT/bench_c2_hostdriven.err; echo "bench c2 host-driven rc=$?"
-CGO_RESIDENT=0 python3 bench.py --workload c1 --steps 15 --warmup 3 --windows 1 --no-cpu-baseline > $OUT/bench_c1_hostdriven.json 2> $OUT/bench_c1_hostdriven.err; echo "bench c1 host-driven rc=$?"
-python3 bench.py --workload c3 --steps 200 --warmup 10 --windows 2 > $OUT/bench_c3.json 2> $OUT/bench_c3.err; echo "bench c3 rc=$?"
-python3 bench.py --workload c3 --size 4e7 --steps 100 --warmup 10 --windows 2 --no-cpu-baseline > $OUT/bench_c3big.json 2> $OUT/bench_c3big.err; echo "bench c3 n=4e7 rc=$?"
-python3 bench.py --workload c4 --steps 45 --warmup 10 --windows 2 > $OUT/bench_c4.json 2> $OUT/bench_c4.err; echo "bench c4 rc=$?"
-CGO_LBFGS_SPEC=0 python3 bench.py --workload c4 --steps 45 --warmup 10 --windows 2 --no-cpu-baseline > $OUT/bench_c4_twopass.json 2> $OUT/bench_c4_twopass.err; echo "bench c4 two-pass rc=$?"
-python3 bench.py --size 1.25e7 --steps 100 --warmup 10 --windows 5 --no-cpu-baseline > $OUT/bench_shard.json 2> $OUT/bench_shard.err; echo "bench shard rc=$?"
-python3 bench.py --gpus 2 --backend gloo --size 4e7 --steps 30 --warmup 5 --windows 3 > $OUT/bench_rehearsal_2ranks.json 2> $OUT/bench_rehearsal_2ranks.err; echo "rehearsal 2 ranks rc=$?"
-python3 bench.py --gpus 4 --backend gloo --size 4e7 --steps 30 --warmup 5 --windows 3 > $OUT/bench_rehearsal_4ranks.json 2> $OUT/bench_rehearsal_4ranks.err; echo "rehearsal 4 ranks rc=$?"
+python3 bench.py --full > $OUT/bench_c5.json 2> $OUT/bench_c5.err; echo "bench c5 rc=$?"; tail -c 400 $OUT/bench_c5.json
+python3 bench.py --full --no-placement-search --no-cpu-baseline > $OUT/bench_c5_nosearch.json 2> $OUT/bench_c5_nosearch.err; echo "bench c5 (no placement search) rc=$?"
+python3 bench.py --full --workload c1 --steps 15 --warmup 3 --windows 1 > $OUT/bench_c1.json 2> $OUT/bench_c1.err; echo "bench c1 rc=$?"
+python3 bench.py --full --workload c1c --steps 15 --warmup 3 --windows 1 > $OUT/bench_c1c.json 2> $OUT/bench_c1c.err; echo "bench c1c rc=$?"
+python3 bench.py --full --workload c2 --steps 200 --warmup 10 > $OUT/bench_c2.json 2> $OUT/bench_c2.err; echo "bench c2 rc=$?"
+CGO_RESIDENT=0 python3 bench.py --full --workload c2 --steps 200 --warmup 10 --no-cpu-baseline > $OUT/bench_c2_hostdriven.json 2> $OUT/bench_c2_hostdriven.err; echo "bench c2 host-driven rc=$?"
+CGO_RESIDENT=0 python3 bench.py --full --workload c1 --steps 15 --warmup 3 --windows 1 --no-cpu-baseline > $OUT/bench_c1_hostdriven.json 2> $OUT/bench_c1_hostdriven.err; echo "bench c1 host-driven rc=$?"
+python3 bench.py --full --workload c3 --steps 200 --warmup 10 --windows 2 > $OUT/bench_c3.json 2> $OUT/bench_c3.err; echo "bench c3 rc=$?"
+python3 bench.py --full --workload c3 --size 4e7 --steps 100 --warmup 10 --windows 2 --no-cpu-baseline > $OUT/bench_c3big.json 2> $OUT/bench_c3big.err; echo "bench c3 n=4e7 rc=$?"
+python3 bench.py --full --workload c4 --steps 45 --warmup 10 --windows 2 > $OUT/bench_c4.json 2> $OUT/bench_c4.err; echo "bench c4 rc=$?"
+CGO_LBFGS_SPEC=0 python3 bench.py --full --workload c4 --steps 45 --warmup 10 --windows 2 --no-cpu-baseline > $OUT/bench_c4_twopass.json 2> $OUT/bench_c4_twopass.err; echo "bench c4 two-pass rc=$?"
+python3 bench.py --full --size 1.25e7 --steps 100 --warmup 10 --windows 5 --no-cpu-baseline > $OUT/bench_shard.json 2> $OUT/bench_shard.err; echo "bench shard rc=$?"
+python3 bench.py --full --gpus 2 --backend gloo --size 4e7 --steps 30 --warmup 5 --windows 3 > $OUT/bench_rehearsal_2ranks.json 2> $OUT/bench_rehearsal_2ranks.err; echo "rehearsal 2 ranks rc=$?"
+python3 bench.py --full --gpus 4 --backend gloo --size 4e7 --steps 30 --warmup 5 --windows 3 > $OUT/bench_rehearsal_4ranks.json 2> $OUT/bench_rehearsal_4ranks.err; echo "rehearsal 4 ranks rc=$?"
 fi
 if [[ " $STAGES " == *" 3 "* ]]; then
 cd /tmp
-st() { tag=$1; shift; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats_$tag -- python3 $R/bench.py "$@" --no-cpu-baseline > $OUT/prof_stats_$tag.log 2>&1; echo "stats $tag rc=$?"; }
+st() { tag=$1; shift; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats_$tag -- python3 $R/bench.py --full "$@" --no-cpu-baseline > $OUT/prof_stats_$tag.log 2>&1; echo "stats $tag rc=$?"; }
 # the headline with the search: from a process that holds a fast triple (5 of 8 do); one that holds none is kept as c5_searchmiss
 for attempt in 1 2 3 4; do
   st c5 --steps 20 --warmup 5

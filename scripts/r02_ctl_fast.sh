@@ -8,7 +8,7 @@ timeout -k 10 600 python3 -m pytest tests -x -q -m gpu -k "controller or fused" 
 [ $rc -ne 0 ] && exit 1
 one() {  # tag depth args...
     local tag=$1 d=$2; shift 2
-    CGO_CTL_DEPTH=$d timeout -k 10 300 python3 bench.py "$@" --no-cpu-baseline > $OUT/$tag.json 2> $OUT/$tag.err || { echo "$tag failed"; tail -3 $OUT/$tag.err; return 1; }
+    CGO_CTL_DEPTH=$d timeout -k 10 300 python3 bench.py --full "$@" --no-cpu-baseline > $OUT/$tag.json 2> $OUT/$tag.err || { echo "$tag failed"; tail -3 $OUT/$tag.err; return 1; }
     python3 -c "
 import json; d=json.loads(open('$OUT/$tag.json').read().strip().splitlines()[-1]); k={n:(v['launches'], round(v['avg_us'],1)) for n,v in d.get('kernels',{}).items()}; print('$tag depth=$d value %.0f med %.0f it/s' % (d['value'], d['value_median']), k)"
 }

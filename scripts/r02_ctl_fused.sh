@@ -11,7 +11,7 @@ run() {  # tag, env assignments..., -- args
     local tag=$1; shift
     local envs=()
     while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-    env "${envs[@]}" timeout -k 10 300 python3 bench.py "$@" --no-cpu-baseline > $OUT/$tag.json 2> $OUT/$tag.err || { echo "$tag failed"; tail -3 $OUT/$tag.err; return 1; }
+    env "${envs[@]}" timeout -k 10 300 python3 bench.py --full "$@" --no-cpu-baseline > $OUT/$tag.json 2> $OUT/$tag.err || { echo "$tag failed"; tail -3 $OUT/$tag.err; return 1; }
     python3 - "$OUT/$tag.json" "$tag" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -14,7 +14,7 @@ CGO_FUSED_TAIL=0 timeout -k 10 600 python3 -m pytest tests -x -q -m gpu -k "ctl 
 [ $rc -ne 0 ] && exit 1
 run() {  # tag, env, args
     local tag=$1 ft=$2; shift 2
-    CGO_FUSED_TAIL=$ft timeout -k 10 300 python3 bench.py "$@" --no-cpu-baseline > $OUT/$tag.json 2> $OUT/$tag.err || { echo "$tag failed"; tail -3 $OUT/$tag.err; return 1; }
+    CGO_FUSED_TAIL=$ft timeout -k 10 300 python3 bench.py --full "$@" --no-cpu-baseline > $OUT/$tag.json 2> $OUT/$tag.err || { echo "$tag failed"; tail -3 $OUT/$tag.err; return 1; }
     python3 - "$OUT/$tag.json" "$tag" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -33,7 +33,7 @@ for ft in 0 1; do
 done
 export CGO_BENCH_NO_PROFILE=1
 cd /tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT/trace_c2 -- python3 $R/bench.py --workload c2 --steps 300 --warmup 10 --windows 1 --no-cpu-baseline > $OUT/trace_c2.log 2>&1; echo "trace c2 rc=$?"
+rocprofv3 --kernel-trace --output-format csv -d $OUT/trace_c2 -- python3 $R/bench.py --full --workload c2 --steps 300 --warmup 10 --windows 1 --no-cpu-baseline > $OUT/trace_c2.log 2>&1; echo "trace c2 rc=$?"
 cd $R
 python3 scripts/gap_table.py $OUT/trace_c2 --skip 60 --out $OUT/gaps_c2.json > $OUT/gaps_c2.txt 2>&1; tail -12 $OUT/gaps_c2.txt
 find $OUT -name '*kernel_trace.csv' -size +20M -delete

@@ -8,7 +8,7 @@ cd $R
 timeout -k 10 900 python3 -m pytest tests -x -q -m gpu > $OUT/pytest_gpu.log 2>&1; rc=$?; echo "pytest rc=$rc"; tail -4 $OUT/pytest_gpu.log
 [ $rc -ne 0 ] && exit 1
 one() { local tag=$1; shift
-    timeout -k 10 300 python3 bench.py "$@" --no-cpu-baseline > $OUT/o.json 2> $OUT/o.err || { echo "$tag failed"; tail -2 $OUT/o.err; return; }
+    timeout -k 10 300 python3 bench.py --full "$@" --no-cpu-baseline > $OUT/o.json 2> $OUT/o.err || { echo "$tag failed"; tail -2 $OUT/o.err; return; }
     python3 -c "
 import json; d=json.loads(open('$OUT/o.json').read().strip().splitlines()[-1]); print('$tag value %.0f med %.0f it/s trials/iter %.2f launches/iter %.2f' % (d['value'], d['value_median'], d['config']['trials_per_iteration'], d['config']['launches_per_iteration']), {k:(v['launches'], round(v['avg_us'],1)) for k,v in d['kernels'].items()})"
 }

@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd $R
 one() { # tag args…
   tag=$1; shift
-  timeout -k 10 200 python3 bench.py "$@" --no-cpu-baseline > $OUT/$tag.json 2> $OUT/$tag.err
+  timeout -k 10 200 python3 bench.py --full "$@" --no-cpu-baseline > $OUT/$tag.json 2> $OUT/$tag.err
   python3 - <<PY
 import json
 d=json.loads(open("$OUT/$tag.json").read().strip().splitlines()[-1]); p=d.get("placement") or {}

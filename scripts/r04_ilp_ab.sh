@@ -6,7 +6,7 @@ mkdir -p $OUT
 cd $R
 ILP=$R/conjugategradientoptim.jl_amd/lib/libcgo_hip_ilp.so
 be() { tag=$1; lib=$2; shift 2; if [ "$lib" = ilp ]; then export CGO_LIB_PATH=$ILP; else unset CGO_LIB_PATH; fi
-  python3 bench.py "$@" --no-cpu-baseline > $OUT/$tag.json 2> $OUT/$tag.err
+  python3 bench.py --full "$@" --no-cpu-baseline > $OUT/$tag.json 2> $OUT/$tag.err
   echo "== $tag: $(python3 -c "import json; d=json.load(open('$OUT/$tag.json')); k=d['kernels']; print(round(d['value']), round(d['value_median']), 'it/s;', {n: (v['launches'], round(v['avg_us'],1)) for n,v in k.items()}, d.get('placement'))")"; }
 for rep in 1 2; do
   for lib in def ilp; do

@@ -115,3 +115,61 @@ def test_a_hung_transport_is_reported_and_the_run_fails():
     body = src[src.index("def give_up(kind):"):src.index("for kind in order:")]
     assert "results[kind] = None" in body and "os._exit(5)" in body and "os._exit(0)" not in body
     assert '"value_rccl"' in src and '"value_shm"' in src and "rccl_failed" in src
+
+
+def test_dump_outputs_writes_float64_at_fixed_positions(tmp_path):
+    """--dump-outputs: every array a caller of minimizeobjective receives, as float64; a vector longer than the sample is
+    written at positions drawn from a fixed seed (the same in every run), and the default sample of n = 1e8 stays within
+    64 MB in all."""
+    import numpy as np
+    from types import SimpleNamespace
+    n, k = 5000, 4
+    trace = SimpleNamespace(objective=np.linspace(3.0, 1.0, k), grad_norm=np.linspace(2.0, 0.5, k),
+                            step_size=np.full(k, 0.25), objective_evals=np.arange(1, k + 1, dtype=np.int64))
+    r = SimpleNamespace(minimizer=np.arange(n) * 0.5, gradient=np.arange(n) * -1.0, objective=1.0, iters_ran=k, trace=trace)
+    bench.dump_outputs(str(tmp_path / "a"), r, sample=100)
+    bench.dump_outputs(str(tmp_path / "b"), r, sample=100)
+    names = {"minimizer", "gradient", "sample_index", "objective", "iters_ran", "trace_objective", "trace_grad_norm",
+             "trace_step_size", "trace_objective_evals"}
+    assert {p.stem for p in (tmp_path / "a").iterdir()} == names
+    for name in names:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, b), name
+    idx = np.load(tmp_path / "a" / "sample_index.npy")
+    assert 90 <= idx.size <= 100 and np.all(np.diff(idx) > 0) and idx[-1] < n
+    assert np.array_equal(np.load(tmp_path / "a" / "minimizer.npy"), 0.5 * idx)
+    assert np.array_equal(np.load(tmp_path / "a" / "trace_objective_evals.npy"), [1.0, 2.0, 3.0, 4.0])
+    bench.dump_outputs(str(tmp_path / "all"), r, sample=n)       # short vectors: every entry
+    assert np.array_equal(np.load(tmp_path / "all" / "gradient.npy"), r.gradient)
+    assert 3 * bench.DUMP_SAMPLE * 8 + 4 * 8 * 300 <= 64e6       # three sampled vectors + four traces of up to 300 iterations
+
+
+def test_dump_outputs_is_refused_for_several_gpus():
+    """Checked before anything starts ranks or touches a GPU."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-outputs", "x"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "single-GPU" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_times_exactly_the_steps_asked_for_and_dumps_its_outputs(tmp_path):
+    """A plain run: one window of --steps steps, no CPU baseline; --dump-outputs writes the results of the last timed step
+    (iteration warmup + steps), and --full keeps the extra windows and the CPU baselines."""
+    import subprocess
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--size", "2e5", "--steps", "7", "--warmup", "2"]
+    r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["windows"] == 1
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 1e3 / d["ms_per_step"]) <= 1e-9 * d["value"]
+    assert "cpu_baseline" not in d and d["unit"] == "iterations/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    out = tmp_path / "out"
+    assert np.load(out / "iters_ran.npy")[0] == 9 and np.load(out / "trace_step_size.npy").size == 9
+    x, idx = np.load(out / "minimizer.npy"), np.load(out / "sample_index.npy")
+    assert x.dtype == np.float64 and x.size == idx.size == 200000 and np.all(np.isfinite(x))
+    assert np.isclose(np.load(out / "objective.npy")[0], np.load(out / "trace_objective.npy")[-1], rtol=1e-12, atol=0)
+    r = subprocess.run(cmd + ["--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.strip().splitlines()[-1])["windows"] == 5

@@ -223,7 +223,7 @@ def run_gpu_traj(cgo, c, ctx, ckpts):
 def test_long_horizon_at_baseline_size_vs_arbiter(cgo, gpu_ctx, tmp_path, config):
     n, iters = GPU_CASES[config]
     if os.environ.get("CGO_TEST_LONG") == "1" and config == "c5":
-        iters = 255                                  # bench.py's default run: 5 warm-up + 5 windows of 50
+        iters = 255                                  # bench.py --full default run: 5 warm-up + 5 windows of 50
     ck = [k for k in (10, 25, 50, 100, 150, 200, 250) if k <= iters]
     threads = _cores()
     arb = oracle_child(config, n, iters, "exact", ck, tmp_path, threads)
