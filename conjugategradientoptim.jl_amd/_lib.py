@@ -135,6 +135,8 @@ SIGNATURES = {
     "cgo_bench_kernel": (C.c_int, [_vp, _vp, C.c_int32, C.c_int64, C.c_int32, dp, dp]),
     "cgo_bench_stream_mix": (C.c_int, [_vp, C.c_int64, C.c_int32, dp, dp]),
     "cgo_solver_placement_info": (C.c_int, [_vp, dp, dp, C.POINTER(C.c_int32)]),
+    "cgo_solver_probe_launch": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_double, C.c_double, dp, C.c_int32, dp, dp, dp,
+                                          dp, C.c_int32, C.POINTER(C.c_int32), dp, dp, dp, C.c_char_p, C.c_int32]),
 }
 
 

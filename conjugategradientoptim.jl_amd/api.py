@@ -733,6 +733,27 @@ class Solver:
                 return buf.value.decode()
         return ""
 
+    def probe_launch(self, kind_name: str, variant: int, a_acc: float, beta: float, a: Sequence[float], x, u=None, aux=None):
+        """ONE launch of kind `kind_name` with mode bits `variant` on this rank's host vectors (cgo_solver_probe_launch): returns
+        dict(sums=the whole reduced row, x=, u=, g= the vectors after the launch, symbol=the instantiation).  A test entry point:
+        the solver is for probing only from the first call on."""
+        L = _lib.lib()
+        kk = [L.cgo_kernel_kind_name(k).decode() for k in range(L.cgo_num_kernel_kinds())].index(kind_name)
+        n = self.obj.n_local
+        vec = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float64)
+        x, u, aux = vec(x), vec(u), vec(aux)
+        for v in (x, u, aux):
+            if v is not None and v.size != n:
+                raise ValueError(f"probe vectors hold n_local = {n} elements")
+        av = np.ascontiguousarray(a, dtype=np.float64) if len(a) else np.zeros(1)
+        sums, ln = np.full(64, np.nan), C.c_int32(0)
+        xo, uo, go = np.empty(n), np.empty(n), np.empty(n)
+        sym = C.create_string_buffer(200)
+        ptr = lambda v: None if v is None else v.ctypes.data_as(dp)
+        check(L.cgo_solver_probe_launch(self._h, kk, int(variant), float(a_acc), float(beta), ptr(av), len(a), ptr(x), ptr(u),
+                                        ptr(aux), ptr(sums), 64, C.byref(ln), ptr(xo), ptr(uo), ptr(go), sym, 200))
+        return dict(sums=sums[:ln.value].copy(), x=xo, u=uo, g=go, symbol=sym.value.decode())
+
     def placement_info(self):
         """(as_allocated_us, chosen_us, candidates) of the solver's placement search (cgo_solver_placement_info);
         candidates == 0: no search was made."""

@@ -5,6 +5,7 @@
 #include "cgo_kernels.hip.hpp"
 #include "cgo_kernels_cg.hip.hpp"
 #include "cgo_kernels_chain.hip.hpp"
+#include "cgo_kernels_lse.hip.hpp"
 #include "cgo_kernels_resident.hip.hpp"
 
 namespace cgo {
@@ -106,11 +107,13 @@ int HipBackend::launch_r(int kk, int mode, double a_acc, double beta, const doub
             const double *e = raw.data() + (size_t)(me + 1) * W + edge;
             halo_xr_[0] = e[0]; halo_xr_[1] = e[1]; halo_ur_[0] = e[2]; halo_ur_[1] = e[3];
         }
+        if (probe_) { std::memcpy(probe_row_, all, sizeof(double) * W); probe_len_ = W; }
     } else if (has_sums) {
         if (!fused) { if (int rc = finalize_rows(ctx_, grid, rows_for(npts), true)) return rc; }
         if (fetch) {
             if (int rc = fetch_sums(ctx_, sums, MERGE_SUM, rows_for(npts))) return rc;
         }
+        if (probe_ && fetch) { std::memcpy(probe_row_, sums, sizeof(double) * rows_for(npts)); probe_len_ = rows_for(npts); }
     }
     if (prof_on_) prof_commit(kk, bytes_r(obj_->kind, mode, obj_->n_local, obj_->uses_param()));
     return CGO_OK;
@@ -154,6 +157,7 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
         const bool big = bytes > big_bytes(mode == R_TRIAL || mode == R_UPG);
         const int grid = big ? GRID_BIG : grid_cg(n, 1);
         *grid_out = grid;
+        last_mode_ = mode; last_npts_ = chain_npts(mode, npts); last_big_ = big;
         if (int rc = prof_begin(kk)) return rc;
         if (int rc = launch_chain_kernel(mode, a_acc, beta, a, k, chain_npts(mode, npts), big, grid, make_tail(has_sums && !ctl && tail_fused(grid)))) return rc;
         return prof_end();
@@ -169,6 +173,7 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
     const bool big = bytes > big_bytes(mode == R_TRIAL || mode == R_UPG);
     const int grid = big ? GRID_BIG : grid_cg(n, npts);
     *grid_out = grid;
+    last_mode_ = mode; last_npts_ = npts; last_big_ = big;
     P.tail = make_tail(has_sums && !ctl && tail_fused(grid));
     if (ctl && pipe_fused(grid)) {
         P.tail.partials2 = ctx_->partials2_f; P.tail.tickets = ctx_->tickets; P.tail.out = ctx_->out_dev;
@@ -253,6 +258,16 @@ int HipBackend::launch_chain_kernel(int mode, double a_acc, double beta, const d
     return CGO_OK;
 }
 
+// A k_cg / k_chain instantiation as rocprofv3 prints it minus namespaces.
+std::string HipBackend::r_symbol(int mode, int npts, bool big) const {
+    const char *on = obj_->kind == CGO_OBJ_QUAD_DIAG ? "ObjQuadDiag" : obj_->kind == CGO_OBJ_ROSENBROCK_PAIRED ? "ObjRosenPaired"
+                     : obj_->kind == CGO_OBJ_BOOTH ? "ObjBooth" : obj_->kind == CGO_OBJ_USER ? "UserObjective" : "";
+    char buf[160];
+    if (chain()) snprintf(buf, sizeof buf, "k_chain<%d, %d, %s>", mode, npts, big ? "true" : "false");
+    else snprintf(buf, sizeof buf, "k_cg<%s, %d, %d, %s>", on, mode, npts, big ? "true" : "false");
+    return buf;
+}
+
 // The instantiation a launch of kind `kk` uses under the current policy, as rocprofv3 prints it minus namespaces.
 std::string HipBackend::kernel_symbol(int kk) const {
     const char *on = obj_->kind == CGO_OBJ_QUAD_DIAG ? "ObjQuadDiag" : obj_->kind == CGO_OBJ_ROSENBROCK_PAIRED ? "ObjRosenPaired"
@@ -275,9 +290,7 @@ std::string HipBackend::kernel_symbol(int kk) const {
         default: return "";
         }
         const bool big = bytes_r(obj_->kind, mode, n, hp) > big_bytes(mode == R_TRIAL || mode == R_UPG);
-        if (chain()) snprintf(buf, sizeof buf, "k_chain<%d, %d, %s>", mode, chain_npts(mode, npts), big ? "true" : "false");
-        else snprintf(buf, sizeof buf, "k_cg<%s, %d, %d, %s>", on, mode, npts, big ? "true" : "false");
-        return buf;
+        return r_symbol(mode, chain() ? chain_npts(mode, npts) : npts, big);
     }
     if (obj_->two_phase()) {
         if (kk == KK_LSE_STATS) return "k_lse_stats";
@@ -646,6 +659,159 @@ void unpack_r(const double *s, int k, Scal *out, bool dir) {
         out[j].yy = q[RS_YY]; out[j].uy = q[RS_UY]; out[j].ygt = q[RS_YGT];
     }
     if (dir) { out[0].gu = s[RS_PER_POINT * npts]; out[0].uu = s[RS_PER_POINT * npts + 1]; }
+}
+
+// ---- one launch on host vectors (cgo_solver_probe_launch) ------------------------------------------------------------
+// Every buffer a launch of this solver can touch — x, u, their ping-pong partners, both gradient buffers (the second one is
+// solvesystem's x2) and the parameter vector — is re-allocated to whole 128-B lines plus one more line, and everything behind
+// the elements in use is a NaN pattern: a launch that reads past n_local sums a NaN, one that writes past it is caught by
+// probe_slack_intact.  Elements in use: n_local (the stencil objective: its one phantom element of padding too, kept at zero).
+constexpr unsigned PROBE_NAN32 = 0x7FF87FF8u;   // both halves equal: hipMemsetD32 fills it; as a double a quiet NaN
+static inline size_t probe_padded(size_t n) { return ((n + 15) & ~(size_t)15) + 16; }
+
+int HipBackend::probe_prepare() {
+    if (probe_) return CGO_OK;
+    if (int rc = pipe_drain()) return rc;
+    HIPCHK(hipSetDevice(ctx_->device));
+    HIPCHK(hipStreamSynchronize(ctx_->stream));
+    (void)pingpong_ready();   // the engine's own decision, taken now: it would allocate its pair unpadded on the first pure-HBM launch
+    const size_t n = (size_t)obj_->n_local, na = n + (chain() ? (n & 1) : 0), np = probe_padded(na);
+    DevBuf *bufs[] = {&x_, &u_, &x2_, &u2_, &ga_, &gb_};
+    for (DevBuf *b : bufs) {
+        if (b == &x2_ || b == &u2_) { if (pingpong_ != 1) continue; }
+        if (int rc = b->alloc(np)) return rc;
+        HIPCHK(hipMemsetAsync(b->p, 0, na * sizeof(double), ctx_->stream));
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(b->p + na), (int)PROBE_NAN32, (np - na) * 2, ctx_->stream));
+    }
+    if (obj_->uses_param() && obj_->p0_set) {   // the objective's parameter vector, contents kept
+        DevBuf p;
+        if (int rc = p.alloc(np)) return rc;
+        HIPCHK(hipMemcpyAsync(p.p, obj_->p0.p, n * sizeof(double), hipMemcpyDeviceToDevice, ctx_->stream));
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(p.p + n), (int)PROBE_NAN32, (np - n) * 2, ctx_->stream));
+        HIPCHK(hipStreamSynchronize(ctx_->stream));
+        std::swap(p.p, obj_->p0.p); std::swap(p.n, obj_->p0.n);
+    }
+    HIPCHK(hipStreamSynchronize(ctx_->stream));
+    xc_ = x_.p; uc_ = u_.p; xalt_ = x2_.p; ualt_ = u2_.p;
+    g_ = ga_.p; gt_ = gb_.p; xn_ = gb_.p;
+    lse_have_ = false;
+    probe_ = true;
+    return CGO_OK;
+}
+
+// CGO_OK while every slack word of every buffer still holds the NaN pattern
+int HipBackend::probe_slack_intact() {
+    const size_t n = (size_t)obj_->n_local, na = n + (chain() ? (n & 1) : 0);
+    struct { const DevBuf *b; const char *name; size_t used; } v[] = {
+        {&x_, "x", na}, {&u_, "u", na}, {&x2_, "x (ping-pong)", na}, {&u2_, "u (ping-pong)", na},
+        {&ga_, "gradient A", na}, {&gb_, "gradient B / x2", na}, {&obj_->p0, "parameter vector", n}};
+    std::vector<unsigned> h;
+    for (const auto &e : v) {
+        if (!e.b->p || (e.b == &obj_->p0 && !(obj_->uses_param() && obj_->p0_set))) continue;
+        const size_t words = (e.b->n - e.used) * 2;
+        h.assign(words, 0u);
+        HIPCHK(hipMemcpyAsync(h.data(), e.b->p + e.used, words * 4, hipMemcpyDeviceToHost, ctx_->stream));
+        HIPCHK(hipStreamSynchronize(ctx_->stream));
+        for (size_t w = 0; w < words; ++w)
+            if (h[w] != PROBE_NAN32) {
+                set_error(std::string("probe: the launch wrote past the ") + std::to_string(e.used) + " elements of " + e.name +
+                          " (element " + std::to_string(e.used + w / 2) + ")");
+                return CGO_ESTATE;
+            }
+    }
+    return CGO_OK;
+}
+
+int HipBackend::probe_launch(int kk, int variant, double a_acc, double beta, const double *a, int k, const double *x,
+                             const double *u, const double *aux, double *sums, int sums_cap, int *sums_len, double *x_out,
+                             double *u_out, double *g_out, std::string &symbol) {
+    *sums_len = 0;
+    const bool lse = obj_->two_phase();
+    if (!rmode_ && !lse) { set_error("probe: the solver runs neither the k_cg / k_chain family nor the log-sum-exp objective"); return CGO_EINVAL; }
+    if (k < 0 || k > MAXP || (k > 0 && !a)) { set_error("probe: 0 ≤ k ≤ 7 trial steps"); return CGO_EINVAL; }
+    int mode = -1;
+    if (lse) {
+        if (kk == KK_LSE_STATS && (variant == 0 || variant == LM_NOU || variant == (LM_ACCEPT | LM_DIR))) mode = variant;
+        if (kk == KK_LSE_GRAD && variant >= 0 && variant <= 2) mode = variant;   // 0 g⁺ only, 1 + the getβ sums, 2 init (u = −g)
+        if (kk == KK_LSE_STATS && mode != LM_NOU && k < 1) mode = -1;
+        if (kk == KK_LSE_GRAD && mode != 2 && k < 1) mode = -1;
+    } else {
+        auto pick = [&](int dflt, std::initializer_list<int> ok) { const int m = variant ? variant : dflt; for (int o : ok) if (o == m) return m; return -1; };
+        switch (kk) {
+        case KK_INIT: mode = chain() ? pick(R_INIT, {R_INIT, R_GRAD, R_EDGES}) : pick(R_INIT, {R_INIT, R_GRAD}); break;
+        case KK_TRIAL: mode = pick(R_TRIAL, {R_TRIAL}); break;
+        case KK_ACCEPT_DIR_TRIAL: mode = pick(R_ACCEPT | R_DIR | R_TRIAL, {R_ACCEPT | R_DIR | R_TRIAL}); break;
+        case KK_ACCEPT_DIR: mode = pick(R_ACCEPT | R_DIR, {R_ACCEPT | R_DIR}); break;
+        case KK_ACCEPT_ONLY: mode = pick(R_ACCEPT, {R_ACCEPT}); break;
+        case KK_RESET_DIR: mode = pick(R_RESET, {R_RESET}); break;
+        case KK_UPG_NORM: mode = pick(R_UPG, {R_UPG}); break;
+        case KK_DIR_TRIAL: mode = pick(R_DIR | R_TRIAL, {R_DIR, R_DIR | R_TRIAL}); break;
+        case KK_SYS_PROJECT: mode = pick(R_PROJ, {R_PROJ}); break;
+        case KK_SCALED_NORM: mode = pick(R_GRAD, {R_GRAD, R_GRADT}); break;
+        default: break;
+        }
+        if (mode > 0 && (mode & (R_TRIAL | R_GRADT | R_PROJ)) && k < 1) mode = -1;
+        if (mode > 0 && chain() && k > 3) mode = -1;
+    }
+    if (mode < 0) { set_error("probe: kernel kind / variant / trial steps not a launch this solver's engine issues"); return CGO_EINVAL; }
+    if (int rc = probe_prepare()) return rc;
+    HIPCHK(hipSetDevice(ctx_->device));
+    hipStream_t st = ctx_->stream;
+    const size_t n = (size_t)obj_->n_local, nb = n * sizeof(double);
+    double *ub = lse ? u_.p : uc_;
+    double *gb = lse ? gt_ : ga_.p;              // where a gradient is written (R_GRAD, R_GRADT; k_lse_grad: g⁺)
+    double *auxb = lse ? g_ : xn_;               // the stored gradient (log-sum-exp) / solvesystem's x2 (R_PROJ)
+    // inputs; every buffer the launch may write (or must not read) starts as NaN, so that a dropped element shows
+    auto put = [&](double *dst, const double *src) -> int {
+        if (src) HIPCHK(hipMemcpyAsync(dst, src, nb, hipMemcpyHostToDevice, st));
+        else HIPCHK(hipMemsetD32Async((hipDeviceptr_t)dst, (int)PROBE_NAN32, n * 2, st));
+        return CGO_OK;
+    };
+    if (int rc = put(xc_, x)) return rc;
+    if (int rc = put(ub, u)) return rc;
+    if (int rc = put(auxb, aux)) return rc;
+    if (gb != auxb) { if (int rc = put(gb, nullptr)) return rc; }
+    if (!lse && pingpong_ == 1) {
+        if (int rc = put(xalt_, nullptr)) return rc;
+        if (int rc = put(ualt_, nullptr)) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    probe_len_ = 0;
+    last_mode_ = -1;
+    int rc = CGO_OK;
+    char buf[160];
+    if (lse) {
+        Scal o;
+        if (kk == KK_LSE_STATS) {
+            lse_have_ = false;   // the running-maximum form: a probe has no earlier point on the line
+            rc = lse_stats(mode, a_acc, beta, k ? a[0] : 0.0, o, mode == (LM_ACCEPT | LM_DIR));
+            snprintf(buf, sizeof buf, "k_lse_stats<%d, %s, %s>", last_mode_, last_big_ ? "true" : "false", last_npts_ ? "true" : "false");
+        } else {   // (max, Σ) of the trial point: those the last LSE_STATS probe of this solver left, as in the engine
+            const bool nb0 = need_beta_;
+            need_beta_ = mode == 1;
+            rc = lse_grad(mode == 2, k ? a[0] : 0.0, o);
+            need_beta_ = nb0;
+            snprintf(buf, sizeof buf, "k_lse_grad<%s, %s, %s>", last_mode_ == 1 ? "true" : "false", last_mode_ == 2 ? "true" : "false",
+                     last_big_ ? "true" : "false");
+        }
+        if (rc) return rc;
+        symbol = buf;
+    } else {
+        double s[64];
+        rc = launch_r(kk, mode, a_acc, beta, a, k, true, s);
+        if (rc) return rc;
+        symbol = r_symbol(last_mode_, last_npts_, last_big_);
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    if (x_out) HIPCHK(hipMemcpyAsync(x_out, xc_, nb, hipMemcpyDeviceToHost, st));
+    if (u_out) HIPCHK(hipMemcpyAsync(u_out, lse ? u_.p : uc_, nb, hipMemcpyDeviceToHost, st));
+    if (g_out) HIPCHK(hipMemcpyAsync(g_out, mode == R_PROJ && !lse ? xn_ : gb, nb, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (int rc2 = probe_slack_intact()) return rc2;
+    *sums_len = probe_len_;
+    if (probe_len_ > sums_cap) { set_error("probe: sums_cap smaller than the launch's row"); return CGO_EINVAL; }
+    if (probe_len_) std::memcpy(sums, probe_row_, sizeof(double) * probe_len_);
+    return CGO_OK;
 }
 
 // ---- resident solver (cgo_resident.hpp, cgo_kernels_resident.hip.hpp) -------------------------------------------------

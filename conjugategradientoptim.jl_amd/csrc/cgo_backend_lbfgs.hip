@@ -40,6 +40,7 @@ int HipBackend::lse_stats(int mode, double a_acc, double beta, double a_trial, S
     const double bytes = 8.0 * (double)n * nvec;
     const bool big = bytes > big_bytes(mode == 0 || mode == LM_NOU);
     const int grid = big ? GRID_BIG : grid_for(n);
+    last_mode_ = mode; last_big_ = big; last_npts_ = ref ? 1 : 0;   // (probe_launch's symbol; npts = the REF form)
     hipStream_t st = ctx_->stream;
     if (int rc = prof_begin(KK_LSE_STATS)) return rc;
     if (mode == 0) launch_lse_stats<0>(P, big, ref, grid, st);
@@ -51,6 +52,7 @@ int HipBackend::lse_stats(int mode, double a_acc, double beta, double a_trial, S
     if (int rc = finalize_launch(ctx_, grid, !ref)) return rc;
     double s[NS];
     if (int rc = fetch_sums(ctx_, s, ref ? MERGE_SUM : MERGE_LSE)) return rc;
+    if (probe_) { std::memcpy(probe_row_, s, sizeof s); probe_len_ = NS; }
     if (prof_on_) prof_commit(KK_LSE_STATS, bytes);
     if (dir) { out.gu = s[S_GU]; out.uu = s[S_UU]; }
     if (ref) {
@@ -86,6 +88,7 @@ int HipBackend::lse_grad(bool init, double a, Scal &out) {
     const double bytes = 8.0 * (double)n * (init ? 3.0 : (beta ? 4.0 : 3.0));
     const bool big = bytes > big_bytes();
     const int grid = big ? GRID_BIG : grid_for(n);
+    last_mode_ = init ? 2 : (beta ? 1 : 0); last_big_ = big;   // (probe_launch's symbol)
     hipStream_t st = ctx_->stream;
     if (int rc = prof_begin(KK_LSE_GRAD)) return rc;
     if (init) { if (big) k_lse_grad<false, true, true><<<grid, BLOCK, 0, st>>>(P); else k_lse_grad<false, true, false><<<grid, BLOCK, 0, st>>>(P); }
@@ -97,6 +100,7 @@ int HipBackend::lse_grad(bool init, double a, Scal &out) {
     if (int rc = finalize_launch(ctx_, grid, false)) return rc;
     double s[NS];
     if (int rc = fetch_sums(ctx_, s)) return rc;
+    if (probe_) { std::memcpy(probe_row_, s, sizeof s); probe_len_ = NS; }
     if (prof_on_) prof_commit(KK_LSE_GRAD, bytes);
     out.gtgt = s[S_GTGT]; out.gtg = s[S_GTG]; out.yy = s[S_YY]; out.uy = s[S_UY]; out.ygt = s[S_YGT];
     return CGO_OK;

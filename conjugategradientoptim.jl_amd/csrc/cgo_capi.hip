@@ -613,6 +613,7 @@ int cgo_solver_set_x0_fill(cgo_solver *s, int32_t kind, uint64_t seed, double lo
 int cgo_solver_start(cgo_solver *s) {
     API_GUARD_BEGIN
     REQUIRE(s, "null argument");
+    if (s->be->probed()) { set_error("a solver that cgo_solver_probe_launch has used is for probing only"); return CGO_ESTATE; }
     return s->sv->start();
     API_GUARD_END
 }
@@ -620,6 +621,7 @@ int cgo_solver_start(cgo_solver *s) {
 int cgo_solver_iterate(cgo_solver *s, int64_t iters, int32_t *finished) {
     API_GUARD_BEGIN
     REQUIRE(s, "null argument");
+    if (s->be->probed()) { set_error("a solver that cgo_solver_probe_launch has used is for probing only"); return CGO_ESTATE; }
     bool fin = false;
     int rc = s->sv->iterate(iters, fin);
     if (rc == CGO_ESTATE) set_error("cgo_solver_iterate before cgo_solver_start");
@@ -902,6 +904,22 @@ int cgo_kernel_trial(cgo_objective *obj, const double *x, const double *u, doubl
     REQUIRE(!obj->o.host_closure() && obj->o.kind != CGO_OBJ_ROSENBROCK_CHAINED,
             "cgo_kernel_trial is an entry point of the element-wise kernel family: not defined for a host closure or the stencil objective");
     return HipBackend::run_trial(&obj->o, x, u, a, g_next_out, out2);
+    API_GUARD_END
+}
+
+int cgo_solver_probe_launch(cgo_solver *s, int32_t kernel_kind, int32_t variant, double a_acc, double beta,
+                            const double *a, int32_t k, const double *x, const double *u, const double *aux,
+                            double *sums, int32_t sums_cap, int32_t *sums_len,
+                            double *x_out, double *u_out, double *g_out, char *symbol, int32_t symbol_cap) {
+    API_GUARD_BEGIN
+    REQUIRE(s && x && sums_len && (sums || sums_cap == 0) && sums_cap >= 0, "bad argument");
+    std::string sym;
+    int len = 0;
+    const int rc = s->be->probe_launch(kernel_kind, variant, a_acc, beta, a, k, x, u, aux, sums, sums_cap, &len, x_out, u_out, g_out, sym);
+    *sums_len = len;
+    if (rc) return rc;
+    if (symbol && symbol_cap > 0) std::snprintf(symbol, (size_t)symbol_cap, "%s", sym.c_str());
+    return CGO_OK;
     API_GUARD_END
 }
 

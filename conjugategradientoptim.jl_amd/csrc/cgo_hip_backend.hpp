@@ -192,6 +192,13 @@ class HipBackend : public VecBackend {
     void set_three_point_band(int64_t lo, int64_t hi) { band3_lo_ = lo; band3_hi_ = hi; }
     bool rmode() const { return rmode_; }
     std::string kernel_symbol(int kernel_kind) const;
+    // Test entry point (cgo_solver_probe_launch): the vectors → this solver's device state, ONE launch of kind `kernel_kind`
+    // with mode bits `variant` through the engine's own launch path, the whole reduced row and the vectors back.  The first
+    // probe re-allocates the solver's buffers with NaN slack behind n_local: a probed solver is for probing only.
+    int probe_launch(int kernel_kind, int variant, double a_acc, double beta, const double *a, int k, const double *x,
+                     const double *u, const double *aux, double *sums, int sums_cap, int *sums_len, double *x_out,
+                     double *u_out, double *g_out, std::string &symbol);
+    bool probed() const { return probe_; }
 
     // raw single-launch helpers used by the kernel-level C entry points
     static int run_dir(HipCtx *ctx, double *u_host, const double *g_host, double beta, int64_t n,
@@ -222,6 +229,16 @@ class HipBackend : public VecBackend {
     // chained Rosenbrock (stencil objective, cgo_kernels_chain.hip.hpp): x / u always advance out of place, and the
     // two elements beyond each shard boundary travel in the scalar block (slots 10–17 of every rank's row)
     bool chain() const { return obj_->kind == CGO_OBJ_ROSENBROCK_CHAINED; }
+    // probe_launch: the buffers carry NaN slack, the last launch's reduced row is kept, and so is what the last k_cg / k_chain
+    // launch instantiated (mode, points, pure-HBM)
+    bool probe_ = false;
+    double probe_row_[64] = {};
+    int probe_len_ = 0;
+    int last_mode_ = -1, last_npts_ = 0;
+    bool last_big_ = false;
+    int probe_prepare();
+    int probe_slack_intact();
+    std::string r_symbol(int mode, int npts, bool big) const;
     double halo_xl_[2] = {0, 0}, halo_ul_[2] = {0, 0}, halo_xr_[2] = {0, 0}, halo_ur_[2] = {0, 0};
     int launch_chain_kernel(int mode, double a_acc, double beta, const double *a, int k, int npts, bool big, int grid, const dev::Tail &tail);
     bool tail_fused(int grid) const;

@@ -456,6 +456,33 @@ int cgo_getbeta(cgo_ctx *ctx, const cgo_beta_config *b, const double *g_next, co
 /* evalϕdϕ!(xp, df_xp, fdf!, a, x, u) (cg_utils.jl:4-23): out2 = {ϕ, dϕ}; g_next_out = df_xp */
 int cgo_kernel_trial(cgo_objective *obj, const double *x, const double *u, double a,
                      double *g_next_out, double *out2);
+/* ONE launch of the solver's gradient-free family (k_cg / k_chain; the log-sum-exp objective: k_lse_stats / k_lse_grad) on
+ * host vectors, for tests that check every slot of a launch's reduced row.  x, u and aux (n_local doubles each) go into the
+ * solver's own device state and the launch goes through the engine's own path: the solver's resolved policy and its context's
+ * tail setting pick the instantiation (points, pure-HBM or not, reduction tail).  `kernel_kind` is a KK kind the engine
+ * issues such launches for, `variant` its mode bits (0: the kind's usual mode):
+ *   init: R_INIT 8 | R_GRAD 64 | R_EDGES 512 (stencil)   trial: R_TRIAL 4   accept_dir_trial: 7   accept_dir: 3   accept_only: 1
+ *   reset_dir: 16   upg_norm: 32   dir_trial: R_DIR 2 | R_DIR|R_TRIAL 6   sys_project: R_PROJ 256   scaled_norm: R_GRAD | R_GRADT 128
+ *   lse_stats: 0 (trial at a[0]) | 4 (at x itself) | 3 (accept a_acc + direction β, then the trial)
+ *   lse_grad: 0 (g⁺ at a[0]) | 1 (+ the getβ sums) | 2 (initial: at x, u = −g); the (max, Σ) are those the last lse_stats
+ *             probe of this solver left, as in the engine.
+ * a[0..k) are the trial steps (k ≤ 7; a launch for more points than k repeats a[k−1]).  u may be NULL where the mode does not
+ * read it, aux is solvesystem's x2 (sys_project) or the stored gradient (lse_stats 3, lse_grad 1), else NULL; what is NULL
+ * reaches the device as NaN.  Out: the WHOLE reduced row (padding points and padding slots included; sums_len = its width,
+ * 0 for a mode without sums), x / u after the launch, g_out = the gradient the mode wrote (x2 for sys_project); any of them
+ * may be NULL.  symbol = the instantiation, as cgo_solver_kernel_symbol prints it (the log-sum-exp kernels with their template
+ * arguments).  The first probe re-allocates the solver's buffers to whole 128-B lines plus one line with NaN behind n_local
+ * (the objective's parameter vector too, contents kept) and checks after every launch that that slack is untouched
+ * (CGO_ESTATE otherwise): a probed solver is for probing only — cgo_solver_start / cgo_solver_iterate refuse it.  The
+ * parameter vector is the OBJECTIVE's: its old buffer is freed, so the objective of a probed solver must not be shared with
+ * another solver in use (one that has started, or keeps a captured graph or a resident slice on it).
+ * CGO_EINVAL for every other kind (armed rounds, the resident solver, L-BFGS passes) and for the stored-gradient family. */
+int cgo_solver_probe_launch(cgo_solver *s, int32_t kernel_kind, int32_t variant, double a_acc, double beta,
+                            const double *a, int32_t k,
+                            const double *x, const double *u, const double *aux,
+                            double *sums, int32_t sums_cap, int32_t *sums_len,
+                            double *x_out, double *u_out, double *g_out,
+                            char *symbol, int32_t symbol_cap);
 /* device-resident micro-benchmark of the fused kernels: allocates vectors of
  * n doubles on the ctx, runs `reps` launches of `kernel_kind`, returns the mean
  * HIP-event time per launch (ms) and the algorithmic bytes per launch */
