@@ -57,6 +57,20 @@ class SolverPolicyC(C.Structure):  # cgo_solver_policy (include/cgo.h)
                 ("reserved", C.c_int32 * 8)]
 
 
+class LbfgsProbeC(C.Structure):  # cgo_lbfgs_probe (include/cgo.h)
+    _fields_ = [("pass_", C.c_int32), ("slot", C.c_int32), ("count", C.c_int32), ("list", C.c_int32 * 16),
+                ("a", C.c_double), ("a_s", C.c_double), ("a_trial", C.c_double), ("cg", C.c_double), ("M", C.c_double),
+                ("S", C.c_double), ("cy", C.c_double * 16), ("cs", C.c_double * 16), ("deferred_push", C.c_int32),
+                ("lite_slot", C.c_int32), ("a_lite", C.c_double), ("a_s_lite", C.c_double), ("M_lite", C.c_double),
+                ("S_lite", C.c_double), ("loop_mode", C.c_int32), ("final_step", C.c_int32), ("apply_scale", C.c_int32),
+                ("k", C.c_int32), ("q_from_g", C.c_int32), ("v_ring", C.c_int32), ("v_slot", C.c_int32), ("w_ring", C.c_int32),
+                ("w_slot", C.c_int32), ("dot_count", C.c_int32), ("rho", C.c_double), ("scale", C.c_double),
+                ("dot_host", C.c_double), ("dots", dp), ("alpha", C.c_double * 64), ("spec_check", C.c_int32),
+                ("spec_slot", C.c_int32), ("spec_count", C.c_int32), ("spec_list", C.c_int32 * 16), ("spec_a_x", C.c_double),
+                ("spec_a_s", C.c_double), ("spec_ok", C.c_int32), ("new_in_list", C.c_int32), ("sums_len", C.c_int32),
+                ("reserved", C.c_int32), ("gram", C.c_double * 85), ("sums", C.c_double * 64), ("symbol", C.c_char * 256)]
+
+
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, dp, dp, C.c_int32)
 FDF_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, dp, dp, C.c_int64)   # cgo_fdf_fn: f = fdf!(g, x)
 
@@ -137,6 +151,7 @@ SIGNATURES = {
     "cgo_solver_placement_info": (C.c_int, [_vp, dp, dp, C.POINTER(C.c_int32)]),
     "cgo_solver_probe_launch": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_double, C.c_double, dp, C.c_int32, dp, dp, dp,
                                           dp, C.c_int32, C.POINTER(C.c_int32), dp, dp, dp, C.c_char_p, C.c_int32]),
+    "cgo_solver_probe_lbfgs": (C.c_int, [_vp, C.POINTER(LbfgsProbeC)] + [dp] * 13),
 }
 
 

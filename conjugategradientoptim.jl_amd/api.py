@@ -754,6 +754,51 @@ class Solver:
                                         ptr(aux), ptr(sums), 64, C.byref(ln), ptr(xo), ptr(uo), ptr(go), sym, 200))
         return dict(sums=sums[:ln.value].copy(), x=xo, u=uo, g=go, symbol=sym.value.decode())
 
+    LBFGS_PASSES = ("push", "push_gram", "direction_gram", "direction_trial", "push_lite", "loop")
+
+    def probe_lbfgs(self, pass_name: str, x=None, u=None, g=None, gt=None, S=None, Y=None, **kw):
+        """ONE L-BFGS pass on host vectors and whole rings (cgo_solver_probe_lbfgs; pass names and fields as in include/cgo.h).
+        S, Y: (m + 1, n_local) arrays, NaN rows for absent slots; `list`, `cy`, `cs`, `spec_list`, `dots` (rows of 10),
+        `alpha` are sequences, `stats` the log-sum-exp statistics (fields M, S), every other keyword a cgo_lbfgs_probe field.  Returns dict(sums=the whole reduced row, x=, xo=,
+        u=, g=, gt=, S=, Y= after the pass, alpha=, symbols=[instantiations launched, in order], new_in_list=, spec_ok=,
+        gram=[sy, yy, sgn, ygn, gtgt, then sjg, yjg, sjyn, yjsn, yjyn per pair] or None).  For probing only from the first call on."""
+        n = self.obj.n_local
+        P = self._cfg_c.beta.lbfgs_m + 1
+        vec = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float64)
+        x, u, g, gt = vec(x), vec(u), vec(g), vec(gt)
+        for v in (x, u, g, gt):
+            if v is not None and v.size != n:
+                raise ValueError(f"probe vectors hold n_local = {n} elements")
+        S = None if S is None else np.ascontiguousarray(S, dtype=np.float64).reshape(P, n)
+        Y = None if Y is None else np.ascontiguousarray(Y, dtype=np.float64).reshape(P, n)
+        p = _lib.LbfgsProbeC()
+        p.pass_ = self.LBFGS_PASSES.index(pass_name)
+        dots = None
+        for key, val in kw.items():
+            if key in ("list", "spec_list"):
+                getattr(p, key)[:len(val)] = [int(v) for v in val]
+                setattr(p, "count" if key == "list" else "spec_count", len(val))
+            elif key in ("cy", "cs", "alpha"):
+                getattr(p, key)[:len(val)] = [float(v) for v in val]
+            elif key == "stats":   # the log-sum-exp statistics (M, S): fields M, S
+                p.M, p.S = float(val[0]), float(val[1])
+            elif key == "dots":
+                dots = np.ascontiguousarray(val, dtype=np.float64).reshape(-1, 10)
+                p.dots, p.dot_count = dots.ctypes.data_as(dp), dots.shape[0]
+            else:
+                if not hasattr(p, key):
+                    raise TypeError(f"probe_lbfgs: no field {key}")
+                setattr(p, key, val)
+        outs = {k: np.full(n, np.nan) for k in ("x", "xo", "u", "g", "gt")}
+        So, Yo = np.full((P, n), np.nan), np.full((P, n), np.nan)
+        ptr = lambda v: None if v is None else v.ctypes.data_as(dp)
+        check(_lib.lib().cgo_solver_probe_lbfgs(self._h, C.byref(p), ptr(x), ptr(u), ptr(g), ptr(gt), ptr(S), ptr(Y),
+                                                *[ptr(outs[k]) for k in ("x", "xo", "u", "g", "gt")], ptr(So), ptr(Yo)))
+        sym = p.symbol.decode()
+        return dict(sums=np.array(p.sums[:p.sums_len]), S=So, Y=Yo, alpha=np.array(p.alpha[:]), symbols=sym.split(" + ") if sym else [],
+                    new_in_list=p.new_in_list, spec_ok=bool(p.spec_ok),
+                    gram=np.array(p.gram[:5 + 5 * p.spec_count]) if p.spec_ok else None, **outs)
+
     def placement_info(self):
         """(as_allocated_us, chosen_us, candidates) of the solver's placement search (cgo_solver_placement_info);
         candidates == 0: no search was made."""

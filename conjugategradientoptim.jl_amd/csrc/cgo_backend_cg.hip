@@ -666,8 +666,6 @@ void unpack_r(const double *s, int k, Scal *out, bool dir) {
 // solvesystem's x2) and the parameter vector — is re-allocated to whole 128-B lines plus one more line, and everything behind
 // the elements in use is a NaN pattern: a launch that reads past n_local sums a NaN, one that writes past it is caught by
 // probe_slack_intact.  Elements in use: n_local (the stencil objective: its one phantom element of padding too, kept at zero).
-constexpr unsigned PROBE_NAN32 = 0x7FF87FF8u;   // both halves equal: hipMemsetD32 fills it; as a double a quiet NaN
-static inline size_t probe_padded(size_t n) { return ((n + 15) & ~(size_t)15) + 16; }
 
 int HipBackend::probe_prepare() {
     if (probe_) return CGO_OK;

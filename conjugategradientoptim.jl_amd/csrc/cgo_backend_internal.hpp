@@ -7,6 +7,7 @@
 #include "cgo_hip_backend.hpp"
 
 #include <algorithm>
+#include <cstdarg>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -31,6 +32,11 @@ static inline double now_ns() {
     clock_gettime(CLOCK_MONOTONIC, &ts);
     return (double)ts.tv_sec * 1e9 + (double)ts.tv_nsec;
 }
+
+// the probes' NaN slack (cgo_solver_probe_launch, cgo_solver_probe_lbfgs): both halves equal, so that hipMemsetD32 fills it;
+// as a double a quiet NaN.  Buffers are padded to whole 128-B lines plus one more line.
+constexpr unsigned PROBE_NAN32 = 0x7FF87FF8u;
+static inline size_t probe_padded(size_t n) { return ((n + 15) & ~(size_t)15) + 16; }
 
 // streaming policy and grids (cgo_hip_backend.hip)
 double big_bytes_for(double forced, bool read_only = false);

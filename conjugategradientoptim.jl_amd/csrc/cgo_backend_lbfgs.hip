@@ -202,6 +202,7 @@ int HipBackend::lbfgs_push_gram(double a_x, double a_s, int slot, const int *pre
     if (int rc = finalize_rows(ctx_, grid, NG)) return rc;
     double s[NG];
     if (int rc = fetch_sums(ctx_, s, MERGE_SUM, NG)) return rc;
+    if (probe_) probe_note(s, NG, "%s<%s>", fused ? "k_lbfgs_push_gram_lse" : "k_lbfgs_push_gram", big ? "true" : "false");
     if (prof_on_) prof_commit(KK_LBFGS_PUSH, bytes);
     out.sy = s[0]; out.yy = s[1]; out.sgn = s[2]; out.ygn = s[3];
     for (int j = 0; j < count; ++j) {
@@ -247,6 +248,7 @@ int HipBackend::lbfgs_direction_gram(const int *slots, const double *cy, const d
     if (int rc = finalize_rows(ctx_, grid, NS)) return rc;
     double s[NS];
     if (int rc = fetch_sums(ctx_, s)) return rc;
+    if (probe_) probe_note(s, NS, "k_lbfgs_combine<%s>", big ? "true" : "false");
     if (prof_on_) prof_commit(KK_LBFGS_FINAL, bytes);
     out.gu = s[S_GU]; out.uu = s[S_UU];
     return CGO_OK;
@@ -288,6 +290,7 @@ int HipBackend::lbfgs_direction_gram_trial(const int *slots, const double *cy, c
     if (int rc = finalize_launch(ctx_, grid, true)) return rc;
     double s[NS];
     if (int rc = fetch_sums(ctx_, s, MERGE_LSE)) return rc;
+    if (probe_) probe_note(s, NS, "k_lbfgs_combine_lse<%s>", big ? "true" : "false");
     if (prof_on_) prof_commit(KK_LBFGS_FINAL, bytes);
     dir.gu = s[S_GU]; dir.uu = s[S_UU];
     lse_a_ = a_trial; lse_M_ = s[L_M]; lse_S_ = s[L_S];
@@ -374,6 +377,7 @@ int HipBackend::lbfgs_direction_spec(const int *slots, const double *cy, const d
     if (int rc = finalize_rows(ctx_, grid, NG)) return rc;
     double s[NG];
     if (int rc = fetch_sums(ctx_, s, MERGE_SUM, NG)) return rc;
+    if (probe_) probe_note(s, NG, "k_lbfgs_combine_spec<%s, %s, %s>", obj_tname(), big ? "true" : "false", push ? "true" : "false");
     if (prof_on_) prof_commit(KK_LBFGS_FINAL, bytes);
     dir.gu = s[SP_GU]; dir.uu = s[SP_UU];
     if (!lse) {   // element-wise objective: the sums ARE the trial's and the next push's
@@ -498,9 +502,23 @@ int HipBackend::lbfgs_push_lite() {
     HIPCHK(hipGetLastError());
     if (int rc = prof_end()) return rc;
     total_launches_++;
+    if (probe_) probe_note(nullptr, 0, "k_lbfgs_push_lite<%s, %s>", obj_tname(), big ? "true" : "false");
     if (prof_on_) prof_commit(KK_LBFGS_PUSH, bytes);
     qn_sgt_slot_ = -1;
     push_counts_[0]++;
+    return CGO_OK;
+}
+
+// one step of the chained two-loop recursion (k_lbfgs_loop); lbfgs_direction issues 2c of them, probe_lbfgs one
+int HipBackend::launch_loop(const LoopParams &P, int kk, double nvec, bool big, int grid) {
+    if (int rc = prof_begin(kk)) return rc;
+    if (big) k_lbfgs_loop<true><<<grid, BLOCK, 0, ctx_->stream>>>(P);
+    else k_lbfgs_loop<false><<<grid, BLOCK, 0, ctx_->stream>>>(P);
+    HIPCHK(hipGetLastError());
+    if (int rc = prof_end()) return rc;
+    total_launches_++;
+    if (probe_) probe_note(nullptr, 0, "k_lbfgs_loop<%s>", big ? "true" : "false");
+    if (prof_on_) prof_commit(kk, 8.0 * (double)P.n * nvec);
     return CGO_OK;
 }
 
@@ -546,6 +564,7 @@ int HipBackend::lbfgs_push(double a_x, double a_s, int slot, double &sy, double 
     if (int rc = finalize_rows(ctx_, grid, NS)) return rc;
     double s[NS];
     if (int rc = fetch_sums(ctx_, s)) return rc;
+    if (probe_) probe_note(s, NS, "k_lbfgs_push<%s>", big ? "true" : "false");
     if (prof_on_) prof_commit(KK_LBFGS_PUSH, bytes);
     sy = s[PS_SY]; yy = s[PS_YY];
     qn_sgt_ = s[PS_SGT];
@@ -561,22 +580,12 @@ int HipBackend::lbfgs_direction(const int *slots, const double *rho, int count, 
     const double bytes = 8.0 * (double)n * 4.0;
     const bool big = bytes > big_bytes();
     const int grid = big ? GRID_BIG : grid_for(n);
-    hipStream_t st = ctx_->stream;
     auto S = [&](int slot) { return qn_S_.p + (size_t)slot * ring_ld(n); };
     auto Y = [&](int slot) { return qn_Y_.p + (size_t)slot * ring_ld(n); };
     LoopParams P;
     std::memset(&P, 0, sizeof(P));
     P.n = n; P.partials = ctx_->partials; P.alpha = qn_alpha_dev_; P.dot_stride = NS; P.dot_slot = S_GU;
-    auto launch = [&](int kk, double nvec) -> int {
-        if (int rc = prof_begin(kk)) return rc;
-        if (big) k_lbfgs_loop<true><<<grid, BLOCK, 0, st>>>(P);
-        else k_lbfgs_loop<false><<<grid, BLOCK, 0, st>>>(P);
-        HIPCHK(hipGetLastError());
-        if (int rc = prof_end()) return rc;
-        total_launches_++;
-        if (prof_on_) prof_commit(kk, 8.0 * (double)n * nvec);
-        return CGO_OK;
-    };
+    auto launch = [&](int kk, double nvec) { return launch_loop(P, kk, nvec, big, grid); };
     // first dot  s_newest · g : already reduced by the push of this very pair, else one dot-only launch
     if (slots[0] == qn_sgt_slot_) {
         P.dot_ptr = nullptr; P.dot_count = 0; P.dot_host = qn_sgt_;
@@ -608,6 +617,197 @@ int HipBackend::lbfgs_direction(const int *slots, const double *rho, int count, 
     double s[NS];
     if (int rc = fetch_sums(ctx_, s)) return rc;
     out.gu = s[S_GU]; out.uu = s[S_UU];
+    return CGO_OK;
+}
+
+// ---- one L-BFGS pass on host vectors (cgo_solver_probe_lbfgs) ----------------------------------------------------------
+const char *HipBackend::obj_tname() const {
+    switch (obj_->kind) {
+    case CGO_OBJ_LSE: return "ObjLse";
+    case CGO_OBJ_QUAD_DIAG: return "ObjQuadDiag";
+    case CGO_OBJ_ROSENBROCK_PAIRED: return "ObjRosenPaired";
+    case CGO_OBJ_USER: return "UserObjective";
+    default: return "";
+    }
+}
+
+void HipBackend::probe_note(const double *row, int len, const char *fmt, ...) {
+    char buf[120];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (!probe_syms_.empty()) probe_syms_ += " + ";
+    probe_syms_ += buf;
+    if (row) { std::memcpy(probe_row_, row, sizeof(double) * len); probe_len_ = len; }
+}
+
+// CGO_OK while the ring_ld(n) − n words behind every ring slot and the line behind the last slot hold the NaN pattern
+int HipBackend::probe_ring_slack_intact() {
+    const size_t n = (size_t)obj_->n_local, ld = ring_ld((long long)n);
+    std::vector<unsigned> h;
+    for (const DevBuf *b : {&qn_S_, &qn_Y_}) {
+        h.assign(b->n * 2, 0u);
+        HIPCHK(hipMemcpyAsync(h.data(), b->p, b->n * sizeof(double), hipMemcpyDeviceToHost, ctx_->stream));
+        HIPCHK(hipStreamSynchronize(ctx_->stream));
+        for (size_t e = 0; e < b->n; ++e) {
+            if (e < ld * (size_t)qn_m_ && e % ld < n) continue;
+            if (h[2 * e] != PROBE_NAN32 || h[2 * e + 1] != PROBE_NAN32) {
+                set_error(std::string("probe: the launch wrote into the slack of ring ") + (b == &qn_S_ ? "S" : "Y") + " (element " +
+                          std::to_string(e) + ", slot stride " + std::to_string(ld) + ", n " + std::to_string(n) + ")");
+                return CGO_ESTATE;
+            }
+        }
+    }
+    return CGO_OK;
+}
+
+int HipBackend::probe_lbfgs(int m, cgo_lbfgs_probe &p, const double *x, const double *u, const double *g, const double *gt,
+                            const double *S, const double *Y, double *x_out, double *xo_out, double *u_out, double *g_out,
+                            double *gt_out, double *S_out, double *Y_out) {
+    p.sums_len = 0; p.spec_ok = 0; p.new_in_list = 0; p.symbol[0] = 0;
+    const int P = m + 1;
+    if (rmode_ || ctx_->world() != 1 || m < 1 || m > 64) { set_error("probe: a single-rank L-BFGS solver of the Gram / two-loop backend"); return CGO_EINVAL; }
+    const bool lists = p.pass >= 1 && p.pass <= 3;
+    if (p.pass < 0 || p.pass > 5 || p.count < 0 || p.count > m || (lists && p.count > GRAM_MAXC)) { set_error("probe: pass / count"); return CGO_EINVAL; }
+    auto bad_slot = [&](int v) { return v < 0 || v >= P; };
+    for (int j = 0; j < p.count; ++j) if (bad_slot(p.list[j])) { set_error("probe: list slot out of range"); return CGO_EINVAL; }
+    if (bad_slot(p.slot) || (p.deferred_push && bad_slot(p.lite_slot))) { set_error("probe: slot out of range"); return CGO_EINVAL; }
+    if (p.pass == 5 && ((p.v_ring < 2 && bad_slot(p.v_slot)) || (p.w_ring < 2 && bad_slot(p.w_slot)) || p.v_ring < 0 || p.v_ring > 2 ||
+                        p.w_ring < 0 || p.w_ring > 2 || p.loop_mode < 0 || p.loop_mode > 2 || p.k < 0 || p.k >= 64 ||
+                        p.dot_count < 0 || p.dot_count > 64 || (p.dot_count > 0 && !p.dots))) {
+        set_error("probe: loop arguments"); return CGO_EINVAL;
+    }
+    if (p.spec_check && (p.spec_count < 0 || p.spec_count > SPEC_MAXC || bad_slot(p.spec_slot))) { set_error("probe: spec_check arguments"); return CGO_EINVAL; }
+    // the engine's own gates: the Gram passes exist only while the Gram form is on, the one-pass kernels only for their objectives
+    if (int rc = probe_prepare()) return rc;
+    HIPCHK(hipSetDevice(ctx_->device));
+    hipStream_t st = ctx_->stream;
+    const size_t n = (size_t)obj_->n_local, nb = n * sizeof(double), ld = ring_ld((long long)n);
+    if (qn_m_ != P) {   // Solver::start's allocation, then the rings (and the fused push's iterate buffer) again with NaN slack
+        if (int rc = lbfgs_alloc(P)) return rc;
+        for (DevBuf *b : {&qn_S_, &qn_Y_}) {
+            if (int rc = b->alloc(ld * (size_t)P + 16)) return rc;
+            HIPCHK(hipMemsetD32Async((hipDeviceptr_t)b->p, (int)PROBE_NAN32, b->n * 2, st));
+        }
+        if (x2_.p && x2_.n < probe_padded(n)) {
+            if (int rc = x2_.alloc(probe_padded(n))) return rc;
+            HIPCHK(hipMemsetD32Async((hipDeviceptr_t)x2_.p, (int)PROBE_NAN32, x2_.n * 2, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    if (lists && !gram_on_) { set_error("probe: the Gram form is off for this solver (m > 12 or lbfgs_form two_loop)"); return CGO_EINVAL; }
+    if (p.pass == 4 && !spec_on_) { set_error("probe: the one-pass form is off for this solver"); return CGO_EINVAL; }
+    if (p.pass == 3 && !lbfgs_direction_gram_can_fuse_trial()) { set_error("probe: this solver's engine does not fuse the first trial into the direction"); return CGO_EINVAL; }
+    if (p.pass == 3 && p.deferred_push && !(spec_on_ && spec_fuse_push_)) { set_error("probe: this solver's engine does not defer the push"); return CGO_EINVAL; }
+    if (p.pass == 5 && gram_on_) { set_error("probe: this solver runs the Gram form, not the two-loop recursion"); return CGO_EINVAL; }
+    if ((p.pass == 0) && gram_on_) { set_error("probe: this solver pushes through the Gram form"); return CGO_EINVAL; }
+    // a fresh iterate: the buffers in their first roles, nothing pending
+    xc_ = x_.p; g_ = ga_.p; gt_ = gb_.p;
+    push_pending_ = push_lite_pending_ = lite_deferred_ = spec_valid_ = spec_unmat_ = false;
+    qn_sgt_slot_ = -1;
+    auto put = [&](double *dst, const double *src) -> int {
+        if (src) HIPCHK(hipMemcpyAsync(dst, src, nb, hipMemcpyHostToDevice, st));
+        else HIPCHK(hipMemsetD32Async((hipDeviceptr_t)dst, (int)PROBE_NAN32, n * 2, st));
+        return CGO_OK;
+    };
+    if (int rc = put(x_.p, x)) return rc;
+    if (int rc = put(u_.p, u)) return rc;
+    if (int rc = put(ga_.p, g)) return rc;
+    if (int rc = put(gb_.p, gt)) return rc;
+    if (x2_.p) { if (int rc = put(x2_.p, nullptr)) return rc; }
+    for (int q = 0; q < P; ++q) {
+        if (int rc = put(qn_S_.p + (size_t)q * ld, S ? S + (size_t)q * n : nullptr)) return rc;
+        if (int rc = put(qn_Y_.p + (size_t)q * ld, Y ? Y + (size_t)q * n : nullptr)) return rc;
+    }
+    HIPCHK(hipMemcpyAsync(qn_alpha_dev_, p.alpha, sizeof(double) * 64, hipMemcpyHostToDevice, st));
+    DevBuf dots;
+    if (p.dot_count > 0) {
+        if (int rc = dots.alloc((size_t)p.dot_count * NS)) return rc;
+        HIPCHK(hipMemcpyAsync(dots.p, p.dots, sizeof(double) * NS * p.dot_count, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    probe_len_ = 0;
+    probe_syms_.clear();
+    int rc = CGO_OK;
+    Scal dir, trial;
+    GramOut G;
+    double sy = 0, yy = 0;
+    switch (p.pass) {
+    case 0: rc = lbfgs_push(p.a, p.a_s, p.slot, sy, yy); break;
+    case 1:
+        if (obj_->two_phase()) { lse_a_ = p.a; lse_M_ = p.M; lse_S_ = p.S; }   // the accepted trial's statistics
+        rc = lbfgs_push_gram(p.a, p.a_s, p.slot, p.list, p.count, G);
+        break;
+    case 2: rc = lbfgs_direction_gram(p.list, p.cy, p.cs, p.count, p.cg, dir); break;
+    case 3:
+        if (obj_->two_phase()) { lse_M_ = p.M; lse_S_ = p.S; lse_have_ = true; }   // the iterate's statistics
+        if (p.deferred_push) {   // as lbfgs_push_spec + lbfgs_push_commit(true) leave it
+            lite_deferred_ = true;
+            lite_a_ = p.a_lite; lite_as_ = p.a_s_lite; lite_slot_ = p.lite_slot; lite_M_ = p.M_lite; lite_S_ = p.S_lite;
+            p.new_in_list = (p.count > 0 && p.list[0] == p.lite_slot) ? 1 : 0;
+        }
+        rc = lbfgs_direction_gram_trial(p.list, p.cy, p.cs, p.count, p.cg, p.a_trial, dir, trial);
+        if (!rc && p.spec_check) {
+            p.spec_ok = lbfgs_push_spec(p.spec_a_x, p.spec_a_s, p.spec_slot, p.spec_list, p.spec_count, G) ? 1 : 0;
+            if (p.spec_ok) {
+                double *o = p.gram;
+                o[0] = G.sy; o[1] = G.yy; o[2] = G.sgn; o[3] = G.ygn; o[4] = G.gtgt;
+                for (int j = 0; j < p.spec_count; ++j) {
+                    double *q = o + 5 + 5 * j;
+                    q[0] = G.sjg[j]; q[1] = G.yjg[j]; q[2] = G.sjyn[j]; q[3] = G.yjsn[j]; q[4] = G.yjyn[j];
+                }
+            }
+            push_lite_pending_ = false;
+        }
+        break;
+    case 4:
+        lite_a_ = p.a; lite_as_ = p.a_s; lite_slot_ = p.slot; lite_M_ = p.M; lite_S_ = p.S;
+        rc = lbfgs_push_lite();
+        break;
+    case 5: {
+        LoopParams L;
+        std::memset(&L, 0, sizeof(L));
+        auto vec = [&](int ring, int slot) -> const double * {
+            return ring == 2 ? ga_.p : (ring == 0 ? qn_S_.p : qn_Y_.p) + (size_t)slot * ld;
+        };
+        L.n = (long long)n; L.partials = ctx_->partials; L.alpha = qn_alpha_dev_; L.dot_stride = NS; L.dot_slot = S_GU;
+        L.mode = p.loop_mode; L.k = p.k; L.rho = p.rho; L.scale = p.scale; L.apply_scale = p.apply_scale; L.final_step = p.final_step;
+        L.qin = p.q_from_g ? ga_.p : u_.p; L.qout = u_.p; L.v = vec(p.v_ring, p.v_slot); L.w = vec(p.w_ring, p.w_slot);
+        L.dot_host = p.dot_host; L.dot_ptr = p.dot_count ? dots.p : nullptr; L.dot_count = p.dot_count;
+        const bool big = 8.0 * (double)n * 4.0 > big_bytes();   // lbfgs_direction's geometry
+        const int grid = big ? GRID_BIG : grid_for((int64_t)n);
+        rc = launch_loop(L, p.final_step ? KK_LBFGS_FINAL : KK_LBFGS_LOOP, 4.0, big, grid);
+        if (!rc) rc = finalize_rows(ctx_, grid, NS);
+        double s[NS];
+        if (!rc) rc = fetch_sums(ctx_, s);
+        if (!rc) { std::memcpy(probe_row_, s, sizeof s); probe_len_ = NS; }
+        break;
+    }
+    }
+    push_pending_ = push_lite_pending_ = lite_deferred_ = spec_valid_ = false;
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    auto get = [&](double *dst, const double *src) -> int {
+        if (dst && src) HIPCHK(hipMemcpyAsync(dst, src, nb, hipMemcpyDeviceToHost, st));
+        return CGO_OK;
+    };
+    if (int r = get(x_out, x_.p)) return r;
+    if (int r = get(xo_out, x2_.p)) return r;
+    if (int r = get(u_out, u_.p)) return r;
+    if (int r = get(g_out, ga_.p)) return r;
+    if (int r = get(gt_out, gb_.p)) return r;
+    for (int q = 0; q < P; ++q) {
+        if (int r = get(S_out ? S_out + (size_t)q * n : nullptr, qn_S_.p + (size_t)q * ld)) return r;
+        if (int r = get(Y_out ? Y_out + (size_t)q * n : nullptr, qn_Y_.p + (size_t)q * ld)) return r;
+    }
+    HIPCHK(hipMemcpyAsync(p.alpha, qn_alpha_dev_, sizeof(double) * 64, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (int r = probe_slack_intact()) return r;
+    if (int r = probe_ring_slack_intact()) return r;
+    p.sums_len = probe_len_;
+    if (probe_len_) std::memcpy(p.sums, probe_row_, sizeof(double) * probe_len_);
+    std::snprintf(p.symbol, sizeof p.symbol, "%s", probe_syms_.c_str());
     return CGO_OK;
 }
 

@@ -613,7 +613,7 @@ int cgo_solver_set_x0_fill(cgo_solver *s, int32_t kind, uint64_t seed, double lo
 int cgo_solver_start(cgo_solver *s) {
     API_GUARD_BEGIN
     REQUIRE(s, "null argument");
-    if (s->be->probed()) { set_error("a solver that cgo_solver_probe_launch has used is for probing only"); return CGO_ESTATE; }
+    if (s->be->probed()) { set_error("a solver that a probe (cgo_solver_probe_launch / _lbfgs) has used is for probing only"); return CGO_ESTATE; }
     return s->sv->start();
     API_GUARD_END
 }
@@ -621,7 +621,7 @@ int cgo_solver_start(cgo_solver *s) {
 int cgo_solver_iterate(cgo_solver *s, int64_t iters, int32_t *finished) {
     API_GUARD_BEGIN
     REQUIRE(s, "null argument");
-    if (s->be->probed()) { set_error("a solver that cgo_solver_probe_launch has used is for probing only"); return CGO_ESTATE; }
+    if (s->be->probed()) { set_error("a solver that a probe (cgo_solver_probe_launch / _lbfgs) has used is for probing only"); return CGO_ESTATE; }
     bool fin = false;
     int rc = s->sv->iterate(iters, fin);
     if (rc == CGO_ESTATE) set_error("cgo_solver_iterate before cgo_solver_start");
@@ -920,6 +920,17 @@ int cgo_solver_probe_launch(cgo_solver *s, int32_t kernel_kind, int32_t variant,
     if (rc) return rc;
     if (symbol && symbol_cap > 0) std::snprintf(symbol, (size_t)symbol_cap, "%s", sym.c_str());
     return CGO_OK;
+    API_GUARD_END
+}
+
+int cgo_solver_probe_lbfgs(cgo_solver *s, cgo_lbfgs_probe *p, const double *x, const double *u, const double *g, const double *gt,
+                           const double *S, const double *Y, double *x_out, double *xo_out, double *u_out, double *g_out,
+                           double *gt_out, double *S_out, double *Y_out) {
+    API_GUARD_BEGIN
+    REQUIRE(s && p, "null argument");
+    const cgo_cg_config &c = s->sv->config();
+    if (c.beta.kind != CGO_BETA_LBFGS) { set_error("probe: the solver's β is not LBFGS(m)"); return CGO_EINVAL; }
+    return s->be->probe_lbfgs(c.beta.lbfgs_m, *p, x, u, g, gt, S, Y, x_out, xo_out, u_out, g_out, gt_out, S_out, Y_out);
     API_GUARD_END
 }
 

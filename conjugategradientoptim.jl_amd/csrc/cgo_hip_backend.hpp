@@ -13,7 +13,7 @@
 
 namespace cgo {
 
-namespace dev { struct CtlArgs; struct Tail; }
+namespace dev { struct CtlArgs; struct Tail; struct LoopParams; }
 
 void set_error(const std::string &msg);
 const char *get_error();
@@ -199,6 +199,11 @@ class HipBackend : public VecBackend {
                      const double *u, const double *aux, double *sums, int sums_cap, int *sums_len, double *x_out,
                      double *u_out, double *g_out, std::string &symbol);
     bool probed() const { return probe_; }
+    // Test entry point (cgo_solver_probe_lbfgs): ONE L-BFGS pass of this solver (β = LBFGS(m)) on host vectors and rings,
+    // through the entry point the engine uses for it; the rings get NaN slack as well.
+    int probe_lbfgs(int m, cgo_lbfgs_probe &p, const double *x, const double *u, const double *g, const double *gt, const double *S,
+                    const double *Y, double *x_out, double *xo_out, double *u_out, double *g_out, double *gt_out, double *S_out,
+                    double *Y_out);
 
     // raw single-launch helpers used by the kernel-level C entry points
     static int run_dir(HipCtx *ctx, double *u_host, const double *g_host, double beta, int64_t n,
@@ -239,6 +244,11 @@ class HipBackend : public VecBackend {
     int probe_prepare();
     int probe_slack_intact();
     std::string r_symbol(int mode, int npts, bool big) const;
+    std::string probe_syms_;   // probe_lbfgs: every instantiation its pass launched (probe_note)
+    void probe_note(const double *row, int len, const char *fmt, ...);
+    int probe_ring_slack_intact();
+    const char *obj_tname() const;
+    int launch_loop(const dev::LoopParams &P, int kk, double nvec, bool big, int grid);
     double halo_xl_[2] = {0, 0}, halo_ul_[2] = {0, 0}, halo_xr_[2] = {0, 0}, halo_ur_[2] = {0, 0};
     int launch_chain_kernel(int mode, double a_acc, double beta, const double *a, int k, int npts, bool big, int grid, const dev::Tail &tail);
     bool tail_fused(int grid) const;

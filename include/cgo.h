@@ -476,13 +476,57 @@ int cgo_kernel_trial(cgo_objective *obj, const double *x, const double *u, doubl
  * (CGO_ESTATE otherwise): a probed solver is for probing only — cgo_solver_start / cgo_solver_iterate refuse it.  The
  * parameter vector is the OBJECTIVE's: its old buffer is freed, so the objective of a probed solver must not be shared with
  * another solver in use (one that has started, or keeps a captured graph or a resident slice on it).
- * CGO_EINVAL for every other kind (armed rounds, the resident solver, L-BFGS passes) and for the stored-gradient family. */
+ * CGO_EINVAL for every other kind (armed rounds, the resident solver; the L-BFGS passes: cgo_solver_probe_lbfgs) and for the
+ * stored-gradient family. */
 int cgo_solver_probe_launch(cgo_solver *s, int32_t kernel_kind, int32_t variant, double a_acc, double beta,
                             const double *a, int32_t k,
                             const double *x, const double *u, const double *aux,
                             double *sums, int32_t sums_cap, int32_t *sums_len,
                             double *x_out, double *u_out, double *g_out,
                             char *symbol, int32_t symbol_cap);
+/* ONE L-BFGS pass of a single-rank solver whose β is LBFGS(m), on host vectors (cgo_solver_probe_lbfgs), through the backend's
+ * own entry point for that pass, so that the engine picks the instantiation, grid and streaming path:
+ *   0 push              lbfgs_push (k_lbfgs_push): a, a_s, slot
+ *   1 push_gram         lbfgs_push_gram (k_lbfgs_push_gram, or k_lbfgs_push_gram_lse where the engine fuses g⁺ into the push:
+ *                       the log-sum-exp objective, M, S = the accepted trial's statistics, out of place into xo_out)
+ *   2 direction_gram    lbfgs_direction_gram (k_lbfgs_combine): list, count, cg, cy, cs
+ *   3 direction_trial   lbfgs_direction_gram_trial (k_lbfgs_combine_lse, or k_lbfgs_combine_spec where the one-pass form is on;
+ *                       M, S = the iterate's statistics; deferred_push: the state update of a_lite, a_s_lite, M_lite, S_lite
+ *                       into lite_slot rides along — new_in_list is the engine's own decision, list[0] == lite_slot, and out)
+ *                       then, with spec_check, lbfgs_push_spec(spec_a_x, spec_a_s, spec_slot, spec_list, spec_count): spec_ok
+ *                       and gram = {sy, yy, sgn, ygn, gtgt, then per pair j: sjg, yjg, sjyn, yjsn, yjyn}
+ *   4 push_lite         lbfgs_push_lite (k_lbfgs_push_lite): a, a_s, slot, M, S
+ *   5 loop              ONE k_lbfgs_loop launch: loop_mode (0 loop 1, 1 loop 2, 2 dot only), final_step, apply_scale, k, rho,
+ *                       scale; q from g (q_from_g) or u, out to u; v and w are ring vectors (ring 0 S, 1 Y) or g (ring 2);
+ *                       the dot from dot_host (dot_count 0) or summed over dot_count rows of 10 (dots, rank order) on the
+ *                       device; alpha[64] is the device α vector before (in) and after (out) the launch.
+ * x, u, g (the stored gradient), gt (g⁺) hold n_local doubles, S and Y the whole rings: m + 1 slots of n_local, slot-major;
+ * what is NULL reaches the device as NaN (an absent ring slot: NaN rows).  Out (each may be NULL): the vectors and both rings
+ * after the launch; sums / sums_len the whole reduced row of the pass's last reducing launch (padding slots included);
+ * symbol every instantiation launched, in order, joined by " + ".  As cgo_solver_probe_launch, the first probe gives every
+ * vector NaN slack, the rings too (the ring_ld padding behind every slot and one line behind the last), and every launch is
+ * checked not to have written into it (CGO_ESTATE): a probed solver is for probing only.  CGO_EINVAL for a solver that is
+ * not single-rank L-BFGS, and for a pass its engine would not issue. */
+typedef struct cgo_lbfgs_probe {
+    int32_t pass, slot, count, list[16];
+    double a, a_s, a_trial, cg, M, S;
+    double cy[16], cs[16];
+    int32_t deferred_push, lite_slot;
+    double a_lite, a_s_lite, M_lite, S_lite;
+    int32_t loop_mode, final_step, apply_scale, k, q_from_g, v_ring, v_slot, w_ring, w_slot, dot_count;
+    double rho, scale, dot_host;
+    const double *dots;
+    double alpha[64];
+    int32_t spec_check, spec_slot, spec_count, spec_list[16];
+    double spec_a_x, spec_a_s;
+    int32_t spec_ok, new_in_list, sums_len, reserved;   /* out */
+    double gram[85];                                     /* out */
+    double sums[64];                                     /* out */
+    char symbol[256];                                    /* out */
+} cgo_lbfgs_probe;
+int cgo_solver_probe_lbfgs(cgo_solver *s, cgo_lbfgs_probe *p,
+                           const double *x, const double *u, const double *g, const double *gt, const double *S, const double *Y,
+                           double *x_out, double *xo_out, double *u_out, double *g_out, double *gt_out, double *S_out, double *Y_out);
 /* device-resident micro-benchmark of the fused kernels: allocates vectors of
  * n doubles on the ctx, runs `reps` launches of `kernel_kind`, returns the mean
  * HIP-event time per launch (ms) and the algorithmic bytes per launch */
