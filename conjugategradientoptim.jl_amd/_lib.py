@@ -71,6 +71,20 @@ class LbfgsProbeC(C.Structure):  # cgo_lbfgs_probe (include/cgo.h)
                 ("reserved", C.c_int32), ("gram", C.c_double * 85), ("sums", C.c_double * 64), ("symbol", C.c_char * 256)]
 
 
+class ResidentPassC(C.Structure):  # cgo_resident_pass (include/cgo.h)
+    _fields_ = [("kind", C.c_int32), ("k", C.c_int32), ("a", C.c_double * 7), ("a_acc", C.c_double), ("beta", C.c_double)]
+
+
+class ResidentPassOutC(C.Structure):  # cgo_resident_pass_out
+    _fields_ = [("ts", (C.c_double * 7) * 7), ("gu", C.c_double), ("uu", C.c_double), ("width", C.c_int64)]
+
+
+class ResidentProbeC(C.Structure):  # cgo_resident_probe
+    _fields_ = [("npass", C.c_int32), ("reserved", C.c_int32), ("pass_", ResidentPassC * 32), ("grid", C.c_int32),
+                ("points", C.c_int32), ("chunk", C.c_int64), ("round0", C.c_int64), ("err_word", C.c_uint32),
+                ("wrote_back", C.c_int32), ("out", ResidentPassOutC * 32), ("symbol", C.c_char * 128)]
+
+
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, dp, dp, C.c_int32)
 FDF_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, dp, dp, C.c_int64)   # cgo_fdf_fn: f = fdf!(g, x)
 
@@ -152,6 +166,7 @@ SIGNATURES = {
     "cgo_solver_probe_launch": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_double, C.c_double, dp, C.c_int32, dp, dp, dp,
                                           dp, C.c_int32, C.POINTER(C.c_int32), dp, dp, dp, C.c_char_p, C.c_int32]),
     "cgo_solver_probe_lbfgs": (C.c_int, [_vp, C.POINTER(LbfgsProbeC)] + [dp] * 13),
+    "cgo_solver_probe_resident": (C.c_int, [_vp, C.POINTER(ResidentProbeC), dp, dp, dp, C.c_int64, dp, dp]),
 }
 
 

@@ -799,6 +799,47 @@ class Solver:
                     new_in_list=p.new_in_list, spec_ok=bool(p.spec_ok),
                     gram=np.array(p.gram[:5 + 5 * p.spec_count]) if p.spec_ok else None, **outs)
 
+    def probe_resident(self, script, x, u):
+        """A scripted sequence of resident passes in ONE launch (cgo_solver_probe_resident).  `script`: up to 32 tuples
+        ("trial", a) or ("accept_dir_trial", a_acc, beta, a), a = the trial steps (k = len(a)).  Returns dict(rows=[per pass:
+        (grid, width) array — the totals every workgroup holds], tail=[per pass: what lies behind the width in the 56-slot
+        stride, (grid, 56 − width)], out=[per pass: dict(ts=(7, 7) array, gu=, uu=) as workgroup 0's member function returned
+        them], grid=, chunk=, points=, round0=, wrote_back=, x=, u= (what the next slice would read), symbol=).  For probing
+        only from the first call on."""
+        n = self.obj.n_local
+        x, u = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
+        if x.size != n or u.size != n:
+            raise ValueError(f"probe vectors hold n_local = {n} elements")
+        p = _lib.ResidentProbeC()
+        if len(script) > 32:
+            raise ValueError("probe_resident: at most 32 passes")
+        p.npass = len(script)
+        for q, item in enumerate(script):
+            c = p.pass_[q]
+            if item[0] == "trial":
+                c.kind, a = 0, item[1]
+            elif item[0] == "accept_dir_trial":
+                c.kind, c.a_acc, c.beta, a = 1, float(item[1]), float(item[2]), item[3]
+            else:
+                raise ValueError(f"probe_resident: no pass kind {item[0]!r}")
+            if len(a) > 7:
+                raise ValueError("probe_resident: at most 7 trial steps")
+            c.k = len(a)
+            c.a[:len(a)] = [float(v) for v in a]
+        rows = np.full((max(p.npass, 1), 256, 56), np.nan)
+        xo, uo = np.empty(n), np.empty(n)
+        check(_lib.lib().cgo_solver_probe_resident(self._h, C.byref(p), x.ctypes.data_as(dp), u.ctypes.data_as(dp),
+                                                   rows.ctypes.data_as(dp), rows.size, xo.ctypes.data_as(dp), uo.ctypes.data_as(dp)))
+        g = p.grid
+        got = rows.ravel()[:p.npass * g * 56].reshape(p.npass, g, 56)
+        outs, rws, tails = [], [], []
+        for q in range(p.npass):
+            w = int(p.out[q].width)
+            rws.append(got[q, :, :w].copy()); tails.append(got[q, :, w:].copy())
+            outs.append(dict(ts=np.array([list(r) for r in p.out[q].ts]), gu=p.out[q].gu, uu=p.out[q].uu))
+        return dict(rows=rws, tail=tails, out=outs, grid=g, chunk=p.chunk, points=p.points, round0=p.round0,
+                    wrote_back=bool(p.wrote_back), x=xo, u=uo, symbol=p.symbol.decode())
+
     def placement_info(self):
         """(as_allocated_us, chosen_us, candidates) of the solver's placement search (cgo_solver_placement_info);
         candidates == 0: no search was made."""

@@ -835,6 +835,21 @@ static const void *res_kernel_for(int obj_kind, int npts) {
     }
 }
 
+// the PROBE instantiations (cgo_solver_probe_resident): same dispatch, the script in place of res_iterate
+template <class Obj>
+static const void *res_probe_kernel(int npts) {
+    return npts >= 7 ? (const void *)k_resident<Obj, 7, true> : (npts >= 3 ? (const void *)k_resident<Obj, 3, true> : (const void *)k_resident<Obj, 1, true>);
+}
+static const void *res_probe_kernel_for(int obj_kind, int npts) {
+    switch (obj_kind) {
+    case CGO_OBJ_ROSENBROCK_CHAINED: return npts >= 3 ? (const void *)k_resident_chain<3, true> : (const void *)k_resident_chain<1, true>;
+    case CGO_OBJ_QUAD_DIAG: return res_probe_kernel<ObjQuadDiag>(npts);
+    case CGO_OBJ_ROSENBROCK_PAIRED: return res_probe_kernel<ObjRosenPaired>(npts);
+    case CGO_OBJ_BOOTH: return res_probe_kernel<ObjBooth>(npts);
+    default: return nullptr;
+    }
+}
+
 int HipBackend::res_plan() {
     if (res_grid_ != 0) return res_grid_ > 0 ? res_grid_ : 0;
     res_grid_ = -1;   // decided: does not fit, unless the plan below completes
@@ -914,6 +929,39 @@ int HipBackend::res_alloc() {
     return CGO_OK;
 }
 
+// The host bookkeeping of a resident launch, shared by resident_run and probe_resident: where the launch leaves x, u (OTHER
+// buffers when it has more than one workgroup), the kernel arguments that do not depend on what the launch computes, the swap
+// after a good GLOBAL verdict, and the reset after a launch whose exchange gave up.
+void HipBackend::res_out_buffers(double *&xo, double *&uo) const {
+    const bool oop = res_grid_ > 1;
+    xo = oop ? ((xc_ == res_xo_.p) ? res_xin_ : res_xo_.p) : xc_;
+    uo = oop ? ((uc_ == res_uo_.p) ? res_uin_ : res_uo_.p) : uc_;
+}
+
+void HipBackend::res_fill_params(ResParams &P, double *xo, double *uo) {
+    P.x = xc_; P.u = uc_; P.p0 = obj_->p0.p; P.n = obj_->n_local; P.chunk = res_chunk_; P.s0 = obj_->s0;
+    P.xo = xo; P.uo = uo; P.arrive = res_err_ + 1;
+    P.inject = -1;
+    P.st_out = res_state_; P.recs = res_recs_dev_;
+    P.recs_host = res_recs_; P.log_host = res_log_;
+    P.xbuf = res_xbuf_; P.round0 = res_round_; P.err = res_err_;
+    P.done_seq = res_done_; P.seq = ++res_seq_;
+}
+
+void HipBackend::res_swap_in(double *xo, double *uo) {
+    res_xin_ = xc_; res_uin_ = uc_;
+    xc_ = xo; uc_ = uo;
+}
+
+int HipBackend::res_error_reset() {
+    HIPCHK(hipStreamSynchronize(ctx_->stream));
+    const size_t xb = sizeof(double) * RES_XBUFS * ((size_t)res_grid_ + RES_GROUPS) * RES_WMAX;
+    HIPCHK(hipMemsetD32((hipDeviceptr_t)res_xbuf_, (int)(TAIL_EMPTY & 0xFFFFFFFFull), xb / 4));
+    HIPCHK(hipMemset(res_err_, 0, 64));
+    res_round_ = 0;
+    return CGO_OK;
+}
+
 int HipBackend::resident_run(const ResConfig &c, ResState &s, int64_t budget, std::vector<ResRecord> &recs, std::vector<ResLog> &log) {
     if (int rc = pipe_drain()) return rc;
     pipe_streak_ = 0;
@@ -926,20 +974,16 @@ int HipBackend::resident_run(const ResConfig &c, ResState &s, int64_t budget, st
         HIPCHK(hipMalloc((void **)&res_log_dev_, sizeof(ResLog) * RES_LOG_CAP));
     }
     ResParams P{};
-    P.x = xc_; P.u = uc_; P.p0 = obj_->p0.p; P.n = obj_->n_local; P.chunk = res_chunk_; P.s0 = obj_->s0;
     const bool oop = res_grid_ > 1;
-    double *xo = oop ? ((xc_ == res_xo_.p) ? res_xin_ : res_xo_.p) : xc_, *uo = oop ? ((uc_ == res_uo_.p) ? res_uin_ : res_uo_.p) : uc_;
-    P.xo = xo; P.uo = uo; P.arrive = res_err_ + 1;
-    P.inject = -1;
+    double *xo, *uo;
+    res_out_buffers(xo, uo);
+    res_fill_params(P, xo, uo);
     if (res_slices_ == 0) { if (const char *e = getenv("CGO_RES_INJECT_GIVEUP")) P.inject = atoi(e); }   // test hook: first slice only
     P.cfg = c; P.cfg.npts = res_npts_;
     P.st = s;
     if (P.st.ncache > res_npts_) P.st.ncache = res_npts_;   // (a wider host launch left more trial results than a pass of this width keeps)
     P.budget = std::min<int64_t>(budget, RES_REC_CAP);
-    P.st_out = res_state_; P.recs = res_recs_dev_; P.log = res_log_dev_; P.log_cap = c.log_on ? RES_LOG_CAP : 0;
-    P.recs_host = res_recs_; P.log_host = res_log_;
-    P.xbuf = res_xbuf_; P.round0 = res_round_; P.err = res_err_;
-    P.done_seq = res_done_; P.seq = ++res_seq_;
+    P.log = res_log_dev_; P.log_cap = c.log_on ? RES_LOG_CAP : 0;
     static const bool timing = getenv("CGO_RES_TIMING") != nullptr;
     P.timing = timing ? 1 : 0;
     const void *fn = res_kernel_for(obj_->kind, res_npts_);
@@ -973,11 +1017,7 @@ int HipBackend::resident_run(const ResConfig &c, ResState &s, int64_t budget, st
         // for workgroups the other one's keep out).  Nothing is lost: a slice writes x, u back only when it ends well, so
         // the state is still that of the slice's start — hand the whole slice to the launch-per-trial engine and keep this
         // solver off the resident path from here on (correct under any sharing of the GPU, at the old speed).
-        HIPCHK(hipStreamSynchronize(ctx_->stream));
-        const size_t xb = sizeof(double) * RES_XBUFS * ((size_t)res_grid_ + RES_GROUPS) * RES_WMAX;
-        HIPCHK(hipMemsetD32((hipDeviceptr_t)res_xbuf_, (int)(TAIL_EMPTY & 0xFFFFFFFFull), xb / 4));
-        HIPCHK(hipMemset(res_err_, 0, 64));
-        res_round_ = 0;
+        if (int rc = res_error_reset()) return rc;
         res_on_ = false;
         res_gave_up_++;
         s = P.st;   // the state the slice started from
@@ -985,15 +1025,150 @@ int HipBackend::resident_run(const ResConfig &c, ResState &s, int64_t budget, st
         recs.clear(); log.clear();
         return CGO_OK;
     }
-    if (oop && s.done > 0) {   // a good slice, by the verdict of ALL its workgroups: its x, u become the iterate
-        res_xin_ = xc_; res_uin_ = uc_;
-        xc_ = xo; uc_ = uo;
-    }
+    if (oop && s.done > 0) res_swap_in(xo, uo);   // a good slice, by the verdict of ALL its workgroups: its x, u become the iterate
     res_iters_ += s.done;
     recs.assign(res_recs_, res_recs_ + s.done);
     if (c.log_on) log.assign(res_log_, res_log_ + s.log_len); else log.clear();
     // state moved once per slice: load x, u (+ D) and store x, u
     if (prof_on_) prof_commit(KK_RESIDENT, 8.0 * (double)obj_->n_local * (double)((obj_->uses_param() ? 3 : 2) + (s.done > 0 ? 2 : 0)));
+    return CGO_OK;
+}
+
+// ---- a script of resident passes in one launch (cgo_solver_probe_resident) ---------------------------------------------
+// Everything but the kernel's PROBE flag is resident_run's: the plan, res_alloc's buffers, the out-of-place rule and its
+// swap, round0 and the rounds added afterwards.  x, u, xo, uo and the parameter vector carry NaN slack (probe_prepare; xo, uo
+// here).  Buffers a good launch must write start as NaN, so that an element it drops shows.
+int HipBackend::probe_resident(const cgo_cg_config &cfg, const cgo_ls_config &ls, cgo_resident_probe &p, const double *x, const double *u,
+                               double *rows, int64_t rows_cap, double *x_out, double *u_out) {
+    static_assert(sizeof(ResProbePass) == sizeof(cgo_resident_pass) && sizeof(ResProbeOut) == sizeof(cgo_resident_pass_out), "C ABI twins");
+    static_assert(RES_MAXP == 7 && RES_WMAX == 56, "include/cgo.h states them");
+    p.grid = 0; p.points = 0; p.chunk = 0; p.round0 = 0; p.err_word = 0; p.wrote_back = 0; p.symbol[0] = 0;
+    if (!resident_ready(cfg, ls)) { set_error("probe: this solver's engine would not run the resident solver (objective, β, line search, size or policy)"); return CGO_EINVAL; }
+    if (obj_->uses_param() && !obj_->p0_set) { set_error("objective parameter vector (slot 0) was never set"); return CGO_ESTATE; }
+    if (p.npass < 1 || p.npass > CGO_RESIDENT_PROBE_MAX_PASSES) { set_error("probe: 1 … 32 passes"); return CGO_EINVAL; }
+    const int npts = res_npts_, nt = npts < 3 ? npts : 3;
+    for (int q = 0; q < p.npass; ++q) {
+        const cgo_resident_pass &c = p.pass[q];
+        const bool ok = c.kind == 0 ? (c.k >= 1 && c.k <= nt) : (c.kind == 1 && c.k >= 0 && c.k <= npts);
+        if (!ok) { set_error("probe: pass " + std::to_string(q) + " is not one the resident loop of this width issues"); return CGO_EINVAL; }
+    }
+    if (rows_cap < (int64_t)p.npass * res_grid_ * RES_WMAX) { set_error("probe: rows_cap smaller than npass · grid · 56"); return CGO_EINVAL; }
+    if (int rc = probe_prepare()) return rc;
+    if (int rc = res_alloc()) return rc;
+    HIPCHK(hipSetDevice(ctx_->device));
+    hipStream_t st = ctx_->stream;
+    const size_t n = (size_t)obj_->n_local, nb = n * sizeof(double);
+    const bool oop = res_grid_ > 1;
+    const size_t rows_n = (size_t)CGO_RESIDENT_PROBE_MAX_PASSES * res_grid_ * RES_WMAX;
+    if (!res_pr_ready_) {
+        if (oop) {   // the out-of-place partners: whole lines + one line of NaN, as probe_prepare gives x and u
+            const size_t np = probe_padded(n);
+            if (int rc = res_xo_.alloc(np)) return rc;
+            if (int rc = res_uo_.alloc(np)) return rc;
+            HIPCHK(hipMemsetD32Async((hipDeviceptr_t)res_xo_.p, (int)PROBE_NAN32, np * 2, st));
+            HIPCHK(hipMemsetD32Async((hipDeviceptr_t)res_uo_.p, (int)PROBE_NAN32, np * 2, st));
+        }
+        HIPCHK(hipMalloc(&res_pr_script_, sizeof(ResProbePass) * CGO_RESIDENT_PROBE_MAX_PASSES));
+        HIPCHK(hipMalloc(&res_pr_out_, sizeof(ResProbeOut) * CGO_RESIDENT_PROBE_MAX_PASSES));
+        HIPCHK(hipMalloc((void **)&res_pr_rows_, sizeof(double) * rows_n));
+        HIPCHK(hipStreamSynchronize(st));
+        res_xin_ = nullptr; res_uin_ = nullptr;
+        res_pr_ready_ = true;
+    }
+    // the script, padded as res_iterate / ResEval pad it: the spare points repeat the last real step
+    ResProbePass script[CGO_RESIDENT_PROBE_MAX_PASSES] = {};
+    for (int q = 0; q < p.npass; ++q) {
+        const cgo_resident_pass &c = p.pass[q];
+        script[q].kind = c.kind; script[q].k = c.k; script[q].a_acc = c.a_acc; script[q].beta = c.beta;
+        double lastp = 0.0;
+        for (int j = 0; j < RES_MAXP; ++j) { if (j < c.k) lastp = c.a[j]; script[q].a[j] = lastp; }
+    }
+    double *xo, *uo;
+    res_out_buffers(xo, uo);
+    HIPCHK(hipMemcpyAsync(res_pr_script_, script, sizeof script, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)res_pr_rows_, (int)PROBE_NAN32, rows_n * 2, st));
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)res_pr_out_, (int)PROBE_NAN32, sizeof(ResProbeOut) * CGO_RESIDENT_PROBE_MAX_PASSES / 4, st));
+    HIPCHK(hipMemcpyAsync(xc_, x, nb, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(uc_, u, nb, hipMemcpyHostToDevice, st));
+    if (oop) {
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)xo, (int)PROBE_NAN32, n * 2, st));
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)uo, (int)PROBE_NAN32, n * 2, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    ResParams P{};
+    res_fill_params(P, xo, uo);
+    P.cfg.ls = ls; P.cfg.eps = cfg.eps; P.cfg.npts = res_npts_;
+    P.budget = 0;
+    P.log = nullptr; P.log_cap = 0;
+    P.timing = 0;
+    P.pr_script = (const ResProbePass *)res_pr_script_; P.pr_n = p.npass; P.pr_rows = res_pr_rows_; P.pr_out = (ResProbeOut *)res_pr_out_;
+    const void *fn = res_probe_kernel_for(obj_->kind, res_npts_);
+    hipFunction_t mf = nullptr;
+    if (!fn && obj_->kind == CGO_OBJ_USER && obj_->rtc && obj_->rtc->resident(res_npts_)) {   // compiled on the first probe, not with the objective
+        std::string log;
+        if (int rc = rtc_compile_resident_probe(*obj_->rtc, log)) { set_error("probe: " + log); return rc; }
+        mf = obj_->rtc->resident_probe(res_npts_);
+    }
+    if (!fn && !mf) { set_error("probe: no PROBE instantiation of this solver's resident kernel"); return CGO_EINVAL; }
+    // the plan was made for the product instantiation: this one has the same static LDS and no more registers, checked here
+    int per_cu = 0;
+    if (fn) {
+        if (res_lds_ > 48 * 1024) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)res_lds_));
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, BLOCK, res_lds_));
+    } else {
+        HIPCHK(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mf, BLOCK, res_lds_));
+    }
+    const int cus = std::min(ctx_->num_cu > 0 ? ctx_->num_cu : 256, RES_GSIZE * RES_GROUPS);
+    if (per_cu < 1 || res_grid_ > cus * per_cu) { set_error("probe: the PROBE instantiation does not fit the engine's plan"); return CGO_ESTATE; }
+    p.grid = res_grid_; p.points = res_npts_; p.chunk = res_chunk_; p.round0 = (int64_t)res_round_;
+    {
+        const char *on = obj_->kind == CGO_OBJ_QUAD_DIAG ? "ObjQuadDiag" : obj_->kind == CGO_OBJ_ROSENBROCK_PAIRED ? "ObjRosenPaired"
+                         : obj_->kind == CGO_OBJ_BOOTH ? "ObjBooth" : "UserObjective";
+        if (chain()) snprintf(p.symbol, sizeof p.symbol, "k_resident_chain<%d, true>", res_npts_);
+        else snprintf(p.symbol, sizeof p.symbol, "k_resident<%s, %d, true>", on, res_npts_);
+    }
+    void *args[] = {&P};
+    if (fn) HIPCHK(hipLaunchKernel(fn, dim3(res_grid_), dim3(BLOCK), args, res_lds_, st));
+    else HIPCHK(hipModuleLaunchKernel(mf, res_grid_, 1, 1, BLOCK, 1, 1, (unsigned)res_lds_, st, args, nullptr));
+    total_launches_++;
+    if (int rc = wait_word(ctx_, res_done_, res_seq_)) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    const ResState s = *res_state_;
+    if (s.reason == RES_ERROR) {   // as resident_run: buffers and counters back to their start; here the caller is told, nothing is retried
+        unsigned int e[2] = {0, 0};
+        HIPCHK(hipMemcpy(e, res_err_, sizeof e, hipMemcpyDeviceToHost));
+        p.err_word = e[0];
+        if (int rc = res_error_reset()) return rc;
+        set_error("probe: a workgroup of the resident launch gave up waiting for a row (error word " + std::to_string(e[0]) + ", " +
+                  std::to_string(e[1]) + " of " + std::to_string(res_grid_ - 1) + " workgroups reported in)");
+        return CGO_ESTATE;
+    }
+    res_round_ += (unsigned long long)s.passes;
+    res_slices_++;
+    if (oop && s.done > 0) res_swap_in(xo, uo);
+    p.wrote_back = s.done > 0 ? 1 : 0;
+    if (s.passes != p.npass) { set_error("probe: the launch ran " + std::to_string((long long)s.passes) + " of " + std::to_string(p.npass) + " passes"); return CGO_ESTATE; }
+    HIPCHK(hipMemcpyAsync(rows, res_pr_rows_, sizeof(double) * (size_t)p.npass * res_grid_ * RES_WMAX, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(p.out, res_pr_out_, sizeof(ResProbeOut) * p.npass, hipMemcpyDeviceToHost, st));
+    if (x_out) HIPCHK(hipMemcpyAsync(x_out, xc_, nb, hipMemcpyDeviceToHost, st));
+    if (u_out) HIPCHK(hipMemcpyAsync(u_out, uc_, nb, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (int rc = probe_slack_intact()) return rc;
+    if (oop) {
+        const DevBuf *bs[2] = {&res_xo_, &res_uo_};
+        std::vector<unsigned> h;
+        for (int b = 0; b < 2; ++b) {
+            const size_t words = (bs[b]->n - n) * 2;
+            h.assign(words, 0u);
+            HIPCHK(hipMemcpy(h.data(), bs[b]->p + n, words * 4, hipMemcpyDeviceToHost));
+            for (size_t w = 0; w < words; ++w)
+                if (h[w] != PROBE_NAN32) {
+                    set_error(std::string("probe: the launch wrote past the ") + std::to_string(n) + " elements of the out-of-place " + (b ? "u" : "x") +
+                              " (element " + std::to_string(n + w / 2) + ")");
+                    return CGO_ESTATE;
+                }
+        }
+    }
     return CGO_OK;
 }
 

@@ -613,7 +613,7 @@ int cgo_solver_set_x0_fill(cgo_solver *s, int32_t kind, uint64_t seed, double lo
 int cgo_solver_start(cgo_solver *s) {
     API_GUARD_BEGIN
     REQUIRE(s, "null argument");
-    if (s->be->probed()) { set_error("a solver that a probe (cgo_solver_probe_launch / _lbfgs) has used is for probing only"); return CGO_ESTATE; }
+    if (s->be->probed()) { set_error("a solver that a probe (cgo_solver_probe_launch / _lbfgs / _resident) has used is for probing only"); return CGO_ESTATE; }
     return s->sv->start();
     API_GUARD_END
 }
@@ -621,7 +621,7 @@ int cgo_solver_start(cgo_solver *s) {
 int cgo_solver_iterate(cgo_solver *s, int64_t iters, int32_t *finished) {
     API_GUARD_BEGIN
     REQUIRE(s, "null argument");
-    if (s->be->probed()) { set_error("a solver that a probe (cgo_solver_probe_launch / _lbfgs) has used is for probing only"); return CGO_ESTATE; }
+    if (s->be->probed()) { set_error("a solver that a probe (cgo_solver_probe_launch / _lbfgs / _resident) has used is for probing only"); return CGO_ESTATE; }
     bool fin = false;
     int rc = s->sv->iterate(iters, fin);
     if (rc == CGO_ESTATE) set_error("cgo_solver_iterate before cgo_solver_start");
@@ -931,6 +931,14 @@ int cgo_solver_probe_lbfgs(cgo_solver *s, cgo_lbfgs_probe *p, const double *x, c
     const cgo_cg_config &c = s->sv->config();
     if (c.beta.kind != CGO_BETA_LBFGS) { set_error("probe: the solver's β is not LBFGS(m)"); return CGO_EINVAL; }
     return s->be->probe_lbfgs(c.beta.lbfgs_m, *p, x, u, g, gt, S, Y, x_out, xo_out, u_out, g_out, gt_out, S_out, Y_out);
+    API_GUARD_END
+}
+
+int cgo_solver_probe_resident(cgo_solver *s, cgo_resident_probe *p, const double *x, const double *u, double *rows,
+                              int64_t rows_cap, double *x_out, double *u_out) {
+    API_GUARD_BEGIN
+    REQUIRE(s && p && x && u && rows && rows_cap >= 0, "bad argument");
+    return s->be->probe_resident(s->sv->config(), s->sv->linesearch(), *p, x, u, rows, rows_cap, x_out, u_out);
     API_GUARD_END
 }
 

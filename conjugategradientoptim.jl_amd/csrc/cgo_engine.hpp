@@ -222,6 +222,7 @@ class Solver {
     void set_log_enabled(bool on) { log_on_ = on; }
     VecBackend *backend() { return be_; }
     const cgo_cg_config &config() const { return cfg_; }
+    const cgo_ls_config &linesearch() const { return ls_; }
 
   private:
     // evalϕdϕ! (cg_utils.jl:4-23).  h1/h2: the (at most two) steps the line search can ask for

@@ -615,6 +615,9 @@ HipBackend::~HipBackend() {
     if (res_recs_dev_) (void)hipFree(res_recs_dev_);
     if (res_log_dev_) (void)hipFree(res_log_dev_);
     if (res_err_) (void)hipFree(res_err_);
+    if (res_pr_script_) (void)hipFree(res_pr_script_);
+    if (res_pr_out_) (void)hipFree(res_pr_out_);
+    if (res_pr_rows_) (void)hipFree(res_pr_rows_);
     for (auto &r : ring_) { if (r.e0) (void)hipEventDestroy(r.e0); if (r.e1) (void)hipEventDestroy(r.e1); }
 }
 

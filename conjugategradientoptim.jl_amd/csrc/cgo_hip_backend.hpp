@@ -13,7 +13,7 @@
 
 namespace cgo {
 
-namespace dev { struct CtlArgs; struct Tail; struct LoopParams; }
+namespace dev { struct CtlArgs; struct Tail; struct LoopParams; struct ResParams; }
 
 void set_error(const std::string &msg);
 const char *get_error();
@@ -205,6 +205,11 @@ class HipBackend : public VecBackend {
                     const double *Y, double *x_out, double *xo_out, double *u_out, double *g_out, double *gt_out, double *S_out,
                     double *Y_out);
 
+    // Test entry point (cgo_solver_probe_resident): a script of resident passes in ONE launch of the PROBE instantiation of this
+    // solver's resident kernel, under the engine's own plan, exchange buffers, write-back rule and round bookkeeping.
+    int probe_resident(const cgo_cg_config &cfg, const cgo_ls_config &ls, cgo_resident_probe &p, const double *x, const double *u,
+                       double *rows, int64_t rows_cap, double *x_out, double *u_out);
+
     // raw single-launch helpers used by the kernel-level C entry points
     static int run_dir(HipCtx *ctx, double *u_host, const double *g_host, double beta, int64_t n,
                        double *out2);
@@ -311,6 +316,11 @@ class HipBackend : public VecBackend {
     size_t res_lds_ = 0;
     int res_plan();                          // grid, chunk, LDS bytes for this shard; 0 workgroups = does not fit
     int res_alloc();
+    // shared by resident_run and probe_resident (cgo_backend_cg.hip)
+    void res_out_buffers(double *&xo, double *&uo) const;
+    void res_fill_params(dev::ResParams &P, double *xo, double *uo);
+    void res_swap_in(double *xo, double *uo);
+    int res_error_reset();
     ResState *res_state_ = nullptr;          // pinned
     ResRecord *res_recs_ = nullptr;          // pinned [RES_REC_CAP]
     ResLog *res_log_ = nullptr;              // pinned [RES_LOG_CAP], allocated when a log is first asked for
@@ -322,6 +332,10 @@ class HipBackend : public VecBackend {
     double *res_xin_ = nullptr, *res_uin_ = nullptr;   // the pair those were swapped against (the next slice's output)
     unsigned long long *res_done_ = nullptr; // pinned
     unsigned long long res_seq_ = 0, res_round_ = 0;
+    // probe_resident: script, per-workgroup rows and member-function results on the device; xo / uo with NaN slack
+    void *res_pr_script_ = nullptr, *res_pr_out_ = nullptr;
+    double *res_pr_rows_ = nullptr;
+    bool res_pr_ready_ = false;
     int64_t res_iters_ = 0, res_slices_ = 0, res_gave_up_ = 0;
     bool prof_on_ = false;
     struct ProfSlot { hipEvent_t e0 = nullptr, e1 = nullptr; int kk = -1; double bytes = 0; };

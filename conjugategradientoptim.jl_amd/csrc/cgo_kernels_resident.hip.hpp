@@ -21,6 +21,10 @@
 //   * the polls are bounded: a workgroup that never sees a row gives up, raises the error word and ends; so do the others.
 //
 // One record per completed iteration (trace) and the trial log go straight to pinned host memory from workgroup 0.
+//
+// PROBE (template flag, default false; cgo_solver_probe_resident): the same kernel with a script of passes in place of
+// res_iterate, every workgroup storing the totals it holds after each pass — what tests/test_resident_kernel_sums.py
+// compares.  Everything else — the LDS load, the passes, the exchange, the global verdict, the write-back — is the code below.
 #pragma once
 
 #include "cgo_kernels_cg.hip.hpp"
@@ -37,6 +41,11 @@ constexpr int RES_GSIZE = 16;            // workgroups per group of the two-leve
 constexpr int RES_GROUPS = 16;           // groups at most (256 workgroups)
 constexpr int RES_WMAX = NR7;            // row stride of the exchange buffers (widest row)
 constexpr int RES_SPIN = 1 << 19;        // polls of one slot before giving up (≈ a second)
+
+// One pass of a probe's script: the arguments of ResDev::trial (kind 0) / ResDev::accept_dir_trial (kind 1), a[] padded by
+// the caller as res_iterate pads it (entries ≥ k repeat a[k − 1]).
+struct ResProbePass { int kind, k; double a[RES_MAXP]; double a_acc, beta; };
+struct ResProbeOut { TrialSums ts[RES_MAXP]; double gu, uu; long long width; };
 
 struct ResParams {
     double *x; double *u; const double *p0;   // this rank's shard in HBM
@@ -58,9 +67,13 @@ struct ResParams {
     unsigned int *err;                        // device: bumped when a poll gave up
     int timing;                               // CGO_RES_TIMING=1: read the clock around the phases of every pass
     unsigned long long *done_seq; unsigned long long seq;   // pinned: released by workgroup 0 once st_out / recs / log are complete
+    // the PROBE instantiations only (cgo_solver_probe_resident): a script of passes instead of res_iterate
+    const ResProbePass *pr_script; int pr_n;  // DEVICE [pr_n]
+    double *pr_rows;                          // DEVICE [pr_n][grid][RES_WMAX]: the totals EVERY workgroup holds after each pass
+    ResProbeOut *pr_out;                      // DEVICE [pr_n]: what the member functions returned in workgroup 0
 };
 
-template <class Obj, int NPTS>
+template <class Obj, int NPTS, bool PROBE = false>
 struct ResDev {
     const ResParams &P;
     double *xs, *us, *ps;      // LDS
@@ -69,6 +82,7 @@ struct ResDev {
     double *tot;               // LDS [RES_WMAX]
     double *fs;                // LDS [BLOCK]
     long long t_compute = 0, t_reduce = 0, t_exchange = 0;   // 100 MHz ticks (wall_clock64) spent in the three phases of a pass
+    int pr_pass = 0;           // PROBE: passes completed
 
     static constexpr int kNpts = NPTS;
     __device__ __forceinline__ bool leader() const { return blockIdx.x == 0 && threadIdx.x == 0; }
@@ -219,6 +233,11 @@ struct ResDev {
         if (int rc = exchange<W>(own)) return rc;
 #pragma unroll
         for (int s = 0; s < W; ++s) sums[s] = tot[s];
+        if constexpr (PROBE) {   // the totals THIS workgroup holds, all W slots
+            if (tid < W) P.pr_rows[((size_t)pr_pass * gridDim.x + blockIdx.x) * RES_WMAX + tid] = tot[tid];
+            if (leader()) P.pr_out[pr_pass].width = W;
+            ++pr_pass;
+        }
         __syncthreads();   // tot and fs are written again by the next pass
         t_compute += t1 - t0; t_reduce += t2 - t1; t_exchange += clock() - t2;
         return 0;
@@ -250,7 +269,31 @@ struct ResDev {
     }
 };
 
-template <class Obj, int NPTS>
+// cgo_solver_probe_resident: the script P.pr_script through the member functions res_iterate calls, in its place.  An accepting
+// pass counts as a completed iteration (s.done), so that the write-back below runs as after a slice that completed one.
+template <class V>
+__device__ __forceinline__ void res_probe_script(const ResParams &P, ResState &s, V &v) {
+    s.done = 0; s.log_len = 0; s.evals = 0; s.passes = 0; s.reason = RES_BUDGET;
+    s.t_machine = 0; s.t_eval = 0; s.t_post = 0;
+    for (int q = 0; q < P.pr_n; ++q) {
+        const ResProbePass c = P.pr_script[q];
+        TrialSums out[RES_MAXP] = {};
+        double gu = 0.0, uu = 0.0;
+        int rc;
+        if (c.kind == 0) rc = v.trial(c.a, c.k, out);
+        else rc = v.accept_dir_trial(c.a_acc, c.beta, c.a, c.k, out, gu, uu);
+        if (rc) { s.reason = RES_ERROR; break; }
+        s.passes++;
+        if (c.kind != 0) s.done++;
+        if (v.leader()) {
+            ResProbeOut &o = P.pr_out[q];
+            for (int j = 0; j < RES_MAXP; ++j) o.ts[j] = out[j];
+            o.gu = gu; o.uu = uu;
+        }
+    }
+}
+
+template <class Obj, int NPTS, bool PROBE = false>
 __global__ __launch_bounds__(BLOCK, 1) void k_resident(const ResParams P) {   // one wave per SIMD is all a CU ever holds of this kernel: up to 512 VGPRs
     extern __shared__ __attribute__((aligned(16))) double res_lds[];
     __shared__ double tot[RES_WMAX];
@@ -268,7 +311,7 @@ __global__ __launch_bounds__(BLOCK, 1) void k_resident(const ResParams P) {   //
         if (Obj::kParam) ps[i] = P.p0[lo + i];
     }
     __syncthreads();
-    ResDev<Obj, NPTS> v{P, xs, us, ps, (int)(cnt >> 1), (cnt & 1) != 0, P.round0, tot, fs, 0, 0, 0};
+    ResDev<Obj, NPTS, PROBE> v{P, xs, us, ps, (int)(cnt >> 1), (cnt & 1) != 0, P.round0, tot, fs, 0, 0, 0};
     // The loop state arrives as kernel arguments, i.e. in SGPRs, and the compiler would keep every value it can prove uniform
     // there: ≈ 160 + 30 scalar registers of state and configuration against 102 available — 300–900 SGPR spills, each reload a
     // v_readlane plus hazard wait states on the critical path of the scalar logic.  All of it is FP64 arithmetic anyway
@@ -285,7 +328,8 @@ __global__ __launch_bounds__(BLOCK, 1) void k_resident(const ResParams P) {   //
     RES_V(cfg.ls.discount_factor); RES_V(cfg.eps); RES_V(cfg.mu);
 #undef RES_V
     const long long t_begin = wall_clock64(), c_begin = clock64();
-    res_iterate(cfg, s, v, (int64_t)P.budget, P.recs, P.log, (int64_t)P.log_cap);
+    if constexpr (PROBE) res_probe_script(P, s, v);
+    else res_iterate(cfg, s, v, (int64_t)P.budget, P.recs, P.log, (int64_t)P.log_cap);
     s.t_cycles = clock64() - c_begin;
     s.t_total = wall_clock64() - t_begin; s.t_compute = v.t_compute; s.t_reduce = v.t_reduce; s.t_exchange = v.t_exchange;
     __syncthreads();
@@ -348,13 +392,14 @@ __global__ __launch_bounds__(BLOCK, 1) void k_resident(const ResParams P) {   //
 // LDS copies each, a pass reads one and writes the other (the launch-per-trial kernels do the same with two HBM buffers), the
 // barriers of the workgroup reduction separate a pass's reads from the next pass's writes.  Up to ≈ 4 800 elements (four
 // arrays in 160 KB); larger stencil problems keep their launches.  Same window arithmetic (chain_window), same row layout.
-template <int NPTS>
+template <int NPTS, bool PROBE = false>
 struct ResDevChain {
     const ResParams &P;
     double *xa, *ua, *xb, *ub;   // LDS: current (a) and other (b) copies of x and u, padded to even length
     int npairs, odd;             // pairs incl. the padded one; odd: the last element is padding
     double *tot;
     long long t_compute = 0, t_reduce = 0, t_exchange = 0;
+    int pr_pass = 0;             // PROBE: passes completed
     static constexpr int kNpts = NPTS;
     __device__ __forceinline__ bool leader() const { return threadIdx.x == 0; }
     __device__ __forceinline__ long long clock() const { return P.timing ? wall_clock64() : 0; }
@@ -397,6 +442,11 @@ struct ResDevChain {
         __syncthreads();
 #pragma unroll
         for (int s = 0; s < W; ++s) sums[s] = tot[s];
+        if constexpr (PROBE) {
+            if (tid < W) P.pr_rows[(size_t)pr_pass * RES_WMAX + tid] = tot[tid];
+            if (leader()) P.pr_out[pr_pass].width = W;
+            ++pr_pass;
+        }
         __syncthreads();
         if (wr_x) { double *t = xa; xa = xb; xb = t; }
         if (wr_u) { double *t = ua; ua = ub; ub = t; }
@@ -428,7 +478,7 @@ struct ResDevChain {
     }
 };
 
-template <int NPTS>
+template <int NPTS, bool PROBE = false>
 __global__ __launch_bounds__(BLOCK, 1) void k_resident_chain(const ResParams P) {
     static_assert(NPTS == 1 || NPTS == 3, "the stencil passes carry one or three trial points");
     extern __shared__ __attribute__((aligned(16))) double res_lds[];
@@ -443,7 +493,7 @@ __global__ __launch_bounds__(BLOCK, 1) void k_resident_chain(const ResParams P) 
         xb[i] = 0.0; ub[i] = 0.0;
     }
     __syncthreads();
-    ResDevChain<NPTS> v{P, xa, ua, xb, ub, (int)(npad >> 1), (int)(P.n & 1), tot, 0, 0, 0};
+    ResDevChain<NPTS, PROBE> v{P, xa, ua, xb, ub, (int)(npad >> 1), (int)(P.n & 1), tot, 0, 0, 0};
     ResState s = P.st;
     ResConfig cfg = P.cfg;
 #define RES_V(x) asm volatile("" : "+v"(x))
@@ -456,7 +506,8 @@ __global__ __launch_bounds__(BLOCK, 1) void k_resident_chain(const ResParams P) 
     RES_V(cfg.ls.discount_factor); RES_V(cfg.eps); RES_V(cfg.mu);
 #undef RES_V
     const long long t_begin = wall_clock64(), c_begin = clock64();
-    res_iterate(cfg, s, v, (int64_t)P.budget, P.recs, P.log, (int64_t)P.log_cap);
+    if constexpr (PROBE) res_probe_script(P, s, v);
+    else res_iterate(cfg, s, v, (int64_t)P.budget, P.recs, P.log, (int64_t)P.log_cap);
     s.t_cycles = clock64() - c_begin;
     s.t_total = wall_clock64() - t_begin; s.t_compute = v.t_compute; s.t_reduce = v.t_reduce; s.t_exchange = v.t_exchange;
     __syncthreads();

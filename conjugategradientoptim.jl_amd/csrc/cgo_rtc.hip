@@ -19,6 +19,7 @@ namespace cgo {
 
 RtcModule::~RtcModule() {
     if (mod) (void)hipModuleUnload(mod);
+    if (probe_mod) (void)hipModuleUnload(probe_mod);
 }
 
 static std::string key_cg(int mode, int npts, bool big) {
@@ -35,6 +36,10 @@ hipFunction_t RtcModule::resident(int npts) const {
     auto it = fn.find("res:" + std::to_string(npts));
     return it == fn.end() ? nullptr : it->second;
 }
+hipFunction_t RtcModule::resident_probe(int npts) const {
+    auto it = fn.find("resprobe:" + std::to_string(npts));
+    return it == fn.end() ? nullptr : it->second;
+}
 hipFunction_t RtcModule::spec(bool big, bool push) const {
     auto it = fn.find(std::string("spec:") + (big ? "1" : "0") + (push ? "1" : "0"));
     return it == fn.end() ? nullptr : it->second;
@@ -48,9 +53,8 @@ hipFunction_t RtcModule::fused(int mode, bool big) const {
     return it == fn.end() ? nullptr : it->second;
 }
 
-int rtc_compile_objective(int device, const std::string &source, bool has_param,
-                          std::shared_ptr<RtcModule> &out, std::string &log) {
-    if (hipSetDevice(device) != hipSuccess) { log = "hipSetDevice failed"; return CGO_EHIP; }
+// the embedded kernel templates + the user's objective as one translation unit
+static std::string rtc_program_source(const std::string &source, bool has_param) {
     std::string src;
     for (const char *c : kRtcKernelSourceChunks) src += c;
     src += "\nnamespace cgo { namespace dev {\n";
@@ -69,6 +73,13 @@ int rtc_compile_objective(int device, const std::string &source, bool has_param,
         src += "        gg.x = g0; gg.y = g1;\n    }\n};\n";
     }
     src += "\n}}\n";
+    return src;
+}
+
+int rtc_compile_objective(int device, const std::string &source, bool has_param,
+                          std::shared_ptr<RtcModule> &out, std::string &log) {
+    if (hipSetDevice(device) != hipSuccess) { log = "hipSetDevice failed"; return CGO_EHIP; }
+    const std::string src = rtc_program_source(source, has_param);
 
     hiprtcProgram prog;
     if (hiprtcCreateProgram(&prog, src.c_str(), "cgo_user_objective.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
@@ -142,7 +153,46 @@ int rtc_compile_objective(int device, const std::string &source, bool has_param,
         mod->fn[w.key] = f;
     }
     hiprtcDestroyProgram(&prog);
+    mod->user_source = source; mod->has_param = has_param; mod->device = device;
     out = mod;
+    return CGO_OK;
+}
+
+int rtc_compile_resident_probe(RtcModule &m, std::string &log) {
+    if (m.probe_mod) return CGO_OK;
+    if (hipSetDevice(m.device) != hipSuccess) { log = "hipSetDevice failed"; return CGO_EHIP; }
+    const std::string src = rtc_program_source(m.user_source, m.has_param);
+    hiprtcProgram prog;
+    if (hiprtcCreateProgram(&prog, src.c_str(), "cgo_user_objective_probe.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
+        log = "hiprtcCreateProgram failed";
+        return CGO_EHIP;
+    }
+    const char *expr = "cgo::dev::k_resident<cgo::dev::UserObjective, 3, true>";   // the PROBE form of "res:3"
+    hiprtcAddNameExpression(prog, expr);
+    const char *opts[] = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
+    const hiprtcResult cr = hiprtcCompileProgram(prog, 4, opts);
+    if (cr != HIPRTC_SUCCESS) {
+        size_t logsz = 0;
+        hiprtcGetProgramLogSize(prog, &logsz);
+        if (logsz > 1) { log.resize(logsz); hiprtcGetProgramLog(prog, &log[0]); } else log = hiprtcGetErrorString(cr);
+        hiprtcDestroyProgram(&prog);
+        return CGO_EINVAL;
+    }
+    size_t codesz = 0;
+    hiprtcGetCodeSize(prog, &codesz);
+    std::vector<char> code(codesz);
+    hiprtcGetCode(prog, code.data());
+    const char *lowered = nullptr;
+    hipFunction_t f = nullptr;
+    if (hipModuleLoadData(&m.probe_mod, code.data()) != hipSuccess || hiprtcGetLoweredName(prog, expr, &lowered) != HIPRTC_SUCCESS || !lowered ||
+        hipModuleGetFunction(&f, m.probe_mod, lowered) != hipSuccess) {
+        hiprtcDestroyProgram(&prog);
+        if (m.probe_mod) { (void)hipModuleUnload(m.probe_mod); m.probe_mod = nullptr; }
+        log = "the PROBE form of the user objective's resident kernel could not be loaded";
+        return CGO_EHIP;
+    }
+    hiprtcDestroyProgram(&prog);
+    m.fn["resprobe:3"] = f;
     return CGO_OK;
 }
 

@@ -17,6 +17,14 @@ struct RtcModule {
     hipFunction_t cg(int mode, int npts, bool big) const;
     hipFunction_t fused(int mode, bool big) const;
     hipFunction_t resident(int npts) const;   // k_resident<UserObjective, npts> (npts = 3 only), or nullptr
+    // k_resident<UserObjective, npts, true> (cgo_solver_probe_resident): NOT part of the module above — a second program,
+    // compiled from the kept source on the first probe (rtc_compile_resident_probe), so that creating an objective costs
+    // what it did before the probe existed
+    hipFunction_t resident_probe(int npts) const;
+    hipModule_t probe_mod = nullptr;
+    std::string user_source;
+    bool has_param = false;
+    int device = 0;
     hipFunction_t spec(bool big, bool push) const;   // k_lbfgs_combine_spec<UserObjective, big, push>
     hipFunction_t lite(bool big) const;              // k_lbfgs_push_lite<UserObjective, big>
 };
@@ -26,5 +34,7 @@ struct RtcModule {
 // `gi` from `x`, `p`, `s0`.  Returns CGO_OK / CGO_EINVAL (compile log in `log`) / CGO_EHIP.
 int rtc_compile_objective(int device, const std::string &source, bool has_param,
                           std::shared_ptr<RtcModule> &out, std::string &log);
+// the PROBE form of the module's resident kernel, compiled and loaded on first use; CGO_OK if it is there already
+int rtc_compile_resident_probe(RtcModule &m, std::string &log);
 
 }  // namespace cgo

@@ -476,8 +476,9 @@ int cgo_kernel_trial(cgo_objective *obj, const double *x, const double *u, doubl
  * (CGO_ESTATE otherwise): a probed solver is for probing only — cgo_solver_start / cgo_solver_iterate refuse it.  The
  * parameter vector is the OBJECTIVE's: its old buffer is freed, so the objective of a probed solver must not be shared with
  * another solver in use (one that has started, or keeps a captured graph or a resident slice on it).
- * CGO_EINVAL for every other kind (armed rounds, the resident solver; the L-BFGS passes: cgo_solver_probe_lbfgs) and for the
- * stored-gradient family. */
+ * CGO_EINVAL for every other kind (the L-BFGS passes: cgo_solver_probe_lbfgs; the resident solver: cgo_solver_probe_resident;
+ * armed rounds — the on-device controller's finisher — have no probe and remain outside) and for the stored-gradient
+ * family, which has no probe either. */
 int cgo_solver_probe_launch(cgo_solver *s, int32_t kernel_kind, int32_t variant, double a_acc, double beta,
                             const double *a, int32_t k,
                             const double *x, const double *u, const double *aux,
@@ -527,6 +528,48 @@ typedef struct cgo_lbfgs_probe {
 int cgo_solver_probe_lbfgs(cgo_solver *s, cgo_lbfgs_probe *p,
                            const double *x, const double *u, const double *g, const double *gt, const double *S, const double *Y,
                            double *x_out, double *xo_out, double *u_out, double *g_out, double *gt_out, double *S_out, double *Y_out);
+/* A scripted sequence of passes of the RESIDENT solver (k_resident / k_resident_chain) in ONE launch, on host vectors, for
+ * tests that check every slot of every pass in EVERY workgroup.  The launch is the engine's own: its plan (grid, chunk, LDS
+ * bytes, points per pass from SolverPolicy.resident_chunk / resident_points), its exchange buffers, the out-of-place write-back
+ * and its swap, and the exchange round carried from one launch to the next — two probes in a row continue the buffer rotation
+ * where the first stopped.  The kernel is the product kernel instantiated with its PROBE flag: in place of the scalar loop
+ * (res_iterate) it runs pass[0..npass) through the member functions that loop calls —
+ *   kind 0  trial(a, k, out)                               1 ≤ k ≤ min(points, 3)
+ *   kind 1  accept_dir_trial(a_acc, beta, a, k, out, gu, uu)   0 ≤ k ≤ points
+ * — with a[k..) repeating a[k − 1] as the loop pads them (done here, the caller fills a[0..k)).  An accepting pass counts as a
+ * completed iteration: x, u are written back and swapped in as after a good slice; a script of trials leaves them alone.
+ * Out: rows[pass][workgroup][56] = the totals every workgroup holds after that pass (out[pass].width slots, the padding
+ * slots of a row included; what lies behind the width is left as it was), rows_cap its capacity in doubles
+ * (≥ npass · grid · 56; npass · 256 · 56 always suffices); out[pass] what the member function returned in workgroup 0;
+ * grid, chunk, points, round0 (the exchange round the launch started at); x_out / u_out (may be NULL) what the next slice
+ * would read; symbol the instantiation.  As with cgo_solver_probe_launch the first probe gives x, u, their out-of-place
+ * partners and the parameter vector NaN slack, checked after every launch (CGO_ESTATE), and the solver is for probing only.
+ * CGO_EINVAL where the engine would not run the resident solver (objective, β, line search, size, policy) and for a pass it
+ * cannot issue.  If a workgroup's bounded poll gives up: CGO_ESTATE, err_word = the launch's error word — nothing is retried. */
+#define CGO_RESIDENT_PROBE_MAX_PASSES 32
+typedef struct cgo_resident_pass {
+    int32_t kind, k;
+    double a[7];
+    double a_acc, beta;
+} cgo_resident_pass;
+typedef struct cgo_resident_pass_out {
+    double ts[7][7];          /* per point: f, gtu, gtgt, gtg, yy, uy, ygt */
+    double gu, uu;
+    int64_t width;
+} cgo_resident_pass_out;
+typedef struct cgo_resident_probe {
+    int32_t npass, reserved;
+    cgo_resident_pass pass[CGO_RESIDENT_PROBE_MAX_PASSES];
+    /* out */
+    int32_t grid, points;
+    int64_t chunk, round0;
+    uint32_t err_word;
+    int32_t wrote_back;
+    cgo_resident_pass_out out[CGO_RESIDENT_PROBE_MAX_PASSES];
+    char symbol[128];
+} cgo_resident_probe;
+int cgo_solver_probe_resident(cgo_solver *s, cgo_resident_probe *p, const double *x, const double *u,
+                              double *rows, int64_t rows_cap, double *x_out, double *u_out);
 /* device-resident micro-benchmark of the fused kernels: allocates vectors of
  * n doubles on the ctx, runs `reps` launches of `kernel_kind`, returns the mean
  * HIP-event time per launch (ms) and the algorithmic bytes per launch */
