@@ -736,7 +736,15 @@ class Solver:
     def probe_launch(self, kind_name: str, variant: int, a_acc: float, beta: float, a: Sequence[float], x, u=None, aux=None):
         """ONE launch of kind `kind_name` with mode bits `variant` on this rank's host vectors (cgo_solver_probe_launch): returns
         dict(sums=the whole reduced row, x=, u=, g= the vectors after the launch, symbol=the instantiation).  A test entry point:
-        the solver is for probing only from the first call on."""
+        the solver is for probing only from the first call on.
+
+        A stored-gradient solver (β = LBFGS on an element-wise objective, a HostObjective, policy stored_gradient) takes M_* bits
+        and one trial step: init 16, trial 4 | 12, accept_dir_trial 15, accept_dir 3, accept_only 1, reset_dir 32, upg_norm 64
+        (0: the kind's usual mode); `aux` is the stored gradient g the launch reads, g= the buffer holding g⁺ afterwards.  With a
+        HostObjective init / trial / accept_dir_trial run k_trial_point, the closure and k_fused<…, 128> (init: then the reset
+        launch; accept_dir_trial: accept_dir first), sums= their rows one after the other.  scaled_norm: variant = which
+        (0 g, 1 g⁺, 3 u, 4 g⁺ − g; g⁺ is passed as `x` for 1 and 4), sums= the pass-0 row {max, #NaN, 0…} then, when it ran,
+        the pass-1 row {Σ (v/max)², 0…}.  symbol joins the launches with " + "."""
         L = _lib.lib()
         kk = [L.cgo_kernel_kind_name(k).decode() for k in range(L.cgo_num_kernel_kinds())].index(kind_name)
         n = self.obj.n_local

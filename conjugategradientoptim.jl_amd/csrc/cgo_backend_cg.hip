@@ -725,8 +725,8 @@ int HipBackend::probe_launch(int kk, int variant, double a_acc, double beta, con
                              double *u_out, double *g_out, std::string &symbol) {
     *sums_len = 0;
     const bool lse = obj_->two_phase();
-    if (!rmode_ && !lse) { set_error("probe: the solver runs neither the k_cg / k_chain family nor the log-sum-exp objective"); return CGO_EINVAL; }
     if (k < 0 || k > MAXP || (k > 0 && !a)) { set_error("probe: 0 ≤ k ≤ 7 trial steps"); return CGO_EINVAL; }
+    if (!rmode_ && !lse) return probe_launch_stored(kk, variant, a_acc, beta, a, k, x, u, aux, sums, sums_cap, sums_len, x_out, u_out, g_out, symbol);
     int mode = -1;
     if (lse) {
         if (kk == KK_LSE_STATS && (variant == 0 || variant == LM_NOU || variant == (LM_ACCEPT | LM_DIR))) mode = variant;
@@ -808,6 +808,101 @@ int HipBackend::probe_launch(int kk, int variant, double a_acc, double beta, con
     if (int rc2 = probe_slack_intact()) return rc2;
     *sums_len = probe_len_;
     if (probe_len_ > sums_cap) { set_error("probe: sums_cap smaller than the launch's row"); return CGO_EINVAL; }
+    if (probe_len_) std::memcpy(sums, probe_row_, sizeof(double) * probe_len_);
+    return CGO_OK;
+}
+
+// The same for a solver of the stored-gradient family (k_fused; the host-closure objective: k_trial_point, the closure, then
+// k_fused<…, M_BETAONLY>; scaled_norm: k_scaled_norm + k_finalize_maxsum).  The probe calls what the engine calls — trial,
+// accept_dir_trial, accept_dir, accept_only, reset_dir, upg_sumsq, host_trial, scaled_norm_parts, and launch itself for M_INIT —
+// so that grid, streaming path, finalize form, publication and the g / g⁺ swap of the accepting entry points are the solve's own;
+// launch, host_trial and scaled_norm_parts note every instantiation and append every fetched row while probe_stored_ is set.
+// `aux` is the vector the launch reads as g: it goes where the entry point's swap will have put g by the time it launches.
+// g⁺ for scaled_norm 1 / 4 travels in `x`, which no norm pass reads.  g_out is the buffer that holds g⁺ after the call.
+void HipBackend::probe_append(const double *row, int len) {
+    if (probe_len_ + len > (int)(sizeof probe_row_ / sizeof probe_row_[0])) return;
+    std::memcpy(probe_row_ + probe_len_, row, sizeof(double) * len);
+    probe_len_ += len;
+}
+
+int HipBackend::probe_launch_stored(int kk, int variant, double a_acc, double beta, const double *a, int k, const double *x,
+                                    const double *u, const double *aux, double *sums, int sums_cap, int *sums_len, double *x_out,
+                                    double *u_out, double *g_out, std::string &symbol) {
+    if (ctx_->world() != 1) { set_error("probe: a single-rank solver"); return CGO_EINVAL; }
+    const bool host = obj_->host_closure();
+    auto pick = [&](int dflt, std::initializer_list<int> ok) { const int m = variant ? variant : dflt; for (int o : ok) if (o == m) return m; return -1; };
+    int mode = -1;
+    switch (kk) {
+    case KK_INIT: mode = host ? pick(M_BETAONLY, {M_BETAONLY}) : pick(M_INIT, {M_INIT}); break;
+    case KK_TRIAL:
+        mode = host ? pick(M_BETAONLY, {M_BETAONLY}) : pick(need_beta_ ? (M_TRIAL | M_BETA) : M_TRIAL, {M_TRIAL, M_TRIAL | M_BETA});
+        break;
+    case KK_ACCEPT_DIR_TRIAL:
+        mode = host ? pick(M_ACCEPT | M_DIR, {M_ACCEPT | M_DIR}) : pick(M_ACCEPT | M_DIR | M_TRIAL | M_BETA, {M_ACCEPT | M_DIR | M_TRIAL | M_BETA});
+        break;
+    case KK_ACCEPT_DIR: mode = pick(M_ACCEPT | M_DIR, {M_ACCEPT | M_DIR}); break;
+    case KK_ACCEPT_ONLY: mode = pick(M_ACCEPT, {M_ACCEPT}); break;
+    case KK_RESET_DIR: mode = pick(M_RESET, {M_RESET}); break;
+    case KK_UPG_NORM: mode = pick(M_UPG, {M_UPG}); break;
+    case KK_SCALED_NORM: mode = (variant == 0 || variant == 1 || variant == 3 || variant == 4) ? variant : -1; break;
+    default: break;
+    }
+    const bool trial_step = kk == KK_TRIAL || kk == KK_ACCEPT_DIR_TRIAL;
+    if (mode >= 0 && trial_step && k != 1) mode = -1;   // one trial step per launch in this family
+    if (mode < 0) { set_error("probe: kernel kind / variant / trial steps not a launch this solver's engine issues"); return CGO_EINVAL; }
+    if (int rc = probe_prepare()) return rc;
+    HIPCHK(hipSetDevice(ctx_->device));
+    hipStream_t st = ctx_->stream;
+    const size_t n = (size_t)obj_->n_local, nb = n * sizeof(double);
+    auto put = [&](double *dst, const double *src) -> int {
+        if (src) HIPCHK(hipMemcpyAsync(dst, src, nb, hipMemcpyHostToDevice, st));
+        else HIPCHK(hipMemsetD32Async((hipDeviceptr_t)dst, (int)PROBE_NAN32, n * 2, st));
+        return CGO_OK;
+    };
+    const bool norm = kk == KK_SCALED_NORM;
+    const bool gt_in_x = norm && (mode == 1 || mode == 4);
+    const bool swaps = kk == KK_ACCEPT_DIR_TRIAL || kk == KK_ACCEPT_DIR || kk == KK_ACCEPT_ONLY;   // std::swap(g_, gt_) before the launch
+    if (int rc = put(xc_, gt_in_x ? nullptr : x)) return rc;
+    if (int rc = put(u_.p, u)) return rc;
+    if (int rc = put(swaps ? gt_ : g_, aux)) return rc;
+    if (int rc = put(swaps ? g_ : gt_, gt_in_x ? x : nullptr)) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    probe_len_ = 0;
+    probe_syms_.clear();
+    probe_stored_ = true;
+    int rc = CGO_OK;
+    Scal o[MAXP];
+    switch (kk) {
+    case KK_INIT: {
+        double s[NS];
+        rc = host ? host_trial(0.0, true, o[0]) : launch(KK_INIT, M_INIT, 0, 0, 0, true, s);
+        break;
+    }
+    case KK_TRIAL: {
+        const bool nb0 = need_beta_;
+        need_beta_ = mode == (M_TRIAL | M_BETA);
+        rc = trial(a, 1, o);
+        need_beta_ = nb0;
+        break;
+    }
+    case KK_ACCEPT_DIR_TRIAL: rc = accept_dir_trial(a_acc, beta, a, 1, o); break;
+    case KK_ACCEPT_DIR: rc = accept_dir(a_acc, beta, o[0]); break;
+    case KK_ACCEPT_ONLY: rc = accept_only(a_acc); break;
+    case KK_RESET_DIR: rc = reset_dir(o[0]); break;
+    case KK_UPG_NORM: { double uu; rc = upg_sumsq(uu); break; }
+    default: { double mx, ss; bool nan; rc = scaled_norm_parts(mode, 0.0, mx, ss, nan); break; }
+    }
+    probe_stored_ = false;
+    if (rc) return rc;
+    symbol = probe_syms_;
+    HIPCHK(hipStreamSynchronize(st));
+    if (x_out) HIPCHK(hipMemcpyAsync(x_out, xc_, nb, hipMemcpyDeviceToHost, st));
+    if (u_out) HIPCHK(hipMemcpyAsync(u_out, u_.p, nb, hipMemcpyDeviceToHost, st));
+    if (g_out) HIPCHK(hipMemcpyAsync(g_out, gt_, nb, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (int rc2 = probe_slack_intact()) return rc2;
+    *sums_len = probe_len_;
+    if (probe_len_ > sums_cap) { set_error("probe: sums_cap smaller than the launch's rows"); return CGO_EINVAL; }
     if (probe_len_) std::memcpy(sums, probe_row_, sizeof(double) * probe_len_);
     return CGO_OK;
 }

@@ -626,6 +626,7 @@ const char *HipBackend::obj_tname() const {
     case CGO_OBJ_LSE: return "ObjLse";
     case CGO_OBJ_QUAD_DIAG: return "ObjQuadDiag";
     case CGO_OBJ_ROSENBROCK_PAIRED: return "ObjRosenPaired";
+    case CGO_OBJ_BOOTH: return "ObjBooth";
     case CGO_OBJ_USER: return "UserObjective";
     default: return "";
     }

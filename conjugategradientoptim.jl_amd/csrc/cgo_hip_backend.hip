@@ -803,6 +803,12 @@ int HipBackend::launch(int kk, int mode, double a_acc, double beta, double a_tri
     if (fetch) {
         if (int rc = fetch_sums(ctx_, sums)) return rc;
     }
+    if (probe_stored_) {   // cgo_solver_probe_launch: the instantiation launch_fused dispatched, and the row
+        const bool objective_mode = (mode & (M_TRIAL | M_INIT)) != 0;
+        probe_note(nullptr, 0, "k_fused<%s, %d, %s>", objective_mode ? obj_tname() : "ObjQuadDiag", mode,
+                   is_big(obj_->kind, mode, obj_->n_local, obj_->uses_param(), pol_.hbm_stream_bytes) ? "true" : "false");
+        if (fetch) probe_append(sums, NS);
+    }
     if (prof_on_) prof_commit(kk, bytes_for(obj_->kind, mode, obj_->n_local, obj_->uses_param()));
     return CGO_OK;
 }
@@ -981,6 +987,7 @@ int HipBackend::host_trial(double a, bool init, Scal &out) {
     if (grid < 1) grid = 1;
     k_trial_point<<<grid, BLOCK, 0, st>>>(xc_, init ? nullptr : u_.p, a, obj_->host_x, n);
     HIPCHK(hipGetLastError());
+    if (probe_stored_) probe_note(nullptr, 0, "k_trial_point");
     HIPCHK(hipStreamSynchronize(st));
     const double f_local = obj_->host_fn(obj_->host_user, obj_->host_g, obj_->host_x, n);
     HIPCHK(hipMemcpyAsync(gt_, obj_->host_g, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
@@ -1049,6 +1056,7 @@ int HipBackend::scaled_norm_parts(int which, double a_trial, double &maxabs, dou
     HIPCHK(hipGetLastError());
     total_launches_++;
     if (int rc = fetch_sums(ctx_, s, MERGE_MAX0)) return rc;
+    if (probe_stored_) { probe_note(nullptr, 0, "k_scaled_norm<0>"); probe_append(s, NS); }
     maxabs = s[0]; has_nan = s[1] > 0.0; scaled_ss = 0.0;
     if (has_nan || maxabs == 0.0 || std::isinf(maxabs)) return CGO_OK;
     k_scaled_norm<1><<<grid, BLOCK, 0, st>>>(v, w, n, maxabs, ctx_->partials);
@@ -1059,6 +1067,7 @@ int HipBackend::scaled_norm_parts(int which, double a_trial, double &maxabs, dou
     HIPCHK(hipGetLastError());
     total_launches_++;
     if (int rc = fetch_sums(ctx_, s)) return rc;
+    if (probe_stored_) { probe_note(nullptr, 0, "k_scaled_norm<1>"); probe_append(s, NS); }
     scaled_ss = s[0];
     if (prof_on_) { prof_cnt_[KK_SCALED_NORM] += 2; prof_bytes_[KK_SCALED_NORM] = 8.0 * (double)n; }
     return CGO_OK;

@@ -199,6 +199,9 @@ class HipBackend : public VecBackend {
                      const double *u, const double *aux, double *sums, int sums_cap, int *sums_len, double *x_out,
                      double *u_out, double *g_out, std::string &symbol);
     bool probed() const { return probe_; }
+    int probe_launch_stored(int kernel_kind, int variant, double a_acc, double beta, const double *a, int k, const double *x,
+                            const double *u, const double *aux, double *sums, int sums_cap, int *sums_len, double *x_out,
+                            double *u_out, double *g_out, std::string &symbol);   // the stored-gradient family's half of it
     // Test entry point (cgo_solver_probe_lbfgs): ONE L-BFGS pass of this solver (β = LBFGS(m)) on host vectors and rings,
     // through the entry point the engine uses for it; the rings get NaN slack as well.
     int probe_lbfgs(int m, cgo_lbfgs_probe &p, const double *x, const double *u, const double *g, const double *gt, const double *S,
@@ -252,6 +255,10 @@ class HipBackend : public VecBackend {
     std::string probe_syms_;   // probe_lbfgs: every instantiation its pass launched (probe_note)
     void probe_note(const double *row, int len, const char *fmt, ...);
     int probe_ring_slack_intact();
+    // probe_launch on a stored-gradient solver: launch, host_trial and scaled_norm_parts note what they launch and append
+    // every row they fetch (several launches per probe: the host closure's init, scaled_norm's two passes)
+    bool probe_stored_ = false;
+    void probe_append(const double *row, int len);
     const char *obj_tname() const;
     int launch_loop(const dev::LoopParams &P, int kk, double nvec, bool big, int grid);
     double halo_xl_[2] = {0, 0}, halo_ul_[2] = {0, 0}, halo_xr_[2] = {0, 0}, halo_ur_[2] = {0, 0};

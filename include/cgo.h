@@ -477,8 +477,27 @@ int cgo_kernel_trial(cgo_objective *obj, const double *x, const double *u, doubl
  * parameter vector is the OBJECTIVE's: its old buffer is freed, so the objective of a probed solver must not be shared with
  * another solver in use (one that has started, or keeps a captured graph or a resident slice on it).
  * CGO_EINVAL for every other kind (the L-BFGS passes: cgo_solver_probe_lbfgs; the resident solver: cgo_solver_probe_resident;
- * armed rounds — the on-device controller's finisher — have no probe and remain outside) and for the stored-gradient
- * family, which has no probe either. */
+ * armed rounds — the on-device controller's finisher — have no probe and remain outside: they are what is left unprobed).
+ *
+ * A solver of the stored-gradient family (k_fused: β = LBFGS(m) on an element-wise objective, a host-closure objective,
+ * policy.stored_gradient) is probed through the same entry point, single rank only, one trial step (k = 1) where the kind
+ * takes one.  `variant` holds M_* bits (0: the kind's usual mode):
+ *   init: M_INIT 16   trial: M_TRIAL 4 | M_TRIAL|M_BETA 12   accept_dir_trial: 15   accept_dir: 3   accept_only: 1
+ *   reset_dir: M_RESET 32   upg_norm: M_UPG 64
+ *   scaled_norm: variant = which, 0 g | 1 g⁺ | 3 u | 4 g⁺ − g: k_scaled_norm<0>, then k_scaled_norm<1> unless the first pass
+ *             found a NaN, a zero vector or an infinity.  sums = the pass-0 row {max|v|, #NaN, 0 …} followed by the pass-1
+ *             row {Σ (v/max)², 0 …} when that pass ran: sums_len = 20 or 10.  For which = 1 and 4, g⁺ is passed in `x`
+ *             (no norm pass reads x, which reaches the device as NaN then).
+ *   host-closure objective: init and trial (variant 0 or M_BETAONLY 128) run k_trial_point → the closure → k_fused<…, 128>,
+ *             whose S_F slot carries the closure's f; init zeroes g and u first and is followed by the reset launch
+ *             (k_fused<…, 32>, u = −g), its row appended (sums_len = 20).  accept_dir_trial (variant 0 or 3) runs accept_dir,
+ *             then the trial: rows of k_fused<…, 3> and k_fused<…, 128>.
+ * aux is the vector the launch reads as the stored gradient g (the accepting kinds swap g and g⁺ before they launch: aux
+ * lands where that swap puts g).  g_out is the buffer that holds g⁺ after the call — what the launch wrote, what the
+ * closure returned, NaN where the mode writes no g⁺; after a host-closure init it is the zeroed former g, the closure's
+ * gradient having become g.  symbol joins the instantiations launched with " + ", e.g.
+ * "k_trial_point + k_fused<ObjQuadDiag, 128, false>" or "k_scaled_norm<0> + k_scaled_norm<1>" (the objective-free modes
+ * are instantiated for ObjQuadDiag only).  Multi-rank solvers are refused (CGO_EINVAL). */
 int cgo_solver_probe_launch(cgo_solver *s, int32_t kernel_kind, int32_t variant, double a_acc, double beta,
                             const double *a, int32_t k,
                             const double *x, const double *u, const double *aux,
