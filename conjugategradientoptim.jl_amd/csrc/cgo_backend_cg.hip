@@ -31,46 +31,31 @@ double bytes_r(int obj_kind, int mode, int64_t n, bool has_param) {
     return 8.0 * (double)n * (double)v;
 }
 
+// The point ladder, written once: f(Pts<N>) for the odd N ≤ MAXPTS a launch of `npts` points takes.  A count that is none of
+// them takes the largest where that is 7 (k_cg), 1 otherwise (k_chain: anything but 3).
+template <int N> using Pts = std::integral_constant<int, N>;
+template <int MAXPTS, class F>
+static inline void with_points(int npts, F f) {
+    static_assert(MAXPTS == 1 || MAXPTS == 3 || MAXPTS == 5 || MAXPTS == 7, "a launch evaluates 1, 3, 5 or 7 trial points");
+    if constexpr (MAXPTS >= 3) { if (npts == 3) return f(Pts<3>{}); }
+    if constexpr (MAXPTS >= 5) { if (npts == 5) return f(Pts<5>{}); }
+    if constexpr (MAXPTS >= 7) { if (npts != 1) return f(Pts<7>{}); }
+    return f(Pts<1>{});
+}
+
+// the rows of cgo_instances.def; -1: no such row
 template <class Obj, bool BIG>
 static int launch_cg(int mode, int npts, const RParams &P, int grid, hipStream_t st) {
+    // a whole controller round in this launch (never BIG: pipe_fused)
+#define ROW(MODE, MAXPTS) if (mode == (MODE) && P.tail.ctl) { with_points<MAXPTS>(npts, [&](auto n) { k_cg_armed<Obj, decltype(n)::value><<<grid, BLOCK, 0, st>>>(P); }); return 0; }
+    CGO_CG_ARMED_ROWS(ROW)
+#undef ROW
     switch (mode) {
-    case R_INIT: k_cg<Obj, R_INIT, 1, BIG><<<grid, BLOCK, 0, st>>>(P); break;
-    case R_TRIAL:
-        if (npts == 1) k_cg<Obj, R_TRIAL, 1, BIG><<<grid, BLOCK, 0, st>>>(P);
-        else if (npts == 3) k_cg<Obj, R_TRIAL, 3, BIG><<<grid, BLOCK, 0, st>>>(P);
-        else if (npts == 5) k_cg<Obj, R_TRIAL, 5, BIG><<<grid, BLOCK, 0, st>>>(P);
-        else k_cg<Obj, R_TRIAL, 7, BIG><<<grid, BLOCK, 0, st>>>(P);
-        break;
-    case R_ACCEPT | R_DIR | R_TRIAL:
-        if (P.tail.ctl) {   // a whole controller round in this launch (never BIG: pipe_fused)
-            if (npts == 1) k_cg_armed<Obj, 1><<<grid, BLOCK, 0, st>>>(P);
-            else if (npts == 3) k_cg_armed<Obj, 3><<<grid, BLOCK, 0, st>>>(P);
-            else if (npts == 5) k_cg_armed<Obj, 5><<<grid, BLOCK, 0, st>>>(P);
-            else k_cg_armed<Obj, 7><<<grid, BLOCK, 0, st>>>(P);
-            break;
-        }
-        if (npts == 1) k_cg<Obj, R_ACCEPT | R_DIR | R_TRIAL, 1, BIG><<<grid, BLOCK, 0, st>>>(P);
-        else if (npts == 3) k_cg<Obj, R_ACCEPT | R_DIR | R_TRIAL, 3, BIG><<<grid, BLOCK, 0, st>>>(P);
-        else if (npts == 5) k_cg<Obj, R_ACCEPT | R_DIR | R_TRIAL, 5, BIG><<<grid, BLOCK, 0, st>>>(P);
-        else k_cg<Obj, R_ACCEPT | R_DIR | R_TRIAL, 7, BIG><<<grid, BLOCK, 0, st>>>(P);
-        break;
-    case R_ACCEPT | R_DIR: k_cg<Obj, R_ACCEPT | R_DIR, 1, BIG><<<grid, BLOCK, 0, st>>>(P); break;
-    case R_ACCEPT: k_cg<Obj, R_ACCEPT, 1, BIG><<<grid, BLOCK, 0, st>>>(P); break;
-    case R_RESET: k_cg<Obj, R_RESET, 1, BIG><<<grid, BLOCK, 0, st>>>(P); break;
-    case R_UPG: k_cg<Obj, R_UPG, 1, BIG><<<grid, BLOCK, 0, st>>>(P); break;
-    case R_GRAD: k_cg<Obj, R_GRAD, 1, BIG><<<grid, BLOCK, 0, st>>>(P); break;
-    case R_GRADT: k_cg<Obj, R_GRADT, 1, BIG><<<grid, BLOCK, 0, st>>>(P); break;
-    case R_DIR: k_cg<Obj, R_DIR, 1, BIG><<<grid, BLOCK, 0, st>>>(P); break;
-    case R_DIR | R_TRIAL:
-        if (npts == 1) k_cg<Obj, R_DIR | R_TRIAL, 1, BIG><<<grid, BLOCK, 0, st>>>(P);
-        else if (npts == 3) k_cg<Obj, R_DIR | R_TRIAL, 3, BIG><<<grid, BLOCK, 0, st>>>(P);
-        else if (npts == 5) k_cg<Obj, R_DIR | R_TRIAL, 5, BIG><<<grid, BLOCK, 0, st>>>(P);
-        else k_cg<Obj, R_DIR | R_TRIAL, 7, BIG><<<grid, BLOCK, 0, st>>>(P);
-        break;
-    case R_PROJ: k_cg<Obj, R_PROJ, 1, BIG><<<grid, BLOCK, 0, st>>>(P); break;
+#define ROW(MODE, MAXPTS) case (MODE): with_points<MAXPTS>(npts, [&](auto n) { k_cg<Obj, (MODE), decltype(n)::value, BIG><<<grid, BLOCK, 0, st>>>(P); }); return 0;
+    CGO_CG_ROWS(ROW)
+#undef ROW
     default: return -1;
     }
-    return 0;
 }
 
 // Row width of a CG launch: 7 sums per trial point + 2 direction sums, padded (10 or 24).
@@ -194,9 +179,9 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
     if (int rc = prof_begin(kk)) return rc;
     int r = -2;
     switch (obj_->kind) {
-    case CGO_OBJ_QUAD_DIAG: r = big ? launch_cg<ObjQuadDiag, true>(mode, npts, P, grid, st) : launch_cg<ObjQuadDiag, false>(mode, npts, P, grid, st); break;
-    case CGO_OBJ_ROSENBROCK_PAIRED: r = big ? launch_cg<ObjRosenPaired, true>(mode, npts, P, grid, st) : launch_cg<ObjRosenPaired, false>(mode, npts, P, grid, st); break;
-    case CGO_OBJ_BOOTH: r = big ? launch_cg<ObjBooth, true>(mode, npts, P, grid, st) : launch_cg<ObjBooth, false>(mode, npts, P, grid, st); break;
+#define ROW(KIND, T) case KIND: r = big ? launch_cg<T, true>(mode, npts, P, grid, st) : launch_cg<T, false>(mode, npts, P, grid, st); break;
+    CGO_OBJ_ROWS(ROW)
+#undef ROW
     case CGO_OBJ_USER:
         if (!obj_->rtc) { set_error("user objective has no compiled module"); return CGO_EINVAL; }
         if (int rc = launch_module(obj_->rtc->cg(mode, npts, big), &P, grid, st)) return rc;
@@ -215,25 +200,11 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
 template <bool BIG>
 static int launch_chain(int mode, int npts, const ChainParams &P, int grid, hipStream_t st) {
     switch (mode) {
-    case R_INIT: k_chain<R_INIT, 1, BIG><<<grid, BLOCK, 0, st>>>(P); break;
-    case R_TRIAL:
-        if (npts == 3) k_chain<R_TRIAL, 3, BIG><<<grid, BLOCK, 0, st>>>(P);
-        else k_chain<R_TRIAL, 1, BIG><<<grid, BLOCK, 0, st>>>(P);
-        break;
-    case R_ACCEPT | R_DIR | R_TRIAL:
-        if (npts == 3) k_chain<R_ACCEPT | R_DIR | R_TRIAL, 3, BIG><<<grid, BLOCK, 0, st>>>(P);
-        else k_chain<R_ACCEPT | R_DIR | R_TRIAL, 1, BIG><<<grid, BLOCK, 0, st>>>(P);
-        break;
-    case R_ACCEPT | R_DIR: k_chain<R_ACCEPT | R_DIR, 1, BIG><<<grid, BLOCK, 0, st>>>(P); break;
-    case R_ACCEPT: k_chain<R_ACCEPT, 1, BIG><<<grid, BLOCK, 0, st>>>(P); break;
-    case R_RESET: k_chain<R_RESET, 1, BIG><<<grid, BLOCK, 0, st>>>(P); break;
-    case R_UPG: k_chain<R_UPG, 1, BIG><<<grid, BLOCK, 0, st>>>(P); break;
-    case R_GRAD: k_chain<R_GRAD, 1, BIG><<<grid, BLOCK, 0, st>>>(P); break;
-    case R_GRADT: k_chain<R_GRADT, 1, BIG><<<grid, BLOCK, 0, st>>>(P); break;
-    case R_EDGES: k_chain<R_EDGES, 1, BIG><<<grid, BLOCK, 0, st>>>(P); break;
+#define ROW(MODE, MAXPTS) case (MODE): with_points<MAXPTS>(npts, [&](auto n) { k_chain<(MODE), decltype(n)::value, BIG><<<grid, BLOCK, 0, st>>>(P); }); return 0;
+    CGO_CHAIN_ROWS(ROW)
+#undef ROW
     default: return -1;
     }
-    return 0;
 }
 
 int HipBackend::launch_chain_kernel(int mode, double a_acc, double beta, const double *a, int k, int npts, bool big, int grid, const Tail &tail) {
@@ -260,18 +231,15 @@ int HipBackend::launch_chain_kernel(int mode, double a_acc, double beta, const d
 
 // A k_cg / k_chain instantiation as rocprofv3 prints it minus namespaces.
 std::string HipBackend::r_symbol(int mode, int npts, bool big) const {
-    const char *on = obj_->kind == CGO_OBJ_QUAD_DIAG ? "ObjQuadDiag" : obj_->kind == CGO_OBJ_ROSENBROCK_PAIRED ? "ObjRosenPaired"
-                     : obj_->kind == CGO_OBJ_BOOTH ? "ObjBooth" : obj_->kind == CGO_OBJ_USER ? "UserObjective" : "";
     char buf[160];
     if (chain()) snprintf(buf, sizeof buf, "k_chain<%d, %d, %s>", mode, npts, big ? "true" : "false");
-    else snprintf(buf, sizeof buf, "k_cg<%s, %d, %d, %s>", on, mode, npts, big ? "true" : "false");
+    else snprintf(buf, sizeof buf, "k_cg<%s, %d, %d, %s>", obj_tname(), mode, npts, big ? "true" : "false");
     return buf;
 }
 
 // The instantiation a launch of kind `kk` uses under the current policy, as rocprofv3 prints it minus namespaces.
 std::string HipBackend::kernel_symbol(int kk) const {
-    const char *on = obj_->kind == CGO_OBJ_QUAD_DIAG ? "ObjQuadDiag" : obj_->kind == CGO_OBJ_ROSENBROCK_PAIRED ? "ObjRosenPaired"
-                     : obj_->kind == CGO_OBJ_BOOTH ? "ObjBooth" : obj_->kind == CGO_OBJ_USER ? "UserObjective" : "";
+    const char *on = obj_tname();
     const int64_t n = obj_->n_local;
     const bool hp = obj_->uses_param();
     char buf[160];
@@ -472,19 +440,13 @@ int HipBackend::pipe_round_kernels() {
     int nrows = grid;
     if (grid > TAIL_GROUP) {
         const int nb = (grid + TAIL_GROUP - 1) / TAIL_GROUP;
-        if (ns == NR) k_finalize_t<NR, BLOCK><<<nb, BLOCK, 0, st>>>(ctx_->partials, TAIL_GROUP, grid, ctx_->partials2, nullptr, nullptr, 0);
-        else if (ns == NR5) k_finalize_t<NR5, BLOCK><<<nb, BLOCK, 0, st>>>(ctx_->partials, TAIL_GROUP, grid, ctx_->partials2, nullptr, nullptr, 0);
-        else if (ns == NR7) k_finalize_t<NR7, BLOCK><<<nb, BLOCK, 0, st>>>(ctx_->partials, TAIL_GROUP, grid, ctx_->partials2, nullptr, nullptr, 0);
-        else k_finalize_t<NS, BLOCK><<<nb, BLOCK, 0, st>>>(ctx_->partials, TAIL_GROUP, grid, ctx_->partials2, nullptr, nullptr, 0);
+        with_width<NR, NR5, NR7, NS>(ns, true, [&](auto w) { k_finalize_t<decltype(w)::value, BLOCK><<<nb, BLOCK, 0, st>>>(ctx_->partials, TAIL_GROUP, grid, ctx_->partials2, nullptr, nullptr, 0); });
         HIPCHK(hipGetLastError());
         src = ctx_->partials2;
         nrows = nb;
     }
     CtlRecord *rec = (CtlRecord *)ctl_rec_;
-    if (ns == NR) k_finalize_ctl<NR, 768><<<1, 768, 0, st>>>(src, nrows, ctx_->out_dev, d, rec, ctl_seq_);
-    else if (ns == NR5) k_finalize_ctl<NR5, 768><<<1, 768, 0, st>>>(src, nrows, ctx_->out_dev, d, rec, ctl_seq_);
-    else if (ns == NR7) k_finalize_ctl<NR7, 768><<<1, 768, 0, st>>>(src, nrows, ctx_->out_dev, d, rec, ctl_seq_);
-    else k_finalize_ctl<NS, BLOCK><<<1, BLOCK, 0, st>>>(src, nrows, ctx_->out_dev, d, rec, ctl_seq_);
+    with_width<NR, NR5, NR7, NS>(ns, true, [&](auto w) { constexpr int N = decltype(w)::value, T = N == NS ? BLOCK : 768; k_finalize_ctl<N, T><<<1, T, 0, st>>>(src, nrows, ctx_->out_dev, d, rec, ctl_seq_); });
     HIPCHK(hipGetLastError());
     return CGO_OK;
 }
@@ -916,31 +878,29 @@ int HipBackend::probe_launch_stored(int kk, int variant, double a_acc, double be
 constexpr int64_t RES_REC_CAP = 4096;     // iterations per slice at most
 constexpr int64_t RES_LOG_CAP = 1 << 16;  // trial-log entries per slice
 
-template <class Obj>
+// The rows of cgo_instances.def, PROBE = the twins cgo_solver_probe_resident launches (the script in place of res_iterate):
+// the last row with NPTS ≤ npts, the first row below that.
+template <class Obj, bool PROBE>
 static const void *res_kernel(int npts) {
-    return npts >= 7 ? (const void *)k_resident<Obj, 7> : (npts >= 3 ? (const void *)k_resident<Obj, 3> : (const void *)k_resident<Obj, 1>);
+    const void *fn = nullptr;
+#define ROW(NPTS) if (!fn || npts >= NPTS) fn = (const void *)k_resident<Obj, NPTS, PROBE>;
+    CGO_RESIDENT_ROWS(ROW)
+#undef ROW
+    return fn;
 }
+template <bool PROBE>
 static const void *res_kernel_for(int obj_kind, int npts) {
     switch (obj_kind) {
-    case CGO_OBJ_ROSENBROCK_CHAINED: return npts >= 3 ? (const void *)k_resident_chain<3> : (const void *)k_resident_chain<1>;   // ONE workgroup
-    case CGO_OBJ_QUAD_DIAG: return res_kernel<ObjQuadDiag>(npts);
-    case CGO_OBJ_ROSENBROCK_PAIRED: return res_kernel<ObjRosenPaired>(npts);
-    case CGO_OBJ_BOOTH: return res_kernel<ObjBooth>(npts);
-    default: return nullptr;
+    case CGO_OBJ_ROSENBROCK_CHAINED: {   // ONE workgroup
+        const void *fn = nullptr;
+#define ROW(NPTS) if (!fn || npts >= NPTS) fn = (const void *)k_resident_chain<NPTS, PROBE>;
+        CGO_RESIDENT_CHAIN_ROWS(ROW)
+#undef ROW
+        return fn;
     }
-}
-
-// the PROBE instantiations (cgo_solver_probe_resident): same dispatch, the script in place of res_iterate
-template <class Obj>
-static const void *res_probe_kernel(int npts) {
-    return npts >= 7 ? (const void *)k_resident<Obj, 7, true> : (npts >= 3 ? (const void *)k_resident<Obj, 3, true> : (const void *)k_resident<Obj, 1, true>);
-}
-static const void *res_probe_kernel_for(int obj_kind, int npts) {
-    switch (obj_kind) {
-    case CGO_OBJ_ROSENBROCK_CHAINED: return npts >= 3 ? (const void *)k_resident_chain<3, true> : (const void *)k_resident_chain<1, true>;
-    case CGO_OBJ_QUAD_DIAG: return res_probe_kernel<ObjQuadDiag>(npts);
-    case CGO_OBJ_ROSENBROCK_PAIRED: return res_probe_kernel<ObjRosenPaired>(npts);
-    case CGO_OBJ_BOOTH: return res_probe_kernel<ObjBooth>(npts);
+#define ROW(KIND, T) case KIND: return res_kernel<T, PROBE>(npts);
+    CGO_OBJ_ROWS(ROW)
+#undef ROW
     default: return nullptr;
     }
 }
@@ -951,7 +911,7 @@ int HipBackend::res_plan() {
     const int64_t want = pol_.resident_chunk >= 2 ? (int64_t)(pol_.resident_chunk & ~1) : (int64_t)4096;
     const int pts = (pol_.resident_points == 1 || pol_.resident_points == 3 || pol_.resident_points == 7) ? pol_.resident_points : 3;
     res_npts_ = pts;
-    const void *fn = res_kernel_for(obj_->kind, res_npts_);
+    const void *fn = res_kernel_for<false>(obj_->kind, res_npts_);
     // a run-time compiled objective carries its own copy of the kernel (k_resident<UserObjective, 3>, cgo_rtc.hip)
     hipFunction_t mf = (obj_->kind == CGO_OBJ_USER && obj_->rtc) ? obj_->rtc->resident(res_npts_) : nullptr;
     if (!fn && !mf) return 0;
@@ -1081,7 +1041,7 @@ int HipBackend::resident_run(const ResConfig &c, ResState &s, int64_t budget, st
     P.log = res_log_dev_; P.log_cap = c.log_on ? RES_LOG_CAP : 0;
     static const bool timing = getenv("CGO_RES_TIMING") != nullptr;
     P.timing = timing ? 1 : 0;
-    const void *fn = res_kernel_for(obj_->kind, res_npts_);
+    const void *fn = res_kernel_for<false>(obj_->kind, res_npts_);
     void *args[] = {&P};
     const double h0 = timing ? now_ns() : 0.0;
     if (int rc = prof_begin(KK_RESIDENT)) return rc;
@@ -1197,7 +1157,7 @@ int HipBackend::probe_resident(const cgo_cg_config &cfg, const cgo_ls_config &ls
     P.log = nullptr; P.log_cap = 0;
     P.timing = 0;
     P.pr_script = (const ResProbePass *)res_pr_script_; P.pr_n = p.npass; P.pr_rows = res_pr_rows_; P.pr_out = (ResProbeOut *)res_pr_out_;
-    const void *fn = res_probe_kernel_for(obj_->kind, res_npts_);
+    const void *fn = res_kernel_for<true>(obj_->kind, res_npts_);
     hipFunction_t mf = nullptr;
     if (!fn && obj_->kind == CGO_OBJ_USER && obj_->rtc && obj_->rtc->resident(res_npts_)) {   // compiled on the first probe, not with the objective
         std::string log;
@@ -1216,12 +1176,8 @@ int HipBackend::probe_resident(const cgo_cg_config &cfg, const cgo_ls_config &ls
     const int cus = std::min(ctx_->num_cu > 0 ? ctx_->num_cu : 256, RES_GSIZE * RES_GROUPS);
     if (per_cu < 1 || res_grid_ > cus * per_cu) { set_error("probe: the PROBE instantiation does not fit the engine's plan"); return CGO_ESTATE; }
     p.grid = res_grid_; p.points = res_npts_; p.chunk = res_chunk_; p.round0 = (int64_t)res_round_;
-    {
-        const char *on = obj_->kind == CGO_OBJ_QUAD_DIAG ? "ObjQuadDiag" : obj_->kind == CGO_OBJ_ROSENBROCK_PAIRED ? "ObjRosenPaired"
-                         : obj_->kind == CGO_OBJ_BOOTH ? "ObjBooth" : "UserObjective";
-        if (chain()) snprintf(p.symbol, sizeof p.symbol, "k_resident_chain<%d, true>", res_npts_);
-        else snprintf(p.symbol, sizeof p.symbol, "k_resident<%s, %d, true>", on, res_npts_);
-    }
+    if (chain()) snprintf(p.symbol, sizeof p.symbol, "k_resident_chain<%d, true>", res_npts_);
+    else snprintf(p.symbol, sizeof p.symbol, "k_resident<%s, %d, true>", obj_tname(), res_npts_);
     void *args[] = {&P};
     if (fn) HIPCHK(hipLaunchKernel(fn, dim3(res_grid_), dim3(BLOCK), args, res_lds_, st));
     else HIPCHK(hipModuleLaunchKernel(mf, res_grid_, 1, 1, BLOCK, 1, 1, (unsigned)res_lds_, st, args, nullptr));

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "cgo_hip_backend.hpp"
+#include "cgo_instances.def"
 
 #include <algorithm>
 #include <cstdarg>
@@ -14,6 +15,7 @@
 #include <cstring>
 #include <ctime>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace cgo {
@@ -37,6 +39,16 @@ static inline double now_ns() {
 // as a double a quiet NaN.  Buffers are padded to whole 128-B lines plus one more line.
 constexpr unsigned PROBE_NAN32 = 0x7FF87FF8u;
 static inline size_t probe_padded(size_t n) { return ((n + 15) & ~(size_t)15) + 16; }
+
+// Row-width dispatch of the reduction launches: f(Width<N>) for the N of the list that equals `ns`; with `or_last`, the last N of
+// the list for every other width.  false: none (each site lists the widths its kernels are instantiated for).
+template <int N> using Width = std::integral_constant<int, N>;
+template <int N, int... Rest, class F>
+static inline bool with_width(int ns, bool or_last, F f) {
+    if (ns == N || (or_last && sizeof...(Rest) == 0)) { f(Width<N>{}); return true; }
+    if constexpr (sizeof...(Rest) > 0) return with_width<Rest...>(ns, or_last, f);
+    else return false;
+}
 
 // streaming policy and grids (cgo_hip_backend.hip)
 double big_bytes_for(double forced, bool read_only = false);

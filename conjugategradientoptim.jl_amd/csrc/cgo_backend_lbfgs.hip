@@ -624,9 +624,9 @@ int HipBackend::lbfgs_direction(const int *slots, const double *rho, int count, 
 const char *HipBackend::obj_tname() const {
     switch (obj_->kind) {
     case CGO_OBJ_LSE: return "ObjLse";
-    case CGO_OBJ_QUAD_DIAG: return "ObjQuadDiag";
-    case CGO_OBJ_ROSENBROCK_PAIRED: return "ObjRosenPaired";
-    case CGO_OBJ_BOOTH: return "ObjBooth";
+#define ROW(KIND, T) case KIND: return #T;
+    CGO_OBJ_ROWS(ROW)
+#undef ROW
     case CGO_OBJ_USER: return "UserObjective";
     default: return "";
     }

@@ -203,34 +203,29 @@ double bytes_for(int obj_kind, int mode, int64_t n, bool has_param) {
     return 8.0 * (double)n * (double)v;
 }
 
+// the rows of cgo_instances.def; -1: no such mode, -2: no such objective
 template <class Obj, bool BIG>
 static int launch_obj(int mode, const KParams &P, int grid, hipStream_t st) {
     switch (mode) {
-    case M_INIT: k_fused<Obj, M_INIT, BIG><<<grid, BLOCK, 0, st>>>(P); break;
-    case M_TRIAL | M_BETA: k_fused<Obj, M_TRIAL | M_BETA, BIG><<<grid, BLOCK, 0, st>>>(P); break;
-    case M_TRIAL: k_fused<Obj, M_TRIAL, BIG><<<grid, BLOCK, 0, st>>>(P); break;
-    case M_ACCEPT | M_DIR | M_TRIAL | M_BETA:
-        k_fused<Obj, M_ACCEPT | M_DIR | M_TRIAL | M_BETA, BIG><<<grid, BLOCK, 0, st>>>(P); break;
+#define ROW(MODE) case (MODE): k_fused<Obj, (MODE), BIG><<<grid, BLOCK, 0, st>>>(P); return 0;
+    CGO_FUSED_OBJ_ROWS(ROW)
+#undef ROW
     default: return -1;
     }
-    return 0;
 }
 
 template <bool BIG>
 static int launch_any(int obj_kind, int mode, const KParams &P, int grid, hipStream_t st) {
     switch (mode) {  // objective-free modes
-    case M_ACCEPT | M_DIR: k_fused<ObjQuadDiag, M_ACCEPT | M_DIR, BIG><<<grid, BLOCK, 0, st>>>(P); return 0;
-    case M_ACCEPT: k_fused<ObjQuadDiag, M_ACCEPT, BIG><<<grid, BLOCK, 0, st>>>(P); return 0;
-    case M_DIR: k_fused<ObjQuadDiag, M_DIR, BIG><<<grid, BLOCK, 0, st>>>(P); return 0;
-    case M_RESET: k_fused<ObjQuadDiag, M_RESET, BIG><<<grid, BLOCK, 0, st>>>(P); return 0;
-    case M_UPG: k_fused<ObjQuadDiag, M_UPG, BIG><<<grid, BLOCK, 0, st>>>(P); return 0;
-    case M_BETAONLY: k_fused<ObjQuadDiag, M_BETAONLY, BIG><<<grid, BLOCK, 0, st>>>(P); return 0;
+#define ROW(MODE) case (MODE): k_fused<ObjQuadDiag, (MODE), BIG><<<grid, BLOCK, 0, st>>>(P); return 0;
+    CGO_FUSED_FREE_ROWS(ROW)
+#undef ROW
     default: break;
     }
     switch (obj_kind) {
-    case CGO_OBJ_QUAD_DIAG: return launch_obj<ObjQuadDiag, BIG>(mode, P, grid, st);
-    case CGO_OBJ_ROSENBROCK_PAIRED: return launch_obj<ObjRosenPaired, BIG>(mode, P, grid, st);
-    case CGO_OBJ_BOOTH: return launch_obj<ObjBooth, BIG>(mode, P, grid, st);
+#define ROW(KIND, T) case KIND: return launch_obj<T, BIG>(mode, P, grid, st);
+    CGO_OBJ_ROWS(ROW)
+#undef ROW
     default: return -2;
     }
 }
@@ -516,13 +511,8 @@ int finalize_rows(HipCtx *ctx, int rows, int ns, bool canon) {
         t.host_out = hp; t.host_seq = hs; t.seq = ctx->seq; t.strict = ctx->tail_strict ? 1 : 0;
         ctx->pub_checked = (hp != nullptr) && !ctx->tail_strict;
         const int nb = (rows + TAIL_GROUP - 1) / TAIL_GROUP;
-        if (ns == NG) k_finalize_one<NG><<<nb, BLOCK, 0, st>>>(ctx->partials, rows, t);
-        else if (ns == NR) k_finalize_one<NR><<<nb, BLOCK, 0, st>>>(ctx->partials, rows, t);
-        else if (ns == NR5) k_finalize_one<NR5><<<nb, BLOCK, 0, st>>>(ctx->partials, rows, t);
-        else if (ns == NR7) k_finalize_one<NR7><<<nb, BLOCK, 0, st>>>(ctx->partials, rows, t);
-        else if (ns == NRC3) k_finalize_one<NRC3><<<nb, BLOCK, 0, st>>>(ctx->partials, rows, t);
-        else if (ns == NS) k_finalize_one<NS><<<nb, BLOCK, 0, st>>>(ctx->partials, rows, t);
-        else { set_error("internal: no single-launch reduction for this row width"); return CGO_EINVAL; }
+        const bool ok = with_width<NG, NR, NR5, NR7, NRC3, NS>(ns, false, [&](auto w) { k_finalize_one<decltype(w)::value><<<nb, BLOCK, 0, st>>>(ctx->partials, rows, t); });
+        if (!ok) { set_error("internal: no single-launch reduction for this row width"); return CGO_EINVAL; }
         HIPCHK(hipGetLastError());
         return CGO_OK;
     }
@@ -532,33 +522,23 @@ int finalize_rows(HipCtx *ctx, int rows, int ns, bool canon) {
         if (rows > TAIL_GROUP * TAIL_GROUP) { set_error("internal: more partial rows than two levels of 64 reduce"); return CGO_EINVAL; }
         if (rows > TAIL_GROUP) {
             const int nb = (rows + TAIL_GROUP - 1) / TAIL_GROUP;
-            if (ns == NR) k_finalize_t<NR, BLOCK><<<nb, BLOCK, 0, st>>>(ctx->partials, TAIL_GROUP, rows, ctx->partials2, nullptr, nullptr, 0);
-            else if (ns == NR5) k_finalize_t<NR5, BLOCK><<<nb, BLOCK, 0, st>>>(ctx->partials, TAIL_GROUP, rows, ctx->partials2, nullptr, nullptr, 0);
-            else if (ns == NR7) k_finalize_t<NR7, BLOCK><<<nb, BLOCK, 0, st>>>(ctx->partials, TAIL_GROUP, rows, ctx->partials2, nullptr, nullptr, 0);
-            else if (ns == NRC3) k_finalize_t<NRC3, BLOCK><<<nb, BLOCK, 0, st>>>(ctx->partials, TAIL_GROUP, rows, ctx->partials2, nullptr, nullptr, 0);
-            else k_finalize_t<NS, BLOCK><<<nb, BLOCK, 0, st>>>(ctx->partials, TAIL_GROUP, rows, ctx->partials2, nullptr, nullptr, 0);
+            with_width<NR, NR5, NR7, NRC3, NS>(ns, true, [&](auto w) { k_finalize_t<decltype(w)::value, BLOCK><<<nb, BLOCK, 0, st>>>(ctx->partials, TAIL_GROUP, rows, ctx->partials2, nullptr, nullptr, 0); });
             HIPCHK(hipGetLastError());
             src = ctx->partials2;
             nrows = nb;
         }
-        if (ns == NR) k_finalize_t<NR, BLOCK><<<1, BLOCK, 0, st>>>(src, nrows, nrows, ctx->out_dev, hp, hs, ctx->seq);
-        else if (ns == NR5) k_finalize_t<NR5, BLOCK><<<1, BLOCK, 0, st>>>(src, nrows, nrows, ctx->out_dev, hp, hs, ctx->seq);
-        else if (ns == NR7) k_finalize_t<NR7, BLOCK><<<1, BLOCK, 0, st>>>(src, nrows, nrows, ctx->out_dev, hp, hs, ctx->seq);
-        else if (ns == NRC3) k_finalize_t<NRC3, BLOCK><<<1, BLOCK, 0, st>>>(src, nrows, nrows, ctx->out_dev, hp, hs, ctx->seq);
-        else k_finalize_t<NS, BLOCK><<<1, BLOCK, 0, st>>>(src, nrows, nrows, ctx->out_dev, hp, hs, ctx->seq);
+        with_width<NR, NR5, NR7, NRC3, NS>(ns, true, [&](auto w) { k_finalize_t<decltype(w)::value, BLOCK><<<1, BLOCK, 0, st>>>(src, nrows, nrows, ctx->out_dev, hp, hs, ctx->seq); });
         HIPCHK(hipGetLastError());
         return CGO_OK;
     }
     if (two_stage_rows(rows, ns)) {
         const int nb = (rows + 63) / 64;
-        if (ns == NG) k_finalize_t<NG, 768><<<nb, 768, 0, st>>>(ctx->partials, 64, rows, ctx->partials2, nullptr, nullptr, 0);
-        else k_finalize_t<NS, BLOCK><<<nb, BLOCK, 0, st>>>(ctx->partials, 64, rows, ctx->partials2, nullptr, nullptr, 0);
+        with_width<NG, NS>(ns, true, [&](auto w) { constexpr int N = decltype(w)::value, T = N == NG ? 768 : BLOCK; k_finalize_t<N, T><<<nb, T, 0, st>>>(ctx->partials, 64, rows, ctx->partials2, nullptr, nullptr, 0); });
         HIPCHK(hipGetLastError());
         src = ctx->partials2;
         nrows = nb;
     }
-    if (ns == NG) k_finalize_t<NG, 768><<<1, 768, 0, st>>>(src, nrows, nrows, ctx->out_dev, hp, hs, ctx->seq);
-    else k_finalize_t<NS, BLOCK><<<1, BLOCK, 0, st>>>(src, nrows, nrows, ctx->out_dev, hp, hs, ctx->seq);
+    with_width<NG, NS>(ns, true, [&](auto w) { constexpr int N = decltype(w)::value, T = N == NG ? 768 : BLOCK; k_finalize_t<N, T><<<1, T, 0, st>>>(src, nrows, nrows, ctx->out_dev, hp, hs, ctx->seq); });
     HIPCHK(hipGetLastError());
     return CGO_OK;
 }

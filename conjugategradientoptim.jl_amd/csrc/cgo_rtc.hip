@@ -13,9 +13,13 @@
 #include <vector>
 
 #include "cgo_hip_backend.hpp"
+#include "cgo_instances.def"
+#include "cgo_kernels_cg.hip.hpp"   // the mode bits the rows of cgo_instances.def are written in
 #include "cgo_rtc_sources.inc"
 
 namespace cgo {
+
+using namespace dev;
 
 RtcModule::~RtcModule() {
     if (mod) (void)hipModuleUnload(mod);
@@ -76,52 +80,19 @@ static std::string rtc_program_source(const std::string &source, bool has_param)
     return src;
 }
 
-int rtc_compile_objective(int device, const std::string &source, bool has_param,
-                          std::shared_ptr<RtcModule> &out, std::string &log) {
-    if (hipSetDevice(device) != hipSuccess) { log = "hipSetDevice failed"; return CGO_EHIP; }
-    const std::string src = rtc_program_source(source, has_param);
-
+// One program → one loaded module: compiles `src` for the name expressions of `wants`, loads the code object as `mod` and
+// files every kernel in `fn` under its key.  On failure `mod` is unloaded again and `fn` is as it was.
+struct Want { std::string key, expr; };
+static int rtc_build(const std::string &src, const char *name, const std::vector<Want> &wants, hipModule_t &mod,
+                     std::map<std::string, hipFunction_t> &fn, std::string &log) {
     hiprtcProgram prog;
-    if (hiprtcCreateProgram(&prog, src.c_str(), "cgo_user_objective.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
-        log = "hiprtcCreateProgram failed";
-        return CGO_EHIP;
-    }
-    struct Want { std::string key, expr; };
-    std::vector<Want> wants;
-    const int cg_modes[] = {8, 4, 7, 3, 1, 16, 32, 64, 128, 2, 6, 256};  // RMode combinations the backend launches
-    for (int big = 0; big < 2; ++big) {
-        for (int m : cg_modes) {
-            const int np_max = (m == 4 || m == 7 || m == 6) ? 4 : 1;
-            for (int q = 0; q < np_max; ++q) {
-                const int npts = 1 + 2 * q;
-                wants.push_back({key_cg(m, npts, big),
-                                 "cgo::dev::k_cg<cgo::dev::UserObjective, " + std::to_string(m) + ", " +
-                                     std::to_string(npts) + ", " + (big ? "true" : "false") + ">"});
-            }
-        }
-        for (int m : {16, 12, 4, 15})  // k_fused: INIT, TRIAL|BETA, TRIAL, ACCEPT|DIR|TRIAL|BETA
-            wants.push_back({key_fused(m, big), "cgo::dev::k_fused<cgo::dev::UserObjective, " + std::to_string(m) + ", " +
-                                                    (big ? "true" : "false") + ">"});
-    }
-    // L-BFGS in one pass over the ring per outer iteration (k_lbfgs_combine_spec, k_lbfgs_push_lite) for this objective
-    for (int big = 0; big < 2; ++big) {
-        for (int push = 0; push < 2; ++push)
-            wants.push_back({std::string("spec:") + (big ? "1" : "0") + (push ? "1" : "0"),
-                             std::string("cgo::dev::k_lbfgs_combine_spec<cgo::dev::UserObjective, ") + (big ? "true" : "false") + ", " + (push ? "true" : "false") + ">"});
-        wants.push_back({std::string("lite:") + (big ? "1" : "0"),
-                         std::string("cgo::dev::k_lbfgs_push_lite<cgo::dev::UserObjective, ") + (big ? "true" : "false") + ">"});
-    }
-    // the resident solver for this objective (cgo_kernels_resident.hip.hpp): whole outer iterations in one launch
-    wants.push_back({"res:3", "cgo::dev::k_resident<cgo::dev::UserObjective, 3>"});
+    if (hiprtcCreateProgram(&prog, src.c_str(), name, 0, nullptr, nullptr) != HIPRTC_SUCCESS) { log = "hiprtcCreateProgram failed"; return CGO_EHIP; }
     for (auto &w : wants) hiprtcAddNameExpression(prog, w.expr.c_str());
     const char *opts[] = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
     const hiprtcResult cr = hiprtcCompileProgram(prog, 4, opts);
     size_t logsz = 0;
     hiprtcGetProgramLogSize(prog, &logsz);
-    if (logsz > 1) {
-        log.resize(logsz);
-        hiprtcGetProgramLog(prog, &log[0]);
-    }
+    if (logsz > 1) { log.resize(logsz); hiprtcGetProgramLog(prog, &log[0]); }
     if (cr != HIPRTC_SUCCESS) {
         hiprtcDestroyProgram(&prog);
         if (log.empty()) log = hiprtcGetErrorString(cr);
@@ -131,28 +102,58 @@ int rtc_compile_objective(int device, const std::string &source, bool has_param,
     hiprtcGetCodeSize(prog, &codesz);
     std::vector<char> code(codesz);
     hiprtcGetCode(prog, code.data());
-    auto mod = std::make_shared<RtcModule>();
-    if (hipModuleLoadData(&mod->mod, code.data()) != hipSuccess) {
-        hiprtcDestroyProgram(&prog);
-        log = "hipModuleLoadData failed for the compiled user objective";
-        return CGO_EHIP;
-    }
-    for (auto &w : wants) {
+    std::string err;
+    std::vector<hipFunction_t> fs(wants.size(), nullptr);
+    if (hipModuleLoadData(&mod, code.data()) != hipSuccess) { mod = nullptr; err = "hipModuleLoadData failed for the compiled user objective"; }
+    for (size_t i = 0; err.empty() && i < wants.size(); ++i) {
         const char *lowered = nullptr;
-        if (hiprtcGetLoweredName(prog, w.expr.c_str(), &lowered) != HIPRTC_SUCCESS || !lowered) {
-            hiprtcDestroyProgram(&prog);
-            log = "no lowered name for " + w.expr;
-            return CGO_EHIP;
-        }
-        hipFunction_t f = nullptr;
-        if (hipModuleGetFunction(&f, mod->mod, lowered) != hipSuccess) {
-            hiprtcDestroyProgram(&prog);
-            log = std::string("kernel not found in module: ") + lowered;
-            return CGO_EHIP;
-        }
-        mod->fn[w.key] = f;
+        if (hiprtcGetLoweredName(prog, wants[i].expr.c_str(), &lowered) != HIPRTC_SUCCESS || !lowered) err = "no lowered name for " + wants[i].expr;
+        else if (hipModuleGetFunction(&fs[i], mod, lowered) != hipSuccess) err = std::string("kernel not found in module: ") + lowered;
     }
     hiprtcDestroyProgram(&prog);
+    if (!err.empty()) {
+        if (mod) { (void)hipModuleUnload(mod); mod = nullptr; }
+        log = err;
+        return CGO_EHIP;
+    }
+    for (size_t i = 0; i < wants.size(); ++i) fn[wants[i].key] = fs[i];
+    return CGO_OK;
+}
+
+int rtc_compile_objective(int device, const std::string &source, bool has_param,
+                          std::shared_ptr<RtcModule> &out, std::string &log) {
+    if (hipSetDevice(device) != hipSuccess) { log = "hipSetDevice failed"; return CGO_EHIP; }
+    std::vector<Want> wants;
+    // every per-objective row of cgo_instances.def for UserObjective, in both streaming policies
+    const std::string uo = "<cgo::dev::UserObjective, ";
+    auto tf = [](int b) { return b ? "true" : "false"; };
+    for (int big = 0; big < 2; ++big) {
+#define ROW(MODE, MAXPTS) \
+        for (int npts = 1; npts <= MAXPTS; npts += 2) \
+            wants.push_back({key_cg((MODE), npts, big), "cgo::dev::k_cg" + uo + std::to_string((int)(MODE)) + ", " + std::to_string(npts) + ", " + tf(big) + ">"});
+        CGO_CG_ROWS(ROW)
+#undef ROW
+#define ROW(MODE) wants.push_back({key_fused((MODE), big), "cgo::dev::k_fused" + uo + std::to_string((int)(MODE)) + ", " + tf(big) + ">"});
+        CGO_FUSED_OBJ_ROWS(ROW)
+#undef ROW
+    }
+    // L-BFGS in one pass over the ring per outer iteration (k_lbfgs_combine_spec, k_lbfgs_push_lite) for this objective: every
+    // combination of the kernel's bool arguments, the first argument the first digit of the key
+#define ROW(KERNEL, KEY, NBOOLS) \
+    for (int bits = 0; bits < (1 << NBOOLS); ++bits) { \
+        Want w{KEY ":", "cgo::dev::" #KERNEL "<cgo::dev::UserObjective"}; \
+        for (int j = NBOOLS - 1; j >= 0; --j) { w.key += "01"[(bits >> j) & 1]; w.expr += std::string(", ") + tf((bits >> j) & 1); } \
+        w.expr += ">"; \
+        wants.push_back(w); \
+    }
+    CGO_RTC_LBFGS_ROWS(ROW)
+#undef ROW
+    // the resident solver for this objective (cgo_kernels_resident.hip.hpp): whole outer iterations in one launch
+#define ROW(NPTS) wants.push_back({"res:" #NPTS, "cgo::dev::k_resident" + uo + #NPTS ">"});
+    CGO_RTC_RESIDENT_ROWS(ROW)
+#undef ROW
+    auto mod = std::make_shared<RtcModule>();
+    if (int rc = rtc_build(rtc_program_source(source, has_param), "cgo_user_objective.hip", wants, mod->mod, mod->fn, log)) return rc;
     mod->user_source = source; mod->has_param = has_param; mod->device = device;
     out = mod;
     return CGO_OK;
@@ -161,39 +162,11 @@ int rtc_compile_objective(int device, const std::string &source, bool has_param,
 int rtc_compile_resident_probe(RtcModule &m, std::string &log) {
     if (m.probe_mod) return CGO_OK;
     if (hipSetDevice(m.device) != hipSuccess) { log = "hipSetDevice failed"; return CGO_EHIP; }
-    const std::string src = rtc_program_source(m.user_source, m.has_param);
-    hiprtcProgram prog;
-    if (hiprtcCreateProgram(&prog, src.c_str(), "cgo_user_objective_probe.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
-        log = "hiprtcCreateProgram failed";
-        return CGO_EHIP;
-    }
-    const char *expr = "cgo::dev::k_resident<cgo::dev::UserObjective, 3, true>";   // the PROBE form of "res:3"
-    hiprtcAddNameExpression(prog, expr);
-    const char *opts[] = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
-    const hiprtcResult cr = hiprtcCompileProgram(prog, 4, opts);
-    if (cr != HIPRTC_SUCCESS) {
-        size_t logsz = 0;
-        hiprtcGetProgramLogSize(prog, &logsz);
-        if (logsz > 1) { log.resize(logsz); hiprtcGetProgramLog(prog, &log[0]); } else log = hiprtcGetErrorString(cr);
-        hiprtcDestroyProgram(&prog);
-        return CGO_EINVAL;
-    }
-    size_t codesz = 0;
-    hiprtcGetCodeSize(prog, &codesz);
-    std::vector<char> code(codesz);
-    hiprtcGetCode(prog, code.data());
-    const char *lowered = nullptr;
-    hipFunction_t f = nullptr;
-    if (hipModuleLoadData(&m.probe_mod, code.data()) != hipSuccess || hiprtcGetLoweredName(prog, expr, &lowered) != HIPRTC_SUCCESS || !lowered ||
-        hipModuleGetFunction(&f, m.probe_mod, lowered) != hipSuccess) {
-        hiprtcDestroyProgram(&prog);
-        if (m.probe_mod) { (void)hipModuleUnload(m.probe_mod); m.probe_mod = nullptr; }
-        log = "the PROBE form of the user objective's resident kernel could not be loaded";
-        return CGO_EHIP;
-    }
-    hiprtcDestroyProgram(&prog);
-    m.fn["resprobe:3"] = f;
-    return CGO_OK;
+    std::vector<Want> wants;   // the PROBE form of the module's resident kernel
+#define ROW(NPTS) wants.push_back({"resprobe:" #NPTS, "cgo::dev::k_resident<cgo::dev::UserObjective, " #NPTS ", true>"});
+    CGO_RTC_RESIDENT_ROWS(ROW)
+#undef ROW
+    return rtc_build(rtc_program_source(m.user_source, m.has_param), "cgo_user_objective_probe.hip", wants, m.probe_mod, m.fn, log);
 }
 
 }  // namespace cgo

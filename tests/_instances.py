@@ -1,0 +1,34 @@
+"""What the library can launch: the rows of csrc/cgo_instances.def, the one table the launch switches, the run-time compiled
+module's name list and obj_tname() are expanded from.  One row per line, `FAMILY(field, field)`; nothing else is parsed."""
+import glob
+import os
+import re
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "conjugategradientoptim.jl_amd", "csrc")
+BITS = dict(R_ACCEPT=1, R_DIR=2, R_TRIAL=4, R_INIT=8, R_RESET=16, R_UPG=32, R_GRAD=64, R_GRADT=128, R_PROJ=256, R_EDGES=512,
+            M_ACCEPT=1, M_DIR=2, M_TRIAL=4, M_BETA=8, M_INIT=16, M_RESET=32, M_UPG=64, M_BETAONLY=128)
+
+
+def _value(field):
+    """a count or mode bits or-ed together as a number, anything else (a name, a key) as written"""
+    terms = [t.strip() for t in field.split("|")]
+    return sum(BITS.get(t) or int(t) for t in terms) if all(t in BITS or t.isdigit() for t in terms) else field.strip().strip('"')
+
+
+def rows(family):
+    """the fields of every row of `family` (CG, CHAIN, FUSED_OBJ, …), in file order"""
+    text = open(os.path.join(CSRC, "cgo_instances.def")).read()
+    return [tuple(_value(f) for f in m.group(1).split(",")) for m in re.finditer(r"^ +%s\((.*)\)(?: \\)?$" % family, text, re.M)]
+
+
+def mode_points(family):
+    """(mode, points) for the odd point counts up to each row's largest"""
+    return {(mode, p) for mode, top in rows(family) for p in range(1, top + 1, 2)}
+
+
+def stray_uses():
+    """Every line of csrc/*.hip that launches, or takes the address of, a kernel of the table's families anywhere but in a
+    `#define ROW(` expander of the table.  Strings (reported symbols, hiprtc names) and comments do not count."""
+    text = "\n".join(open(p).read() for p in sorted(glob.glob(os.path.join(CSRC, "*.hip")))).replace("\\\n", " ")
+    code = [re.sub(r'"(?:\\.|[^"\\])*"', '""', line).split("//")[0] for line in text.split("\n")]
+    return [c.strip() for c in code if re.search(r"\bk_(cg|cg_armed|chain|fused|resident|resident_chain)<", c) and not c.startswith("#define ROW(")]

@@ -14,7 +14,7 @@ vector a launch writes are compared with references that leave no room for toler
     summation over the launch's own summation depth;
 (c) the log-sum-exp launches against a 50-digit mpmath reference;
 (d) the instantiations the probes reached cover every k_cg / k_chain instantiation launch_cg / launch_chain can dispatch
-    (checked against the source by a CPU-tier test, so that a new variant cannot come without a test here).
+    (checked against the table they expand from by a CPU-tier test, so that a new variant cannot come without a test here).
 
 The data of (a) are periodic with a period of 1531 pairs (a prime: no chunk, wave or grid stride of a launch is a multiple of
 it), so that the expected rows of the large sizes come from one period and per-pair multiplicities; below one period the
@@ -22,14 +22,14 @@ vectors are not periodic at all.
 """
 import math
 import os
-import re
 from collections import defaultdict
 
 import numpy as np
 import pytest
 
+import _instances as I
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "conjugategradientoptim.jl_amd", "csrc")
 
 # launch geometry (csrc/cgo_kernels.hip.hpp, cgo_hip_backend.hip)
 BLOCK, GRID_BIG, TAIL_GROUP = 256, 4096, 64
@@ -1029,19 +1029,6 @@ def test_lse_stats_and_grad_against_mpmath(cgo, contexts, case, n):
 
 
 # ---- (d) coverage --------------------------------------------------------------------------------------------------------
-def _dispatch_table(fn):
-    """(mode expression, points) pairs of launch_cg / launch_chain, parsed from csrc/cgo_backend_cg.hip."""
-    src = open(os.path.join(CSRC, "cgo_backend_cg.hip")).read()
-    body = re.search(r"static int " + fn + r"\(.*?\n}\n", src, flags=re.S).group(0)
-    kern = "k_cg<Obj, " if fn == "launch_cg" else "k_chain<"
-    found = set()
-    for m in re.finditer(re.escape(kern) + r"([A-Z_ |]+), (\d), BIG>", body):
-        mode = sum({"R_ACCEPT": 1, "R_DIR": 2, "R_TRIAL": 4, "R_INIT": 8, "R_RESET": 16, "R_UPG": 32, "R_GRAD": 64,
-                    "R_GRADT": 128, "R_PROJ": 256, "R_EDGES": 512}[t.strip()] for t in m.group(1).split("|"))
-        found.add((mode, int(m.group(2))))
-    return found
-
-
 def expected_cg_instantiations():
     out = set()
     for kind, mode, k in launches("quad_diag"):
@@ -1054,10 +1041,19 @@ def expected_chain_instantiations():
 
 
 def test_dispatch_tables_have_tests():
-    """CPU tier: every instantiation launch_cg / launch_chain can dispatch is in this module's launch lists (a new variant
-    cannot be added without a test)."""
-    assert _dispatch_table("launch_cg") == expected_cg_instantiations()
-    assert _dispatch_table("launch_chain") == expected_chain_instantiations()
+    """CPU tier: every instantiation launch_cg / launch_chain can dispatch (the rows of csrc/cgo_instances.def they expand
+    from) is in this module's launch lists: a new variant cannot be added without a test.  The armed form exists for the
+    points of its mode's rows and for no other mode."""
+    assert I.mode_points("CG") == expected_cg_instantiations()
+    assert I.mode_points("CHAIN") == expected_chain_instantiations()
+    assert I.mode_points("CG_ARMED") == {(m, p) for m, p in I.mode_points("CG") if m == R_ACCEPT | R_DIR | R_TRIAL}
+
+
+def test_no_launch_outside_the_table():
+    """CPU tier: what makes the rows "everything the dispatcher can launch" — in csrc/*.hip no kernel of the table's families
+    (k_cg, k_cg_armed, k_chain, k_fused, k_resident, k_resident_chain) is launched or has its address taken anywhere but in
+    the macros that expand the table."""
+    assert I.stray_uses() == []
 
 
 @pytest.mark.gpu

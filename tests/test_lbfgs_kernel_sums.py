@@ -36,11 +36,11 @@ from collections import defaultdict
 import numpy as np
 import pytest
 
+import _instances as I
 from test_kernel_sums import (BLOCK, GRID_BIG, NAN_BITS, SIZES, A, M, S as SUB, _dy, _f, _lse_phi_check, big_chunk_pairs,
                               bits, busy_workgroups, exact_sum, lse_reference, two_prod)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "conjugategradientoptim.jl_amd", "csrc")
+CSRC = I.CSRC
 NS, NG, GRAM_MAXC, GRAM_MAXC_LSE, SPEC_MAXC, GRID_SMALL = 10, 64, 12, 11, 10, 1024
 S_GU, S_UU = 7, 8
 COUNTS = (0, 1, 3, 4, 5, 8, 9, 10, 11, 12)
@@ -980,13 +980,11 @@ def test_push_spec_gram_entries(cgo, n):
 
 # ---- (f) coverage --------------------------------------------------------------------------------------------------------
 def dispatched_lbfgs_kernels():
-    """k_lbfgs_* names launched in cgo_backend_lbfgs.hip and compiled at run time in cgo_rtc.hip"""
+    """k_lbfgs_* names launched in cgo_backend_lbfgs.hip and compiled at run time (rows of csrc/cgo_instances.def)"""
     src = open(os.path.join(CSRC, "cgo_backend_lbfgs.hip")).read()
     names = set(re.findall(r"\b(k_lbfgs_[a-z_]+)<", src))
-    rtc = open(os.path.join(CSRC, "cgo_rtc.hip")).read()
-    rtc_names = set(re.findall(r"cgo::dev::(k_lbfgs_[a-z_]+)<cgo::dev::UserObjective", rtc))
     objs = set(re.findall(r"launch_(?:spec|lite)<(Obj[A-Za-z]+)>", src))
-    return names, rtc_names, objs
+    return names, {kernel for kernel, key, nbools in I.rows("RTC_LBFGS")}, objs
 
 
 def expected_instantiations():

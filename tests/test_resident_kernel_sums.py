@@ -15,7 +15,7 @@ after every pass every workgroup stores the whole row of totals it holds:
     whole replicated-control-flow design rests on, which exact data cannot test; (ii) each slot within γ_d·Σ|t| of the
     correctly rounded exact sum, d from the resident summation tree; vectors bitwise equal to the plain IEEE model's — with
     several accepting passes in a row, mixed widths in one launch;
-(c) every dispatchable k_resident* instantiation (parsed from the sources on the CPU tier) was probed.
+(c) every dispatchable k_resident* instantiation (the rows of csrc/cgo_instances.def, on the CPU tier) was probed.
 """
 import os
 import re
@@ -24,12 +24,12 @@ from collections import defaultdict
 import numpy as np
 import pytest
 
+import _instances as I
 from test_kernel_sums import (rosen_valley_period, CHAIN_SCAL, CHAIN_STEPS, CHECK_EXACT, NAN_BITS, R_ACCEPT, R_DIR, R_TRIAL, RS, STEPS, Booth, Data,
                               Quad, Rosen, User, _chain_x, _make_objective, _slot_refs, bits, expected_cg, expected_chain,
                               float_cg, launch_inputs, random_data)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "conjugategradientoptim.jl_amd", "csrc")
+CSRC = I.CSRC
 ACC, ACC_T = R_ACCEPT | R_DIR, R_ACCEPT | R_DIR | R_TRIAL
 
 
@@ -787,34 +787,16 @@ def test_random_default_policy_all_workgroups_agree(cgo, ctx):
 
 
 # ---- (c) coverage ----------------------------------------------------------------------------------------------------------
-def dispatchable():
-    """every k_resident* instantiation the engine can launch, parsed from res_kernel / res_kernel_for and the run-time
-    compiled module's name list — and their PROBE twins, which must be the same set"""
-    be = open(os.path.join(CSRC, "cgo_backend_cg.hip")).read()
-    rtc = open(os.path.join(CSRC, "cgo_rtc.hip")).read()
-
-    def table(gen, disp, probe):
-        body = re.search(r"static const void \*" + gen + r"\(int npts\) \{(.*?)\n}", be, flags=re.S).group(1)
-        pts = sorted(int(m) for m in re.findall(r"k_resident<Obj, (\d)" + (", true" if probe else "") + ">", body))
-        body = re.search(r"static const void \*" + disp + r"\(int obj_kind, int npts\) \{(.*?)\n}", be, flags=re.S).group(1)
-        out = {f"k_resident_chain<{m}>" for m in re.findall(r"k_resident_chain<(\d)" + (", true" if probe else "") + ">", body)}
-        for on in re.findall(gen + r"<(\w+)>\(npts\)", body):
-            out |= {f"k_resident<{on}, {p}>" for p in pts}
-        return out
-    prod, prob = table("res_kernel", "res_kernel_for", False), table("res_probe_kernel", "res_probe_kernel_for", True)
-    prod |= {f"k_resident<UserObjective, {m}>" for m in re.findall(r'"cgo::dev::k_resident<cgo::dev::UserObjective, (\d)>"', rtc)}
-    prob |= {f"k_resident<UserObjective, {m}>" for m in re.findall(r'"cgo::dev::k_resident<cgo::dev::UserObjective, (\d), true>"', rtc)}
-    return prod, prob
-
-
 WANT = {f"k_resident<{on}, {p}>" for on in ("ObjQuadDiag", "ObjRosenPaired", "ObjBooth") for p in (1, 3, 7)} | \
     {"k_resident_chain<1>", "k_resident_chain<3>", "k_resident<UserObjective, 3>"}
 
 
 def test_dispatch_tables_have_tests():
-    """CPU tier: the dispatchable instantiations are the ones this module probes, and each has its PROBE twin."""
-    prod, prob = dispatchable()
-    assert prod == WANT and prob == WANT
+    """CPU tier: the dispatchable instantiations (the rows of csrc/cgo_instances.def) are the ones this module probes; each has
+    its PROBE twin: res_kernel / res_kernel_for and the run-time module expand both forms from the same row."""
+    can = {f"k_resident<{on}, {p}>" for kind, on in I.rows("OBJ") for p, in I.rows("RESIDENT")}
+    can |= {f"k_resident_chain<{p}>" for p, in I.rows("RESIDENT_CHAIN")} | {f"k_resident<UserObjective, {p}>" for p, in I.rows("RTC_RESIDENT")}
+    assert can == WANT
 
 
 @pytest.mark.gpu

@@ -24,7 +24,6 @@ A cell is (instantiation symbol, n, tail); it counts only when its whole row and
 """
 import math
 import os
-import re
 import subprocess
 import sys
 from collections import defaultdict
@@ -32,15 +31,15 @@ from collections import defaultdict
 import numpy as np
 import pytest
 
+import _instances as I
 import test_kernel_sums as K
 from test_kernel_sums import (BLOCK, GRID_BIG, NAN_BITS, SIZES, TAILS, A, M, S, Booth, Data, Quad, Rosen, User, _dy, _f,
                               big_chunk_pairs, bits, contexts, exact_period, exact_sum, two_prod)  # noqa: F401 (contexts: fixture)
 
-ROOT, CSRC = K.ROOT, K.CSRC
+ROOT = K.ROOT
 NS, GRID_SMALL = 10, 1024
 F, GTU, GTGT, GTG, YY, UY, YGT, GU, UU, GG = range(NS)
 M_ACCEPT, M_DIR, M_TRIAL, M_BETA, M_INIT, M_RESET, M_UPG, M_BETAONLY = 1, 2, 4, 8, 16, 32, 64, 128
-MBITS = dict(M_ACCEPT=1, M_DIR=2, M_TRIAL=4, M_BETA=8, M_INIT=16, M_RESET=32, M_UPG=64, M_BETAONLY=128)
 FINALIZE_2STAGE_BYTES = 131072                             # cgo_hip_backend.hip two_stage_rows: rows·ns·8 above this
 
 # what a solver's engine issues (kind, mode); M_DIR alone and M_BETAONLY come from the kernel-level entries / the host closure
@@ -794,24 +793,13 @@ def test_kernel_level_entries_exact_pure_hbm():
 
 
 # ---- (f) coverage --------------------------------------------------------------------------------------------------------------
-def _dispatch():
-    src = open(os.path.join(CSRC, "cgo_hip_backend.hip")).read()
-    rtc = open(os.path.join(CSRC, "cgo_rtc.hip")).read()
-    body = lambda fn: re.search(r"static int " + fn + r"\(.*?\n}\n", src, flags=re.S).group(0)
-    modes = lambda text, who: {sum(MBITS[t.strip()] for t in m.group(1).split("|"))
-                               for m in re.finditer(r"k_fused<" + who + r", ([A-Z_ |]+), BIG>", text)}
-    objs = set(re.findall(r"launch_obj<(\w+), BIG>", body("launch_any")))
-    m = re.search(r"for \(int m : \{([\d, ]+)\}\)\s*// k_fused", rtc)
-    return modes(body("launch_obj"), "Obj"), modes(body("launch_any"), "ObjQuadDiag"), objs, {int(t) for t in m.group(1).split(",")}
-
-
 def test_dispatch_tables_have_tests():
-    """CPU tier: every (objective, mode) launch_obj / launch_any and the run-time module's k_fused list can dispatch is in this
-    module's launch lists, so that a new instantiation cannot arrive untested."""
-    per_obj, free, objs, rtc = _dispatch()
-    assert per_obj == set(OBJ_MODES) == rtc
-    assert free == set(FREE_MODES)
-    assert objs == set(OBJ_NAMES.values()) - {"UserObjective"}
+    """CPU tier: every (objective, mode) launch_obj / launch_any can dispatch — the rows of csrc/cgo_instances.def, from which the
+    run-time module's k_fused list is built too — is in this module's launch lists, so that a new instantiation cannot arrive
+    untested."""
+    assert {m for m, in I.rows("FUSED_OBJ")} == set(OBJ_MODES)
+    assert {m for m, in I.rows("FUSED_FREE")} == set(FREE_MODES)
+    assert {functor for kind, functor in I.rows("OBJ")} == set(OBJ_NAMES.values()) - {"UserObjective"}
     engine = {mode for _, mode in LAUNCHES}
     assert set(OBJ_MODES) <= engine and set(FREE_MODES) - {M_DIR, M_BETAONLY} <= engine   # those two: (c), (e)
 
