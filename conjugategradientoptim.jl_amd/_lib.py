@@ -119,7 +119,10 @@ SIGNATURES = {
     "cgo_objective_create_from_source": (C.c_int, [_vp, C.c_char_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _pp]),
     "cgo_objective_create_callback": (C.c_int, [_vp, FDF_FN, _vp, C.c_int64, C.c_int64, C.c_int64, _pp]),
     "cgo_objective_destroy": (C.c_int, [_vp]),
+    "cgo_objective_create_from_source_ex": (C.c_int, [_vp, C.c_char_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _pp]),
+    "cgo_objective_num_params": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
     "cgo_objective_set_param_host": (C.c_int, [_vp, C.c_int32, dp]),
+    "cgo_objective_set_param_device": (C.c_int, [_vp, C.c_int32, _vp]),
     "cgo_objective_fill_param": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_uint64, C.c_double, C.c_double]),
     "cgo_objective_set_scalar": (C.c_int, [_vp, C.c_int32, C.c_double]),
     "cgo_objective_set_cost_class": (C.c_int, [_vp, C.c_int32]),

@@ -23,8 +23,9 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import re
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Union
 
 import numpy as np
 
@@ -454,7 +455,7 @@ class DeviceObjective:
     """Descriptor of an element-wise objective evaluated inside the fused kernels."""
 
     def __init__(self, kind: str, n_global: int, ctx: Optional[Context] = None, source: Optional[str] = None,
-                 has_param: bool = False):
+                 has_param: bool = False, n_params: Optional[int] = None):
         self.ctx = ctx or default_context()
         self.kind = kind
         self.n_global = int(n_global)
@@ -463,9 +464,14 @@ class DeviceObjective:
         self.offset, self.n_local = shard(self.n_global, self.ctx.rank, self.ctx.world)
         self._h = C.c_void_p()
         if source is not None:
-            check(_lib.lib().cgo_objective_create_from_source(
-                self.ctx._h, source.encode(), int(has_param), self.n_global, self.offset, self.n_local,
-                C.byref(self._h)))
+            if n_params is None:   # zero or one parameter vector
+                check(_lib.lib().cgo_objective_create_from_source(
+                    self.ctx._h, source.encode(), int(has_param), self.n_global, self.offset, self.n_local,
+                    C.byref(self._h)))
+            else:                  # up to MAX_PARAM_SLOTS of them
+                check(_lib.lib().cgo_objective_create_from_source_ex(
+                    self.ctx._h, source.encode(), int(n_params), self.n_global, self.offset, self.n_local,
+                    C.byref(self._h)))
             return
         check(_lib.lib().cgo_objective_create(self.ctx._h, OBJ_KINDS[kind], self.n_global,
                                               self.offset, self.n_local, C.byref(self._h)))
@@ -477,6 +483,20 @@ class DeviceObjective:
     def set_param(self, v_global: np.ndarray, slot: int = 0):
         loc = self.local(np.asarray(v_global, dtype=np.float64))
         check(_lib.lib().cgo_objective_set_param_host(self._h, slot, loc.ctypes.data_as(dp)))
+
+    def set_param_device(self, v, slot: int = 0):
+        """Parameter vector `slot` from THIS rank's shard already on the GPU: a contiguous float64 torch tensor of
+        n_local elements or a raw device pointer (int).  Device-to-device copy (cgo_objective_set_param_device)."""
+        if v is None:
+            raise TypeError("expected a torch.Tensor on the GPU or a raw device pointer")
+        check(_lib.lib().cgo_objective_set_param_device(self._h, slot, _dev_ptr(v, self.n_local)))
+
+    @property
+    def n_params(self) -> int:
+        """How many parameter vectors the objective's kernels read (cgo_objective_num_params)."""
+        k = C.c_int32()
+        check(_lib.lib().cgo_objective_num_params(self._h, C.byref(k)))
+        return k.value
 
     def fill_param(self, fill: str, seed: int, lo: float, hi: float, slot: int = 0):
         check(_lib.lib().cgo_objective_fill_param(self._h, slot, FILL_KINDS[fill], seed, lo, hi))
@@ -574,13 +594,40 @@ def LogSumExp(n: int, λ: float = 0.0, ctx: Optional[Context] = None) -> DeviceO
     return o
 
 
-def ElementwiseObjective(n: int, source: str, param: Optional[np.ndarray] = None,
+MAX_PARAM_SLOTS = 4   # CGO_MAX_PARAM_SLOTS
+
+
+def _param_list(param) -> Optional[list]:
+    """`param=` of ElementwiseObjective / primalbarriermethod → None (one array or none: the one-slot form) or the list of
+    slots of a sequence of arrays.  An entry that is None is a slot the caller sets later (fill_param, set_param_device)."""
+    if param is None or isinstance(param, np.ndarray):
+        return None
+    if isinstance(param, (list, tuple)) and (len(param) == 0 or any(p is None or np.ndim(p) >= 1 for p in param)):
+        return list(param)
+    return None
+
+
+def ElementwiseObjective(n: int, source: str, param=None,
                          ctx: Optional[Context] = None, cheap: bool = False) -> DeviceObjective:
     """A USER-SUPPLIED element-wise f/∇f — the GPU-side form of passing `minimizeobjective` your own
     `fdf!` closure.  `source` is HIP C++: the statements of an element-wise body setting `fi` and `gi`
     from `x`, `p`, `s0` (e.g. "gi = p*x; fi = 0.5*(gi*x);"), or a full `struct UserObjective {...}`
-    functor for pair-coupled objectives.  Compiled at run time (hiprtc) into the fused kernels."""
-    o = DeviceObjective("user", n, ctx, source=source, has_param=param is not None)
+    functor for pair-coupled objectives.  Compiled at run time (hiprtc) into the fused kernels.
+
+    `param` is one array (parameter slot 0, `p` in a body) or a sequence of up to 4 arrays: slots 0–3, `p`, `p1`, `p2`,
+    `p3` in a body; a struct then declares `static constexpr int kParams = K` and takes `const double (&p)[K]` /
+    `const d2 (&p)[K]` (include/cgo.h, cgo_objective_create_from_source_ex).  A None entry of the sequence reserves
+    its slot for fill_param / set_param_device."""
+    slots = _param_list(param)
+    if slots is not None:
+        assert len(slots) <= MAX_PARAM_SLOTS, f"at most {MAX_PARAM_SLOTS} parameter vectors"
+        o = DeviceObjective("user", n, ctx, source=source, n_params=len(slots))
+        for j, p in enumerate(slots):
+            if p is not None:
+                o.set_param(np.asarray(p, dtype=np.float64), slot=j)
+        param = None
+    else:
+        o = DeviceObjective("user", n, ctx, source=source, has_param=param is not None)
     if param is not None:
         o.set_param(np.asarray(param, dtype=np.float64))
     if cheap:   # ≲ 10 flops per element for f and ∇f: seven speculative trial steps per launch (DESIGN.md §2.2)
@@ -1018,20 +1065,116 @@ class BoxConstraints:
     `CvxInequalityConstraint` buffers, primal_barrier.jl:38-60) as a device-side descriptor: 2·D strict
     inequalities h(x) < 0, rows 1..D = x − ub, rows D+1..2D = lb − x.  The reference evaluates them as a
     dense 2D×D Jacobian on the host (O(D²) per call); here the log barrier ψ = −Σ log(−h_i) and its
-    gradient (primal_barrier.jl:70-94) are element-wise terms inlined into the fused kernels."""
-    lb: float
-    ub: float
+    gradient (primal_barrier.jl:70-94) are element-wise terms inlined into the fused kernels.
+
+    `lb`, `ub` are floats (one interval for every variable: the bounds are constants of the generated source) or
+    length-D arrays (`lbs::Vector{T}`, `ubs::Vector{T}` of examples/constrained.jl:22-31: every variable its own
+    interval; the bounds travel as the objective's last two parameter vectors).  One float and one array: the float
+    is the same for every variable."""
+    lb: Union[float, Sequence[float], np.ndarray]
+    ub: Union[float, Sequence[float], np.ndarray]
+
+    def __post_init__(self):
+        for name in ("lb", "ub"):
+            v = getattr(self, name)
+            if np.ndim(v) == 0:
+                setattr(self, name, float(v))
+            else:
+                a = np.ascontiguousarray(v, dtype=np.float64)
+                assert a.ndim == 1, f"BoxConstraints.{name}: a float or a one-dimensional array"
+                setattr(self, name, a)
+        if self.per_variable and np.ndim(self.lb) == 1 and np.ndim(self.ub) == 1:
+            assert self.lb.size == self.ub.size, "BoxConstraints: lb and ub differ in length"
+
+    @property
+    def per_variable(self) -> bool:
+        return np.ndim(self.lb) == 1 or np.ndim(self.ub) == 1
+
+    def vectors(self, D: int):
+        """(lbs, ubs) as length-D arrays; AssertionError if an array bound has another length."""
+        out = []
+        for name in ("lb", "ub"):
+            v = getattr(self, name)
+            if np.ndim(v) == 0:
+                v = np.full(D, float(v))
+            assert v.size == D, f"BoxConstraints.{name} has {v.size} entries for {D} variables"
+            out.append(v)
+        return out[0], out[1]
 
     def n_constraints(self, D: int) -> int:
         return 2 * D
 
 
+_BUILTIN_BASE_PARAMS = {"ObjQuadDiag": 1, "ObjRosenPaired": 0, "ObjBooth": 0}
+
+
+def base_objective_params(base: str) -> int:
+    """How many parameter vectors the base functor of barrier_objective_source reads."""
+    if base.strip() in _BUILTIN_BASE_PARAMS:
+        return _BUILTIN_BASE_PARAMS[base.strip()]
+    m = re.search(r"\bkParams\s*=\s*(\d+)", base)
+    if m:
+        return int(m.group(1))
+    m = re.search(r"\bkParam\s*=\s*(true|false)", base)
+    assert m, "BaseObjective declares neither kParam nor kParams"
+    return 1 if m.group(1) == "true" else 0
+
+
 def barrier_objective_source(base: str, box: BoxConstraints) -> str:
     """HIP source of `t·f0(x) + ψ(x)` (evalbarrier!, primal_barrier.jl:111-128) around a base functor.
     `base` is the name of a built-in functor (ObjQuadDiag, ObjRosenPaired, ObjBooth) or the source of a
-    `struct BaseObjective { kParam; kPairOnly; eval1; eval2 }`; t lives in the objective's scalar slot."""
-    name = base.strip() if base.strip() in ("ObjQuadDiag", "ObjRosenPaired", "ObjBooth") else "BaseObjective"
+    `struct BaseObjective { kParam | kParams; kPairOnly; eval1; eval2 }`; t lives in the objective's scalar slot.
+    Float bounds are constants of the source; array bounds are read from the two parameter slots after the base's own
+    (lb, then ub), so the functor declares kParams = K_base + 2 (AssertionError if that exceeds 4)."""
+    name = base.strip() if base.strip() in _BUILTIN_BASE_PARAMS else "BaseObjective"
     pre = "" if name != "BaseObjective" else base
+    if box.per_variable:
+        kb = base_objective_params(base)
+        assert kb + 2 <= MAX_PARAM_SLOTS, f"the base objective reads {kb} parameter vectors: no two slots left for the bounds"
+        return pre + f"""
+struct UserObjective {{
+    using B = {name};
+    static constexpr int KB = obj_nparams<B>();                     // the base's own slots come first, then lb, then ub
+    static_assert(KB == {kb}, "the base objective's parameter slots");
+    static constexpr int kParams = KB + 2;
+    static constexpr bool kParam = true;
+    static constexpr bool kPairOnly = B::kPairOnly;
+    __device__ static inline void bar(double x, double lb, double ub, double &psi, double &dpsi) {{
+        const double hu = x - (ub), hl = (lb) - x;                   // fi_evals (examples/constrained.jl:31-32)
+        const double cu = hu > 0.0 ? 0.0 : hu, cl = hl > 0.0 ? 0.0 : hl;  // clamp!(fi_evals, -Inf, 0)  (primal_barrier.jl:81)
+        psi = -(log(-cu) + log(-cl));                                // ψ = −Σ log(−f_i)  (:82)
+        double d = 0.0;
+        d -= 1.0 / cu;                                               // dψ[d] −= df_i[d]/f_i  (:85-89), upper row
+        d -= -1.0 / cl;                                              //                           lower row
+        dpsi = d;
+    }}
+    __device__ static inline void eval1(double x, const double (&p)[kParams], double s0, double &f, double &g) {{
+        double f0 = 0.0, g0 = 0.0, psi, dpsi;
+        PS<B> pb;
+        pb.v[0] = 0.0;
+#pragma unroll
+        for (int j = 0; j < KB; ++j) pb.v[j] = p[j];
+        obj_eval1<B>(x, pb, 0.0, f0, g0);
+        bar(x, p[KB], p[KB + 1], psi, dpsi);
+        f += s0 * f0 + psi;                                          // t·f0 + ψ  (:127)
+        g = s0 * g0 + dpsi;                                          // df = t·df0 + dψ  (:125)
+    }}
+    __device__ static inline void eval2(d2 xx, const d2 (&pp)[kParams], double s0, double &f, d2 &gg) {{
+        double f0 = 0.0, psi0, psi1, d0, d1;
+        d2 g0;
+        PV<B> pb;
+        pb.v[0] = d2{{0.0, 0.0}};
+#pragma unroll
+        for (int j = 0; j < KB; ++j) pb.v[j] = pp[j];
+        obj_eval2<B>(xx, pb, 0.0, f0, g0);
+        bar(xx.x, pp[KB].x, pp[KB + 1].x, psi0, d0);
+        bar(xx.y, pp[KB].y, pp[KB + 1].y, psi1, d1);
+        f += s0 * f0 + (psi0 + psi1);
+        gg.x = s0 * g0.x + d0;
+        gg.y = s0 * g0.y + d1;
+    }}
+}};
+"""
     ub, lb = float(box.ub).hex(), float(box.lb).hex()
     return pre + f"""
 struct UserObjective {{
@@ -1071,6 +1214,8 @@ struct UserObjective {{
 def _base_objective_source(base: str) -> str:
     name = base.strip() if base.strip() in ("ObjQuadDiag", "ObjRosenPaired", "ObjBooth") else "BaseObjective"
     pre = "" if name != "BaseObjective" else base
+    if base_objective_params(base) > 1:   # the array interface, as it is
+        return pre + "\nstruct UserObjective : BaseObjective {};\n"
     return pre + f"""
 struct UserObjective {{
     using B = {name};
@@ -1085,16 +1230,28 @@ struct UserObjective {{
 def primalbarriermethod(constraints: BoxConstraints, f0df0: str, x_initial: Sequence[float],
                         centering_config: CGConfig, linesearch_config: LineSearchConfig,
                         barrier_config: PrimalBarrierConfig, *rerun_config_tuples,
-                        param: Optional[np.ndarray] = None, ctx: Optional[Context] = None) -> PrimalBarrierResults:
+                        param=None, ctx: Optional[Context] = None) -> PrimalBarrierResults:
     """primalbarriermethod!(constraints, f0df0!, hdh!, x_initial, centering_config, linesearch_config,
     barrier_config, rerun_config_tuples...)  (primal_barrier.jl:156-255; algorithm 11.1 of Boyd 2004).
 
     `(constraints, hdh!)` is a BoxConstraints descriptor and `f0df0` the base objective as device source
     (see barrier_objective_source); every centering step is one minimizeobjectivererun on the GPU.
     As in the reference, `x` is a copy of `x_initial` that is never updated (:172,:214-220): every centering
-    step restarts from `x_initial`."""
+    step restarts from `x_initial`.  `param` holds the base objective's own parameter vectors: one array or a
+    sequence of them.  Array bounds (BoxConstraints with length-D `lb` / `ub`) take two more slots."""
     x0 = np.ascontiguousarray(x_initial, dtype=np.float64)
     D = x0.size
+    own = _param_list(param)
+    if own is None:
+        own = [] if param is None else [param]
+    bar_param = base_param = param
+    if constraints.per_variable:
+        lbs, ubs = constraints.vectors(D)
+        assert len(own) + 2 <= MAX_PARAM_SLOTS, f"{len(own)} parameter vectors of the base objective leave no two slots for the bounds"
+        bar_param = own + [lbs, ubs]
+        base_param = own if len(own) != 1 else own[0]
+        if len(own) == 0:
+            base_param = None
     bc = barrier_config
     rets: List[List[Results]] = []
 
@@ -1104,11 +1261,11 @@ def primalbarriermethod(constraints: BoxConstraints, f0df0: str, x_initial: Sequ
 
     if np.any(x0 - constraints.ub >= 0.0) or np.any(constraints.lb - x0 >= 0.0):   # :178-191
         return assemble("infeasible_start", 0, bc.t_initial)
-    obj = ElementwiseObjective(D, barrier_objective_source(f0df0, constraints), param=param, ctx=ctx)
+    obj = ElementwiseObjective(D, barrier_objective_source(f0df0, constraints), param=bar_param, ctx=ctx)
     try:
         t = bc.t_initial
         if not math.isfinite(t) or t < 0.0:                         # verifyt0  (:259-276)
-            base = ElementwiseObjective(D, _base_objective_source(f0df0), param=param, ctx=ctx)   # f0 alone
+            base = ElementwiseObjective(D, _base_objective_source(f0df0), param=base_param, ctx=ctx)   # f0 alone
             try:
                 f_x0 = base(np.empty(D), x0)
             finally:

@@ -13,8 +13,8 @@ namespace cgo {
 using namespace dev;
 
 // ---- gradient-free multi-point CG family (cgo_kernels_cg.hip.hpp) ---------------------------
-double bytes_r(int obj_kind, int mode, int64_t n, bool has_param) {
-    const int p = (obj_kind == CGO_OBJ_QUAD_DIAG || has_param) ? 1 : 0;
+double bytes_r(int obj_kind, int mode, int64_t n, int n_params) {
+    const int p = std::max(obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0, n_params);
     int v = 0;
     if (mode == R_INIT) v = 1 + p + 1;
     else if (mode == R_TRIAL) v = 2 + p;
@@ -100,7 +100,7 @@ int HipBackend::launch_r(int kk, int mode, double a_acc, double beta, const doub
         }
         if (probe_ && fetch) { std::memcpy(probe_row_, sums, sizeof(double) * rows_for(npts)); probe_len_ = rows_for(npts); }
     }
-    if (prof_on_) prof_commit(kk, bytes_r(obj_->kind, mode, obj_->n_local, obj_->uses_param()));
+    if (prof_on_) prof_commit(kk, bytes_r(obj_->kind, mode, obj_->n_local, obj_->nparams()));
     return CGO_OK;
 }
 
@@ -133,7 +133,7 @@ Tail HipBackend::make_tail(bool on) {
 int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, const double *a, int k, int npts,
                                 const CtlArgs *ctl, int *grid_out) {
     HIPCHK(hipSetDevice(ctx_->device));
-    if (obj_->uses_param() && !obj_->p0_set) { set_error("objective parameter vector (slot 0) was never set"); return CGO_ESTATE; }
+    if (obj_->unset_slot() >= 0) return param_unset_error(obj_->unset_slot());
     const int64_t n = obj_->n_local;
     if (mode & (R_GRAD | R_GRADT)) { if (int rc = ensure_ga()) return rc; }
     const bool has_sums = (mode != R_ACCEPT && mode != R_GRAD && mode != R_GRADT);
@@ -148,13 +148,13 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
         return prof_end();
     }
     RParams P;
-    P.x = xc_; P.u = uc_; P.gout = ga_.p; P.p0 = obj_->p0.p; P.n = n;
+    P.x = xc_; P.u = uc_; P.gout = ga_.p; obj_->param_args(P); P.n = n;
     P.xo = xc_; P.uo = uc_;
     P.a_acc = a_acc; P.beta = beta; P.s0 = obj_->s0; P.partials = ctx_->partials;
     P.ctl = ctl;
     P.x2 = xn_;
     for (int j = 0; j < MAXP; ++j) P.a[j] = (a && j < k) ? a[j] : ((a && k > 0) ? a[k - 1] : 0.0);
-    const double bytes = bytes_r(obj_->kind, mode, n, obj_->uses_param());
+    const double bytes = bytes_r(obj_->kind, mode, n, obj_->nparams());
     const bool big = bytes > big_bytes(mode == R_TRIAL || mode == R_UPG);
     const int grid = big ? GRID_BIG : grid_cg(n, npts);
     *grid_out = grid;
@@ -241,7 +241,7 @@ std::string HipBackend::r_symbol(int mode, int npts, bool big) const {
 std::string HipBackend::kernel_symbol(int kk) const {
     const char *on = obj_tname();
     const int64_t n = obj_->n_local;
-    const bool hp = obj_->uses_param();
+    const int hp = obj_->nparams();
     char buf[160];
     if (rmode_) {
         int mode = -1, npts = 1;
@@ -289,7 +289,7 @@ std::string HipBackend::kernel_symbol(int kk) const {
     case KK_LBFGS_LOOP: return "k_lbfgs_loop";
     case KK_LBFGS_FINAL:
         if (spec_on_ && qn_m_ > 0 && qn_m_ - 1 <= SPEC_MAXC) {   // the one-pass form (a full ring assumed for the policy bit)
-            snprintf(buf, sizeof buf, "k_lbfgs_combine_spec<%s, %s, %s>", on, 8.0 * (double)n * (3.0 + (hp ? 1.0 : 0.0) + 2.0 * (qn_m_ - 1)) > big_bytes() ? "true" : "false",
+            snprintf(buf, sizeof buf, "k_lbfgs_combine_spec<%s, %s, %s>", on, 8.0 * (double)n * (3.0 + (double)hp + 2.0 * (qn_m_ - 1)) > big_bytes() ? "true" : "false",
                      spec_fuse_push_ ? "true" : "false");
             return buf;
         }
@@ -392,7 +392,7 @@ int HipBackend::ctl_depth() const {
     if (!(rmode_ && ctx_->host_publish && !obj_->two_phase())) return 0;
     if (ctx_->single()) return ctl_depth_;
     if (!ctx_->dev_exchange() || ctx_->force_gather) return 0;
-    const bool big = bytes_r(obj_->kind, R_ACCEPT | R_DIR | R_TRIAL, obj_->n_local, obj_->uses_param()) > big_bytes(false);
+    const bool big = bytes_r(obj_->kind, R_ACCEPT | R_DIR | R_TRIAL, obj_->n_local, obj_->nparams()) > big_bytes(false);
     return (!big && pipe_fused(grid_cg(obj_->n_local, policy_points()))) ? ctl_depth_ : 0;
 }
 
@@ -413,7 +413,7 @@ int HipBackend::pipe_alloc() {
 int HipBackend::prepare_controller() {
     if (ctl_depth() <= 0) return CGO_OK;
     if (int rc = pipe_alloc()) return rc;
-    if (obj_->uses_param() && !obj_->p0_set) return CGO_OK;   // nothing to launch on yet
+    if (obj_->unset_slot() >= 0) return CGO_OK;   // nothing to launch on yet
     HIPCHK(hipSetDevice(ctx_->device));
     CtlConfig cc{};
     CtlState st{};
@@ -468,7 +468,7 @@ int HipBackend::pipe_launch_graph(int rounds) {
     HIPCHK(hipSetDevice(ctx_->device));
     PipeGraph *g = nullptr;
     for (auto &c : graphs_)
-        if (c.rounds == rounds && c.npts == pipe_npts_ && c.x == xc_ && c.u == uc_ && c.p0 == obj_->p0.p && c.n == obj_->n_local) { g = &c; break; }
+        if (c.rounds == rounds && c.npts == pipe_npts_ && c.x == xc_ && c.u == uc_ && c.p0 == obj_->p[0].p && c.n == obj_->n_local) { g = &c; break; }
     if (!g) {
         hipStream_t st = ctx_->stream;
         hipGraph_t graph = nullptr;
@@ -487,7 +487,7 @@ int HipBackend::pipe_launch_graph(int rounds) {
         e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
         if (e != hipSuccess) { set_error(std::string("hipGraphInstantiate failed: ") + hipGetErrorString(e)); return CGO_EHIP; }
-        graphs_.push_back(PipeGraph{exec, rounds, pipe_npts_, xc_, uc_, obj_->p0.p, obj_->n_local});
+        graphs_.push_back(PipeGraph{exec, rounds, pipe_npts_, xc_, uc_, obj_->p[0].p, obj_->n_local});
         g = &graphs_.back();
     }
     HIPCHK(hipGraphLaunch((hipGraphExec_t)g->exec, ctx_->stream));
@@ -588,7 +588,7 @@ int HipBackend::accept_dir_trial_ctl(const CtlConfig &cc, const CtlState &s0, in
     const auto &pp = pipe_prof_[(int)(id % PIPE_RING)];
     if (prof_on_) {
         prof_cnt_[KK_ACCEPT_DIR_TRIAL]++;
-        prof_bytes_[KK_ACCEPT_DIR_TRIAL] = bytes_r(obj_->kind, R_ACCEPT | R_DIR | R_TRIAL, obj_->n_local, obj_->uses_param());
+        prof_bytes_[KK_ACCEPT_DIR_TRIAL] = bytes_r(obj_->kind, R_ACCEPT | R_DIR | R_TRIAL, obj_->n_local, obj_->nparams());
         if (pp.first >= 0 && pp.second == prof_gen_ && pp.first < ring_used_) {
             ring_[pp.first].kk = KK_ACCEPT_DIR_TRIAL;
             ring_[pp.first].bytes = prof_bytes_[KK_ACCEPT_DIR_TRIAL];
@@ -643,13 +643,14 @@ int HipBackend::probe_prepare() {
         HIPCHK(hipMemsetAsync(b->p, 0, na * sizeof(double), ctx_->stream));
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(b->p + na), (int)PROBE_NAN32, (np - na) * 2, ctx_->stream));
     }
-    if (obj_->uses_param() && obj_->p0_set) {   // the objective's parameter vector, contents kept
+    for (int j = 0; j < obj_->nparams(); ++j) {   // the objective's parameter vectors, contents kept
+        if (!obj_->p_set[j]) continue;
         DevBuf p;
         if (int rc = p.alloc(np)) return rc;
-        HIPCHK(hipMemcpyAsync(p.p, obj_->p0.p, n * sizeof(double), hipMemcpyDeviceToDevice, ctx_->stream));
+        HIPCHK(hipMemcpyAsync(p.p, obj_->p[j].p, n * sizeof(double), hipMemcpyDeviceToDevice, ctx_->stream));
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(p.p + n), (int)PROBE_NAN32, (np - n) * 2, ctx_->stream));
         HIPCHK(hipStreamSynchronize(ctx_->stream));
-        std::swap(p.p, obj_->p0.p); std::swap(p.n, obj_->p0.n);
+        std::swap(p.p, obj_->p[j].p); std::swap(p.n, obj_->p[j].n);
     }
     HIPCHK(hipStreamSynchronize(ctx_->stream));
     xc_ = x_.p; uc_ = u_.p; xalt_ = x2_.p; ualt_ = u2_.p;
@@ -662,12 +663,13 @@ int HipBackend::probe_prepare() {
 // CGO_OK while every slack word of every buffer still holds the NaN pattern
 int HipBackend::probe_slack_intact() {
     const size_t n = (size_t)obj_->n_local, na = n + (chain() ? (n & 1) : 0);
-    struct { const DevBuf *b; const char *name; size_t used; } v[] = {
-        {&x_, "x", na}, {&u_, "u", na}, {&x2_, "x (ping-pong)", na}, {&u2_, "u (ping-pong)", na},
-        {&ga_, "gradient A", na}, {&gb_, "gradient B / x2", na}, {&obj_->p0, "parameter vector", n}};
+    struct { const DevBuf *b; const char *name; size_t used; int slot; } v[] = {
+        {&x_, "x", na, -1}, {&u_, "u", na, -1}, {&x2_, "x (ping-pong)", na, -1}, {&u2_, "u (ping-pong)", na, -1},
+        {&ga_, "gradient A", na, -1}, {&gb_, "gradient B / x2", na, -1}, {&obj_->p[0], "parameter vector", n, 0},
+        {&obj_->p[1], "parameter vector 1", n, 1}, {&obj_->p[2], "parameter vector 2", n, 2}, {&obj_->p[3], "parameter vector 3", n, 3}};
     std::vector<unsigned> h;
     for (const auto &e : v) {
-        if (!e.b->p || (e.b == &obj_->p0 && !(obj_->uses_param() && obj_->p0_set))) continue;
+        if (!e.b->p || (e.slot >= 0 && !(e.slot < obj_->nparams() && obj_->p_set[e.slot]))) continue;
         const size_t words = (e.b->n - e.used) * 2;
         h.assign(words, 0u);
         HIPCHK(hipMemcpyAsync(h.data(), e.b->p + e.used, words * 4, hipMemcpyDeviceToHost, ctx_->stream));
@@ -916,7 +918,7 @@ int HipBackend::res_plan() {
     hipFunction_t mf = (obj_->kind == CGO_OBJ_USER && obj_->rtc) ? obj_->rtc->resident(res_npts_) : nullptr;
     if (!fn && !mf) return 0;
     const int64_t n = obj_->n_local;
-    const int vecs = chain() ? 4 : (obj_->uses_param() ? 3 : 2);   // (the stencil objective: two LDS copies of x and of u)
+    const int vecs = chain() ? 4 : 2 + obj_->nparams();   // x, u and every parameter slot (the stencil objective: two LDS copies of x and of u)
     if (chain() && res_npts_ > 3) res_npts_ = 3;
     int max_lds = 0;
     if (hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx_->device) != hipSuccess) { (void)hipGetLastError(); return 0; }
@@ -994,7 +996,7 @@ void HipBackend::res_out_buffers(double *&xo, double *&uo) const {
 }
 
 void HipBackend::res_fill_params(ResParams &P, double *xo, double *uo) {
-    P.x = xc_; P.u = uc_; P.p0 = obj_->p0.p; P.n = obj_->n_local; P.chunk = res_chunk_; P.s0 = obj_->s0;
+    P.x = xc_; P.u = uc_; obj_->param_args(P); P.n = obj_->n_local; P.chunk = res_chunk_; P.s0 = obj_->s0;
     P.xo = xo; P.uo = uo; P.arrive = res_err_ + 1;
     P.inject = -1;
     P.st_out = res_state_; P.recs = res_recs_dev_;
@@ -1021,7 +1023,7 @@ int HipBackend::resident_run(const ResConfig &c, ResState &s, int64_t budget, st
     if (int rc = pipe_drain()) return rc;
     pipe_streak_ = 0;
     if (res_plan() <= 0) { set_error("internal: resident slice on a shard that does not fit"); return CGO_ESTATE; }
-    if (obj_->uses_param() && !obj_->p0_set) { set_error("objective parameter vector (slot 0) was never set"); return CGO_ESTATE; }
+    if (obj_->unset_slot() >= 0) return param_unset_error(obj_->unset_slot());
     if (int rc = res_alloc()) return rc;
     HIPCHK(hipSetDevice(ctx_->device));
     if (c.log_on && !res_log_) {
@@ -1085,7 +1087,7 @@ int HipBackend::resident_run(const ResConfig &c, ResState &s, int64_t budget, st
     recs.assign(res_recs_, res_recs_ + s.done);
     if (c.log_on) log.assign(res_log_, res_log_ + s.log_len); else log.clear();
     // state moved once per slice: load x, u (+ D) and store x, u
-    if (prof_on_) prof_commit(KK_RESIDENT, 8.0 * (double)obj_->n_local * (double)((obj_->uses_param() ? 3 : 2) + (s.done > 0 ? 2 : 0)));
+    if (prof_on_) prof_commit(KK_RESIDENT, 8.0 * (double)obj_->n_local * (double)(2 + obj_->nparams() + (s.done > 0 ? 2 : 0)));
     return CGO_OK;
 }
 
@@ -1099,7 +1101,7 @@ int HipBackend::probe_resident(const cgo_cg_config &cfg, const cgo_ls_config &ls
     static_assert(RES_MAXP == 7 && RES_WMAX == 56, "include/cgo.h states them");
     p.grid = 0; p.points = 0; p.chunk = 0; p.round0 = 0; p.err_word = 0; p.wrote_back = 0; p.symbol[0] = 0;
     if (!resident_ready(cfg, ls)) { set_error("probe: this solver's engine would not run the resident solver (objective, β, line search, size or policy)"); return CGO_EINVAL; }
-    if (obj_->uses_param() && !obj_->p0_set) { set_error("objective parameter vector (slot 0) was never set"); return CGO_ESTATE; }
+    if (obj_->unset_slot() >= 0) return param_unset_error(obj_->unset_slot());
     if (p.npass < 1 || p.npass > CGO_RESIDENT_PROBE_MAX_PASSES) { set_error("probe: 1 … 32 passes"); return CGO_EINVAL; }
     const int npts = res_npts_, nt = npts < 3 ? npts : 3;
     for (int q = 0; q < p.npass; ++q) {

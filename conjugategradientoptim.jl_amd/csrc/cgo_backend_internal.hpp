@@ -53,10 +53,10 @@ static inline bool with_width(int ns, bool or_last, F f) {
 // streaming policy and grids (cgo_hip_backend.hip)
 double big_bytes_for(double forced, bool read_only = false);
 double env_big_bytes();
-bool is_big(int obj_kind, int mode, int64_t n, bool hp, double forced);
+bool is_big(int obj_kind, int mode, int64_t n, int n_params, double forced);
 int grid_cg(int64_t n, int npts = 1);
 // ALGORITHMIC bytes of a k_cg / k_chain launch (cgo_backend_cg.hip)
-double bytes_r(int obj_kind, int mode, int64_t n, bool has_param);
+double bytes_r(int obj_kind, int mode, int64_t n, int n_params);
 void unpack_r(const double *s, int k, Scal *out, bool dir);
 // host side of the publish protocols (cgo_hip_backend.hip)
 int launch_module(hipFunction_t f, void *params, int grid, hipStream_t st);

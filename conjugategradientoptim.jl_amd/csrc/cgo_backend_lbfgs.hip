@@ -315,9 +315,9 @@ static void launch_spec(bool big, bool push, int grid, hipStream_t st, const Gra
 }
 template <class Obj>
 static void launch_lite(bool big, int grid, hipStream_t st, double *x, const double *u, double *g, double *sn, double *yn, const double *p0, long long n,
-                        double a, double a_s, double M, double S, double lambda) {
-    if (big) k_lbfgs_push_lite<Obj, true><<<grid, BLOCK, 0, st>>>(x, u, g, sn, yn, p0, n, a, a_s, M, S, lambda);
-    else k_lbfgs_push_lite<Obj, false><<<grid, BLOCK, 0, st>>>(x, u, g, sn, yn, p0, n, a, a_s, M, S, lambda);
+                        double a, double a_s, double M, double S, double lambda) {   // (built-in objectives: one parameter slot at most)
+    if (big) k_lbfgs_push_lite<Obj, true><<<grid, BLOCK, 0, st>>>(x, u, g, sn, yn, p0, n, a, a_s, M, S, lambda, nullptr, nullptr, nullptr);
+    else k_lbfgs_push_lite<Obj, false><<<grid, BLOCK, 0, st>>>(x, u, g, sn, yn, p0, n, a, a_s, M, S, lambda, nullptr, nullptr, nullptr);
 }
 
 int HipBackend::lbfgs_direction_spec(const int *slots, const double *cy, const double *cs, int count, double cg, double a_trial,
@@ -337,8 +337,9 @@ int HipBackend::lbfgs_direction_spec(const int *slots, const double *cy, const d
     // along the step.  The reference follows the iterate, whichever kernel produced its statistics.
     const bool lse = obj_->two_phase();
     const double Mr = lse ? lse_M_ + std::log(lse_S_) : 0.0, Sr = 1.0;
-    SpecParams Q{Mr, 1.0 / Sr, obj_->s0, obj_->p0.p};
-    const double hp = obj_->uses_param() ? 1.0 : 0.0;
+    SpecParams Q{Mr, 1.0 / Sr, obj_->s0, nullptr, nullptr, nullptr, nullptr};
+    obj_->param_args(Q);
+    const double hp = (double)obj_->nparams();
     // the state update of the accepted speculated trial, if it was left to this pass (lbfgs_push_commit(direction_follows))
     const bool push = lite_deferred_;
     lite_deferred_ = false;
@@ -477,23 +478,23 @@ int HipBackend::lbfgs_push_lite() {
     HIPCHK(hipSetDevice(ctx_->device));
     const int64_t n = obj_->n_local;
     double *sn = qn_S_.p + (size_t)lite_slot_ * ring_ld(n), *yn = qn_Y_.p + (size_t)lite_slot_ * ring_ld(n);
-    const double bytes = 8.0 * (double)n * (7.0 + (obj_->uses_param() ? 1.0 : 0.0));
+    const double bytes = 8.0 * (double)n * (7.0 + (double)obj_->nparams());
     const bool big = bytes > big_bytes();
     const int grid = big ? GRID_BIG : grid_for(n);
     hipStream_t st = ctx_->stream;
     if (int rc = prof_begin(KK_LBFGS_PUSH)) return rc;
     switch (obj_->kind) {
-    case CGO_OBJ_LSE: launch_lite<ObjLse>(big, grid, st, xc_, u_.p, g_, sn, yn, obj_->p0.p, n, lite_a_, lite_as_, lite_M_, lite_S_, obj_->s0); break;
-    case CGO_OBJ_QUAD_DIAG: launch_lite<ObjQuadDiag>(big, grid, st, xc_, u_.p, g_, sn, yn, obj_->p0.p, n, lite_a_, lite_as_, lite_M_, lite_S_, obj_->s0); break;
-    case CGO_OBJ_ROSENBROCK_PAIRED: launch_lite<ObjRosenPaired>(big, grid, st, xc_, u_.p, g_, sn, yn, obj_->p0.p, n, lite_a_, lite_as_, lite_M_, lite_S_, obj_->s0); break;
+    case CGO_OBJ_LSE: launch_lite<ObjLse>(big, grid, st, xc_, u_.p, g_, sn, yn, obj_->p[0].p, n, lite_a_, lite_as_, lite_M_, lite_S_, obj_->s0); break;
+    case CGO_OBJ_QUAD_DIAG: launch_lite<ObjQuadDiag>(big, grid, st, xc_, u_.p, g_, sn, yn, obj_->p[0].p, n, lite_a_, lite_as_, lite_M_, lite_S_, obj_->s0); break;
+    case CGO_OBJ_ROSENBROCK_PAIRED: launch_lite<ObjRosenPaired>(big, grid, st, xc_, u_.p, g_, sn, yn, obj_->p[0].p, n, lite_a_, lite_as_, lite_M_, lite_S_, obj_->s0); break;
     case CGO_OBJ_USER: {
         hipFunction_t f = obj_->rtc ? obj_->rtc->lite(big) : nullptr;
         if (!f) { set_error("internal: kernel missing from the run-time compiled objective module"); return CGO_EINVAL; }
         double *xa = xc_, *ga = g_, *sna = sn, *yna = yn;
-        const double *ua = u_.p, *pa = obj_->p0.p;
+        const double *ua = u_.p, *pa = obj_->p[0].p, *pb = obj_->p[1].p, *pc = obj_->p[2].p, *pd = obj_->p[3].p;
         long long nn = n;
         double a = lite_a_, as = lite_as_, M = lite_M_, S = lite_S_, lam = obj_->s0;
-        void *args[] = {&xa, &ua, &ga, &sna, &yna, &pa, &nn, &a, &as, &M, &S, &lam};
+        void *args[] = {&xa, &ua, &ga, &sna, &yna, &pa, &nn, &a, &as, &M, &S, &lam, &pb, &pc, &pd};
         HIPCHK(hipModuleLaunchKernel(f, grid, 1, 1, BLOCK, 1, 1, 0, st, args, nullptr));
         break;
     }

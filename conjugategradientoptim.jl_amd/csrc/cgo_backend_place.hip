@@ -44,10 +44,11 @@ bool HipBackend::pingpong_ready() {
 int HipBackend::tune_placement() {
     const bool on = pol_.placement_search != 0;
     const int64_t n = obj_->n_local;
-    const bool hp = obj_->uses_param();
+    const int np = obj_->nparams();
+    const bool hp = np > 0;
     static const bool dbg = getenv("CGO_DEBUG_PLACE") != nullptr;
     if (dbg) fprintf(stderr, "[cgo place] on=%d rmode=%d chain=%d bytes=%.3g big=%.3g\n", (int)on, (int)rmode_, (int)chain(),
-                     bytes_r(obj_->kind, R_ACCEPT | R_DIR | R_TRIAL, n, hp), big_bytes(false));
+                     bytes_r(obj_->kind, R_ACCEPT | R_DIR | R_TRIAL, n, np), big_bytes(false));
     // Searched for the pure-HBM (BIG) launches only.  Round 3 measured the grid-stride launches that exceed the 256 MiB
     // Infinity Cache as well (CGO_PLACE_MIN_BYTES=2.7e8; the 8-GPU shard of config 5, n/8 = 1.25e7, and config 3 at
     // n = 1e7): there the bare mix on the launch's own policy differs by 3–5 % between triples, with no
@@ -55,12 +56,13 @@ int HipBackend::tune_placement() {
     // does not move at all (87.0 vs 87.2 µs, 53.7 vs 54.6 µs; scripts/r03_shard.sh) — at those sizes the launch is 20 µs above
     // its own mix for other reasons (two waves per SIMD do not hide the FP64 work behind the stream).  Not worth 24 spare
     // buffers and 30–40 ms per solver: off by default below the BIG threshold.
-    const double launch_bytes = bytes_r(obj_->kind, R_ACCEPT | R_DIR | R_TRIAL, n, hp);
+    const double launch_bytes = bytes_r(obj_->kind, R_ACCEPT | R_DIR | R_TRIAL, n, np);
     static const double min_env = [] { const char *e = getenv("CGO_PLACE_MIN_BYTES"); double v = e ? atof(e) : 0.0; return v > 0.0 ? v : 0.0; }();   // (experiments: the search below the pure-HBM threshold)
     const double min_bytes = min_env > 0.0 ? min_env : big_bytes(false);
     const bool big = launch_bytes > big_bytes(false);
     const int mix_grid = big ? GRID_BIG : grid_cg(n, policy_points());
-    if (!on || !rmode_ || chain() || launch_bytes <= min_bytes) return CGO_OK;
+    // (the mix that is timed has three streams — x, u and ONE parameter vector: an objective with more slots is not searched)
+    if (!on || !rmode_ || chain() || np > 1 || launch_bytes <= min_bytes) return CGO_OK;
     HIPCHK(hipSetDevice(ctx_->device));
     if (ctx_->placed_n == n && ctx_->placed_x.p && ctx_->placed_u.p) {   // an earlier solver of this size already searched
         x_.release(); u_.release();
@@ -133,7 +135,7 @@ int HipBackend::tune_placement() {
         us = (double)std::min(t[0], t[1]) * 1e3;
         return CGO_OK;
     };
-    const double *d0 = hp ? obj_->p0.p : nullptr;
+    const double *d0 = hp ? obj_->p[0].p : nullptr;
     double best = 0.0, first = 0.0, worst = 0.0;
     int bx = 0, bu = 1, bd = -1;   // bd = −1: D stays where it is
     // The times come in levels ≈ 10–15 % apart (≈ 640 / 715 / 755 µs at n = 1e8 — none, one, several of the three streams
@@ -180,10 +182,10 @@ int HipBackend::tune_placement() {
     };
     double *px = pool[bx], *pu = pool[bu], *pd = bd >= 0 ? pool[bd] : nullptr;
     if (pd) {
-        HIPCHK(hipMemcpyAsync(pd, obj_->p0.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(pd, obj_->p[0].p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipStreamSynchronize(st));
         DevBuf *o = owner(pd);
-        std::swap(o->p, obj_->p0.p); std::swap(o->n, obj_->p0.n);
+        std::swap(o->p, obj_->p[0].p); std::swap(o->n, obj_->p[0].n);
     }
     if (px != x_.p) { DevBuf *o = owner(px); std::swap(o->p, x_.p); std::swap(o->n, x_.n); }
     if (pu != u_.p) { DevBuf *o = owner(pu); std::swap(o->p, u_.p); std::swap(o->n, u_.n); }

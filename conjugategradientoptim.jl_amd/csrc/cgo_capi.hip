@@ -207,7 +207,7 @@ int cgo_objective_create(cgo_ctx *ctx, int32_t kind, int64_t n_global, int64_t o
     o->o.ctx = &ctx->c; o->o.kind = kind; o->o.n_global = n_global; o->o.offset = offset; o->o.n_local = n_local;
     if (o->o.uses_param()) {
         HIPCHK2(hipSetDevice(ctx->c.device));
-        int rc = o->o.p0.alloc((size_t)n_local);
+        int rc = o->o.p[0].alloc((size_t)n_local);
         if (rc) { obj_unref(o); return rc; }
     }
     *out = o;
@@ -217,22 +217,28 @@ int cgo_objective_create(cgo_ctx *ctx, int32_t kind, int64_t n_global, int64_t o
 
 int cgo_objective_create_from_source(cgo_ctx *ctx, const char *source, int32_t has_param, int64_t n_global,
                                      int64_t offset, int64_t n_local, cgo_objective **out) {
+    return cgo_objective_create_from_source_ex(ctx, source, has_param != 0 ? 1 : 0, n_global, offset, n_local, out);
+}
+
+int cgo_objective_create_from_source_ex(cgo_ctx *ctx, const char *source, int32_t n_params, int64_t n_global,
+                                        int64_t offset, int64_t n_local, cgo_objective **out) {
     API_GUARD_BEGIN
     REQUIRE(ctx && source && out, "null argument");
     *out = nullptr;
+    REQUIRE(n_params >= 0 && n_params <= CGO_MAX_PARAM_SLOTS, "n_params must be 0 … CGO_MAX_PARAM_SLOTS");
     REQUIRE(n_local >= 1 && offset >= 0 && offset + n_local <= n_global, "bad shard extents");
     REQUIRE(offset % 2 == 0, "shard offset must be even");
     std::shared_ptr<RtcModule> mod;
     std::string log;
-    int rc = rtc_compile_objective(ctx->c.device, source, has_param != 0, mod, log);
+    int rc = rtc_compile_objective(ctx->c.device, source, n_params, mod, log);
     if (rc) { set_error("user objective did not compile:\n" + log); return rc; }
     cgo_objective *o = new cgo_objective();
     o->owner = ctx; ctx->refs++;
     o->o.ctx = &ctx->c; o->o.kind = CGO_OBJ_USER; o->o.n_global = n_global; o->o.offset = offset; o->o.n_local = n_local;
-    o->o.rtc = mod; o->o.user_has_param = has_param != 0;
-    if (o->o.uses_param()) {
+    o->o.rtc = mod; o->o.user_nparams = n_params;
+    for (int j = 0; j < n_params; ++j) {
         HIPCHK2(hipSetDevice(ctx->c.device));
-        rc = o->o.p0.alloc((size_t)n_local);
+        rc = o->o.p[j].alloc((size_t)n_local);
         if (rc) { obj_unref(o); return rc; }
     }
     *out = o;
@@ -274,12 +280,33 @@ int cgo_objective_destroy(cgo_objective *obj) {
 int cgo_objective_set_param_host(cgo_objective *obj, int32_t slot, const double *host) {
     API_GUARD_BEGIN
     REQUIRE(obj && host, "null argument");
-    REQUIRE(slot == 0 && obj->o.uses_param(), "objective has no such parameter vector");
+    REQUIRE(slot >= 0 && slot < obj->o.nparams(), "objective has no such parameter vector");
     HipCtx *c = obj->o.ctx;
     HIPCHK2(hipSetDevice(c->device));
-    HIPCHK2(hipMemcpyAsync(obj->o.p0.p, host, sizeof(double) * (size_t)obj->o.n_local, hipMemcpyHostToDevice, c->stream));
+    HIPCHK2(hipMemcpyAsync(obj->o.p[slot].p, host, sizeof(double) * (size_t)obj->o.n_local, hipMemcpyHostToDevice, c->stream));
     HIPCHK2(hipStreamSynchronize(c->stream));
-    obj->o.p0_set = true;
+    obj->o.p_set[slot] = true;
+    return CGO_OK;
+    API_GUARD_END
+}
+
+int cgo_objective_set_param_device(cgo_objective *obj, int32_t slot, const double *dev_local) {
+    API_GUARD_BEGIN
+    REQUIRE(obj && dev_local, "null argument");
+    REQUIRE(slot >= 0 && slot < obj->o.nparams(), "objective has no such parameter vector");
+    HipCtx *c = obj->o.ctx;
+    HIPCHK2(hipSetDevice(c->device));
+    HIPCHK2(hipMemcpyAsync(obj->o.p[slot].p, dev_local, sizeof(double) * (size_t)obj->o.n_local, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK2(hipStreamSynchronize(c->stream));
+    obj->o.p_set[slot] = true;
+    return CGO_OK;
+    API_GUARD_END
+}
+
+int cgo_objective_num_params(cgo_objective *obj, int32_t *n_params) {
+    API_GUARD_BEGIN
+    REQUIRE(obj && n_params, "null argument");
+    *n_params = obj->o.nparams();
     return CGO_OK;
     API_GUARD_END
 }
@@ -288,13 +315,13 @@ int cgo_objective_fill_param(cgo_objective *obj, int32_t slot, int32_t fill_kind
                              double lo, double hi) {
     API_GUARD_BEGIN
     REQUIRE(obj, "null argument");
-    REQUIRE(slot == 0 && obj->o.uses_param(), "objective has no such parameter vector");
+    REQUIRE(slot >= 0 && slot < obj->o.nparams(), "objective has no such parameter vector");
     REQUIRE(fill_kind >= 0 && fill_kind <= 2, "unknown fill kind");
     HipCtx *c = obj->o.ctx;
     HIPCHK2(hipSetDevice(c->device));
-    if (int rc = fill_device(c, obj->o.p0.p, obj->o.n_local, obj->o.offset, fill_kind, seed, lo, hi)) return rc;
+    if (int rc = fill_device(c, obj->o.p[slot].p, obj->o.n_local, obj->o.offset, fill_kind, seed, lo, hi)) return rc;
     HIPCHK2(hipStreamSynchronize(c->stream));
-    obj->o.p0_set = true;
+    obj->o.p_set[slot] = true;
     return CGO_OK;
     API_GUARD_END
 }

@@ -149,7 +149,11 @@ double env_big_bytes() {
     return forced;
 }
 double HipBackend::big_bytes(bool read_only) const { return big_bytes_for(pol_.hbm_stream_bytes, read_only); }
-bool is_big(int obj_kind, int mode, int64_t n, bool hp, double forced) {
+int param_unset_error(int slot) {
+    set_error("objective parameter vector (slot " + std::to_string(slot) + ") was never set");
+    return CGO_ESTATE;
+}
+bool is_big(int obj_kind, int mode, int64_t n, int hp, double forced) {
     const bool ro = (mode == M_UPG || mode == M_BETAONLY);
     return bytes_for(obj_kind, mode, n, hp) > big_bytes_for(forced, ro);
 }
@@ -187,8 +191,8 @@ int grid_cg(int64_t n, int npts) {
 }
 
 // ALGORITHMIC bytes of one launch: 8·n·(distinct n-vectors read + written)
-double bytes_for(int obj_kind, int mode, int64_t n, bool has_param) {
-    const int p = (obj_kind == CGO_OBJ_QUAD_DIAG || has_param) ? 1 : 0;
+double bytes_for(int obj_kind, int mode, int64_t n, int n_params) {
+    const int p = std::max(obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0, n_params);
     int v = 0;
     if (mode == M_INIT) v = 1 + p + 2;
     else if (mode == (M_TRIAL | M_BETA)) v = 3 + p + 1;
@@ -242,7 +246,7 @@ int launch_fused(HipCtx *ctx, int obj_kind, int mode, const void *kparams, int64
                  const HipObjective *obj, hipEvent_t e0, hipEvent_t e1, double big_forced) {
     if (!e0) { e0 = ctx->ev0; e1 = ctx->ev1; }
     const KParams &P = *(const KParams *)kparams;
-    const bool hp = obj && obj->uses_param();
+    const int hp = obj ? obj->nparams() : 0;
     const bool big = is_big(obj_kind, mode, n, hp, big_forced < 0.0 ? env_big_bytes() : big_forced);
     const int grid = big ? GRID_BIG : grid_for(n);
     hipStream_t st = ctx->stream;
@@ -766,12 +770,9 @@ void HipBackend::profile_get(int kind, int64_t *launches, double *ms, double *by
 int HipBackend::launch(int kk, int mode, double a_acc, double beta, double a_trial, bool fetch,
                        double *sums) {
     HIPCHK(hipSetDevice(ctx_->device));
-    if (obj_->uses_param() && !obj_->p0_set && (mode & (M_TRIAL | M_INIT))) {
-        set_error("objective parameter vector (slot 0) was never set");
-        return CGO_ESTATE;
-    }
+    if (obj_->unset_slot() >= 0 && (mode & (M_TRIAL | M_INIT))) return param_unset_error(obj_->unset_slot());
     KParams P;
-    P.x = xc_; P.u = u_.p; P.g = g_; P.gt = gt_; P.p0 = obj_->p0.p;
+    P.x = xc_; P.u = u_.p; P.g = g_; P.gt = gt_; obj_->param_args(P);
     P.n = obj_->n_local; P.offset = obj_->offset;
     P.a_acc = a_acc; P.beta = beta; P.a_trial = a_trial; P.s0 = obj_->s0;
     P.partials = ctx_->partials; P.out = ctx_->out_dev;
@@ -786,10 +787,10 @@ int HipBackend::launch(int kk, int mode, double a_acc, double beta, double a_tri
     if (probe_stored_) {   // cgo_solver_probe_launch: the instantiation launch_fused dispatched, and the row
         const bool objective_mode = (mode & (M_TRIAL | M_INIT)) != 0;
         probe_note(nullptr, 0, "k_fused<%s, %d, %s>", objective_mode ? obj_tname() : "ObjQuadDiag", mode,
-                   is_big(obj_->kind, mode, obj_->n_local, obj_->uses_param(), pol_.hbm_stream_bytes) ? "true" : "false");
+                   is_big(obj_->kind, mode, obj_->n_local, obj_->nparams(), pol_.hbm_stream_bytes) ? "true" : "false");
         if (fetch) probe_append(sums, NS);
     }
-    if (prof_on_) prof_commit(kk, bytes_for(obj_->kind, mode, obj_->n_local, obj_->uses_param()));
+    if (prof_on_) prof_commit(kk, bytes_for(obj_->kind, mode, obj_->n_local, obj_->nparams()));
     return CGO_OK;
 }
 
@@ -1186,7 +1187,7 @@ int HipBackend::run_trial(HipObjective *obj, const double *x, const double *u, d
     if (int rc = du.up(ctx, u, n)) return rc;
     if (int rc = dgt.up(ctx, nullptr, n)) return rc;
     KParams P = base_params(ctx, n);
-    P.x = dx.b.p; P.u = du.b.p; P.gt = dgt.b.p; P.p0 = obj->p0.p; P.a_trial = a; P.s0 = obj->s0;
+    P.x = dx.b.p; P.u = du.b.p; P.gt = dgt.b.p; obj->param_args(P); P.a_trial = a; P.s0 = obj->s0;
     P.offset = obj->offset;
     if (int rc = launch_fused(ctx, obj->kind, M_TRIAL, &P, n, false, obj)) return rc;
     double s[NS];
@@ -1218,7 +1219,7 @@ int HipBackend::run_eval(HipObjective *obj, const double *x, double *g_out, doub
     if (int rc = du.up(ctx, nullptr, n)) return rc;
     if (int rc = dgt.up(ctx, nullptr, n)) return rc;
     KParams P = base_params(ctx, n);
-    P.x = dx.b.p; P.u = du.b.p; P.gt = dgt.b.p; P.p0 = obj->p0.p; P.s0 = obj->s0;
+    P.x = dx.b.p; P.u = du.b.p; P.gt = dgt.b.p; obj->param_args(P); P.s0 = obj->s0;
     P.offset = obj->offset;
     if (int rc = launch_fused(ctx, obj->kind, M_INIT, &P, n, false, obj)) return rc;
     double s[NS];
@@ -1251,7 +1252,7 @@ int HipBackend::bench_kernel(HipCtx *ctx, HipObjective *obj, int kernel_kind, in
     default: set_error("bench_kernel: unknown kernel kind"); return CGO_EINVAL;
     }
     const int okind = obj ? obj->kind : CGO_OBJ_ROSENBROCK_PAIRED;
-    if (obj && obj->uses_param() && (!obj->p0_set || obj->n_local < n)) {
+    if (obj && obj->uses_param() && (obj->unset_slot() >= 0 || obj->n_local < n)) {
         set_error("bench_kernel: objective parameter vector missing or shorter than n");
         return CGO_EINVAL;
     }
@@ -1266,7 +1267,8 @@ int HipBackend::bench_kernel(HipCtx *ctx, HipObjective *obj, int kernel_kind, in
     k_fill<<<fg, BLOCK, 0, ctx->stream>>>(g.p, n, 0, 1, 3, -1.0, 1.0);
     k_fill<<<fg, BLOCK, 0, ctx->stream>>>(gt.p, n, 0, 1, 4, -1.0, 1.0);
     KParams P = base_params(ctx, n);
-    P.x = x.p; P.u = u.p; P.g = g.p; P.gt = gt.p; P.p0 = obj ? obj->p0.p : nullptr;
+    P.x = x.p; P.u = u.p; P.g = g.p; P.gt = gt.p;
+    if (obj) obj->param_args(P);
     P.s0 = obj ? obj->s0 : 0.0;
     P.a_acc = 1e-9; P.beta = 0.5; P.a_trial = 1e-3;  // keeps values bounded over many reps
     for (int w = 0; w < 2; ++w)
@@ -1279,7 +1281,7 @@ int HipBackend::bench_kernel(HipCtx *ctx, HipObjective *obj, int kernel_kind, in
     float t = 0;
     HIPCHK(hipEventElapsedTime(&t, ctx->ev0, ctx->ev1));
     *ms = (double)t / reps;
-    *bytes = bytes_for(okind, mode, n, obj && obj->uses_param());
+    *bytes = bytes_for(okind, mode, n, obj ? obj->nparams() : 0);
     return CGO_OK;
 }
 

@@ -83,11 +83,11 @@ struct HipObjective {
     HipCtx *ctx = nullptr;
     int kind = 0;
     int64_t n_global = 0, offset = 0, n_local = 0;
-    DevBuf p0;
-    bool p0_set = false;
+    DevBuf p[CGO_MAX_PARAM_SLOTS];   // parameter vectors, slots 0 … nparams() − 1
+    bool p_set[CGO_MAX_PARAM_SLOTS] = {};
     double s0 = 0.0;
     std::shared_ptr<RtcModule> rtc;  // CGO_OBJ_USER: the run-time compiled kernels
-    bool user_has_param = false;
+    int user_nparams = 0;     // CGO_OBJ_USER: parameter slots its kernels read (0 … CGO_MAX_PARAM_SLOTS)
     bool user_cheap = false;  // cgo_objective_set_cost_class: seven trial steps per launch
     int users = 0;            // live solvers on this objective (the placement search moves the parameter vector only for a sole user)
     // CGO_OBJ_HOST: the reference's closure contract f = fdf!(g, x) on host vectors (cgo_objective_create_callback)
@@ -96,7 +96,10 @@ struct HipObjective {
     double *host_x = nullptr, *host_g = nullptr;   // pinned staging, n_local doubles each
     bool host_closure() const { return kind == CGO_OBJ_HOST; }
     ~HipObjective();
-    bool uses_param() const { return kind == CGO_OBJ_QUAD_DIAG || (kind == CGO_OBJ_USER && user_has_param); }
+    int nparams() const { return kind == CGO_OBJ_QUAD_DIAG ? 1 : (kind == CGO_OBJ_USER ? user_nparams : 0); }
+    bool uses_param() const { return nparams() > 0; }
+    int unset_slot() const { for (int j = 0; j < nparams(); ++j) if (!p_set[j]) return j; return -1; }   // −1: every slot is set
+    template <class A> void param_args(A &P) const { P.p0 = p[0].p; P.p1 = p[1].p; P.p2 = p[2].p; P.p3 = p[3].p; }   // KParams, RParams, SpecParams, ResParams
     bool two_phase() const { return kind == CGO_OBJ_LSE; }
 };
 
@@ -307,7 +310,7 @@ class HipBackend : public VecBackend {
     int pipe_enqueue_round();
     int pipe_launch_graph(int rounds);
     int pipe_enqueue(int64_t count);
-    struct PipeGraph { void *exec; int rounds, npts; double *x, *u; const double *p0; int64_t n; };
+    struct PipeGraph { void *exec; int rounds, npts; double *x, *u; const double *p0; int64_t n; };   // (armed rounds: built-in objectives, one slot)
     std::vector<PipeGraph> graphs_;      // instantiated hipGraphs of 2 / 4 / 8 controller rounds
     bool graph_on_ = false;              // CGO_CTL_GRAPH=1: batches of armed rounds replay from instantiated hipGraphs (measured 3–8 % slower than kernel-by-kernel enqueue)
     bool capturing_ = false;
@@ -398,7 +401,8 @@ int launch_fused(HipCtx *ctx, int obj_kind, int mode, const void *kparams, int64
                  bool timed = false, const HipObjective *obj = nullptr, hipEvent_t e0 = nullptr,
                  hipEvent_t e1 = nullptr, double big_forced = -1.0 /* < 0: no solver — the CGO_BIG_BYTES experiment override, else the library's thresholds */);
 int grid_for(int64_t n);
-double bytes_for(int obj_kind, int mode, int64_t n, bool has_param = false);
+double bytes_for(int obj_kind, int mode, int64_t n, int n_params = 0);
+int param_unset_error(int slot);   // CGO_ESTATE, the message names the slot
 enum MergeKind { MERGE_SUM = 0, MERGE_LSE = 1, MERGE_MAX0 = 2 };
 int fetch_sums(HipCtx *ctx, double *sums, int merge = MERGE_SUM, int ns = 10, double *raw = nullptr);  // raw: every rank's block, [world][ns]
 int finalize_launch(HipCtx *ctx, int grid, bool lse);

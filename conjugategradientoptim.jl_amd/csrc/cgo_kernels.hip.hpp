@@ -75,6 +75,7 @@ struct KParams {
     double s0;          // objective scalar (e.g. λ)
     double *partials;   // [gridDim.x][NS]
     double *out;        // [NS] local sums (written by k_finalize)
+    const double *p1, *p2, *p3;   // parameter slots 1–3 (run-time compiled objectives with kParams > 1 only)
 };
 
 // ---- objective functors (device form of the `fdf!` contract) ---------------
@@ -119,7 +120,41 @@ struct ObjBooth {  // examples/helpers/test_funcs.jl:3-12, n = 2
     __device__ static inline void eval1(double, double, double, double &, double &g) { g = 0.0; }
 };
 
-// ---- reduction tail --------------------------------------------------------
+// ---- parameter slots ---------------------------------------------------------
+// A functor reads K parameter vectors: K = kParam ? 1 : 0 with the scalar-`p` signatures above (every built-in), or — run-time
+// compiled objectives only — `static constexpr int kParams = K` (2 ≤ K ≤ MAX_PARAM_SLOTS) with
+//     eval1(double x, const double (&p)[K], double s0, double &f, double &g)
+//     eval2(d2 x,     const d2     (&p)[K], double s0, double &f, d2 &g).
+// The kernels hold an element's parameters in a PV / PS bundle (one register set per slot), fill it with pv_load / ps_load
+// and evaluate through obj_eval1 / obj_eval2, which hand slot 0 to a scalar-`p` functor: no kernel body tells the two apart.
+constexpr int MAX_PARAM_SLOTS = 4;   // = CGO_MAX_PARAM_SLOTS
+template <class Obj, class = void> struct ObjParams { static constexpr int K = Obj::kParam ? 1 : 0; static constexpr bool array = false; };
+template <class Obj> struct ObjParams<Obj, decltype((void)Obj::kParams)> {
+    static constexpr int K = Obj::kParams; static constexpr bool array = true;
+    static_assert(K >= 2 && K <= MAX_PARAM_SLOTS, "kParams must be 2, 3 or 4 (0 or 1 slot: kParam and the scalar-p signatures)");
+};
+template <class Obj> constexpr int obj_nparams() { return ObjParams<Obj>::K; }
+template <class Obj> struct PV { d2 v[obj_nparams<Obj>() > 1 ? obj_nparams<Obj>() : 1]; };       // an aligned pair of every slot
+template <class Obj> struct PS { double v[obj_nparams<Obj>() > 1 ? obj_nparams<Obj>() : 1]; };   // one element of every slot
+template <class Obj> __device__ inline void obj_eval2(d2 x, const PV<Obj> &p, double s0, double &f, d2 &g) {
+    if constexpr (ObjParams<Obj>::array) Obj::eval2(x, p.v, s0, f, g);
+    else Obj::eval2(x, p.v[0], s0, f, g);
+}
+template <class Obj> __device__ inline void obj_eval1(double x, const PS<Obj> &p, double s0, double &f, double &g) {
+    if constexpr (ObjParams<Obj>::array) Obj::eval1(x, p.v, s0, f, g);
+    else Obj::eval1(x, p.v[0], s0, f, g);
+}
+// Slot J of an argument block that carries p0 … p3.  J is a compile-time constant at every use: a run-time index into the
+// argument copy would send the whole block to scratch (the note at cg_launch's reduction tail, cgo_kernels_cg.hip.hpp).
+template <int J, class A> __device__ inline const double *param_slot(const A &P) {
+    static_assert(J >= 0 && J < MAX_PARAM_SLOTS, "no such slot");
+    if constexpr (J == 0) return P.p0;
+    else if constexpr (J == 1) return P.p1;
+    else if constexpr (J == 2) return P.p2;
+    else return P.p3;
+}
+struct ParamPtrs { const double *p0, *p1, *p2, *p3; };
+
 // One term of a dot product: acc + a·b with ONE rounding (v_fma_f64).  The reference's dots are BLAS calls
 // (LinearAlgebra.dot → OpenBLAS ddot: FMA kernels, SIMD order — SURVEY.md §8a "Julia numerics facts"), so how a
 // partial sum is rounded is not part of its contract, and the 7-point launches are short of FP64 issue slots, not of
@@ -290,7 +325,7 @@ template <int MODE> struct Needs {
     static constexpr bool p = (MODE & (M_TRIAL | M_INIT)) != 0;
 };
 
-struct Lanes { d2 x, u, g, p, gt; };
+template <class Obj> struct Lanes { d2 x, u, g, gt; PV<Obj> p; };
 
 template <bool NT> __device__ inline d2 ldg2(const double *base, long long i) {
     const d2 *q = reinterpret_cast<const d2 *>(base) + i;
@@ -303,17 +338,39 @@ template <bool NT> __device__ inline void stg2(double *base, long long i, d2 v) 
     else *q = v;
 }
 
+// every parameter slot of the objective at pair i / element i (zero where it has none), with the policy of the launch's other streams
+template <class Obj, bool NT, class A> __device__ inline PV<Obj> pv_load(const A &P, long long i) {
+    constexpr int K = obj_nparams<Obj>();
+    PV<Obj> r;
+    r.v[0] = d2{0.0, 0.0};
+    if constexpr (K > 0) r.v[0] = ldg2<NT>(param_slot<0>(P), i);
+    if constexpr (K > 1) r.v[1] = ldg2<NT>(param_slot<1>(P), i);
+    if constexpr (K > 2) r.v[2] = ldg2<NT>(param_slot<2>(P), i);
+    if constexpr (K > 3) r.v[3] = ldg2<NT>(param_slot<3>(P), i);
+    return r;
+}
+template <class Obj, class A> __device__ inline PS<Obj> ps_load(const A &P, long long i) {
+    constexpr int K = obj_nparams<Obj>();
+    PS<Obj> r;
+    r.v[0] = 0.0;
+    if constexpr (K > 0) r.v[0] = param_slot<0>(P)[i];
+    if constexpr (K > 1) r.v[1] = param_slot<1>(P)[i];
+    if constexpr (K > 2) r.v[2] = param_slot<2>(P)[i];
+    if constexpr (K > 3) r.v[3] = param_slot<3>(P)[i];
+    return r;
+}
+
 template <class Obj, int MODE, bool NT>
-__device__ inline void load2(const KParams &P, long long i, Lanes &v) {
+__device__ inline void load2(const KParams &P, long long i, Lanes<Obj> &v) {
     if (Needs<MODE>::x) v.x = ldg2<NT>(P.x, i);
     if (Needs<MODE>::u) v.u = ldg2<NT>(P.u, i);
     if (Needs<MODE>::g) v.g = ldg2<NT>(P.g, i);
     if (Needs<MODE>::gt_in) v.gt = ldg2<NT>(P.gt, i);
-    if (Needs<MODE>::p && Obj::kParam) v.p = ldg2<NT>(P.p0, i);
+    if (Needs<MODE>::p && obj_nparams<Obj>() > 0) v.p = pv_load<Obj, NT>(P, i);
 }
 
 template <class Obj, int MODE, bool NT>
-__device__ inline void body2(const KParams &P, long long i, Lanes &v, double (&acc)[NS]) {
+__device__ inline void body2(const KParams &P, long long i, Lanes<Obj> &v, double (&acc)[NS]) {
     if (MODE & M_ACCEPT) {
         v.x.x = v.x.x + P.a_acc * v.u.x;
         v.x.y = v.x.y + P.a_acc * v.u.y;
@@ -339,7 +396,7 @@ __device__ inline void body2(const KParams &P, long long i, Lanes &v, double (&a
         d2 xp, gt;
         xp.x = v.x.x + P.a_trial * v.u.x;
         xp.y = v.x.y + P.a_trial * v.u.y;
-        Obj::eval2(xp, v.p, P.s0, acc[S_F], gt);
+        obj_eval2<Obj>(xp, v.p, P.s0, acc[S_F], gt);
         stg2<NT>(P.gt, i, gt);
         acc[S_GTU] = dsum(acc[S_GTU], gt.x, v.u.x);
         acc[S_GTU] = dsum(acc[S_GTU], gt.y, v.u.y);
@@ -359,7 +416,7 @@ __device__ inline void body2(const KParams &P, long long i, Lanes &v, double (&a
     }
     if (MODE & M_INIT) {
         d2 gt, un;
-        Obj::eval2(v.x, v.p, P.s0, acc[S_F], gt);
+        obj_eval2<Obj>(v.x, v.p, P.s0, acc[S_F], gt);
         un.x = -gt.x;
         un.y = -gt.y;
         stg2<NT>(P.gt, i, gt);
@@ -392,7 +449,9 @@ __device__ inline void body1(const KParams &P, long long i, double (&acc)[NS]) {
     double x = Needs<MODE>::x ? P.x[i] : 0.0;
     double u = Needs<MODE>::u ? P.u[i] : 0.0;
     const double g = Needs<MODE>::g ? P.g[i] : 0.0;
-    const double p = (Needs<MODE>::p && Obj::kParam) ? P.p0[i] : 0.0;
+    PS<Obj> p;
+    p.v[0] = 0.0;
+    if (Needs<MODE>::p && obj_nparams<Obj>() > 0) p = ps_load<Obj>(P, i);
     if (MODE & M_ACCEPT) { x = x + P.a_acc * u; P.x[i] = x; }
     if (MODE & (M_DIR | M_RESET)) {
         const double un = (MODE & M_DIR) ? (-g + P.beta * u) : -g;
@@ -404,7 +463,7 @@ __device__ inline void body1(const KParams &P, long long i, double (&acc)[NS]) {
     if (MODE & M_TRIAL) {
         const double xp = x + P.a_trial * u;
         double gt;
-        Obj::eval1(xp, p, P.s0, acc[S_F], gt);
+        obj_eval1<Obj>(xp, p, P.s0, acc[S_F], gt);
         P.gt[i] = gt;
         acc[S_GTU] = dsum(acc[S_GTU], gt, u);
         acc[S_GTGT] = dsum(acc[S_GTGT], gt, gt);
@@ -415,7 +474,7 @@ __device__ inline void body1(const KParams &P, long long i, double (&acc)[NS]) {
     }
     if (MODE & M_INIT) {
         double gt;
-        Obj::eval1(x, p, P.s0, acc[S_F], gt);
+        obj_eval1<Obj>(x, p, P.s0, acc[S_F], gt);
         P.gt[i] = gt;
         P.u[i] = -gt;
         acc[S_GTGT] = dsum(acc[S_GTGT], gt, gt);
@@ -441,14 +500,14 @@ __global__ __launch_bounds__(BLOCK) void k_fused(const KParams P) {
         const long long hi = (lo + per < n2) ? lo + per : n2;
         long long i = lo + threadIdx.x;
         for (; i + BLOCK < hi; i += 2 * BLOCK) {
-            Lanes a, b;
+            Lanes<Obj> a, b;
             load2<Obj, MODE, true>(P, i, a);
             load2<Obj, MODE, true>(P, i + BLOCK, b);
             body2<Obj, MODE, true>(P, i, a, acc);
             body2<Obj, MODE, true>(P, i + BLOCK, b, acc);
         }
         if (i < hi) {
-            Lanes a;
+            Lanes<Obj> a;
             load2<Obj, MODE, true>(P, i, a);
             body2<Obj, MODE, true>(P, i, a, acc);
         }
@@ -456,14 +515,14 @@ __global__ __launch_bounds__(BLOCK) void k_fused(const KParams P) {
         const long long T = (long long)gridDim.x * BLOCK;
         long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
         for (; i + T < n2; i += 2 * T) {
-            Lanes a, b;
+            Lanes<Obj> a, b;
             load2<Obj, MODE, false>(P, i, a);
             load2<Obj, MODE, false>(P, i + T, b);
             body2<Obj, MODE, false>(P, i, a, acc);
             body2<Obj, MODE, false>(P, i + T, b, acc);
         }
         if (i < n2) {
-            Lanes a;
+            Lanes<Obj> a;
             load2<Obj, MODE, false>(P, i, a);
             body2<Obj, MODE, false>(P, i, a, acc);
         }
@@ -958,7 +1017,7 @@ constexpr int SE_F = 0, SE_GTU = 1, SE_GTGT = 2, SE_YGT = 3, SE_UY = 4, SE_YY = 
 struct ObjLse { static constexpr bool kTwoPhase = true; static constexpr bool kParam = false; static constexpr bool kPairOnly = false; };
 template <class Obj> struct SpecKind { static constexpr bool lse = false; };
 template <> struct SpecKind<ObjLse> { static constexpr bool lse = true; };
-struct SpecParams { double Mr, rSr, lambda; const double *p0; };   // log-sum-exp: reference maximum, 1/S_r, λ · element-wise: –, –, the objective's scalar, its parameter vector
+struct SpecParams { double Mr, rSr, lambda; const double *p0, *p1, *p2, *p3; };   // log-sum-exp: reference maximum, 1/S_r, λ · element-wise: –, –, the objective's scalar, its parameter vector
 // PUSH: the state update of the PREVIOUS iteration's accepted speculated trial rides in this pass instead of a launch of its
 // own (k_lbfgs_push_lite): x ← x + a·u_old, g ← g⁺ (log-sum-exp: exp(x − M)/S + λ·x; element-wise: ∇f(x)), and the new pair
 // s = a_s·u_old, y = g⁺ − g_old is FORMED in registers — written to its ring slot for the passes to come, used here by its
@@ -1028,7 +1087,7 @@ __global__ __launch_bounds__(BLOCK) void k_lbfgs_combine_spec(const GramDirParam
             }
         }
     };
-    auto pair = [&](d2 xv, d2 g, d2 u, d2 pv, const d2 (&sj)[LPW], const d2 (&yj)[LPW]) {
+    auto pair = [&](d2 xv, d2 g, d2 u, const PV<Obj> &pv, const d2 (&sj)[LPW], const d2 (&yj)[LPW]) {
         double sx[LPW], sy[LPW], yx[LPW], yy[LPW];
 #pragma unroll
         for (int l = 0; l < LPW; ++l) { sx[l] = sj[l].x; sy[l] = sj[l].y; yx[l] = yj[l].x; yy[l] = yj[l].y; }
@@ -1039,12 +1098,12 @@ __global__ __launch_bounds__(BLOCK) void k_lbfgs_combine_spec(const GramDirParam
             d2 xp, gt;
             xp.x = xv.x + a_trial * u.x; xp.y = xv.y + a_trial * u.y;
             double fl = 0.0;
-            Obj::eval2(xp, pv, Q.lambda, fl, gt);
+            obj_eval2<Obj>(xp, pv, Q.lambda, fl, gt);
             sums_ew(g.x, gt.x, u.x, fl, sx, yx);
             sums_ew(g.y, gt.y, u.y, 0.0, sy, yy);
         }
     };
-    auto push_pair = [&](d2 &xv, d2 &g, d2 uo, d2 pv, d2 &s, d2 &y) {   // k_lbfgs_push_lite's expressions
+    auto push_pair = [&](d2 &xv, d2 &g, d2 uo, const PV<Obj> &pv, d2 &s, d2 &y) {   // k_lbfgs_push_lite's expressions
         xv.x = xv.x + U.a * uo.x; xv.y = xv.y + U.a * uo.y;
         d2 gt;
         if constexpr (LSE) {
@@ -1052,7 +1111,7 @@ __global__ __launch_bounds__(BLOCK) void k_lbfgs_combine_spec(const GramDirParam
             gt.y = exp(xv.y - U.M) / U.S + Q.lambda * xv.y;
         } else {
             double fl = 0.0;
-            Obj::eval2(xv, pv, Q.lambda, fl, gt);
+            obj_eval2<Obj>(xv, pv, Q.lambda, fl, gt);
         }
         s.x = U.a_s * uo.x; s.y = U.a_s * uo.y;
         y.x = gt.x - g.x; y.y = gt.y - g.y;
@@ -1074,11 +1133,14 @@ __global__ __launch_bounds__(BLOCK) void k_lbfgs_combine_spec(const GramDirParam
     for (; i0 < hi; i0 += step, buf ^= 1) {   // (trip count is uniform over the workgroup: the barrier is reached by all)
         const long long i = i0 + lane;
         const bool valid = i < hi;
-        d2 g{0.0, 0.0}, xv{0.0, 0.0}, pv{0.0, 0.0}, sn{0.0, 0.0}, yn{0.0, 0.0}, sj[LPW], yj[LPW];
+        d2 g{0.0, 0.0}, xv{0.0, 0.0}, sn{0.0, 0.0}, yn{0.0, 0.0}, sj[LPW], yj[LPW];
+        PV<Obj> pv;
+#pragma unroll
+        for (int k = 0; k < (int)(sizeof(pv.v) / sizeof(pv.v[0])); ++k) pv.v[k] = d2{0.0, 0.0};
         d2 r{0.0, 0.0};
         if (valid) {
             g = ldg2<false>(P.g, i); xv = ldg2<false>(x, i);
-            if (Obj::kParam) pv = ldg2<false>(Q.p0, i);
+            if (obj_nparams<Obj>() > 0) pv = pv_load<Obj, false>(Q, i);
             d2 uo{0.0, 0.0};
             if (PUSH) uo = ldg2<false>(P.u, i);
 #pragma unroll
@@ -1115,16 +1177,19 @@ __global__ __launch_bounds__(BLOCK) void k_lbfgs_combine_spec(const GramDirParam
     }
     if ((P.n & 1) && blockIdx.x == 0) {   // odd tail element: lane 0 of every wave forms the same u (wave order) and takes its own sums
         const long long e = P.n - 1;
-        double g = 0.0, xe = 0.0, pe = 0.0, u = 0.0, sne = 0.0, yne = 0.0;
+        double g = 0.0, xe = 0.0, u = 0.0, sne = 0.0, yne = 0.0;
+        PS<Obj> pe;
+#pragma unroll
+        for (int k = 0; k < (int)(sizeof(pe.v) / sizeof(pe.v[0])); ++k) pe.v[k] = 0.0;
         double sv[LPW], yv[LPW];
         auto grad1 = [&](double xx, double &fl) {   // ∇f at one element
             double gt = 0.0;
-            if constexpr (!LSE) Obj::eval1(xx, pe, Q.lambda, fl, gt);
+            if constexpr (!LSE) obj_eval1<Obj>(xx, pe, Q.lambda, fl, gt);
             return gt;
         };
         if (lane == 0) {
             g = P.g[e]; xe = x[e];
-            if (Obj::kParam) pe = Q.p0[e];
+            if (obj_nparams<Obj>() > 0) pe = ps_load<Obj>(Q, e);
             if (PUSH) {
                 const double uo = P.u[e];
                 xe = xe + U.a * uo;
@@ -1202,8 +1267,10 @@ __global__ __launch_bounds__(BLOCK) void k_lbfgs_combine_spec(const GramDirParam
 // ‖g⁺‖ finite (optim.jl:107-121).
 template <class Obj, bool BIG>
 __global__ __launch_bounds__(BLOCK) void k_lbfgs_push_lite(double *x, const double *u, double *g, double *sn, double *yn, const double *p0, long long n,
-                                                           double a, double a_s, double M, double S, double lambda) {
+                                                           double a, double a_s, double M, double S, double lambda,
+                                                           const double *p1, const double *p2, const double *p3) {
     constexpr bool LSE = SpecKind<Obj>::lse;
+    const ParamPtrs pp{p0, p1, p2, p3};
     const long long n2 = n >> 1;
     long long i, hi, step;
     if (BIG) {
@@ -1219,7 +1286,7 @@ __global__ __launch_bounds__(BLOCK) void k_lbfgs_push_lite(double *x, const doub
     for (; i < hi; i += step) {
         d2 xv = ldg2<BIG>(x, i);
         const d2 gv = ldg2<BIG>(g, i), uv = ldg2<BIG>(u, i);
-        const d2 pv = Obj::kParam ? ldg2<BIG>(p0, i) : d2{0.0, 0.0};
+        const PV<Obj> pv = pv_load<Obj, BIG>(pp, i);
         xv.x = xv.x + a * uv.x; xv.y = xv.y + a * uv.y;
         d2 gt, s, y;
         if constexpr (LSE) {
@@ -1227,7 +1294,7 @@ __global__ __launch_bounds__(BLOCK) void k_lbfgs_push_lite(double *x, const doub
             gt.y = exp(xv.y - M) / S + lambda * xv.y;
         } else {
             double fl = 0.0;
-            Obj::eval2(xv, pv, lambda, fl, gt);
+            obj_eval2<Obj>(xv, pv, lambda, fl, gt);
         }
         s.x = a_s * uv.x; s.y = a_s * uv.y;
         y.x = gt.x - gv.x; y.y = gt.y - gv.y;
@@ -1238,7 +1305,7 @@ __global__ __launch_bounds__(BLOCK) void k_lbfgs_push_lite(double *x, const doub
         const double uv = u[e], xe = x[e] + a * uv;
         double gt = 0.0;
         if constexpr (LSE) gt = exp(xe - M) / S + lambda * xe;
-        else { double fl = 0.0; Obj::eval1(xe, Obj::kParam ? p0[e] : 0.0, lambda, fl, gt); }
+        else { double fl = 0.0; obj_eval1<Obj>(xe, ps_load<Obj>(pp, e), lambda, fl, gt); }
         sn[e] = a_s * uv; yn[e] = gt - g[e];
         x[e] = xe; g[e] = gt;
     }

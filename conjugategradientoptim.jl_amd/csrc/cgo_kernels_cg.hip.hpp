@@ -88,6 +88,7 @@ struct RParams {
     // 648–652 µs); at Infinity-Cache sizes the extra footprint costs more than it gains, so only BIG launches use it.
     double *xo; double *uo;
     Tail tail;
+    const double *p1, *p2, *p3;   // parameter slots 1–3 (run-time compiled objectives with kParams > 1 only)
 };
 
 // Workgroup reduction of N per-lane accumulators → one row of `partials`.
@@ -563,7 +564,7 @@ __device__ inline void store_partials_n(double (&acc)[N], double *partials, cons
 template <int NPTS> struct RW { static constexpr int W = (NPTS == 1) ? NR1 : (NPTS == 3 ? NR : (NPTS == 5 ? NR5 : NR7)); static constexpr int GU = RS_PER_POINT * NPTS, UU = GU + 1; };
 
 template <class Obj, int MODE, int NPTS>
-__device__ inline void cg_pair(const RParams &P, d2 &x, d2 &u, d2 p, double (&acc)[RW<NPTS>::W], bool &wx, bool &wu, d2 &gout) {
+__device__ inline void cg_pair(const RParams &P, d2 &x, d2 &u, const PV<Obj> &p, double (&acc)[RW<NPTS>::W], bool &wx, bool &wu, d2 &gout) {
     constexpr int R_GU = RW<NPTS>::GU, R_UU = RW<NPTS>::UU;
     if (MODE & R_ACCEPT) {
         x.x = x.x + P.a_acc * u.x;
@@ -574,7 +575,7 @@ __device__ inline void cg_pair(const RParams &P, d2 &x, d2 &u, d2 p, double (&ac
     double f0 = 0.0;
     constexpr bool need_g = (MODE & (R_DIR | R_TRIAL | R_INIT | R_RESET | R_UPG | R_GRAD | R_PROJ)) != 0;
     g = d2{0.0, 0.0};
-    if (need_g) Obj::eval2(x, p, P.s0, f0, g);  // g = ∇f(x), recomputed — never read from HBM
+    if (need_g) obj_eval2<Obj>(x, p, P.s0, f0, g);  // g = ∇f(x), recomputed — never read from HBM
     if (MODE & R_INIT) {
         acc[RS_F] += f0;
         acc[RS_GTGT] = dsum(acc[RS_GTGT], g.x, g.x);
@@ -601,17 +602,17 @@ __device__ inline void cg_pair(const RParams &P, d2 &x, d2 &u, d2 p, double (&ac
         double fd = 0.0;
         xp.x = x.x + P.a[0] * u.x;
         xp.y = x.y + P.a[0] * u.y;
-        Obj::eval2(xp, p, P.s0, fd, gout);
+        obj_eval2<Obj>(xp, p, P.s0, fd, gout);
     }
     if (MODE & R_PROJ) {  // gout carries x2 in and out (the caller loads/stores it)
         d2 z, gz, gt;
         double fz = 0.0;
         z.x = x.x + P.a[0] * u.x;
         z.y = x.y + P.a[0] * u.y;
-        Obj::eval2(z, p, P.s0, fz, gz);                 // df_xp of the accepted trial (solve_system.jl:46)
+        obj_eval2<Obj>(z, p, P.s0, fz, gz);                 // df_xp of the accepted trial (solve_system.jl:46)
         gout.x = gout.x + P.beta * gz.x;                // x_next[i] = x_next[i] + m*df_xp[i]   (:250-252)
         gout.y = gout.y + P.beta * gz.y;
-        Obj::eval2(gout, p, P.s0, acc[RS_F], gt);       // f_x_next = fdf!(df_xp, x_next)        (:177)
+        obj_eval2<Obj>(gout, p, P.s0, acc[RS_F], gt);       // f_x_next = fdf!(df_xp, x_next)        (:177)
         const double y0 = gt.x - g.x, y1 = gt.y - g.y;  // getβ(β_config, df_xp, df_x, u)       (:199-204)
         acc[RS_GTU] = dsum(acc[RS_GTU], gt.x, u.x);   acc[RS_GTU] = dsum(acc[RS_GTU], gt.y, u.y);
         acc[RS_GTGT] = dsum(acc[RS_GTGT], gt.x, gt.x); acc[RS_GTGT] = dsum(acc[RS_GTGT], gt.y, gt.y);
@@ -627,7 +628,7 @@ __device__ inline void cg_pair(const RParams &P, d2 &x, d2 &u, d2 p, double (&ac
             d2 xp, gt;
             xp.x = x.x + P.a[j] * u.x;
             xp.y = x.y + P.a[j] * u.y;
-            Obj::eval2(xp, p, P.s0, acc[b + RS_F], gt);
+            obj_eval2<Obj>(xp, p, P.s0, acc[b + RS_F], gt);
             const double y0 = gt.x - g.x, y1 = gt.y - g.y;
             acc[b + RS_GTU] = dsum(acc[b + RS_GTU], gt.x, u.x);   acc[b + RS_GTU] = dsum(acc[b + RS_GTU], gt.y, u.y);
             acc[b + RS_GTGT] = dsum(acc[b + RS_GTGT], gt.x, gt.x); acc[b + RS_GTGT] = dsum(acc[b + RS_GTGT], gt.y, gt.y);
@@ -645,10 +646,10 @@ __device__ inline void cg_single(const RParams &P, long long i, double (&acc)[RW
     constexpr int R_GU = RW<NPTS>::GU, R_UU = RW<NPTS>::UU;
     double x = P.x[i];
     double u = (MODE & (R_ACCEPT | R_DIR | R_TRIAL | R_UPG | R_GRADT | R_PROJ)) ? P.u[i] : 0.0;
-    const double p = Obj::kParam ? P.p0[i] : 0.0;
+    const PS<Obj> p = ps_load<Obj>(P, i);
     if (MODE & R_ACCEPT) { x = x + P.a_acc * u; P.xo[i] = x; }
     double g = 0.0, f0 = 0.0;
-    Obj::eval1(x, p, P.s0, f0, g);
+    obj_eval1<Obj>(x, p, P.s0, f0, g);
     if (MODE & R_INIT) { acc[RS_F] += f0; acc[RS_GTGT] = dsum(acc[RS_GTGT], g, g); P.uo[i] = -g; }
     if (MODE & (R_DIR | R_RESET)) {
         const double un = (MODE & R_DIR) ? (-g + P.beta * u) : -g;
@@ -657,13 +658,13 @@ __device__ inline void cg_single(const RParams &P, long long i, double (&acc)[RW
     }
     if (MODE & R_UPG) { const double t = u + g; acc[R_UU] = dsum(acc[R_UU], t, t); }
     if (MODE & R_GRAD) P.gout[i] = g;
-    if (MODE & R_GRADT) { double fd = 0.0, gg; Obj::eval1(x + P.a[0] * u, p, P.s0, fd, gg); P.gout[i] = gg; }
+    if (MODE & R_GRADT) { double fd = 0.0, gg; obj_eval1<Obj>(x + P.a[0] * u, p, P.s0, fd, gg); P.gout[i] = gg; }
     if (MODE & R_PROJ) {
         double fz = 0.0, gz, gt;
-        Obj::eval1(x + P.a[0] * u, p, P.s0, fz, gz);
+        obj_eval1<Obj>(x + P.a[0] * u, p, P.s0, fz, gz);
         const double xn = P.x2[i] + P.beta * gz;
         P.x2[i] = xn;
-        Obj::eval1(xn, p, P.s0, acc[RS_F], gt);
+        obj_eval1<Obj>(xn, p, P.s0, acc[RS_F], gt);
         const double y = gt - g;
         acc[RS_GTU] = dsum(acc[RS_GTU], gt, u); acc[RS_GTGT] = dsum(acc[RS_GTGT], gt, gt); acc[RS_GTG] = dsum(acc[RS_GTG], gt, g);
         acc[RS_YY] = dsum(acc[RS_YY], y, y); acc[RS_UY] = dsum(acc[RS_UY], u, y); acc[RS_YGT] = dsum(acc[RS_YGT], y, gt);
@@ -674,7 +675,7 @@ __device__ inline void cg_single(const RParams &P, long long i, double (&acc)[RW
             const int b = RS_PER_POINT * j;
             const double xp = x + P.a[j] * u;
             double gt;
-            Obj::eval1(xp, p, P.s0, acc[b + RS_F], gt);
+            obj_eval1<Obj>(xp, p, P.s0, acc[b + RS_F], gt);
             const double y = gt - g;
             acc[b + RS_GTU] = dsum(acc[b + RS_GTU], gt, u); acc[b + RS_GTGT] = dsum(acc[b + RS_GTGT], gt, gt); acc[b + RS_GTG] = dsum(acc[b + RS_GTG], gt, g);
             acc[b + RS_YY] = dsum(acc[b + RS_YY], y, y); acc[b + RS_UY] = dsum(acc[b + RS_UY], u, y); acc[b + RS_YGT] = dsum(acc[b + RS_YGT], y, gt);
@@ -735,8 +736,7 @@ __device__ inline void cg_launch(const RParams &Pin) {
     for (; i + step < hi; i += 2 * step) {
         d2 xa = ldg2<BIG>(P.x, i), xb = ldg2<BIG>(P.x, i + step);
         d2 ua = rd_u ? ldg2<BIG>(P.u, i) : d2{0.0, 0.0}, ub = rd_u ? ldg2<BIG>(P.u, i + step) : d2{0.0, 0.0};
-        const d2 pa = Obj::kParam ? ldg2<BIG>(P.p0, i) : d2{0.0, 0.0};
-        const d2 pb = Obj::kParam ? ldg2<BIG>(P.p0, i + step) : d2{0.0, 0.0};
+        const PV<Obj> pa = pv_load<Obj, BIG>(P, i), pb = pv_load<Obj, BIG>(P, i + step);
         bool wxa = false, wua = false, wxb = false, wub = false;
         d2 ga, gb;
         if (proj) { ga = ldg2<BIG>(P.x2, i); gb = ldg2<BIG>(P.x2, i + step); }
@@ -754,7 +754,7 @@ __device__ inline void cg_launch(const RParams &Pin) {
     if (i < hi) {
         d2 xa = ldg2<BIG>(P.x, i);
         d2 ua = rd_u ? ldg2<BIG>(P.u, i) : d2{0.0, 0.0};
-        const d2 pa = Obj::kParam ? ldg2<BIG>(P.p0, i) : d2{0.0, 0.0};
+        const PV<Obj> pa = pv_load<Obj, BIG>(P, i);
         bool wxa = false, wua = false;
         d2 ga;
         if (proj) ga = ldg2<BIG>(P.x2, i);

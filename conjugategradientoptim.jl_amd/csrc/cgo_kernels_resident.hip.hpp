@@ -71,12 +71,13 @@ struct ResParams {
     const ResProbePass *pr_script; int pr_n;  // DEVICE [pr_n]
     double *pr_rows;                          // DEVICE [pr_n][grid][RES_WMAX]: the totals EVERY workgroup holds after each pass
     ResProbeOut *pr_out;                      // DEVICE [pr_n]: what the member functions returned in workgroup 0
+    const double *p1, *p2, *p3;               // parameter slots 1–3 (run-time compiled objectives with kParams > 1 only)
 };
 
 template <class Obj, int NPTS, bool PROBE = false>
 struct ResDev {
     const ResParams &P;
-    double *xs, *us, *ps;      // LDS
+    double *xs, *us, *ps;      // LDS (ps: one chunk per parameter slot, P.chunk apart)
     int npairs; bool odd;      // pairs of this chunk; does this workgroup own the odd tail element (local index 2·npairs)?
     unsigned long long round;
     double *tot;               // LDS [RES_WMAX]
@@ -200,11 +201,11 @@ struct ResDev {
         for (int s = 0; s < W; ++s) acc[s] = 0.0;
         const long long t0 = clock();
         d2 *x2 = reinterpret_cast<d2 *>(xs), *u2 = reinterpret_cast<d2 *>(us);
-        const d2 *p2 = reinterpret_cast<const d2 *>(ps);
+        const ParamPtrs pl{ps, ps + P.chunk, ps + 2 * P.chunk, ps + 3 * P.chunk};   // (addresses only: slots ≥ K are never read)
         int i = tid;
         for (; i + BLOCK < npairs; i += 2 * BLOCK) {     // two independent pairs per trip
             d2 xa = x2[i], xb = x2[i + BLOCK], ua = u2[i], ub = u2[i + BLOCK];
-            const d2 pa = Obj::kParam ? p2[i] : d2{0.0, 0.0}, pb = Obj::kParam ? p2[i + BLOCK] : d2{0.0, 0.0};
+            const PV<Obj> pa = pv_load<Obj, false>(pl, i), pb = pv_load<Obj, false>(pl, i + BLOCK);
             bool wxa = false, wua = false, wxb = false, wub = false;
             d2 ga, gb;
             cg_pair<Obj, MODE, NP>(rp, xa, ua, pa, acc, wxa, wua, ga);
@@ -216,7 +217,7 @@ struct ResDev {
         }
         if (i < npairs) {
             d2 xa = x2[i], ua = u2[i];
-            const d2 pa = Obj::kParam ? p2[i] : d2{0.0, 0.0};
+            const PV<Obj> pa = pv_load<Obj, false>(pl, i);
             bool wxa = false, wua = false;
             d2 ga;
             cg_pair<Obj, MODE, NP>(rp, xa, ua, pa, acc, wxa, wua, ga);
@@ -224,7 +225,7 @@ struct ResDev {
             if (wua) u2[i] = ua;
         }
         if (odd && tid == 0) {   // the odd tail element of the global vector (objectives that are not pair-only)
-            rp.x = xs; rp.u = us; rp.p0 = ps; rp.xo = xs; rp.uo = us; rp.gout = nullptr; rp.x2 = nullptr;
+            rp.x = xs; rp.u = us; rp.p0 = pl.p0; rp.p1 = pl.p1; rp.p2 = pl.p2; rp.p3 = pl.p3; rp.xo = xs; rp.uo = us; rp.gout = nullptr; rp.x2 = nullptr;
             cg_single<Obj, MODE, NP>(rp, 2LL * npairs, acc);
         }
         const long long t1 = clock();
@@ -308,7 +309,11 @@ __global__ __launch_bounds__(BLOCK, 1) void k_resident(const ResParams P) {   //
     for (long long i = tid; i < cnt; i += BLOCK) {
         xs[i] = P.x[lo + i];
         us[i] = P.u[lo + i];
-        if (Obj::kParam) ps[i] = P.p0[lo + i];
+        constexpr int K = obj_nparams<Obj>();
+        if constexpr (K > 0) ps[i] = P.p0[lo + i];
+        if constexpr (K > 1) ps[P.chunk + i] = P.p1[lo + i];
+        if constexpr (K > 2) ps[2 * P.chunk + i] = P.p2[lo + i];
+        if constexpr (K > 3) ps[3 * P.chunk + i] = P.p3[lo + i];
     }
     __syncthreads();
     ResDev<Obj, NPTS, PROBE> v{P, xs, us, ps, (int)(cnt >> 1), (cnt & 1) != 0, P.round0, tot, fs, 0, 0, 0};

@@ -10,6 +10,8 @@
 
 #include <hip/hiprtc.h>
 
+#include <mutex>
+#include <tuple>
 #include <vector>
 
 #include "cgo_hip_backend.hpp"
@@ -58,12 +60,34 @@ hipFunction_t RtcModule::fused(int mode, bool big) const {
 }
 
 // the embedded kernel templates + the user's objective as one translation unit
-static std::string rtc_program_source(const std::string &source, bool has_param) {
+static std::string rtc_program_source(const std::string &source, int n_params) {
+    const bool has_param = n_params > 0;
+    const std::string K = std::to_string(n_params);
     std::string src;
     for (const char *c : kRtcKernelSourceChunks) src += c;
     src += "\nnamespace cgo { namespace dev {\n";
     if (source.find("struct UserObjective") != std::string::npos) {
         src += source;
+        // the slots the struct reads are the slots the objective holds (scalar-p structs: as ever, kParam is taken as given)
+        src += "\nstatic_assert(!(ObjParams<UserObjective>::array || " + K + " > 1) || obj_nparams<UserObjective>() == " + K + ",\n"
+               "              \"UserObjective: kParams does not match the n_params the objective was created with (" + K + ")\");\n";
+    } else if (n_params > 1) {
+        // element-wise body with more than one parameter slot: slot 0 is `p`, slots 1–3 are `p1`, `p2`, `p3`
+        src += "struct UserObjective {\n";
+        src += "    static constexpr int kParams = " + K + ";\n";
+        src += "    static constexpr bool kParam = true;\n";
+        src += "    static constexpr bool kPairOnly = false;\n";
+        src += "    __device__ static inline void eval1(double x, const double (&pv)[" + K + "], double s0, double &f, double &g) {\n";
+        src += "        const double p = pv[0]";
+        for (int j = 1; j < n_params; ++j) src += ", p" + std::to_string(j) + " = pv[" + std::to_string(j) + "]";
+        src += ";\n";
+        for (int j = 1; j < n_params; ++j) src += "        (void)p" + std::to_string(j) + ";\n";
+        src += "        (void)p;\n        double fi = 0.0, gi = 0.0;\n        {\n" + source + "\n        }\n        f += fi; g = gi;\n    }\n";
+        src += "    __device__ static inline void eval2(d2 xx, const d2 (&pp)[" + K + "], double s0, double &f, d2 &gg) {\n";
+        src += "        double g0, g1, pa[" + K + "], pb[" + K + "];\n";
+        for (int j = 0; j < n_params; ++j) src += "        pa[" + std::to_string(j) + "] = pp[" + std::to_string(j) + "].x; pb[" + std::to_string(j) + "] = pp[" + std::to_string(j) + "].y;\n";
+        src += "        eval1(xx.x, pa, s0, f, g0);\n        eval1(xx.y, pb, s0, f, g1);\n";
+        src += "        gg.x = g0; gg.y = g1;\n    }\n};\n";
     } else {
         // element-wise body: statements computing `fi` (objective term) and `gi` (its derivative)
         // from `x` (the element), `p` (its parameter, 0 if none) and `s0` (a scalar)
@@ -120,9 +144,20 @@ static int rtc_build(const std::string &src, const char *name, const std::vector
     return CGO_OK;
 }
 
-int rtc_compile_objective(int device, const std::string &source, bool has_param,
+int rtc_compile_objective(int device, const std::string &source, int n_params,
                           std::shared_ptr<RtcModule> &out, std::string &log) {
     if (hipSetDevice(device) != hipSuccess) { log = "hipSetDevice failed"; return CGO_EHIP; }
+    // A module depends on (device, source, n_params) only, not on the objective's length, and is never changed once loaded: while
+    // an objective still holds the module of the same text, the next one shares it instead of compiling for seconds again
+    // (the barrier method's two objectives per call, a sweep over sizes).  Not owned here: the last objective unloads it.
+    static std::mutex mu;
+    static std::map<std::tuple<int, int, std::string>, std::weak_ptr<RtcModule>> live;
+    const auto key = std::make_tuple(device, n_params, source);
+    std::lock_guard<std::mutex> lock(mu);
+    if (auto it = live.find(key); it != live.end()) {
+        if (auto m = it->second.lock()) { out = m; return CGO_OK; }
+        live.erase(it);
+    }
     std::vector<Want> wants;
     // every per-objective row of cgo_instances.def for UserObjective, in both streaming policies
     const std::string uo = "<cgo::dev::UserObjective, ";
@@ -153,8 +188,9 @@ int rtc_compile_objective(int device, const std::string &source, bool has_param,
     CGO_RTC_RESIDENT_ROWS(ROW)
 #undef ROW
     auto mod = std::make_shared<RtcModule>();
-    if (int rc = rtc_build(rtc_program_source(source, has_param), "cgo_user_objective.hip", wants, mod->mod, mod->fn, log)) return rc;
-    mod->user_source = source; mod->has_param = has_param; mod->device = device;
+    if (int rc = rtc_build(rtc_program_source(source, n_params), "cgo_user_objective.hip", wants, mod->mod, mod->fn, log)) return rc;
+    mod->user_source = source; mod->n_params = n_params; mod->device = device;
+    live[key] = mod;
     out = mod;
     return CGO_OK;
 }
@@ -166,7 +202,7 @@ int rtc_compile_resident_probe(RtcModule &m, std::string &log) {
 #define ROW(NPTS) wants.push_back({"resprobe:" #NPTS, "cgo::dev::k_resident<cgo::dev::UserObjective, " #NPTS ", true>"});
     CGO_RTC_RESIDENT_ROWS(ROW)
 #undef ROW
-    return rtc_build(rtc_program_source(m.user_source, m.has_param), "cgo_user_objective_probe.hip", wants, m.probe_mod, m.fn, log);
+    return rtc_build(rtc_program_source(m.user_source, m.n_params), "cgo_user_objective_probe.hip", wants, m.probe_mod, m.fn, log);
 }
 
 }  // namespace cgo

@@ -23,7 +23,7 @@ struct RtcModule {
     hipFunction_t resident_probe(int npts) const;
     hipModule_t probe_mod = nullptr;
     std::string user_source;
-    bool has_param = false;
+    int n_params = 0;   // parameter slots the objective was created with (0 … CGO_MAX_PARAM_SLOTS)
     int device = 0;
     hipFunction_t spec(bool big, bool push) const;   // k_lbfgs_combine_spec<UserObjective, big, push>
     hipFunction_t lite(bool big) const;              // k_lbfgs_push_lite<UserObjective, big>
@@ -31,8 +31,9 @@ struct RtcModule {
 
 // `source`: either a complete `struct UserObjective { … };` (functor interface of
 // cgo_kernels.hip.hpp) or just the statements of an element-wise body that compute `fi` and
-// `gi` from `x`, `p`, `s0`.  Returns CGO_OK / CGO_EINVAL (compile log in `log`) / CGO_EHIP.
-int rtc_compile_objective(int device, const std::string &source, bool has_param,
+// `gi` from `x`, `p` (slot 0), `p1`, `p2`, `p3` (slots 1–3, as far as n_params goes), `s0`.  A struct that declares kParams
+// must declare n_params of them.  Returns CGO_OK / CGO_EINVAL (compile log in `log`) / CGO_EHIP.
+int rtc_compile_objective(int device, const std::string &source, int n_params,
                           std::shared_ptr<RtcModule> &out, std::string &log);
 // the PROBE form of the module's resident kernel, compiled and loaded on first use; CGO_OK if it is there already
 int rtc_compile_resident_probe(RtcModule &m, std::string &log);

@@ -271,6 +271,21 @@ mutable struct DeviceObjective
         return o
     end
 end
+const MAX_PARAM_SLOTS = 4   # CGO_MAX_PARAM_SLOTS
+"parameter vector `slot` (0-based, < numparams(o)) from a host vector"
+function setparam!(o::DeviceObjective, v::Vector{Float64}, slot::Integer = 0)
+    check(ccall((:cgo_objective_set_param_host, libcgo), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), o.h, slot, v))
+end
+"the same from `o.n` doubles already in this GPU's memory (a ROCArray's pointer): device-to-device copy"
+function setparamdevice!(o::DeviceObjective, dev::Ptr{Float64}, slot::Integer = 0)
+    check(ccall((:cgo_objective_set_param_device, libcgo), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), o.h, slot, dev))
+end
+"how many parameter vectors the objective's kernels read"
+function numparams(o::DeviceObjective)
+    k = Ref{Int32}(0)
+    check(ccall((:cgo_objective_num_params, libcgo), Cint, (Ptr{Cvoid}, Ref{Int32}), o.h, k))
+    return Int(k[])
+end
 "f(x) = ½ Σ D_i x_i²"
 function QuadDiag(D::Vector{Float64}, ctx::Context = defaultcontext())
     o = DeviceObjective(0, length(D), ctx)
@@ -286,15 +301,30 @@ RosenbrockChained(n::Integer, ctx::Context = defaultcontext()) = DeviceObjective
 A user-supplied element-wise f/∇f: `source` is the HIP C++ body setting `fi` and `gi` from `x`, `p`,
 `s0` (e.g. `"gi = p*x; fi = 0.5*(gi*x);"`), compiled at run time into the fused kernels — the device
 counterpart of handing `minimizeobjective` your own `fdf!` closure (src/engine/optim.jl:25).
+`param` is one vector (slot 0, `p`) or a vector of up to 4 vectors (slots 0–3: `p`, `p1`, `p2`, `p3` in a body;
+a `struct UserObjective` declares `kParams = K` and takes `const double (&p)[K]`, include/cgo.h).
 """
-function ElementwiseObjective(n::Integer, source::String; param::Union{Nothing,Vector{Float64}} = nothing, ctx::Context = defaultcontext(),
+function ElementwiseObjective(n::Integer, source::String; param::Union{Nothing,Vector{Float64},Vector{Vector{Float64}}} = nothing,
+                              ctx::Context = defaultcontext(),
                               cheap::Bool = false)   # cheap: ≲ 10 flops per element → seven speculative trial steps per launch
     r = Ref{Ptr{Cvoid}}(C_NULL)
-    check(ccall((:cgo_objective_create_from_source, libcgo), Cint,
-                (Ptr{Cvoid}, Cstring, Int32, Int64, Int64, Int64, Ref{Ptr{Cvoid}}),
-                ctx.h, source, param === nothing ? 0 : 1, n, 0, n, r))
-    o = DeviceObjective(r[], ctx, Int(n))
-    param === nothing || check(ccall((:cgo_objective_set_param_host, libcgo), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), o.h, 0, param))
+    if param isa Vector{Vector{Float64}}
+        @assert length(param) <= MAX_PARAM_SLOTS
+        check(ccall((:cgo_objective_create_from_source_ex, libcgo), Cint,
+                    (Ptr{Cvoid}, Cstring, Int32, Int64, Int64, Int64, Ref{Ptr{Cvoid}}),
+                    ctx.h, source, length(param), n, 0, n, r))
+        o = DeviceObjective(r[], ctx, Int(n))
+        for (j, v) in enumerate(param)
+            @assert length(v) == n
+            setparam!(o, v, j - 1)
+        end
+    else
+        check(ccall((:cgo_objective_create_from_source, libcgo), Cint,
+                    (Ptr{Cvoid}, Cstring, Int32, Int64, Int64, Int64, Ref{Ptr{Cvoid}}),
+                    ctx.h, source, param === nothing ? 0 : 1, n, 0, n, r))
+        o = DeviceObjective(r[], ctx, Int(n))
+        param === nothing || setparam!(o, param, 0)
+    end
     cheap && check(ccall((:cgo_objective_set_cost_class, libcgo), Cint, (Ptr{Cvoid}, Int32), o.h, 1))
     return o
 end
@@ -449,19 +479,50 @@ setupPrimalBarrierConfig(barrier_tol::T, barrier_growth_factor::T, max_iters::In
 
 # The box constraints of examples/constrained.jl:18-48 (`boxhdh!` + CvxInequalityConstraint, :38-60) as a
 # device-side descriptor: ψ = −Σ log(−h_i) and ∇ψ (:70-94) become element-wise terms of the fused kernels.
+# `lb`, `ub`: one interval for every variable (Float64: constants of the generated source) or `lbs::Vector`, `ubs::Vector` as in
+# examples/constrained.jl:22-31 (the bounds travel as the objective's last two parameter vectors).
 struct BoxConstraints
-    lb::Float64
-    ub::Float64
+    lb::Union{Float64,Vector{Float64}}
+    ub::Union{Float64,Vector{Float64}}
 end
+pervariable(box::BoxConstraints) = box.lb isa Vector || box.ub isa Vector
+boundvector(v, D::Integer) = v isa Vector ? (@assert(length(v) == D); v) : fill(v, D)
+baseparams(base::String) = strip(base) == "ObjQuadDiag" ? 1 : strip(base) in ("ObjRosenPaired", "ObjBooth") ? 0 :
+    (m = match(r"\bkParams\s*=\s*(\d+)", base)) !== nothing ? parse(Int, m.captures[1]) :
+    (occursin(r"\bkParam\s*=\s*true", base) ? 1 : 0)
 hexlit(v::Float64) = isinf(v) ? (v > 0 ? "(1.0/0.0)" : "(-1.0/0.0)") : string(v)   # shortest round-trip decimal
 function barrier_objective_source(base::String, box::BoxConstraints; barrier::Bool = true)
     name = strip(base) in ("ObjQuadDiag", "ObjRosenPaired", "ObjBooth") ? strip(base) : "BaseObjective"
     pre = name == "BaseObjective" ? base : ""
+    (!barrier && baseparams(base) > 1) && return pre * "\nstruct UserObjective : BaseObjective {};\n"   # the array interface, as it is
     barrier || return pre * """
 struct UserObjective { using B = $name; static constexpr bool kParam = B::kParam; static constexpr bool kPairOnly = B::kPairOnly;
   __device__ static inline void eval1(double x, double p, double s0, double &f, double &g) { B::eval1(x, p, s0, f, g); }
   __device__ static inline void eval2(d2 xx, d2 pp, double s0, double &f, d2 &gg) { B::eval2(xx, pp, s0, f, gg); } };
 """
+    if pervariable(box)   # the base's own slots, then lb, then ub; the same bar() expression on loaded bounds
+        kb = baseparams(base)
+        @assert kb + 2 <= MAX_PARAM_SLOTS
+        return pre * """
+struct UserObjective { using B = $name; static constexpr int KB = obj_nparams<B>(); static_assert(KB == $kb, "the base objective's parameter slots");
+  static constexpr int kParams = KB + 2; static constexpr bool kParam = true; static constexpr bool kPairOnly = B::kPairOnly;
+  __device__ static inline void bar(double x, double lb, double ub, double &psi, double &dpsi) {
+    const double hu = x - (ub), hl = (lb) - x;
+    const double cu = hu > 0.0 ? 0.0 : hu, cl = hl > 0.0 ? 0.0 : hl;        // clamp!(fi_evals, -Inf, 0)  :81
+    psi = -(log(-cu) + log(-cl));                                            // :82
+    double d = 0.0; d -= 1.0 / cu; d -= -1.0 / cl; dpsi = d; }               // :85-89
+  __device__ static inline void eval1(double x, const double (&p)[kParams], double s0, double &f, double &g) {
+    double f0 = 0.0, g0 = 0.0, psi, dpsi; PS<B> pb; pb.v[0] = 0.0;
+    for (int j = 0; j < KB; ++j) pb.v[j] = p[j];
+    obj_eval1<B>(x, pb, 0.0, f0, g0); bar(x, p[KB], p[KB + 1], psi, dpsi);
+    f += s0 * f0 + psi; g = s0 * g0 + dpsi; }                                // evalbarrier!  :111-128
+  __device__ static inline void eval2(d2 xx, const d2 (&pp)[kParams], double s0, double &f, d2 &gg) {
+    double f0 = 0.0, psi0, psi1, d0, d1; d2 g0; PV<B> pb; pb.v[0] = d2{0.0, 0.0};
+    for (int j = 0; j < KB; ++j) pb.v[j] = pp[j];
+    obj_eval2<B>(xx, pb, 0.0, f0, g0); bar(xx.x, pp[KB].x, pp[KB + 1].x, psi0, d0); bar(xx.y, pp[KB].y, pp[KB + 1].y, psi1, d1);
+    f += s0 * f0 + (psi0 + psi1); gg.x = s0 * g0.x + d0; gg.y = s0 * g0.y + d1; } };
+"""
+    end
     return pre * """
 struct UserObjective { using B = $name; static constexpr bool kParam = B::kParam; static constexpr bool kPairOnly = B::kPairOnly;
   __device__ static inline void bar(double x, double &psi, double &dpsi) {
@@ -486,14 +547,20 @@ end
 function primalbarriermethod!(constraints::BoxConstraints, f0df0::String, x_initial::Vector{Float64},
                               centering_config::CGConfig{Float64,BT,ET}, linesearch_config::LineSearchConfig,
                               barrier_config::PrimalBarrierConfig{Float64}, rerun_config_tuples...;
-                              param::Union{Nothing,Vector{Float64}} = nothing) where {BT,ET}
+                              param::Union{Nothing,Vector{Float64},Vector{Vector{Float64}}} = nothing) where {BT,ET}
     bc = barrier_config
     D = length(x_initial)
+    barparam = param                                                           # array bounds: two more slots after the base's own
+    if pervariable(constraints)
+        own = param === nothing ? Vector{Float64}[] : (param isa Vector{Float64} ? [param] : param)
+        @assert length(own) + 2 <= MAX_PARAM_SLOTS
+        barparam = vcat(own, [boundvector(constraints.lb, D), boundvector(constraints.ub, D)])
+    end
     rets = Vector{Vector{Results{Float64,TraceContainer{Float64,ET}}}}()
     assemble(status, it, t) = PrimalBarrierResults(rets[1:it], status, it, t,
         isempty(rets) ? 0 : sum(sum(sum(r.trace.objective_evals; init = 0) for r in rr; init = 0) for rr in rets[1:it]; init = 0))
     (any(x_initial .- constraints.ub .>= 0) || any(constraints.lb .- x_initial .>= 0)) && return assemble(:infeasible_start, 0, bc.t_initial)
-    obj = ElementwiseObjective(D, barrier_objective_source(f0df0, constraints); param = param)
+    obj = ElementwiseObjective(D, barrier_objective_source(f0df0, constraints); param = barparam)
     t = bc.t_initial
     if !isfinite(t) || t < 0                                                   # verifyt0  :259-276
         base = ElementwiseObjective(D, barrier_objective_source(f0df0, constraints; barrier = false); param = param)

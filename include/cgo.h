@@ -247,10 +247,33 @@ int cgo_objective_create(cgo_ctx *ctx, int32_t kind, int64_t n_global, int64_t o
  *     (scalar slot 0), e.g.  "gi = p*x; fi = 0.5*(gi*x);"   or
  *   - a complete `struct UserObjective { kParam; kPairOnly; eval2(); eval1(); };` (the functor
  *     interface of csrc/cgo_kernels.hip.hpp) for objectives coupling the two elements of a pair.
- * On a compile error returns CGO_EINVAL; cgo_last_error() holds the hiprtc log. */
+ * On a compile error returns CGO_EINVAL; cgo_last_error() holds the hiprtc log.
+ * has_param != 0 means one parameter vector (n_params = 1 of the _ex form below). */
 int cgo_objective_create_from_source(cgo_ctx *ctx, const char *source, int32_t has_param,
                                      int64_t n_global, int64_t offset, int64_t n_local,
                                      cgo_objective **out);
+/* The same with up to CGO_MAX_PARAM_SLOTS parameter vectors (per-element data: weights, targets, bounds …), each of
+ * n_local doubles, read by every kernel the objective is compiled into.
+ *   - An element-wise body sees slot 0 as `p` and slots 1, 2, 3 as `p1`, `p2`, `p3`, e.g. (n_params = 3)
+ *       "const double d = x - p1; gi = p*d + p2; fi = 0.5*((p*d)*d) + p2*x;"
+ *   - A `struct UserObjective` that reads more than one slot declares `static constexpr int kParams = K;` (2 ≤ K ≤ 4)
+ *     instead of relying on kParam, and takes the slots as arrays:
+ *       eval1(double x, const double (&p)[K], double s0, double &f, double &g)
+ *       eval2(d2 x,     const d2     (&p)[K], double s0, double &f, d2 &g)
+ *     A struct whose kParams differs from n_params (or that declares none while n_params > 1) does not compile:
+ *     CGO_EINVAL, the message in cgo_last_error().
+ * Every slot must be set (cgo_objective_set_param_host / _device / cgo_objective_fill_param) before a solve starts:
+ * CGO_ESTATE otherwise, naming the first slot that is missing.  Built-in objectives keep their 0 or 1 slot.
+ * Each slot adds 8 B per element to every launch that evaluates the objective (accept + direction + trial:
+ * (32 + 8·n_params) B, trial: (16 + 8·n_params) B), and one vector to what the resident solver keeps in LDS, so the
+ * largest shard it takes shrinks by the factor 3/(2 + n_params) against a one-slot objective.  The placement search
+ * (cgo_solver_placement_info) times a three-stream mix and does not run for n_params > 1. */
+#define CGO_MAX_PARAM_SLOTS 4
+int cgo_objective_create_from_source_ex(cgo_ctx *ctx, const char *source, int32_t n_params /* 0 … CGO_MAX_PARAM_SLOTS */,
+                                        int64_t n_global, int64_t offset, int64_t n_local,
+                                        cgo_objective **out);
+/* how many parameter slots the objective reads (built-in: 0 or 1) */
+int cgo_objective_num_params(cgo_objective *obj, int32_t *n_params);
 /* The reference's objective contract itself: `f = fdf!(g, x)` (src/engine/optim.jl:25, src/cg_utils.jl:19; exemplar
  * examples/helpers/test_funcs.jl:3-12) as a C callback — what Julia's `@cfunction` of an existing `fdf!` closure
  * produces, so that `minimizeobjective(boothfdf!, x0, config, ls)` (examples/min.jl:41) is a drop-in without rewriting
@@ -268,6 +291,9 @@ int cgo_objective_destroy(cgo_objective *obj);
 int cgo_objective_set_param_host(cgo_objective *obj, int32_t slot, const double *host_local);
 int cgo_objective_fill_param(cgo_objective *obj, int32_t slot, int32_t fill_kind, uint64_t seed,
                              double lo, double hi);
+/* The same for a vector that already lives in THIS GPU's memory: n_local doubles, copied device-to-device like
+ * cgo_solver_set_x0_device.  All three setters take slot < cgo_objective_num_params (CGO_EINVAL otherwise). */
+int cgo_objective_set_param_device(cgo_objective *obj, int32_t slot, const double *dev_local);
 int cgo_objective_set_scalar(cgo_objective *obj, int32_t slot, double value);
 /* Cost class of a user objective: how many speculative trial steps a fused launch evaluates.
  * 0 (default for cgo_objective_create_from_source): heavier than a few flops per element — one step per launch
@@ -602,7 +628,8 @@ int cgo_bench_kernel(cgo_ctx *ctx, cgo_objective *obj, int32_t kernel_kind, int6
 int cgo_bench_stream_mix(cgo_ctx *ctx, int64_t n, int32_t reps, double *median_us, double *best_us);
 /* Placement search of a solver on a pure-HBM problem size: the time of that bare mix on the buffers as
  * first allocated, on the triple (x, u, D) the solver kept, and how many candidate triples were timed (0 = no search:
- * problem below the pure-HBM threshold, CGO_PLACE_TUNE=0, or not enough free memory for the spare buffers). */
+ * problem below the pure-HBM threshold, CGO_PLACE_TUNE=0, not enough free memory for the spare buffers, or an objective
+ * with more than one parameter slot: the mix that is timed has the three streams x, u, D). */
 int cgo_solver_placement_info(cgo_solver *s, double *as_allocated_us, double *chosen_us, int32_t *candidates);
 
 #ifdef __cplusplus
