@@ -780,7 +780,13 @@ class Solver:
                 return buf.value.decode()
         return ""
 
-    def probe_launch(self, kind_name: str, variant: int, a_acc: float, beta: float, a: Sequence[float], x, u=None, aux=None):
+    def set_lazy_direction(self, on: bool = True):
+        """Force the lazy-direction launches on or off for this solver, before start() (cgo_solver_set_lazy_direction): on an
+        eligible solver every second accept + direction + trial launch leaves u unstored and the next one rebuilds it."""
+        check(_lib.lib().cgo_solver_set_lazy_direction(self._h, int(bool(on))))
+
+    def probe_launch(self, kind_name: str, variant: int, a_acc: float, beta: float, a: Sequence[float], x, u=None, aux=None,
+                     beta_prev: Optional[float] = None):
         """ONE launch of kind `kind_name` with mode bits `variant` on this rank's host vectors (cgo_solver_probe_launch): returns
         dict(sums=the whole reduced row, x=, u=, g= the vectors after the launch, symbol=the instantiation).  A test entry point:
         the solver is for probing only from the first call on.
@@ -794,6 +800,8 @@ class Solver:
         the pass-1 row {Σ (v/max)², 0…}.  symbol joins the launches with " + "."""
         L = _lib.lib()
         kk = [L.cgo_kernel_kind_name(k).decode() for k in range(L.cgo_num_kernel_kinds())].index(kind_name)
+        if beta_prev is not None:   # the lazy-direction variants (R_ULAG = 1024): u ← −∇f(x) + beta_prev·u on load
+            check(L.cgo_solver_probe_set_beta_prev(self._h, float(beta_prev)))
         n = self.obj.n_local
         vec = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float64)
         x, u, aux = vec(x), vec(u), vec(aux)

@@ -28,6 +28,12 @@ double bytes_r(int obj_kind, int mode, int64_t n, int n_params) {
     else if (mode == R_DIR || mode == (R_DIR | R_TRIAL)) v = 2 + p + 1;
     else if (mode == R_PROJ) v = 3 + p + 1;
     else if (mode == R_EDGES) v = 0;
+    // lazy direction: A reads x, u, D and writes x; B is the plain launch on the lagged pair; a trial in the lagged state
+    // writes nothing; the materialise pass writes u
+    else if (mode == (R_ACCEPT | R_DIR | R_TRIAL | R_NOWU)) v = 2 + p + 1;
+    else if (mode == (R_ULAG | R_ACCEPT | R_DIR | R_TRIAL)) v = 2 + p + 2;
+    else if (mode == (R_ULAG | R_TRIAL)) v = 2 + p;
+    else if (mode == R_ULAG) v = 2 + p + 1;
     return 8.0 * (double)n * (double)v;
 }
 
@@ -54,8 +60,17 @@ static int launch_cg(int mode, int npts, const RParams &P, int grid, hipStream_t
 #define ROW(MODE, MAXPTS) case (MODE): with_points<MAXPTS>(npts, [&](auto n) { k_cg<Obj, (MODE), decltype(n)::value, BIG><<<grid, BLOCK, 0, st>>>(P); }); return 0;
     CGO_CG_ROWS(ROW)
 #undef ROW
-    default: return -1;
+    default: break;
     }
+    if constexpr (BIG) {   // the lazy-direction rows: pure-HBM streaming only
+        switch (mode) {
+#define ROW(MODE, MAXPTS) case (MODE): with_points<MAXPTS>(npts, [&](auto n) { k_cg<Obj, (MODE), decltype(n)::value, true><<<grid, BLOCK, 0, st>>>(P); }); return 0;
+        CGO_CG_LAG_ROWS(ROW)
+#undef ROW
+        default: break;
+        }
+    }
+    return -1;
 }
 
 // Row width of a CG launch: 7 sums per trial point + 2 direction sums, padded (10 or 24).
@@ -69,11 +84,18 @@ int HipBackend::launch_r(int kk, int mode, double a_acc, double beta, const doub
                          double *sums) {
     if (int rc = pipe_drain()) return rc;
     pipe_streak_ = 0;  // a host-driven launch: the streak of controller-eligible launches ends
+    // A launch that does not rebuild the lagged direction itself: one that reads u gets it stored first, one that overwrites
+    // u without reading it (R_INIT, R_RESET) simply ends the lag.  (accept_dir_trial / trial choose the lag modes; a probe
+    // never meets the flag.)
+    if (u_lag_ && !(mode & R_ULAG)) {
+        if (mode & (R_ACCEPT | R_DIR | R_TRIAL | R_UPG | R_GRADT | R_PROJ)) { if (int rc = materialize_u()) return rc; }
+        else if (mode & (R_INIT | R_RESET)) u_lag_ = false;
+    }
     int grid = 0;
     const int npts = npts_for(k);
     if (int rc = launch_r_kernel(kk, mode, a_acc, beta, a, k, npts, nullptr, &grid)) return rc;
     total_launches_++;
-    const bool has_sums = (mode != R_ACCEPT && mode != R_GRAD && mode != R_GRADT);
+    const bool has_sums = (mode != R_ACCEPT && mode != R_GRAD && mode != R_GRADT && mode != R_ULAG);
     const bool fused = has_sums && tail_fused(grid);   // the launch's last workgroup already left the sums (finish_tail)
     if (has_sums && chain()) {   // 24- or 32-slot rows: the sums + this rank's eight edge values (cgo_kernels_chain.hip.hpp)
         const bool three = chain_npts(mode, npts) == 3;
@@ -102,6 +124,50 @@ int HipBackend::launch_r(int kk, int mode, double a_acc, double beta, const doub
     }
     if (prof_on_) prof_commit(kk, bytes_r(obj_->kind, mode, obj_->n_local, obj_->nparams()));
     return CGO_OK;
+}
+
+// ---- lazy direction -------------------------------------------------------------------------------------
+// Eligible: the pure-HBM, host-driven launches of a built-in element-wise objective, updated in place.  The lag launches exist
+// as BIG instantiations only, and lazy on must compute bit for bit what lazy off computes, so both the plain accept + dir +
+// trial launch and the plain trial launch of this solver have to be BIG ones (same partition, same order of additions).
+bool HipBackend::lazy_eligible() const {
+    if (!lazy_on_ || !rmode_ || chain() || sys_on_ || probe_ || pingpong_ == 1) return false;
+    if (obj_->kind != CGO_OBJ_QUAD_DIAG && obj_->kind != CGO_OBJ_ROSENBROCK_PAIRED && obj_->kind != CGO_OBJ_BOOTH) return false;
+    if (const char *e = getenv("CGO_PINGPONG")) { if (e[0] == '1') return false; }
+    if (ctl_depth() > 0) return false;
+    const int64_t n = obj_->n_local;
+    const int hp = obj_->nparams();
+    return bytes_r(obj_->kind, R_ACCEPT | R_DIR | R_TRIAL, n, hp) > big_bytes(false) && bytes_r(obj_->kind, R_TRIAL, n, hp) > big_bytes(true);
+}
+
+// Every reader of the stored direction other than the lag launches: store u_{k+1} = −∇f(x_{k+1}) + β_k·u_k now.  Not a launch
+// the solve asked for (total_launches stays); the profile shows it under its own kind.
+int HipBackend::materialize_u() {
+    if (!u_lag_) return CGO_OK;
+    const int64_t asked = total_launches_;
+    const int rc = launch_r(KK_MATERIALIZE_U, R_ULAG, 0.0, 0.0, nullptr, 0, false, nullptr);
+    total_launches_ = asked;
+    if (rc) return rc;
+    u_lag_ = false;
+    return CGO_OK;
+}
+
+// accept + direction + trial and trial of the k_cg family, alternating between the two lag launches where eligible
+int HipBackend::accept_dir_trial_r(double a_acc, double beta, const double *a, int k, double *s) {
+    if (!lazy_eligible()) return launch_r(KK_ACCEPT_DIR_TRIAL, R_ACCEPT | R_DIR | R_TRIAL, a_acc, beta, a, k, true, s);
+    if (!u_lag_) {   // launch A: x ← x + a·u, the new direction in registers only
+        if (int rc = launch_r(KK_ACCEPT_TRIAL_LAZY, R_ACCEPT | R_DIR | R_TRIAL | R_NOWU, a_acc, beta, a, k, true, s)) return rc;
+        u_lag_ = true; beta_lag_ = beta;
+        return CGO_OK;
+    }
+    // launch B: rebuilds the direction A left unstored, then today's launch
+    if (int rc = launch_r(KK_ACCEPT_DIR_TRIAL, R_ULAG | R_ACCEPT | R_DIR | R_TRIAL, a_acc, beta, a, k, true, s)) return rc;
+    u_lag_ = false;
+    return CGO_OK;
+}
+int HipBackend::trial_r(const double *a, int k, double *s) {
+    if (u_lag_ && lazy_eligible()) return launch_r(KK_TRIAL, R_ULAG | R_TRIAL, 0, 0, a, k, true, s);   // 24 B: nothing stored, still lagged
+    return launch_r(KK_TRIAL, R_TRIAL, 0, 0, a, k, true, s);
 }
 
 // Fused reduction tail (finish_tail): a host-driven launch of the k_cg / k_chain family takes the next sequence number
@@ -136,7 +202,7 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
     if (obj_->unset_slot() >= 0) return param_unset_error(obj_->unset_slot());
     const int64_t n = obj_->n_local;
     if (mode & (R_GRAD | R_GRADT)) { if (int rc = ensure_ga()) return rc; }
-    const bool has_sums = (mode != R_ACCEPT && mode != R_GRAD && mode != R_GRADT);
+    const bool has_sums = (mode != R_ACCEPT && mode != R_GRAD && mode != R_GRADT && mode != R_ULAG);
     if (chain()) {
         const double bytes = bytes_r(obj_->kind, mode, n, false);
         const bool big = bytes > big_bytes(mode == R_TRIAL || mode == R_UPG);
@@ -151,11 +217,13 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
     P.x = xc_; P.u = uc_; P.gout = ga_.p; obj_->param_args(P); P.n = n;
     P.xo = xc_; P.uo = uc_;
     P.a_acc = a_acc; P.beta = beta; P.s0 = obj_->s0; P.partials = ctx_->partials;
+    P.beta_prev = beta_lag_;
     P.ctl = ctl;
     P.x2 = xn_;
     for (int j = 0; j < MAXP; ++j) P.a[j] = (a && j < k) ? a[j] : ((a && k > 0) ? a[k - 1] : 0.0);
     const double bytes = bytes_r(obj_->kind, mode, n, obj_->nparams());
-    const bool big = bytes > big_bytes(mode == R_TRIAL || mode == R_UPG);
+    const bool lag = (mode & (R_ULAG | R_NOWU)) != 0;   // BIG instantiations only (lazy_eligible)
+    const bool big = lag || bytes > big_bytes(mode == R_TRIAL || mode == R_UPG);
     const int grid = big ? GRID_BIG : grid_cg(n, npts);
     *grid_out = grid;
     last_mode_ = mode; last_npts_ = npts; last_big_ = big;
@@ -170,7 +238,7 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
         }
     }
     if (P.tail.tickets) P.partials = ctx_->partials_f;
-    const bool wr_x = (mode & R_ACCEPT) != 0, wr_u = (mode & (R_DIR | R_INIT | R_RESET)) != 0;
+    const bool wr_x = (mode & R_ACCEPT) != 0, wr_u = ((mode & (R_DIR | R_INIT | R_RESET)) != 0 && !(mode & R_NOWU)) || mode == R_ULAG;
     const bool pp = big && !ctl && (wr_x || wr_u) && !(mode & R_PROJ) && pingpong_ready();
     if (pp && wr_x) P.xo = xalt_;
     if (pp && wr_u) P.uo = ualt_;
@@ -184,6 +252,7 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
 #undef ROW
     case CGO_OBJ_USER:
         if (!obj_->rtc) { set_error("user objective has no compiled module"); return CGO_EINVAL; }
+        if (lag) break;   // built-in objectives only: r stays −2
         if (int rc = launch_module(obj_->rtc->cg(mode, npts, big), &P, grid, st)) return rc;
         r = 0;
         break;
@@ -248,7 +317,9 @@ std::string HipBackend::kernel_symbol(int kk) const {
         switch (kk) {
         case KK_INIT: mode = R_INIT; break;
         case KK_TRIAL: mode = R_TRIAL; npts = npts_for(std::min(max_points(), 3)); break;
-        case KK_ACCEPT_DIR_TRIAL: mode = R_ACCEPT | R_DIR | R_TRIAL; npts = npts_for(max_points()); break;
+        case KK_ACCEPT_DIR_TRIAL: mode = (lazy_eligible() ? R_ULAG : 0) | R_ACCEPT | R_DIR | R_TRIAL; npts = npts_for(max_points()); break;
+        case KK_ACCEPT_TRIAL_LAZY: if (!lazy_eligible()) return ""; mode = R_ACCEPT | R_DIR | R_TRIAL | R_NOWU; npts = npts_for(max_points()); break;
+        case KK_MATERIALIZE_U: if (!lazy_eligible()) return ""; mode = R_ULAG; break;
         case KK_ACCEPT_DIR: mode = R_ACCEPT | R_DIR; break;
         case KK_ACCEPT_ONLY: mode = R_ACCEPT; break;
         case KK_RESET_DIR: mode = R_RESET; break;
@@ -257,7 +328,7 @@ std::string HipBackend::kernel_symbol(int kk) const {
         case KK_SYS_PROJECT: mode = R_PROJ; break;
         default: return "";
         }
-        const bool big = bytes_r(obj_->kind, mode, n, hp) > big_bytes(mode == R_TRIAL || mode == R_UPG);
+        const bool big = (mode & (R_ULAG | R_NOWU)) != 0 || bytes_r(obj_->kind, mode, n, hp) > big_bytes(mode == R_TRIAL || mode == R_UPG);
         return r_symbol(mode, chain() ? chain_npts(mode, npts) : npts, big);
     }
     if (obj_->two_phase()) {
@@ -632,6 +703,7 @@ void unpack_r(const double *s, int k, Scal *out, bool dir) {
 int HipBackend::probe_prepare() {
     if (probe_) return CGO_OK;
     if (int rc = pipe_drain()) return rc;
+    u_lag_ = false;   // the probes upload u
     HIPCHK(hipSetDevice(ctx_->device));
     HIPCHK(hipStreamSynchronize(ctx_->stream));
     (void)pingpong_ready();   // the engine's own decision, taken now: it would allocate its pair unpadded on the first pure-HBM launch
@@ -701,8 +773,10 @@ int HipBackend::probe_launch(int kk, int variant, double a_acc, double beta, con
         auto pick = [&](int dflt, std::initializer_list<int> ok) { const int m = variant ? variant : dflt; for (int o : ok) if (o == m) return m; return -1; };
         switch (kk) {
         case KK_INIT: mode = chain() ? pick(R_INIT, {R_INIT, R_GRAD, R_EDGES}) : pick(R_INIT, {R_INIT, R_GRAD}); break;
-        case KK_TRIAL: mode = pick(R_TRIAL, {R_TRIAL}); break;
-        case KK_ACCEPT_DIR_TRIAL: mode = pick(R_ACCEPT | R_DIR | R_TRIAL, {R_ACCEPT | R_DIR | R_TRIAL}); break;
+        case KK_TRIAL: mode = pick(R_TRIAL, {R_TRIAL, R_ULAG | R_TRIAL}); break;
+        case KK_ACCEPT_DIR_TRIAL: mode = pick(R_ACCEPT | R_DIR | R_TRIAL, {R_ACCEPT | R_DIR | R_TRIAL, R_ULAG | R_ACCEPT | R_DIR | R_TRIAL}); break;
+        case KK_ACCEPT_TRIAL_LAZY: mode = pick(R_ACCEPT | R_DIR | R_TRIAL | R_NOWU, {R_ACCEPT | R_DIR | R_TRIAL | R_NOWU}); break;
+        case KK_MATERIALIZE_U: mode = pick(R_ULAG, {R_ULAG}); break;
         case KK_ACCEPT_DIR: mode = pick(R_ACCEPT | R_DIR, {R_ACCEPT | R_DIR}); break;
         case KK_ACCEPT_ONLY: mode = pick(R_ACCEPT, {R_ACCEPT}); break;
         case KK_RESET_DIR: mode = pick(R_RESET, {R_RESET}); break;
@@ -714,6 +788,7 @@ int HipBackend::probe_launch(int kk, int variant, double a_acc, double beta, con
         }
         if (mode > 0 && (mode & (R_TRIAL | R_GRADT | R_PROJ)) && k < 1) mode = -1;
         if (mode > 0 && chain() && k > 3) mode = -1;
+        if (mode > 0 && (mode & (R_ULAG | R_NOWU)) && chain()) mode = -1;
     }
     if (mode < 0) { set_error("probe: kernel kind / variant / trial steps not a launch this solver's engine issues"); return CGO_EINVAL; }
     if (int rc = probe_prepare()) return rc;
@@ -740,6 +815,7 @@ int HipBackend::probe_launch(int kk, int variant, double a_acc, double beta, con
     HIPCHK(hipStreamSynchronize(st));
     probe_len_ = 0;
     last_mode_ = -1;
+    beta_lag_ = probe_beta_prev_;   // what a launch with R_ULAG reads as β_prev (cgo_solver_probe_set_beta_prev)
     int rc = CGO_OK;
     char buf[160];
     if (lse) {
@@ -1022,6 +1098,7 @@ int HipBackend::res_error_reset() {
 int HipBackend::resident_run(const ResConfig &c, ResState &s, int64_t budget, std::vector<ResRecord> &recs, std::vector<ResLog> &log) {
     if (int rc = pipe_drain()) return rc;
     pipe_streak_ = 0;
+    if (int rc = materialize_u()) return rc;   // the slice loads the stored direction
     if (res_plan() <= 0) { set_error("internal: resident slice on a shard that does not fit"); return CGO_ESTATE; }
     if (obj_->unset_slot() >= 0) return param_unset_error(obj_->unset_slot());
     if (int rc = res_alloc()) return rc;

@@ -531,6 +531,16 @@ static int make_solver(cgo_ctx *ctx, cgo_objective *obj, const cgo_cg_config *cf
     s->be->set_ctl_depth((ls && !cheap && !chain && s->be->policy_points() <= 3 && (ctx->c.world() == 1 || ctx->c.dev_exchange()) && obj->o.n_local <= 100000) ? 4 : 0);
     if (pol.controller_depth >= 0) s->be->set_ctl_depth(chain ? 0 : pol.controller_depth);  // 0: host drives every launch
     s->be->set_ctl_graph(pol.controller_graph != 0);                                       // 0: armed rounds kernel by kernel
+    // Lazy direction: every second accept + dir + trial launch of a pure-HBM, host-driven solve leaves u
+    // unstored — 36 instead of 40 B/element per iteration on the separable quadratic.  Library policy: on for that objective;
+    // off for the paired Rosenbrock, whose launch B pays a second gradient evaluation near its VALU limit.
+    // CGO_LAZY_DIR=0|1 forces it for every built-in objective; cgo_solver_set_lazy_direction has the last word.
+    {
+        bool lazy = obj->o.kind == CGO_OBJ_QUAD_DIAG;
+        const int forced = env_tri("CGO_LAZY_DIR");
+        if (forced >= 0) lazy = forced != 0;
+        s->be->set_lazy_direction(lazy);
+    }
     if (int prc = s->be->place()) { delete s; obj_unref(obj); return prc; }
     if (pol.resident >= 0) s->be->set_resident(pol.resident != 0);
     if (int prc = s->be->prepare_controller()) { delete s; obj_unref(obj); return prc; }   // the controller's blocks: now, not inside the first armed iteration
@@ -736,6 +746,21 @@ int cgo_solver_kernel_symbol(cgo_solver *s, int32_t kernel_kind, char *buf, int3
     REQUIRE(s && buf && cap > 0, "bad argument");
     const std::string sym = s->be->kernel_symbol(kernel_kind);
     std::snprintf(buf, (size_t)cap, "%s", sym.c_str());
+    return CGO_OK;
+    API_GUARD_END
+}
+
+int cgo_solver_set_lazy_direction(cgo_solver *s, int32_t on) {
+    API_GUARD_BEGIN
+    REQUIRE(s, "null argument");
+    return s->be->set_lazy_direction_now(on != 0);
+    API_GUARD_END
+}
+
+int cgo_solver_probe_set_beta_prev(cgo_solver *s, double beta_prev) {
+    API_GUARD_BEGIN
+    REQUIRE(s, "null argument");
+    s->be->set_probe_beta_prev(beta_prev);
     return CGO_OK;
     API_GUARD_END
 }

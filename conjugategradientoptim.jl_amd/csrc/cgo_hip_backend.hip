@@ -651,6 +651,7 @@ int HipBackend::ensure_gb() {
 int HipBackend::set_x0_host(const double *x0) {
     if (int rc = pipe_drain()) return rc;
     discard_pending();   // a new x_initial: nothing of an earlier solve may be applied to it
+    u_lag_ = false;      // … nor is the stored direction still one step behind it: init_eval writes u
     HIPCHK(hipSetDevice(ctx_->device));
     xc_ = x_.p; xn_ = gb_.p;   // gb_ may not exist yet (sys_begin creates it)
     if (pingpong_ == 1) xalt_ = x2_.p;
@@ -662,6 +663,7 @@ int HipBackend::set_x0_host(const double *x0) {
 int HipBackend::set_x0_device(const double *x0_dev) {
     if (int rc = pipe_drain()) return rc;
     discard_pending();   // a new x_initial: nothing of an earlier solve may be applied to it
+    u_lag_ = false;      // … nor is the stored direction still one step behind it: init_eval writes u
     HIPCHK(hipSetDevice(ctx_->device));
     xc_ = x_.p; xn_ = gb_.p;
     if (pingpong_ == 1) xalt_ = x2_.p;
@@ -683,6 +685,7 @@ int fill_device(HipCtx *ctx, double *v, int64_t n, int64_t offset, int kind, uin
 int HipBackend::set_x0_fill(int kind, uint64_t seed, double lo, double hi) {
     if (int rc = pipe_drain()) return rc;
     discard_pending();   // a new x_initial: nothing of an earlier solve may be applied to it
+    u_lag_ = false;      // … nor is the stored direction still one step behind it: init_eval writes u
     xc_ = x_.p; xn_ = gb_.p;
     if (pingpong_ == 1) xalt_ = x2_.p;
     return fill_device(ctx_, xc_, obj_->n_local, obj_->offset, kind, seed, lo, hi);
@@ -836,7 +839,7 @@ int HipBackend::init_eval(Scal &out) {
 int HipBackend::trial(const double *a, int k, Scal *out) {
     if (rmode_) {
         double s[NR7];
-        if (int rc = launch_r(KK_TRIAL, R_TRIAL, 0, 0, a, k, true, s)) return rc;
+        if (int rc = trial_r(a, k, s)) return rc;
         unpack_r(s, k, out, false);
         return CGO_OK;
     }
@@ -854,7 +857,7 @@ int HipBackend::trial(const double *a, int k, Scal *out) {
 int HipBackend::accept_dir_trial(double a_acc, double beta, const double *a, int k, Scal *out) {
     if (rmode_) {
         double s[NR7];
-        if (int rc = launch_r(KK_ACCEPT_DIR_TRIAL, R_ACCEPT | R_DIR | R_TRIAL, a_acc, beta, a, k, true, s)) return rc;
+        if (int rc = accept_dir_trial_r(a_acc, beta, a, k, s)) return rc;
         unpack_r(s, k, out, true);
         return CGO_OK;
     }
@@ -999,6 +1002,7 @@ int HipBackend::scaled_norm_parts(int which, double a_trial, double &maxabs, dou
     const double *v = nullptr, *w = nullptr;   // the vector is v, or v − w
     if (which == 3) {                         // u is always stored
         if (int rc = pipe_drain()) return rc;
+        if (int rc = materialize_u()) return rc;
         v = rmode_ ? uc_ : u_.p;
     } else if (rmode_) {  // rare path: materialise the vector whose norm is asked for (g, or g⁺ of the last trial,
         const double a1[1] = {a_trial};  // or — which = 2, solvesystem — the gradient at the second iterate buffer)

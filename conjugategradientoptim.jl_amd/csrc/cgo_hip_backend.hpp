@@ -194,6 +194,11 @@ class HipBackend : public VecBackend {
     void set_multi7_min_n(int64_t n) { multi7_min_n_ = n; }
     void set_three_point_band(int64_t lo, int64_t hi) { band3_lo_ = lo; band3_hi_ = hi; }
     bool rmode() const { return rmode_; }
+    // Lazy direction: every second accept + dir + trial launch of an eligible solver leaves u unstored.
+    void set_lazy_direction(bool on) { lazy_on_ = on; }
+    bool lazy_direction() const { return lazy_on_; }
+    int set_lazy_direction_now(bool on) { if (!on) { if (int rc = materialize_u()) return rc; } lazy_on_ = on; return 0; }   // (mid-solve: the lag ends first)
+    void set_probe_beta_prev(double b) { probe_beta_prev_ = b; }
     std::string kernel_symbol(int kernel_kind) const;
     // Test entry point (cgo_solver_probe_launch): the vectors → this solver's device state, ONE launch of kind `kernel_kind`
     // with mode bits `variant` through the engine's own launch path, the whole reduced row and the vectors back.  The first
@@ -287,6 +292,13 @@ class HipBackend : public VecBackend {
     int64_t multi7_min_n_ = INT64_MAX;
     int64_t band3_lo_ = 0, band3_hi_ = 0;  // sizes inside [lo, hi) stay at three points
     int launch_r(int kk, int mode, double a_acc, double beta, const double *a, int k, bool fetch, double *sums);
+    // lazy direction: memory holds (x_{k+1}, u_k) while u_lag_ is set, and beta_lag_ = β_k rebuilds u_{k+1} from them
+    bool lazy_on_ = false, u_lag_ = false;
+    double beta_lag_ = 0.0, probe_beta_prev_ = 0.0;
+    bool lazy_eligible() const;
+    int materialize_u();   // store the rebuilt direction for any reader but the lag launches; clears u_lag_
+    int accept_dir_trial_r(double a_acc, double beta, const double *a, int k, double *s);
+    int trial_r(const double *a, int k, double *s);
     int launch_r_kernel(int kk, int mode, double a_acc, double beta, const double *a, int k, int npts,
                         const struct dev::CtlArgs *ctl, int *grid_out);
     // on-device controller (cgo_ctl.hpp): rounds armed on the device ahead of the host

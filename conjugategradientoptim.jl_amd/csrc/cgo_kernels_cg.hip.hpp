@@ -52,8 +52,14 @@ enum RMode : int {
     R_UPG = 32,    // Σ (u + ∇f(x))²                          wolfe.jl:123
     R_GRAD = 64,   // gout = ∇f(x)                            (materialise for Results.gradient)
     R_GRADT = 128, // gout = ∇f(x + a_0·u)                    (rare: LinearAlgebra.norm scaled path on g⁺)
-    R_PROJ = 256   // solvesystem: x2 ← x2 + m·∇f(x + a_0·u) ; g⁺ = ∇f(x2) ; trial sums of g⁺ against ∇f(x), u
+    R_PROJ = 256,  // solvesystem: x2 ← x2 + m·∇f(x + a_0·u) ; g⁺ = ∇f(x2) ; trial sums of g⁺ against ∇f(x), u
                    //                                          solve_system.jl:169-177,199-204,239-253  (m = P.beta)
+    // (512: R_EDGES of the stencil launches, cgo_kernels_chain.hip.hpp)
+    // Lazy direction: the direction is recoverable from the stored iterate one step later, so every second
+    // accept + direction + trial launch leaves the OLD u in memory and the next launch forms the new one itself.
+    R_ULAG = 1024, // on load, before anything else: u ← −∇f(x) + β_prev·u — memory holds (x_{k+1}, u_k), β_prev = β_k; no sums
+                   // (those of this direction were formed by the launch that did not store it).  Alone: store that u.
+    R_NOWU = 2048  // R_DIR without the store of u: registers, sums and trials use the new direction, memory keeps the old one
 };
 
 // Launch scalars kept in device memory for launches armed by the on-device controller
@@ -79,6 +85,7 @@ struct RParams {
     double a_acc, beta;
     double a[MAXP];
     double s0;
+    double beta_prev;    // R_ULAG: the β of the direction update the previous launch left unstored
     double *partials;
     const CtlArgs *ctl;  // non-null: a_acc, beta, a[] come from device memory instead of the arguments
     double *x2;          // R_PROJ: the second iterate buffer (`x_next` of solve_system.jl:82)
@@ -566,6 +573,13 @@ template <int NPTS> struct RW { static constexpr int W = (NPTS == 1) ? NR1 : (NP
 template <class Obj, int MODE, int NPTS>
 __device__ inline void cg_pair(const RParams &P, d2 &x, d2 &u, const PV<Obj> &p, double (&acc)[RW<NPTS>::W], bool &wx, bool &wu, d2 &gout) {
     constexpr int R_GU = RW<NPTS>::GU, R_UU = RW<NPTS>::UU;
+    d2 g0 = d2{0.0, 0.0};
+    double f00 = 0.0;
+    if (MODE & R_ULAG) {  // the direction the previous launch formed and did not store: same expression, same operands as R_DIR
+        obj_eval2<Obj>(x, p, P.s0, f00, g0);
+        u.x = -g0.x + P.beta_prev * u.x; u.y = -g0.y + P.beta_prev * u.y;
+        if (MODE == R_ULAG) wu = true;
+    }
     if (MODE & R_ACCEPT) {
         x.x = x.x + P.a_acc * u.x;
         x.y = x.y + P.a_acc * u.y;
@@ -575,7 +589,10 @@ __device__ inline void cg_pair(const RParams &P, d2 &x, d2 &u, const PV<Obj> &p,
     double f0 = 0.0;
     constexpr bool need_g = (MODE & (R_DIR | R_TRIAL | R_INIT | R_RESET | R_UPG | R_GRAD | R_PROJ)) != 0;
     g = d2{0.0, 0.0};
-    if (need_g) obj_eval2<Obj>(x, p, P.s0, f0, g);  // g = ∇f(x), recomputed — never read from HBM
+    if (need_g) {  // g = ∇f(x), recomputed — never read from HBM
+        if ((MODE & R_ULAG) && !(MODE & R_ACCEPT)) { g = g0; f0 = f00; }  // x has not moved since R_ULAG evaluated it
+        else obj_eval2<Obj>(x, p, P.s0, f0, g);
+    }
     if (MODE & R_INIT) {
         acc[RS_F] += f0;
         acc[RS_GTGT] = dsum(acc[RS_GTGT], g.x, g.x);
@@ -590,7 +607,7 @@ __device__ inline void cg_pair(const RParams &P, d2 &x, d2 &u, const PV<Obj> &p,
         acc[R_GU] = dsum(acc[R_GU], g.x, un.x); acc[R_GU] = dsum(acc[R_GU], g.y, un.y);
         acc[R_UU] = dsum(acc[R_UU], un.x, un.x); acc[R_UU] = dsum(acc[R_UU], un.y, un.y);
         u = un;
-        wu = true;
+        wu = (MODE & R_NOWU) == 0;
     }
     if (MODE & R_UPG) {
         const double t0 = u.x + g.x, t1 = u.y + g.y;
@@ -645,8 +662,14 @@ template <class Obj, int MODE, int NPTS>
 __device__ inline void cg_single(const RParams &P, long long i, double (&acc)[RW<NPTS>::W]) {
     constexpr int R_GU = RW<NPTS>::GU, R_UU = RW<NPTS>::UU;
     double x = P.x[i];
-    double u = (MODE & (R_ACCEPT | R_DIR | R_TRIAL | R_UPG | R_GRADT | R_PROJ)) ? P.u[i] : 0.0;
+    double u = (MODE & (R_ACCEPT | R_DIR | R_TRIAL | R_UPG | R_GRADT | R_PROJ | R_ULAG)) ? P.u[i] : 0.0;
     const PS<Obj> p = ps_load<Obj>(P, i);
+    if (MODE & R_ULAG) {
+        double g0 = 0.0, f00 = 0.0;
+        obj_eval1<Obj>(x, p, P.s0, f00, g0);
+        u = -g0 + P.beta_prev * u;
+        if (MODE == R_ULAG) P.uo[i] = u;
+    }
     if (MODE & R_ACCEPT) { x = x + P.a_acc * u; P.xo[i] = x; }
     double g = 0.0, f0 = 0.0;
     obj_eval1<Obj>(x, p, P.s0, f0, g);
@@ -654,7 +677,8 @@ __device__ inline void cg_single(const RParams &P, long long i, double (&acc)[RW
     if (MODE & (R_DIR | R_RESET)) {
         const double un = (MODE & R_DIR) ? (-g + P.beta * u) : -g;
         acc[R_GU] = dsum(acc[R_GU], g, un); acc[R_UU] = dsum(acc[R_UU], un, un);
-        P.uo[i] = un; u = un;
+        if (!(MODE & R_NOWU)) P.uo[i] = un;
+        u = un;
     }
     if (MODE & R_UPG) { const double t = u + g; acc[R_UU] = dsum(acc[R_UU], t, t); }
     if (MODE & R_GRAD) P.gout[i] = g;
@@ -713,7 +737,7 @@ __device__ inline void cg_launch(const RParams &Pin) {
     double acc[W];
 #pragma unroll
     for (int s = 0; s < W; ++s) acc[s] = 0.0;
-    constexpr bool rd_u = (MODE & (R_ACCEPT | R_DIR | R_TRIAL | R_UPG | R_GRADT | R_PROJ)) != 0;
+    constexpr bool rd_u = (MODE & (R_ACCEPT | R_DIR | R_TRIAL | R_UPG | R_GRADT | R_PROJ | R_ULAG)) != 0;
     constexpr bool wr_g = (MODE & (R_GRAD | R_GRADT)) != 0;
     constexpr bool proj = (MODE & R_PROJ) != 0;  // the gout argument of cg_pair carries x2
     const long long n2 = P.n >> 1;
@@ -765,7 +789,7 @@ __device__ inline void cg_launch(const RParams &Pin) {
         if (proj) stg2<BIG>(P.x2, i, ga);
     }
     if ((P.n & 1) && blockIdx.x == 0 && threadIdx.x == 0) cg_single<Obj, MODE, NPTS>(P, P.n - 1, acc);
-    if (MODE == R_ACCEPT || MODE == R_GRAD || MODE == R_GRADT) return;  // no sums
+    if (MODE == R_ACCEPT || MODE == R_GRAD || MODE == R_GRADT || MODE == R_ULAG) return;  // no sums
 #if defined(CGO_STAMPS) && !defined(CGO_RTC)
     const unsigned long long st1 = (unsigned long long)wall_clock64();
 #endif

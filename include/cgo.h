@@ -414,6 +414,15 @@ int cgo_solver_resident_stats(cgo_solver *s, int64_t *slices, int64_t *iteration
  * Environment: CGO_LBFGS_SPEC=0 (1: the state update always as its own launch), CGO_LBFGS_FUSE_GRAD=0 switch the first two off. */
 int cgo_solver_lbfgs_stats(cgo_solver *s, int64_t *speculated, int64_t *fused, int64_t *plain);
 int cgo_num_kernel_kinds(void);
+/* Lazy direction.  u_{k+1} = −∇f(x_{k+1}) + β_k·u_k is recoverable, bit for bit, from the stored x_{k+1},
+ * the stored u_k and the host scalar β_k, so on an eligible solver — a built-in element-wise objective whose launches are
+ * pure-HBM streams driven by the host, updated in place — every second accept + direction + trial launch does not store u
+ * (kernel kind "accept_trial_lazy", 8n(2+p+1) bytes) and the next one rebuilds it on load ("accept_dir_trial", R_ULAG
+ * instantiation, 8n(2+p+2) bytes); any other reader of u gets it stored first ("materialize_u", not counted in
+ * total_launches).  Results are those of the plain launches bit for bit.  Library policy: on for the separable quadratic;
+ * env CGO_LAZY_DIR=0|1 forces it for every built-in objective; this call has the last word for one solver.  Meant to be
+ * called before cgo_solver_start; later it takes effect at the next launch (switching off stores a lagged u first). */
+int cgo_solver_set_lazy_direction(cgo_solver *s, int32_t on);
 /* The kernel instantiation a launch of `kernel_kind` uses under the solver's current policy, as the profiler
  * prints it without namespaces — e.g. "k_cg<ObjQuadDiag, 7, 7, true>" (objective, mode bits, trial points, pure-HBM
  * streaming policy).  Written NUL-terminated into buf[cap]. */
@@ -524,6 +533,10 @@ int cgo_kernel_trial(cgo_objective *obj, const double *x, const double *u, doubl
  * gradient having become g.  symbol joins the instantiations launched with " + ", e.g.
  * "k_trial_point + k_fused<ObjQuadDiag, 128, false>" or "k_scaled_norm<0> + k_scaled_norm<1>" (the objective-free modes
  * are instantiated for ObjQuadDiag only).  Multi-rank solvers are refused (CGO_EINVAL). */
+/* The lazy-direction instantiations (pure-HBM form only, built-in objectives) are probed through cgo_solver_probe_launch too:
+ *   accept_dir_trial: R_ULAG|7 = 1031   accept_trial_lazy: 7|R_NOWU = 2055   trial: R_ULAG|R_TRIAL = 1028   materialize_u: R_ULAG 1024
+ * R_ULAG rebuilds u ← −∇f(x) + β_prev·u on load; β_prev is what this call set last (0 until then). */
+int cgo_solver_probe_set_beta_prev(cgo_solver *s, double beta_prev);
 int cgo_solver_probe_launch(cgo_solver *s, int32_t kernel_kind, int32_t variant, double a_acc, double beta,
                             const double *a, int32_t k,
                             const double *x, const double *u, const double *aux,
