@@ -785,8 +785,14 @@ class Solver:
         eligible solver every second accept + direction + trial launch leaves u unstored and the next one rebuilds it."""
         check(_lib.lib().cgo_solver_set_lazy_direction(self._h, int(bool(on))))
 
+    def set_replay_depth(self, d: int):
+        """Replay depth of this solver, 1 … 8 (cgo_solver_set_replay_depth): on an eligible solver d − 1 of every d accept +
+        direction + trial launches store neither x nor u and the d-th replays them and stores both; 1 = the lazy direction's
+        alternation.  Mid-solve, outstanding steps are stored first."""
+        check(_lib.lib().cgo_solver_set_replay_depth(self._h, int(d)))
+
     def probe_launch(self, kind_name: str, variant: int, a_acc: float, beta: float, a: Sequence[float], x, u=None, aux=None,
-                     beta_prev: Optional[float] = None):
+                     beta_prev: Optional[float] = None, replay: Optional[Sequence] = None):
         """ONE launch of kind `kind_name` with mode bits `variant` on this rank's host vectors (cgo_solver_probe_launch): returns
         dict(sums=the whole reduced row, x=, u=, g= the vectors after the launch, symbol=the instantiation).  A test entry point:
         the solver is for probing only from the first call on.
@@ -802,6 +808,10 @@ class Solver:
         kk = [L.cgo_kernel_kind_name(k).decode() for k in range(L.cgo_num_kernel_kinds())].index(kind_name)
         if beta_prev is not None:   # the lazy-direction variants (R_ULAG = 1024): u ← −∇f(x) + beta_prev·u on load
             check(L.cgo_solver_probe_set_beta_prev(self._h, float(beta_prev)))
+        if replay is not None:      # the replay variants (R_REPLAY = 4096): the (a*, β) pairs replayed on load, oldest first
+            ra = np.ascontiguousarray([p[0] for p in replay], dtype=np.float64)
+            rb = np.ascontiguousarray([p[1] for p in replay], dtype=np.float64)
+            check(L.cgo_solver_probe_set_replay(self._h, len(replay), ra.ctypes.data_as(dp), rb.ctypes.data_as(dp)))
         n = self.obj.n_local
         vec = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float64)
         x, u, aux = vec(x), vec(u), vec(aux)

@@ -34,6 +34,12 @@ double bytes_r(int obj_kind, int mode, int64_t n, int n_params) {
     else if (mode == (R_ULAG | R_ACCEPT | R_DIR | R_TRIAL)) v = 2 + p + 2;
     else if (mode == (R_ULAG | R_TRIAL)) v = 2 + p;
     else if (mode == R_ULAG) v = 2 + p + 1;
+    // replay: N reads x, u, D and writes nothing; S is the plain launch on the replayed pair; a trial with steps outstanding
+    // writes nothing; the materialise pass writes x and u
+    else if (mode == (R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL | R_NOWU | R_NOWX)) v = 2 + p;
+    else if (mode == (R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL)) v = 2 + p + 2;
+    else if (mode == (R_REPLAY | R_TRIAL)) v = 2 + p;
+    else if (mode == R_REPLAY) v = 2 + p + 2;
     return 8.0 * (double)n * (double)v;
 }
 
@@ -62,10 +68,11 @@ static int launch_cg(int mode, int npts, const RParams &P, int grid, hipStream_t
 #undef ROW
     default: break;
     }
-    if constexpr (BIG) {   // the lazy-direction rows: pure-HBM streaming only
+    if constexpr (BIG) {   // the lazy-direction and replay rows: pure-HBM streaming only
         switch (mode) {
 #define ROW(MODE, MAXPTS) case (MODE): with_points<MAXPTS>(npts, [&](auto n) { k_cg<Obj, (MODE), decltype(n)::value, true><<<grid, BLOCK, 0, st>>>(P); }); return 0;
         CGO_CG_LAG_ROWS(ROW)
+        CGO_CG_REPLAY_ROWS(ROW)
 #undef ROW
         default: break;
         }
@@ -91,11 +98,14 @@ int HipBackend::launch_r(int kk, int mode, double a_acc, double beta, const doub
         if (mode & (R_ACCEPT | R_DIR | R_TRIAL | R_UPG | R_GRADT | R_PROJ)) { if (int rc = materialize_u()) return rc; }
         else if (mode & (R_INIT | R_RESET)) u_lag_ = false;
     }
+    // Steps outstanding (replay): x lags too, and every launch reads x — R_RESET and R_INIT included.  Any launch but N / S / T
+    // gets both vectors stored first.
+    if (rep_n_ > 0 && !(mode & R_REPLAY)) { if (int rc = materialize_lag()) return rc; }
     int grid = 0;
     const int npts = npts_for(k);
     if (int rc = launch_r_kernel(kk, mode, a_acc, beta, a, k, npts, nullptr, &grid)) return rc;
     total_launches_++;
-    const bool has_sums = (mode != R_ACCEPT && mode != R_GRAD && mode != R_GRADT && mode != R_ULAG);
+    const bool has_sums = (mode != R_ACCEPT && mode != R_GRAD && mode != R_GRADT && mode != R_ULAG && mode != R_REPLAY);
     const bool fused = has_sums && tail_fused(grid);   // the launch's last workgroup already left the sums (finish_tail)
     if (has_sums && chain()) {   // 24- or 32-slot rows: the sums + this rank's eight edge values (cgo_kernels_chain.hip.hpp)
         const bool three = chain_npts(mode, npts) == 3;
@@ -152,9 +162,48 @@ int HipBackend::materialize_u() {
     return CGO_OK;
 }
 
-// accept + direction + trial and trial of the k_cg family, alternating between the two lag launches where eligible
+// Replay: memory holds (x_k, u_k) and rep_a_ / rep_b_ the (a*, β) of the rep_n_ steps accepted since.  Every
+// reader of x or u other than the replay launches: store the current pair now (after a one-step lag of u, if any).  Like
+// materialize_u not a launch the solve asked for; the profile shows it under its own kind.
+int HipBackend::materialize_lag() {
+    if (int rc = materialize_u()) return rc;
+    if (rep_n_ == 0) return CGO_OK;
+    const int64_t asked = total_launches_;
+    const int rc = launch_r(KK_MATERIALIZE_XU, R_REPLAY, 0.0, 0.0, nullptr, 0, false, nullptr);
+    total_launches_ = asked;
+    if (rc) return rc;
+    rep_n_ = 0;
+    return CGO_OK;
+}
+
+int HipBackend::set_replay_depth_now(int d) {
+    if (d < 1 || d > RMAX + 1) { set_error("replay depth: 1 … 8"); return CGO_EINVAL; }
+    if (d != replay_depth_) { if (int rc = materialize_lag()) return rc; }   // mid-solve: a cycle of the old depth ends first
+    replay_depth_ = d;
+    return CGO_OK;
+}
+
+void HipBackend::set_probe_replay(int nrep, const double *a, const double *beta) {
+    probe_rep_n_ = std::max(0, std::min(nrep, (int)RMAX));
+    for (int j = 0; j < probe_rep_n_; ++j) { probe_rep_a_[j] = a[j]; probe_rep_b_[j] = beta[j]; }
+}
+
+// accept + direction + trial and trial of the k_cg family.  Where eligible: depth d ≥ 2 — d − 1 launches that store nothing
+// (N), then one that replays them and stores both vectors (S); depth 1 — alternating between the two lag launches.
 int HipBackend::accept_dir_trial_r(double a_acc, double beta, const double *a, int k, double *s) {
     if (!lazy_eligible()) return launch_r(KK_ACCEPT_DIR_TRIAL, R_ACCEPT | R_DIR | R_TRIAL, a_acc, beta, a, k, true, s);
+    if (replay_depth_ >= 2) {
+        if (int rc = materialize_u()) return rc;
+        if (rep_n_ < replay_depth_ - 1 && rep_n_ < RMAX) {   // launch N: the new pair in registers only
+            if (int rc = launch_r(KK_ACCEPT_TRIAL_NOSTORE, R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL | R_NOWU | R_NOWX, a_acc, beta, a, k, true, s)) return rc;
+            rep_a_[rep_n_] = a_acc; rep_b_[rep_n_] = beta; rep_n_++;
+            return CGO_OK;
+        }
+        // launch S: replays the outstanding steps, then today's launch
+        if (int rc = launch_r(KK_ACCEPT_DIR_TRIAL, R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL, a_acc, beta, a, k, true, s)) return rc;
+        rep_n_ = 0;
+        return CGO_OK;
+    }
     if (!u_lag_) {   // launch A: x ← x + a·u, the new direction in registers only
         if (int rc = launch_r(KK_ACCEPT_TRIAL_LAZY, R_ACCEPT | R_DIR | R_TRIAL | R_NOWU, a_acc, beta, a, k, true, s)) return rc;
         u_lag_ = true; beta_lag_ = beta;
@@ -166,6 +215,7 @@ int HipBackend::accept_dir_trial_r(double a_acc, double beta, const double *a, i
     return CGO_OK;
 }
 int HipBackend::trial_r(const double *a, int k, double *s) {
+    if (rep_n_ > 0 && lazy_eligible()) return launch_r(KK_TRIAL, R_REPLAY | R_TRIAL, 0, 0, a, k, true, s);   // 24 B: nothing stored, steps still outstanding
     if (u_lag_ && lazy_eligible()) return launch_r(KK_TRIAL, R_ULAG | R_TRIAL, 0, 0, a, k, true, s);   // 24 B: nothing stored, still lagged
     return launch_r(KK_TRIAL, R_TRIAL, 0, 0, a, k, true, s);
 }
@@ -202,7 +252,7 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
     if (obj_->unset_slot() >= 0) return param_unset_error(obj_->unset_slot());
     const int64_t n = obj_->n_local;
     if (mode & (R_GRAD | R_GRADT)) { if (int rc = ensure_ga()) return rc; }
-    const bool has_sums = (mode != R_ACCEPT && mode != R_GRAD && mode != R_GRADT && mode != R_ULAG);
+    const bool has_sums = (mode != R_ACCEPT && mode != R_GRAD && mode != R_GRADT && mode != R_ULAG && mode != R_REPLAY);
     if (chain()) {
         const double bytes = bytes_r(obj_->kind, mode, n, false);
         const bool big = bytes > big_bytes(mode == R_TRIAL || mode == R_UPG);
@@ -218,11 +268,13 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
     P.xo = xc_; P.uo = uc_;
     P.a_acc = a_acc; P.beta = beta; P.s0 = obj_->s0; P.partials = ctx_->partials;
     P.beta_prev = beta_lag_;
+    P.nrep = (mode & R_REPLAY) ? rep_n_ : 0;
+    for (int j = 0; j < RMAX; ++j) { P.ra[j] = j < P.nrep ? rep_a_[j] : 0.0; P.rb[j] = j < P.nrep ? rep_b_[j] : 0.0; }
     P.ctl = ctl;
     P.x2 = xn_;
     for (int j = 0; j < MAXP; ++j) P.a[j] = (a && j < k) ? a[j] : ((a && k > 0) ? a[k - 1] : 0.0);
     const double bytes = bytes_r(obj_->kind, mode, n, obj_->nparams());
-    const bool lag = (mode & (R_ULAG | R_NOWU)) != 0;   // BIG instantiations only (lazy_eligible)
+    const bool lag = (mode & (R_ULAG | R_NOWU | R_REPLAY | R_NOWX)) != 0;   // BIG instantiations only (lazy_eligible)
     const bool big = lag || bytes > big_bytes(mode == R_TRIAL || mode == R_UPG);
     const int grid = big ? GRID_BIG : grid_cg(n, npts);
     *grid_out = grid;
@@ -238,7 +290,8 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
         }
     }
     if (P.tail.tickets) P.partials = ctx_->partials_f;
-    const bool wr_x = (mode & R_ACCEPT) != 0, wr_u = ((mode & (R_DIR | R_INIT | R_RESET)) != 0 && !(mode & R_NOWU)) || mode == R_ULAG;
+    const bool wr_x = ((mode & R_ACCEPT) != 0 && !(mode & R_NOWX)) || mode == R_REPLAY;
+    const bool wr_u = ((mode & (R_DIR | R_INIT | R_RESET)) != 0 && !(mode & R_NOWU)) || mode == R_ULAG || mode == R_REPLAY;
     const bool pp = big && !ctl && (wr_x || wr_u) && !(mode & R_PROJ) && pingpong_ready();
     if (pp && wr_x) P.xo = xalt_;
     if (pp && wr_u) P.uo = ualt_;
@@ -317,9 +370,11 @@ std::string HipBackend::kernel_symbol(int kk) const {
         switch (kk) {
         case KK_INIT: mode = R_INIT; break;
         case KK_TRIAL: mode = R_TRIAL; npts = npts_for(std::min(max_points(), 3)); break;
-        case KK_ACCEPT_DIR_TRIAL: mode = (lazy_eligible() ? R_ULAG : 0) | R_ACCEPT | R_DIR | R_TRIAL; npts = npts_for(max_points()); break;
-        case KK_ACCEPT_TRIAL_LAZY: if (!lazy_eligible()) return ""; mode = R_ACCEPT | R_DIR | R_TRIAL | R_NOWU; npts = npts_for(max_points()); break;
-        case KK_MATERIALIZE_U: if (!lazy_eligible()) return ""; mode = R_ULAG; break;
+        case KK_ACCEPT_DIR_TRIAL: mode = (lazy_eligible() ? (replay_depth_ >= 2 ? R_REPLAY : R_ULAG) : 0) | R_ACCEPT | R_DIR | R_TRIAL; npts = npts_for(max_points()); break;
+        case KK_ACCEPT_TRIAL_LAZY: if (!lazy_eligible() || replay_depth_ >= 2) return ""; mode = R_ACCEPT | R_DIR | R_TRIAL | R_NOWU; npts = npts_for(max_points()); break;
+        case KK_MATERIALIZE_U: if (!lazy_eligible() || replay_depth_ >= 2) return ""; mode = R_ULAG; break;
+        case KK_ACCEPT_TRIAL_NOSTORE: if (!lazy_eligible() || replay_depth_ < 2) return ""; mode = R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL | R_NOWU | R_NOWX; npts = npts_for(max_points()); break;
+        case KK_MATERIALIZE_XU: if (!lazy_eligible() || replay_depth_ < 2) return ""; mode = R_REPLAY; break;
         case KK_ACCEPT_DIR: mode = R_ACCEPT | R_DIR; break;
         case KK_ACCEPT_ONLY: mode = R_ACCEPT; break;
         case KK_RESET_DIR: mode = R_RESET; break;
@@ -328,7 +383,7 @@ std::string HipBackend::kernel_symbol(int kk) const {
         case KK_SYS_PROJECT: mode = R_PROJ; break;
         default: return "";
         }
-        const bool big = (mode & (R_ULAG | R_NOWU)) != 0 || bytes_r(obj_->kind, mode, n, hp) > big_bytes(mode == R_TRIAL || mode == R_UPG);
+        const bool big = (mode & (R_ULAG | R_NOWU | R_REPLAY | R_NOWX)) != 0 || bytes_r(obj_->kind, mode, n, hp) > big_bytes(mode == R_TRIAL || mode == R_UPG);
         return r_symbol(mode, chain() ? chain_npts(mode, npts) : npts, big);
     }
     if (obj_->two_phase()) {
@@ -703,7 +758,7 @@ void unpack_r(const double *s, int k, Scal *out, bool dir) {
 int HipBackend::probe_prepare() {
     if (probe_) return CGO_OK;
     if (int rc = pipe_drain()) return rc;
-    u_lag_ = false;   // the probes upload u
+    u_lag_ = false; rep_n_ = 0;   // the probes upload x and u
     HIPCHK(hipSetDevice(ctx_->device));
     HIPCHK(hipStreamSynchronize(ctx_->stream));
     (void)pingpong_ready();   // the engine's own decision, taken now: it would allocate its pair unpadded on the first pure-HBM launch
@@ -773,8 +828,10 @@ int HipBackend::probe_launch(int kk, int variant, double a_acc, double beta, con
         auto pick = [&](int dflt, std::initializer_list<int> ok) { const int m = variant ? variant : dflt; for (int o : ok) if (o == m) return m; return -1; };
         switch (kk) {
         case KK_INIT: mode = chain() ? pick(R_INIT, {R_INIT, R_GRAD, R_EDGES}) : pick(R_INIT, {R_INIT, R_GRAD}); break;
-        case KK_TRIAL: mode = pick(R_TRIAL, {R_TRIAL, R_ULAG | R_TRIAL}); break;
-        case KK_ACCEPT_DIR_TRIAL: mode = pick(R_ACCEPT | R_DIR | R_TRIAL, {R_ACCEPT | R_DIR | R_TRIAL, R_ULAG | R_ACCEPT | R_DIR | R_TRIAL}); break;
+        case KK_TRIAL: mode = pick(R_TRIAL, {R_TRIAL, R_ULAG | R_TRIAL, R_REPLAY | R_TRIAL}); break;
+        case KK_ACCEPT_DIR_TRIAL: mode = pick(R_ACCEPT | R_DIR | R_TRIAL, {R_ACCEPT | R_DIR | R_TRIAL, R_ULAG | R_ACCEPT | R_DIR | R_TRIAL, R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL}); break;
+        case KK_ACCEPT_TRIAL_NOSTORE: mode = pick(R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL | R_NOWU | R_NOWX, {R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL | R_NOWU | R_NOWX}); break;
+        case KK_MATERIALIZE_XU: mode = pick(R_REPLAY, {R_REPLAY}); break;
         case KK_ACCEPT_TRIAL_LAZY: mode = pick(R_ACCEPT | R_DIR | R_TRIAL | R_NOWU, {R_ACCEPT | R_DIR | R_TRIAL | R_NOWU}); break;
         case KK_MATERIALIZE_U: mode = pick(R_ULAG, {R_ULAG}); break;
         case KK_ACCEPT_DIR: mode = pick(R_ACCEPT | R_DIR, {R_ACCEPT | R_DIR}); break;
@@ -788,7 +845,7 @@ int HipBackend::probe_launch(int kk, int variant, double a_acc, double beta, con
         }
         if (mode > 0 && (mode & (R_TRIAL | R_GRADT | R_PROJ)) && k < 1) mode = -1;
         if (mode > 0 && chain() && k > 3) mode = -1;
-        if (mode > 0 && (mode & (R_ULAG | R_NOWU)) && chain()) mode = -1;
+        if (mode > 0 && (mode & (R_ULAG | R_NOWU | R_REPLAY | R_NOWX)) && (chain() || obj_->kind == CGO_OBJ_USER)) mode = -1;
     }
     if (mode < 0) { set_error("probe: kernel kind / variant / trial steps not a launch this solver's engine issues"); return CGO_EINVAL; }
     if (int rc = probe_prepare()) return rc;
@@ -816,6 +873,8 @@ int HipBackend::probe_launch(int kk, int variant, double a_acc, double beta, con
     probe_len_ = 0;
     last_mode_ = -1;
     beta_lag_ = probe_beta_prev_;   // what a launch with R_ULAG reads as β_prev (cgo_solver_probe_set_beta_prev)
+    rep_n_ = (!lse && (mode & R_REPLAY)) ? probe_rep_n_ : 0;   // … and one with R_REPLAY as its list (cgo_solver_probe_set_replay)
+    for (int j = 0; j < rep_n_; ++j) { rep_a_[j] = probe_rep_a_[j]; rep_b_[j] = probe_rep_b_[j]; }
     int rc = CGO_OK;
     char buf[160];
     if (lse) {
@@ -837,6 +896,7 @@ int HipBackend::probe_launch(int kk, int variant, double a_acc, double beta, con
     } else {
         double s[64];
         rc = launch_r(kk, mode, a_acc, beta, a, k, true, s);
+        rep_n_ = 0;
         if (rc) return rc;
         symbol = r_symbol(last_mode_, last_npts_, last_big_);
     }
@@ -1098,7 +1158,7 @@ int HipBackend::res_error_reset() {
 int HipBackend::resident_run(const ResConfig &c, ResState &s, int64_t budget, std::vector<ResRecord> &recs, std::vector<ResLog> &log) {
     if (int rc = pipe_drain()) return rc;
     pipe_streak_ = 0;
-    if (int rc = materialize_u()) return rc;   // the slice loads the stored direction
+    if (int rc = materialize_lag()) return rc;   // the slice loads the stored iterate and direction
     if (res_plan() <= 0) { set_error("internal: resident slice on a shard that does not fit"); return CGO_ESTATE; }
     if (obj_->unset_slot() >= 0) return param_unset_error(obj_->unset_slot());
     if (int rc = res_alloc()) return rc;

@@ -377,6 +377,7 @@ int cgo_ctx_set_default_policy(cgo_ctx *ctx, const cgo_solver_policy *policy) {
 }
 
 // explicit argument > context default > CGO_* experiment override > library policy, field by field
+static const int kReplayDepth = 6;   // best median of 1, 2, 3, 4, 6, 8 on one MI355X at n = 1e8: BASELINE.md, profiles/r06_replay_*
 static int env_tri(const char *name) { const char *e = getenv(name); return e ? (e[0] != '0' ? 1 : 0) : -1; }
 static int resolve_policy(cgo_ctx *ctx, const cgo_solver_policy *arg, cgo_solver_policy &r, std::string &why) {
     cgo_solver_policy lib; cgo_solver_policy_init(&lib);
@@ -540,6 +541,17 @@ static int make_solver(cgo_ctx *ctx, cgo_objective *obj, const cgo_cg_config *cf
         const int forced = env_tri("CGO_LAZY_DIR");
         if (forced >= 0) lazy = forced != 0;
         s->be->set_lazy_direction(lazy);
+    }
+    // Replay: of every d accepting launches of such a solve d − 1 store neither x nor u and the d-th replays
+    // them and stores both — (24d + 16)/d B/element per iteration on the separable quadratic.  Library policy: kReplayDepth
+    // for that objective where an accepting launch exceeds the library's OWN pure-HBM threshold (a threshold lowered through
+    // hbm_stream_bytes does not lower this one: nothing has been measured at such sizes); 1 — the lazy direction's
+    // alternation — everywhere else.  CGO_REPLAY_DEPTH=1…8 forces it; cgo_solver_set_replay_depth has the last word.
+    {
+        int depth = 1;
+        if (obj->o.kind == CGO_OBJ_QUAD_DIAG && 8.0 * (double)obj->o.n_local * 5.0 > 1.4e9) depth = kReplayDepth;
+        if (const char *e = getenv("CGO_REPLAY_DEPTH")) { const int v = atoi(e); if (v >= 1 && v <= 8) depth = v; }
+        s->be->set_replay_depth(depth);
     }
     if (int prc = s->be->place()) { delete s; obj_unref(obj); return prc; }
     if (pol.resident >= 0) s->be->set_resident(pol.resident != 0);
@@ -754,6 +766,23 @@ int cgo_solver_set_lazy_direction(cgo_solver *s, int32_t on) {
     API_GUARD_BEGIN
     REQUIRE(s, "null argument");
     return s->be->set_lazy_direction_now(on != 0);
+    API_GUARD_END
+}
+
+int cgo_solver_set_replay_depth(cgo_solver *s, int32_t d) {
+    API_GUARD_BEGIN
+    REQUIRE(s, "null argument");
+    REQUIRE(d >= 1 && d <= 8, "replay depth: 1 … 8");
+    return s->be->set_replay_depth_now(d);
+    API_GUARD_END
+}
+
+int cgo_solver_probe_set_replay(cgo_solver *s, int32_t nrep, const double *a, const double *beta) {
+    API_GUARD_BEGIN
+    REQUIRE(s, "null argument");
+    REQUIRE(nrep >= 0 && nrep <= 7 && (nrep == 0 || (a && beta)), "probe replay list: 0 … 7 (a*, β) pairs");
+    s->be->set_probe_replay(nrep, a, beta);
+    return CGO_OK;
     API_GUARD_END
 }
 

@@ -56,7 +56,8 @@ const char *status_name(int s) {
 static const char *kKernelNames[KK_COUNT] = {
     "init", "trial", "accept_dir_trial", "accept_dir", "accept_only",
     "reset_dir", "upg_norm", "lbfgs_push", "lbfgs_loop", "lbfgs_final", "lse_stats", "lse_grad",
-    "scaled_norm", "dir_trial", "sys_project", "resident", "accept_trial_lazy", "materialize_u",
+    "scaled_norm", "dir_trial", "sys_project", "resident", "accept_trial_nostore", "materialize_xu",
+    "accept_trial_lazy", "materialize_u",
 };
 
 const char *kernel_kind_name(int k) { return (k >= 0 && k < KK_COUNT) ? kKernelNames[k] : "unknown"; }

@@ -54,6 +54,8 @@ enum KernelKind : int {
     KK_DIR_TRIAL,         // solvesystem: updatedir! + the first trials of the next line search   solve_system.jl:210,43-46
     KK_SYS_PROJECT,       // solvesystem: x_next += m·g(z); g⁺ = g(x_next); getβ sums              solve_system.jl:169-204
     KK_RESIDENT,          // a slice of WHOLE outer iterations in one launch, state in LDS (cgo_resident.hpp)
+    KK_ACCEPT_TRIAL_NOSTORE, // accept + direction + trial that stores neither x nor u (HIP backend, replay)
+    KK_MATERIALIZE_XU,    // the pass that stores the pair such launches left in registers, for any other reader
     KK_ACCEPT_TRIAL_LAZY, // accept + direction + trial that leaves the new u unstored (HIP backend, lazy direction)
     KK_MATERIALIZE_U,     // the pass that stores the direction such a launch left in registers, for any other reader
     KK_COUNT

@@ -652,6 +652,7 @@ int HipBackend::set_x0_host(const double *x0) {
     if (int rc = pipe_drain()) return rc;
     discard_pending();   // a new x_initial: nothing of an earlier solve may be applied to it
     u_lag_ = false;      // … nor is the stored direction still one step behind it: init_eval writes u
+    rep_n_ = 0;          // … nor are there steps to replay on it
     HIPCHK(hipSetDevice(ctx_->device));
     xc_ = x_.p; xn_ = gb_.p;   // gb_ may not exist yet (sys_begin creates it)
     if (pingpong_ == 1) xalt_ = x2_.p;
@@ -664,6 +665,7 @@ int HipBackend::set_x0_device(const double *x0_dev) {
     if (int rc = pipe_drain()) return rc;
     discard_pending();   // a new x_initial: nothing of an earlier solve may be applied to it
     u_lag_ = false;      // … nor is the stored direction still one step behind it: init_eval writes u
+    rep_n_ = 0;          // … nor are there steps to replay on it
     HIPCHK(hipSetDevice(ctx_->device));
     xc_ = x_.p; xn_ = gb_.p;
     if (pingpong_ == 1) xalt_ = x2_.p;
@@ -686,6 +688,7 @@ int HipBackend::set_x0_fill(int kind, uint64_t seed, double lo, double hi) {
     if (int rc = pipe_drain()) return rc;
     discard_pending();   // a new x_initial: nothing of an earlier solve may be applied to it
     u_lag_ = false;      // … nor is the stored direction still one step behind it: init_eval writes u
+    rep_n_ = 0;          // … nor are there steps to replay on it
     xc_ = x_.p; xn_ = gb_.p;
     if (pingpong_ == 1) xalt_ = x2_.p;
     return fill_device(ctx_, xc_, obj_->n_local, obj_->offset, kind, seed, lo, hi);
@@ -928,6 +931,7 @@ int HipBackend::upg_sumsq(double &out) {
 int HipBackend::sys_begin() {
     if (!rmode_) { set_error("solvesystem needs an element-wise objective (k_cg kernel family)"); return CGO_EINVAL; }
     if (int rc = pipe_drain()) return rc;
+    if (int rc = materialize_lag()) return rc;   // solvesystem copies the stored iterate
     sys_on_ = true;
     HIPCHK(hipSetDevice(ctx_->device));
     if (int rc = ensure_gb()) return rc;
@@ -1002,7 +1006,7 @@ int HipBackend::scaled_norm_parts(int which, double a_trial, double &maxabs, dou
     const double *v = nullptr, *w = nullptr;   // the vector is v, or v − w
     if (which == 3) {                         // u is always stored
         if (int rc = pipe_drain()) return rc;
-        if (int rc = materialize_u()) return rc;
+        if (int rc = materialize_lag()) return rc;
         v = rmode_ ? uc_ : u_.p;
     } else if (rmode_) {  // rare path: materialise the vector whose norm is asked for (g, or g⁺ of the last trial,
         const double a1[1] = {a_trial};  // or — which = 2, solvesystem — the gradient at the second iterate buffer)
@@ -1082,6 +1086,7 @@ int HipBackend::tail_errors() {
 int HipBackend::download(double *x, double *g) {
     if (int rc = flush_lite()) return rc;
     if (int rc = pipe_drain()) return rc;
+    if (int rc = materialize_lag()) return rc;   // the stored iterate may be steps behind (replay)
     HIPCHK(hipSetDevice(ctx_->device));
     if (rmode_ && g) {  // the gradient lives only in registers during the solve: materialise ∇f(x) now
         if (int rc = launch_r(KK_INIT, R_GRAD, 0, 0, nullptr, 0, false, nullptr)) return rc;
@@ -1097,6 +1102,7 @@ int HipBackend::download(double *x, double *g) {
 int HipBackend::download_device(double *x_dev, double *g_dev) {
     if (int rc = flush_lite()) return rc;
     if (int rc = pipe_drain()) return rc;
+    if (int rc = materialize_lag()) return rc;   // the stored iterate may be steps behind (replay)
     HIPCHK(hipSetDevice(ctx_->device));
     if (rmode_ && g_dev) {  // the gradient lives only in registers during the solve: materialise ∇f(x) now
         if (int rc = launch_r(KK_INIT, R_GRAD, 0, 0, nullptr, 0, false, nullptr)) return rc;

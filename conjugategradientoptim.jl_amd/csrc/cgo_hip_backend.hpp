@@ -197,8 +197,14 @@ class HipBackend : public VecBackend {
     // Lazy direction: every second accept + dir + trial launch of an eligible solver leaves u unstored.
     void set_lazy_direction(bool on) { lazy_on_ = on; }
     bool lazy_direction() const { return lazy_on_; }
-    int set_lazy_direction_now(bool on) { if (!on) { if (int rc = materialize_u()) return rc; } lazy_on_ = on; return 0; }   // (mid-solve: the lag ends first)
+    int set_lazy_direction_now(bool on) { if (!on) { if (int rc = materialize_lag()) return rc; } lazy_on_ = on; return 0; }   // (mid-solve: the lag ends first)
     void set_probe_beta_prev(double b) { probe_beta_prev_ = b; }
+    // Replay: of every d accepting launches of an eligible solver d − 1 store nothing and the d-th stores x and u.
+    // d = 1: the lazy direction's alternation.
+    void set_replay_depth(int d) { replay_depth_ = d < 1 ? 1 : (d > 8 ? 8 : d); }
+    int replay_depth() const { return replay_depth_; }
+    int set_replay_depth_now(int d);   // (mid-solve: outstanding steps are stored first)
+    void set_probe_replay(int nrep, const double *a, const double *beta);
     std::string kernel_symbol(int kernel_kind) const;
     // Test entry point (cgo_solver_probe_launch): the vectors → this solver's device state, ONE launch of kind `kernel_kind`
     // with mode bits `variant` through the engine's own launch path, the whole reduced row and the vectors back.  The first
@@ -297,6 +303,10 @@ class HipBackend : public VecBackend {
     double beta_lag_ = 0.0, probe_beta_prev_ = 0.0;
     bool lazy_eligible() const;
     int materialize_u();   // store the rebuilt direction for any reader but the lag launches; clears u_lag_
+    // replay: memory holds (x_k, u_k); rep_a_[j], rep_b_[j] = (a*, β) of the rep_n_ steps accepted since, oldest first
+    int replay_depth_ = 1, rep_n_ = 0, probe_rep_n_ = 0;
+    double rep_a_[7] = {}, rep_b_[7] = {}, probe_rep_a_[7] = {}, probe_rep_b_[7] = {};
+    int materialize_lag();   // … and the replayed pair (x, u) likewise; clears u_lag_ and rep_n_
     int accept_dir_trial_r(double a_acc, double beta, const double *a, int k, double *s);
     int trial_r(const double *a, int k, double *s);
     int launch_r_kernel(int kk, int mode, double a_acc, double beta, const double *a, int k, int npts,

@@ -59,8 +59,14 @@ enum RMode : int {
     // accept + direction + trial launch leaves the OLD u in memory and the next launch forms the new one itself.
     R_ULAG = 1024, // on load, before anything else: u ← −∇f(x) + β_prev·u — memory holds (x_{k+1}, u_k), β_prev = β_k; no sums
                    // (those of this direction were formed by the launch that did not store it).  Alone: store that u.
-    R_NOWU = 2048  // R_DIR without the store of u: registers, sums and trials use the new direction, memory keeps the old one
+    R_NOWU = 2048, // R_DIR without the store of u: registers, sums and trials use the new direction, memory keeps the old one
+    // Replay: x may lag as well.  Memory holds (x_k, u_k) and the host the scalars (a*_k, β_k), (a*_{k+1}, β_{k+1}), …
+    // of the steps accepted since; a launch rebuilds the current pair in registers from them.
+    R_REPLAY = 4096, // on load, before anything else, for j < nrep: x ← x + ra[j]·u ; u ← −∇f(x) + rb[j]·u — the R_ACCEPT and R_DIR
+                     // expressions; no sums (they belonged to the launches that first formed these directions).  Alone: store x and u.
+    R_NOWX = 8192    // R_ACCEPT without the store of x (always together with R_NOWU)
 };
+constexpr int RMAX = 7;  // most replayed steps (replay depth up to 8)
 
 // Launch scalars kept in device memory for launches armed by the on-device controller
 // (cgo_ctl.hpp): written by the controller after launch k, read by launch k+1 — no host in between.
@@ -96,6 +102,8 @@ struct RParams {
     double *xo; double *uo;
     Tail tail;
     const double *p1, *p2, *p3;   // parameter slots 1–3 (run-time compiled objectives with kParams > 1 only)
+    int nrep;                     // R_REPLAY: how many accepted steps to replay on load (0 … RMAX), and their a* and β
+    double ra[RMAX], rb[RMAX];
 };
 
 // Workgroup reduction of N per-lane accumulators → one row of `partials`.
@@ -580,10 +588,25 @@ __device__ inline void cg_pair(const RParams &P, d2 &x, d2 &u, const PV<Obj> &p,
         u.x = -g0.x + P.beta_prev * u.x; u.y = -g0.y + P.beta_prev * u.y;
         if (MODE == R_ULAG) wu = true;
     }
+    if (MODE & R_REPLAY) {  // the steps accepted since (x, u) was stored.  Compile-time slot indices under a wave-uniform guard: a
+        // run-time index into the modifiable copy of the arguments would send the whole block to scratch (see cg_launch)
+#pragma unroll
+        for (int j = 0; j < RMAX; ++j) {
+            if (j < P.nrep) {
+                d2 gr;
+                double fr = 0.0;
+                x.x = x.x + P.ra[j] * u.x;
+                x.y = x.y + P.ra[j] * u.y;
+                obj_eval2<Obj>(x, p, P.s0, fr, gr);
+                u.x = -gr.x + P.rb[j] * u.x; u.y = -gr.y + P.rb[j] * u.y;
+            }
+        }
+        if (MODE == R_REPLAY) { wx = true; wu = true; }
+    }
     if (MODE & R_ACCEPT) {
         x.x = x.x + P.a_acc * u.x;
         x.y = x.y + P.a_acc * u.y;
-        wx = true;
+        wx = (MODE & R_NOWX) == 0;
     }
     d2 g;
     double f0 = 0.0;
@@ -662,7 +685,7 @@ template <class Obj, int MODE, int NPTS>
 __device__ inline void cg_single(const RParams &P, long long i, double (&acc)[RW<NPTS>::W]) {
     constexpr int R_GU = RW<NPTS>::GU, R_UU = RW<NPTS>::UU;
     double x = P.x[i];
-    double u = (MODE & (R_ACCEPT | R_DIR | R_TRIAL | R_UPG | R_GRADT | R_PROJ | R_ULAG)) ? P.u[i] : 0.0;
+    double u = (MODE & (R_ACCEPT | R_DIR | R_TRIAL | R_UPG | R_GRADT | R_PROJ | R_ULAG | R_REPLAY)) ? P.u[i] : 0.0;
     const PS<Obj> p = ps_load<Obj>(P, i);
     if (MODE & R_ULAG) {
         double g0 = 0.0, f00 = 0.0;
@@ -670,7 +693,19 @@ __device__ inline void cg_single(const RParams &P, long long i, double (&acc)[RW
         u = -g0 + P.beta_prev * u;
         if (MODE == R_ULAG) P.uo[i] = u;
     }
-    if (MODE & R_ACCEPT) { x = x + P.a_acc * u; P.xo[i] = x; }
+    if (MODE & R_REPLAY) {
+#pragma unroll
+        for (int j = 0; j < RMAX; ++j) {
+            if (j < P.nrep) {
+                double gr = 0.0, fr = 0.0;
+                x = x + P.ra[j] * u;
+                obj_eval1<Obj>(x, p, P.s0, fr, gr);
+                u = -gr + P.rb[j] * u;
+            }
+        }
+        if (MODE == R_REPLAY) { P.xo[i] = x; P.uo[i] = u; }
+    }
+    if (MODE & R_ACCEPT) { x = x + P.a_acc * u; if (!(MODE & R_NOWX)) P.xo[i] = x; }
     double g = 0.0, f0 = 0.0;
     obj_eval1<Obj>(x, p, P.s0, f0, g);
     if (MODE & R_INIT) { acc[RS_F] += f0; acc[RS_GTGT] = dsum(acc[RS_GTGT], g, g); P.uo[i] = -g; }
@@ -737,7 +772,7 @@ __device__ inline void cg_launch(const RParams &Pin) {
     double acc[W];
 #pragma unroll
     for (int s = 0; s < W; ++s) acc[s] = 0.0;
-    constexpr bool rd_u = (MODE & (R_ACCEPT | R_DIR | R_TRIAL | R_UPG | R_GRADT | R_PROJ | R_ULAG)) != 0;
+    constexpr bool rd_u = (MODE & (R_ACCEPT | R_DIR | R_TRIAL | R_UPG | R_GRADT | R_PROJ | R_ULAG | R_REPLAY)) != 0;
     constexpr bool wr_g = (MODE & (R_GRAD | R_GRADT)) != 0;
     constexpr bool proj = (MODE & R_PROJ) != 0;  // the gout argument of cg_pair carries x2
     const long long n2 = P.n >> 1;
@@ -789,7 +824,7 @@ __device__ inline void cg_launch(const RParams &Pin) {
         if (proj) stg2<BIG>(P.x2, i, ga);
     }
     if ((P.n & 1) && blockIdx.x == 0 && threadIdx.x == 0) cg_single<Obj, MODE, NPTS>(P, P.n - 1, acc);
-    if (MODE == R_ACCEPT || MODE == R_GRAD || MODE == R_GRADT || MODE == R_ULAG) return;  // no sums
+    if (MODE == R_ACCEPT || MODE == R_GRAD || MODE == R_GRADT || MODE == R_ULAG || MODE == R_REPLAY) return;  // no sums
 #if defined(CGO_STAMPS) && !defined(CGO_RTC)
     const unsigned long long st1 = (unsigned long long)wall_clock64();
 #endif

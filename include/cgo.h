@@ -423,6 +423,16 @@ int cgo_num_kernel_kinds(void);
  * env CGO_LAZY_DIR=0|1 forces it for every built-in objective; this call has the last word for one solver.  Meant to be
  * called before cgo_solver_start; later it takes effect at the next launch (switching off stores a lagged u first). */
 int cgo_solver_set_lazy_direction(cgo_solver *s, int32_t on);
+/* Replay.  The iterate is recoverable as well: x_{k+1} = x_k + a*_k·u_k with the host scalar a*_k.  At replay
+ * depth d ≥ 2 an eligible solver (as above) stores NOTHING in d − 1 of every d accept + direction + trial launches (kernel kind
+ * "accept_trial_nostore", 8n(2+p) bytes): each rebuilds the current (x, u) in registers from the stored pair and the list of
+ * (a*, β) of the steps accepted since, and the d-th ("accept_dir_trial", R_REPLAY instantiation, 8n(2+p+2) bytes) stores both.
+ * Any other reader of x or u gets both stored first ("materialize_xu", not counted in total_launches).  Results are those of
+ * the plain launches bit for bit.  d = 1 is the lazy direction's alternation.  Library policy: d > 1 only for the separable
+ * quadratic where an accepting launch exceeds the library's own pure-HBM threshold (1.4 GB); env CGO_REPLAY_DEPTH=1…8 forces
+ * it; this call has the last word for one solver (1 ≤ d ≤ 8; mid-solve, outstanding steps are stored first).
+ * cgo_solver_set_lazy_direction(s, 0) and CGO_LAZY_DIR=0 switch all of it off. */
+int cgo_solver_set_replay_depth(cgo_solver *s, int32_t d);
 /* The kernel instantiation a launch of `kernel_kind` uses under the solver's current policy, as the profiler
  * prints it without namespaces — e.g. "k_cg<ObjQuadDiag, 7, 7, true>" (objective, mode bits, trial points, pure-HBM
  * streaming policy).  Written NUL-terminated into buf[cap]. */
@@ -537,6 +547,11 @@ int cgo_kernel_trial(cgo_objective *obj, const double *x, const double *u, doubl
  *   accept_dir_trial: R_ULAG|7 = 1031   accept_trial_lazy: 7|R_NOWU = 2055   trial: R_ULAG|R_TRIAL = 1028   materialize_u: R_ULAG 1024
  * R_ULAG rebuilds u ← −∇f(x) + β_prev·u on load; β_prev is what this call set last (0 until then). */
 int cgo_solver_probe_set_beta_prev(cgo_solver *s, double beta_prev);
+/* The replay instantiations likewise (R_REPLAY = 4096, R_NOWX = 8192):
+ *   accept_trial_nostore: 4096|7|2048|8192 = 14343   accept_dir_trial: 4096|7 = 4103   trial: 4096|4 = 4100   materialize_xu: 4096
+ * R_REPLAY does, on load, for j < nrep: x ← x + a[j]·u ; u ← −∇f(x) + beta[j]·u.  The list is what this call set last (empty
+ * until then; 0 ≤ nrep ≤ 7). */
+int cgo_solver_probe_set_replay(cgo_solver *s, int32_t nrep, const double *a, const double *beta);
 int cgo_solver_probe_launch(cgo_solver *s, int32_t kernel_kind, int32_t variant, double a_acc, double beta,
                             const double *a, int32_t k,
                             const double *x, const double *u, const double *aux,
