@@ -791,6 +791,12 @@ class Solver:
         alternation.  Mid-solve, outstanding steps are stored first."""
         check(_lib.lib().cgo_solver_set_replay_depth(self._h, int(d)))
 
+    def set_lean_sums(self, on: bool):
+        """Lean sums for this solver (cgo_solver_set_lean_sums): the replay cycle's launches N and S leave out the trial sums
+        the solver's β flavour never reads, where the library has such kernels (Polak–Ribière); every number a solve returns
+        stays bit for bit.  Takes effect at the next launch."""
+        check(_lib.lib().cgo_solver_set_lean_sums(self._h, int(bool(on))))
+
     def probe_launch(self, kind_name: str, variant: int, a_acc: float, beta: float, a: Sequence[float], x, u=None, aux=None,
                      beta_prev: Optional[float] = None, replay: Optional[Sequence] = None):
         """ONE launch of kind `kind_name` with mode bits `variant` on this rank's host vectors (cgo_solver_probe_launch): returns

@@ -16,6 +16,7 @@ using namespace dev;
 double bytes_r(int obj_kind, int mode, int64_t n, int n_params) {
     const int p = std::max(obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0, n_params);
     int v = 0;
+    mode &= ~R_LEAN;   // lean sums drop arithmetic, not bytes
     if (mode == R_INIT) v = 1 + p + 1;
     else if (mode == R_TRIAL) v = 2 + p;
     else if (mode == (R_ACCEPT | R_DIR | R_TRIAL)) v = 2 + p + 2;
@@ -73,12 +74,22 @@ static int launch_cg(int mode, int npts, const RParams &P, int grid, hipStream_t
 #define ROW(MODE, MAXPTS) case (MODE): with_points<MAXPTS>(npts, [&](auto n) { k_cg<Obj, (MODE), decltype(n)::value, true><<<grid, BLOCK, 0, st>>>(P); }); return 0;
         CGO_CG_LAG_ROWS(ROW)
         CGO_CG_REPLAY_ROWS(ROW)
+        CGO_CG_LEAN_ROWS(ROW)
 #undef ROW
         default: break;
         }
     }
     return -1;
 }
+
+// Lean sums: the R_NO… bits to or into `mode` — those of the solver's β flavour where the table has that row.
+static inline bool lean_row(int mode) {
+#define ROW(MODE, MAXPTS) if (mode == (MODE)) return true;
+    CGO_CG_LEAN_ROWS(ROW)
+#undef ROW
+    return false;
+}
+int HipBackend::lean_for(int mode) const { return (lean_bits_ && lean_row(mode | lean_bits_)) ? lean_bits_ : 0; }
 
 // Row width of a CG launch: 7 sums per trial point + 2 direction sums, padded (10 or 24).
 static inline int rows_for(int npts) { return npts == 1 ? NR1 : (npts == 3 ? NR : (npts == 5 ? NR5 : NR7)); }
@@ -195,12 +206,14 @@ int HipBackend::accept_dir_trial_r(double a_acc, double beta, const double *a, i
     if (replay_depth_ >= 2) {
         if (int rc = materialize_u()) return rc;
         if (rep_n_ < replay_depth_ - 1 && rep_n_ < RMAX) {   // launch N: the new pair in registers only
-            if (int rc = launch_r(KK_ACCEPT_TRIAL_NOSTORE, R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL | R_NOWU | R_NOWX, a_acc, beta, a, k, true, s)) return rc;
+            const int mode_n = R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL | R_NOWU | R_NOWX;
+            if (int rc = launch_r(KK_ACCEPT_TRIAL_NOSTORE, mode_n | lean_for(mode_n), a_acc, beta, a, k, true, s)) return rc;
             rep_a_[rep_n_] = a_acc; rep_b_[rep_n_] = beta; rep_n_++;
             return CGO_OK;
         }
         // launch S: replays the outstanding steps, then today's launch
-        if (int rc = launch_r(KK_ACCEPT_DIR_TRIAL, R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL, a_acc, beta, a, k, true, s)) return rc;
+        const int mode_s = R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL;
+        if (int rc = launch_r(KK_ACCEPT_DIR_TRIAL, mode_s | lean_for(mode_s), a_acc, beta, a, k, true, s)) return rc;
         rep_n_ = 0;
         return CGO_OK;
     }
@@ -384,6 +397,7 @@ std::string HipBackend::kernel_symbol(int kk) const {
         default: return "";
         }
         const bool big = (mode & (R_ULAG | R_NOWU | R_REPLAY | R_NOWX)) != 0 || bytes_r(obj_->kind, mode, n, hp) > big_bytes(mode == R_TRIAL || mode == R_UPG);
+        if ((mode & R_REPLAY) && (mode & R_ACCEPT)) mode |= lean_for(mode);   // N and S: the lean row where that is what runs
         return r_symbol(mode, chain() ? chain_npts(mode, npts) : npts, big);
     }
     if (obj_->two_phase()) {
@@ -829,8 +843,12 @@ int HipBackend::probe_launch(int kk, int variant, double a_acc, double beta, con
         switch (kk) {
         case KK_INIT: mode = chain() ? pick(R_INIT, {R_INIT, R_GRAD, R_EDGES}) : pick(R_INIT, {R_INIT, R_GRAD}); break;
         case KK_TRIAL: mode = pick(R_TRIAL, {R_TRIAL, R_ULAG | R_TRIAL, R_REPLAY | R_TRIAL}); break;
-        case KK_ACCEPT_DIR_TRIAL: mode = pick(R_ACCEPT | R_DIR | R_TRIAL, {R_ACCEPT | R_DIR | R_TRIAL, R_ULAG | R_ACCEPT | R_DIR | R_TRIAL, R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL}); break;
-        case KK_ACCEPT_TRIAL_NOSTORE: mode = pick(R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL | R_NOWU | R_NOWX, {R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL | R_NOWU | R_NOWX}); break;
+        case KK_ACCEPT_DIR_TRIAL:
+            if (variant & R_LEAN) { mode = (lean_row(variant) && (variant & ~R_LEAN) == (R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL)) ? variant : -1; break; }   // lean S
+            mode = pick(R_ACCEPT | R_DIR | R_TRIAL, {R_ACCEPT | R_DIR | R_TRIAL, R_ULAG | R_ACCEPT | R_DIR | R_TRIAL, R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL}); break;
+        case KK_ACCEPT_TRIAL_NOSTORE:
+            if (variant & R_LEAN) { mode = (lean_row(variant) && (variant & ~R_LEAN) == (R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL | R_NOWU | R_NOWX)) ? variant : -1; break; }   // lean N
+            mode = pick(R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL | R_NOWU | R_NOWX, {R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL | R_NOWU | R_NOWX}); break;
         case KK_MATERIALIZE_XU: mode = pick(R_REPLAY, {R_REPLAY}); break;
         case KK_ACCEPT_TRIAL_LAZY: mode = pick(R_ACCEPT | R_DIR | R_TRIAL | R_NOWU, {R_ACCEPT | R_DIR | R_TRIAL | R_NOWU}); break;
         case KK_MATERIALIZE_U: mode = pick(R_ULAG, {R_ULAG}); break;

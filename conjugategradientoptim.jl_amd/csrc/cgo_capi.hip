@@ -378,6 +378,7 @@ int cgo_ctx_set_default_policy(cgo_ctx *ctx, const cgo_solver_policy *policy) {
 
 // explicit argument > context default > CGO_* experiment override > library policy, field by field
 static const int kReplayDepth = 6;   // best median of 1, 2, 3, 4, 6, 8 on one MI355X at n = 1e8: BASELINE.md, profiles/r06_replay_*
+static const bool kLeanSums = true;   // lean sums where replay's default is on: BASELINE.md, profiles/r07_lean_*
 static int env_tri(const char *name) { const char *e = getenv(name); return e ? (e[0] != '0' ? 1 : 0) : -1; }
 static int resolve_policy(cgo_ctx *ctx, const cgo_solver_policy *arg, cgo_solver_policy &r, std::string &why) {
     cgo_solver_policy lib; cgo_solver_policy_init(&lib);
@@ -552,6 +553,18 @@ static int make_solver(cgo_ctx *ctx, cgo_objective *obj, const cgo_cg_config *cf
         if (obj->o.kind == CGO_OBJ_QUAD_DIAG && 8.0 * (double)obj->o.n_local * 5.0 > 1.4e9) depth = kReplayDepth;
         if (const char *e = getenv("CGO_REPLAY_DEPTH")) { const int v = atoi(e); if (v >= 1 && v <= 8) depth = v; }
         s->be->set_replay_depth(depth);
+    }
+    // Lean sums: launches N and S of the replay cycle do not form the trial sums the β flavour never reads
+    // (beta_unread_sums) — arithmetic of launches short of FP64 issue slots, not bytes; every sum that is read keeps its bits.
+    // Library policy: on exactly where replay's own default is on (same objective, same threshold of the library's own) and
+    // the flavour's mask has rows (cgo_instances.def: Polak–Ribière's); a flavour without rows keeps the full ones whatever is
+    // asked.  CGO_LEAN_SUMS=0|1 forces it for every built-in objective and size; cgo_solver_set_lean_sums has the last word.
+    {
+        bool lean = kLeanSums && obj->o.kind == CGO_OBJ_QUAD_DIAG && 8.0 * (double)obj->o.n_local * 5.0 > 1.4e9;
+        const int forced = env_tri("CGO_LEAN_SUMS");
+        if (forced >= 0) lean = forced != 0;
+        s->be->set_beta_unread(beta_unread_sums(cfg->beta.kind));
+        s->be->set_lean_sums(lean);
     }
     if (int prc = s->be->place()) { delete s; obj_unref(obj); return prc; }
     if (pol.resident >= 0) s->be->set_resident(pol.resident != 0);
@@ -774,6 +787,14 @@ int cgo_solver_set_replay_depth(cgo_solver *s, int32_t d) {
     REQUIRE(s, "null argument");
     REQUIRE(d >= 1 && d <= 8, "replay depth: 1 … 8");
     return s->be->set_replay_depth_now(d);
+    API_GUARD_END
+}
+
+int cgo_solver_set_lean_sums(cgo_solver *s, int32_t on) {
+    API_GUARD_BEGIN
+    REQUIRE(s, "null argument");
+    s->be->set_lean_sums(on != 0);
+    return CGO_OK;
     API_GUARD_END
 }
 

@@ -88,6 +88,22 @@ CGO_HD inline double beta_from_sums(int kind, double mu, const TrialSums &t, dou
     }
 }
 
+// Which trial sums a flavour NEVER reads — not in beta_from_sums, not in beta_norms_fast_ok or the rare-path norms that
+// follow it, not in the engine (which reads f, gtu, gtgt of every point whatever the flavour) — as the R_NO… mode bits of the
+// k_cg family (cgo_kernels_cg.hip.hpp; repeated here: this header knows no kernels).  A launch may leave those slots +0.0.
+constexpr int CTL_NOGTG = 16384, CTL_NOYY = 32768, CTL_NOUY = 65536, CTL_NOYGT = 131072;
+CGO_HD inline int beta_unread_sums(int kind) {
+    switch (kind) {
+    case CGO_BETA_HAGER_ZHANG: return CTL_NOGTG;                                 // reads uy, yy, ygt, gtu
+    case CGO_BETA_SALLEH_ALHAWARAT: return CTL_NOYY | CTL_NOUY | CTL_NOYGT;      // reads gtg, gtu, norm(g⁺)
+    case CGO_BETA_LIU_STORREY:
+    case CGO_BETA_HESTENES_STIEFEL: return CTL_NOGTG | CTL_NOYY;                 // read ygt, uy
+    case CGO_BETA_POLAK_RIBIERE: return CTL_NOGTG | CTL_NOYY | CTL_NOUY;         // reads ygt
+    case CGO_BETA_DAI_YUAN: return CTL_NOGTG | CTL_NOYY | CTL_NOYGT;             // reads gtgt, uy
+    default: return 0;   // Yuan–Wang–Sheng (its norms and rare paths read the rest), L-BFGS, Broyden: every sum stays
+    }
+}
+
 // first step of a line search from the previous accepted step (optim.jl:92)
 CGO_HD inline double ls_first_step(const cgo_ls_config &ls, double a_initial) {
     if (ls.kind == CGO_LS_BACKTRACKING) return a_initial;  // geometric.jl:48-56 (non-finite → |ϕ₀|/u·u, later)

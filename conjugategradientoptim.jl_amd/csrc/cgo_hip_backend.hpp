@@ -205,6 +205,11 @@ class HipBackend : public VecBackend {
     int replay_depth() const { return replay_depth_; }
     int set_replay_depth_now(int d);   // (mid-solve: outstanding steps are stored first)
     void set_probe_replay(int nrep, const double *a, const double *beta);
+    // Lean sums: launches N and S without the trial sums the solver's β flavour never reads (beta_unread_sums),
+    // where cgo_instances.def has rows for that mask.  The stored state is the same either way: no pass is needed to switch.
+    void set_beta_unread(int bits) { lean_mask_ = bits; if (lean_bits_) lean_bits_ = bits; }
+    void set_lean_sums(bool on) { lean_bits_ = on ? lean_mask_ : 0; }
+    bool lean_sums() const { return lean_bits_ != 0; }
     std::string kernel_symbol(int kernel_kind) const;
     // Test entry point (cgo_solver_probe_launch): the vectors → this solver's device state, ONE launch of kind `kernel_kind`
     // with mode bits `variant` through the engine's own launch path, the whole reduced row and the vectors back.  The first
@@ -307,6 +312,8 @@ class HipBackend : public VecBackend {
     int replay_depth_ = 1, rep_n_ = 0, probe_rep_n_ = 0;
     double rep_a_[7] = {}, rep_b_[7] = {}, probe_rep_a_[7] = {}, probe_rep_b_[7] = {};
     int materialize_lag();   // … and the replayed pair (x, u) likewise; clears u_lag_ and rep_n_
+    int lean_mask_ = 0, lean_bits_ = 0;   // the flavour's R_NO… bits; those in force (0: full rows)
+    int lean_for(int mode) const;         // … for this mode: lean_bits_ where a lean row exists, else 0
     int accept_dir_trial_r(double a_acc, double beta, const double *a, int k, double *s);
     int trial_r(const double *a, int k, double *s);
     int launch_r_kernel(int kk, int mode, double a_acc, double beta, const double *a, int k, int npts,

@@ -64,8 +64,19 @@ enum RMode : int {
     // of the steps accepted since; a launch rebuilds the current pair in registers from them.
     R_REPLAY = 4096, // on load, before anything else, for j < nrep: x ← x + ra[j]·u ; u ← −∇f(x) + rb[j]·u — the R_ACCEPT and R_DIR
                      // expressions; no sums (they belonged to the launches that first formed these directions).  Alone: store x and u.
-    R_NOWX = 8192    // R_ACCEPT without the store of x (always together with R_NOWU)
+    R_NOWX = 8192,   // R_ACCEPT without the store of x (always together with R_NOWU)
+    // Lean sums: trial sums the solver's β flavour never reads (beta_unread_sums, cgo_ctl.hpp) are not formed —
+    // compile-time only, no branch in the loop.  Row width and slot positions stay; a dropped slot leaves the tail as +0.0, the
+    // others keep their accumulator chains bit for bit.  R_TRIAL block only.
+    R_NOGTG = 16384,   // no Σ g⁺·g
+    R_NOYY = 32768,    // no Σ y·y
+    R_NOUY = 65536,    // no Σ u·y
+    R_NOYGT = 131072   // no Σ y·g⁺
 };
+constexpr int R_LEAN = R_NOGTG | R_NOYY | R_NOUY | R_NOYGT;   // transparent to every decision taken on a mode but the row that runs
+#ifndef CGO_RTC
+static_assert(CTL_NOGTG == R_NOGTG && CTL_NOYY == R_NOYY && CTL_NOUY == R_NOUY && CTL_NOYGT == R_NOYGT, "beta_unread_sums speaks in these bits");
+#endif
 constexpr int RMAX = 7;  // most replayed steps (replay depth up to 8)
 
 // Launch scalars kept in device memory for launches armed by the on-device controller
@@ -672,10 +683,10 @@ __device__ inline void cg_pair(const RParams &P, d2 &x, d2 &u, const PV<Obj> &p,
             const double y0 = gt.x - g.x, y1 = gt.y - g.y;
             acc[b + RS_GTU] = dsum(acc[b + RS_GTU], gt.x, u.x);   acc[b + RS_GTU] = dsum(acc[b + RS_GTU], gt.y, u.y);
             acc[b + RS_GTGT] = dsum(acc[b + RS_GTGT], gt.x, gt.x); acc[b + RS_GTGT] = dsum(acc[b + RS_GTGT], gt.y, gt.y);
-            acc[b + RS_GTG] = dsum(acc[b + RS_GTG], gt.x, g.x);   acc[b + RS_GTG] = dsum(acc[b + RS_GTG], gt.y, g.y);
-            acc[b + RS_YY] = dsum(acc[b + RS_YY], y0, y0);       acc[b + RS_YY] = dsum(acc[b + RS_YY], y1, y1);
-            acc[b + RS_UY] = dsum(acc[b + RS_UY], u.x, y0);      acc[b + RS_UY] = dsum(acc[b + RS_UY], u.y, y1);
-            acc[b + RS_YGT] = dsum(acc[b + RS_YGT], y0, gt.x);    acc[b + RS_YGT] = dsum(acc[b + RS_YGT], y1, gt.y);
+            if (!(MODE & R_NOGTG)) { acc[b + RS_GTG] = dsum(acc[b + RS_GTG], gt.x, g.x);   acc[b + RS_GTG] = dsum(acc[b + RS_GTG], gt.y, g.y); }
+            if (!(MODE & R_NOYY)) { acc[b + RS_YY] = dsum(acc[b + RS_YY], y0, y0);       acc[b + RS_YY] = dsum(acc[b + RS_YY], y1, y1); }
+            if (!(MODE & R_NOUY)) { acc[b + RS_UY] = dsum(acc[b + RS_UY], u.x, y0);      acc[b + RS_UY] = dsum(acc[b + RS_UY], u.y, y1); }
+            if (!(MODE & R_NOYGT)) { acc[b + RS_YGT] = dsum(acc[b + RS_YGT], y0, gt.x);    acc[b + RS_YGT] = dsum(acc[b + RS_YGT], y1, gt.y); }
         }
     }
 }
@@ -736,8 +747,11 @@ __device__ inline void cg_single(const RParams &P, long long i, double (&acc)[RW
             double gt;
             obj_eval1<Obj>(xp, p, P.s0, acc[b + RS_F], gt);
             const double y = gt - g;
-            acc[b + RS_GTU] = dsum(acc[b + RS_GTU], gt, u); acc[b + RS_GTGT] = dsum(acc[b + RS_GTGT], gt, gt); acc[b + RS_GTG] = dsum(acc[b + RS_GTG], gt, g);
-            acc[b + RS_YY] = dsum(acc[b + RS_YY], y, y); acc[b + RS_UY] = dsum(acc[b + RS_UY], u, y); acc[b + RS_YGT] = dsum(acc[b + RS_YGT], y, gt);
+            acc[b + RS_GTU] = dsum(acc[b + RS_GTU], gt, u); acc[b + RS_GTGT] = dsum(acc[b + RS_GTGT], gt, gt);
+            if (!(MODE & R_NOGTG)) acc[b + RS_GTG] = dsum(acc[b + RS_GTG], gt, g);
+            if (!(MODE & R_NOYY)) acc[b + RS_YY] = dsum(acc[b + RS_YY], y, y);
+            if (!(MODE & R_NOUY)) acc[b + RS_UY] = dsum(acc[b + RS_UY], u, y);
+            if (!(MODE & R_NOYGT)) acc[b + RS_YGT] = dsum(acc[b + RS_YGT], y, gt);
         }
     }
 }

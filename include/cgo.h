@@ -433,6 +433,15 @@ int cgo_solver_set_lazy_direction(cgo_solver *s, int32_t on);
  * it; this call has the last word for one solver (1 ≤ d ≤ 8; mid-solve, outstanding steps are stored first).
  * cgo_solver_set_lazy_direction(s, 0) and CGO_LAZY_DIR=0 switch all of it off. */
 int cgo_solver_set_replay_depth(cgo_solver *s, int32_t d);
+/* Lean sums.  A β flavour reads only some of the seven sums a trial point delivers (Polak–Ribière: f, g⁺·u,
+ * g⁺·g⁺ and y·g⁺); the seven-point launches are short of FP64 issue slots, not of bytes.  With lean sums on, launches N and S of
+ * the replay cycle run instantiations that do not form the sums the solver's flavour never reads (R_NOGTG = 16384,
+ * R_NOYY = 32768, R_NOUY = 65536, R_NOYGT = 131072 in the reported symbol): those slots of the row come back +0.0, every other
+ * slot, x and u bit for bit as before; kernel kinds and bytes per launch are unchanged.  Kernels exist for Polak–Ribière's mask;
+ * a solver of any other flavour keeps the full rows whatever is asked.  Library policy: on where the replay depth's own default
+ * is > 1; env CGO_LEAN_SUMS=0|1 forces it for every built-in objective and size; this call has the last word for one solver
+ * and takes effect at the next launch (the stored state is the same either way). */
+int cgo_solver_set_lean_sums(cgo_solver *s, int32_t on);
 /* The kernel instantiation a launch of `kernel_kind` uses under the solver's current policy, as the profiler
  * prints it without namespaces — e.g. "k_cg<ObjQuadDiag, 7, 7, true>" (objective, mode bits, trial points, pure-HBM
  * streaming policy).  Written NUL-terminated into buf[cap]. */
@@ -550,7 +559,8 @@ int cgo_solver_probe_set_beta_prev(cgo_solver *s, double beta_prev);
 /* The replay instantiations likewise (R_REPLAY = 4096, R_NOWX = 8192):
  *   accept_trial_nostore: 4096|7|2048|8192 = 14343   accept_dir_trial: 4096|7 = 4103   trial: 4096|4 = 4100   materialize_xu: 4096
  * R_REPLAY does, on load, for j < nrep: x ← x + a[j]·u ; u ← −∇f(x) + beta[j]·u.  The list is what this call set last (empty
- * until then; 0 ≤ nrep ≤ 7). */
+ * until then; 0 ≤ nrep ≤ 7).
+ * Lean N and S (Polak–Ribière's mask 16384|32768|65536 = 114688 or-ed in): accept_trial_nostore 129031, accept_dir_trial 118791. */
 int cgo_solver_probe_set_replay(cgo_solver *s, int32_t nrep, const double *a, const double *beta);
 int cgo_solver_probe_launch(cgo_solver *s, int32_t kernel_kind, int32_t variant, double a_acc, double beta,
                             const double *a, int32_t k,
