@@ -85,6 +85,27 @@ class ResidentProbeC(C.Structure):  # cgo_resident_probe
                 ("wrote_back", C.c_int32), ("out", ResidentPassOutC * 32), ("symbol", C.c_char * 128)]
 
 
+class CtlStateC(C.Structure):  # cgo_ctl_state = CtlState (csrc/cgo_ctl.hpp)
+    _fields_ = [("f_x", C.c_double), ("gg", C.c_double), ("a_acc", C.c_double), ("beta", C.c_double), ("a", C.c_double * 7),
+                ("npts", C.c_int32), ("go", C.c_int32), ("it", C.c_int64)]
+
+
+class CtlArgsC(C.Structure):  # cgo_ctl_args = CtlArgs (csrc/cgo_kernels_cg.hip.hpp)
+    _fields_ = [("a_acc", C.c_double), ("beta", C.c_double), ("a", C.c_double * 7), ("go", C.c_int64)]
+
+
+class CtlRecordC(C.Structure):  # cgo_ctl_record = CtlRecord (csrc/cgo_ctl.hpp)
+    _fields_ = [("sums", C.c_double * 56), ("a_acc", C.c_double), ("beta", C.c_double), ("a", C.c_double * 7),
+                ("npts", C.c_int32), ("accepted", C.c_int32), ("xwait", C.c_int64)]
+
+
+class ArmedProbeC(C.Structure):  # cgo_armed_probe
+    _fields_ = [("rounds", C.c_int32), ("form", C.c_int32), ("use_eps", C.c_int32), ("reserved", C.c_int32),
+                ("max_iters", C.c_int64), ("eps", C.c_double), ("st", CtlStateC), ("row", C.c_double * 56),
+                ("width", C.c_int32), ("maxp", C.c_int32), ("round_out", C.c_uint64), ("st_out", CtlStateC),
+                ("args_out", CtlArgsC), ("out_dev", C.c_double * 56), ("rec", CtlRecordC * 32), ("symbol", C.c_char * 4096)]
+
+
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, dp, dp, C.c_int32)
 FDF_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, dp, dp, C.c_int64)   # cgo_fdf_fn: f = fdf!(g, x)
 
@@ -175,6 +196,7 @@ SIGNATURES = {
                                           dp, C.c_int32, C.POINTER(C.c_int32), dp, dp, dp, C.c_char_p, C.c_int32]),
     "cgo_solver_probe_lbfgs": (C.c_int, [_vp, C.POINTER(LbfgsProbeC)] + [dp] * 13),
     "cgo_solver_probe_resident": (C.c_int, [_vp, C.POINTER(ResidentProbeC), dp, dp, dp, C.c_int64, dp, dp]),
+    "cgo_solver_probe_armed": (C.c_int, [_vp, C.POINTER(ArmedProbeC), dp, dp, dp, dp]),
 }
 
 

@@ -919,6 +919,53 @@ class Solver:
         return dict(rows=rws, tail=tails, out=outs, grid=g, chunk=p.chunk, points=p.points, round0=p.round0,
                     wrote_back=bool(p.wrote_back), x=xo, u=uo, symbol=p.symbol.decode())
 
+    ARMED_FORMS = ("rounds", "graph", "controller")
+
+    def probe_armed(self, state, rounds=1, form="rounds", x=None, u=None, max_iters=1 << 40, eps=None, row=None):
+        """A batch of controller-armed rounds on host vectors (cgo_solver_probe_armed).  `state`: dict(f_x=, gg=, a_acc=, beta=,
+        a=[1 … 7 trial steps, the last one repeated into the slots behind], npts= (default len(a)), go= (default 1), it=
+        (default 0)) — the CtlState k_ctl_init writes; max_iters and eps (None: the solver's) complete the controller's
+        config.  form "rounds": launched one by one, "graph": the engine's captured batches of 8 / 4 / 2, "controller":
+        k_finalize_ctl alone on `row` (up to 56 sums), one round, x and u not needed.  Returns dict(records=[per round:
+        dict(sums= all 56, a_acc=, beta=, a= all 7, npts=, accepted=, xwait=, bytes= the record as it was published)],
+        st=, args= (dicts of the device block's state and argument block after the last round, each with bytes=), round=,
+        out_dev= (56 slots), width=, maxp=, x=, u=, symbols=[every instantiation launched, in order]).  For probing only from
+        the first call on."""
+        n = self.obj.n_local
+        p = _lib.ArmedProbeC()
+        p.rounds, p.form = int(rounds), self.ARMED_FORMS.index(form)
+        p.max_iters = int(max_iters)
+        if eps is not None:
+            p.use_eps, p.eps = 1, float(eps)
+        a = [float(v) for v in state["a"]]
+        if not 1 <= len(a) <= 7:
+            raise ValueError("probe_armed: 1 to 7 trial steps")
+        p.st.f_x, p.st.gg = float(state["f_x"]), float(state["gg"])
+        p.st.a_acc, p.st.beta = float(state["a_acc"]), float(state["beta"])
+        p.st.a[:] = a + [a[-1]] * (7 - len(a))
+        p.st.npts, p.st.go, p.st.it = int(state.get("npts", len(a))), int(state.get("go", 1)), int(state.get("it", 0))
+        if row is not None:
+            r = [float(v) for v in row]
+            p.row[:len(r)] = r
+        vec = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float64)
+        x, u = vec(x), vec(u)
+        for v in (x, u):
+            if v is not None and v.size != n:
+                raise ValueError(f"probe vectors hold n_local = {n} elements")
+        xo, uo = np.full(n, np.nan), np.full(n, np.nan)
+        ptr = lambda v: None if v is None else v.ctypes.data_as(dp)
+        check(_lib.lib().cgo_solver_probe_armed(self._h, C.byref(p), ptr(x), ptr(u), ptr(xo), ptr(uo)))
+
+        def block(c, names):
+            d = {k: (np.array(getattr(c, k)[:]) if k in ("a", "sums") else getattr(c, k)) for k in names}
+            d["bytes"] = bytes(c)
+            return d
+        recs = [block(p.rec[r], ("sums", "a_acc", "beta", "a", "npts", "accepted", "xwait")) for r in range(p.rounds)]
+        sym = p.symbol.decode()
+        return dict(records=recs, st=block(p.st_out, ("f_x", "gg", "a_acc", "beta", "a", "npts", "go", "it")),
+                    args=block(p.args_out, ("a_acc", "beta", "a", "go")), round=int(p.round_out), out_dev=np.array(p.out_dev[:]),
+                    width=p.width, maxp=p.maxp, x=xo, u=uo, symbols=sym.split(" + ") if sym else [])
+
     def placement_info(self):
         """(as_allocated_us, chosen_us, candidates) of the solver's placement search (cgo_solver_placement_info);
         candidates == 0: no search was made."""

@@ -574,7 +574,11 @@ int HipBackend::pipe_round_kernels() {
     CtlDev *d = (CtlDev *)ctl_dev_;
     if (int rc = launch_r_kernel(KK_ACCEPT_DIR_TRIAL, R_ACCEPT | R_DIR | R_TRIAL, 0.0, 0.0, nullptr, 0, npts, &d->args, &grid)) return rc;
     pipe_checked_ = pipe_fused(grid) && !ctx_->tail_strict;
-    if (pipe_fused(grid)) return CGO_OK;   // the launch's own finisher reduced, ran the controller and published the record
+    if (pipe_fused(grid)) {   // the launch's own finisher reduced, ran the controller and published the record
+        if (probe_) probe_note(nullptr, 0, "k_cg_armed<%s, %d>", obj_tname(), last_npts_);
+        return CGO_OK;
+    }
+    if (probe_) probe_note(nullptr, 0, "%s", r_symbol(last_mode_, last_npts_, last_big_).c_str());
     hipStream_t st = ctx_->stream;
     const double *src = ctx_->partials;
     int nrows = grid;
@@ -582,12 +586,21 @@ int HipBackend::pipe_round_kernels() {
         const int nb = (grid + TAIL_GROUP - 1) / TAIL_GROUP;
         with_width<NR, NR5, NR7, NS>(ns, true, [&](auto w) { k_finalize_t<decltype(w)::value, BLOCK><<<nb, BLOCK, 0, st>>>(ctx_->partials, TAIL_GROUP, grid, ctx_->partials2, nullptr, nullptr, 0); });
         HIPCHK(hipGetLastError());
+        if (probe_) probe_note(nullptr, 0, "k_finalize_t<%d>", ns);
         src = ctx_->partials2;
         nrows = nb;
     }
+    return pipe_finalize_ctl(src, nrows, ns);
+}
+
+// the last kernel of an un-fused round: `nrows` rows of width `ns` → sums → ctl_step → state, arguments, record
+int HipBackend::pipe_finalize_ctl(const double *src, int nrows, int ns) {
+    CtlDev *d = (CtlDev *)ctl_dev_;
     CtlRecord *rec = (CtlRecord *)ctl_rec_;
+    hipStream_t st = ctx_->stream;
     with_width<NR, NR5, NR7, NS>(ns, true, [&](auto w) { constexpr int N = decltype(w)::value, T = N == NS ? BLOCK : 768; k_finalize_ctl<N, T><<<1, T, 0, st>>>(src, nrows, ctx_->out_dev, d, rec, ctl_seq_); });
     HIPCHK(hipGetLastError());
+    if (probe_) probe_note(nullptr, 0, "k_finalize_ctl<%d>", ns);
     return CGO_OK;
 }
 
@@ -613,6 +626,7 @@ int HipBackend::pipe_launch_graph(int rounds) {
         hipStream_t st = ctx_->stream;
         hipGraph_t graph = nullptr;
         capturing_ = true;
+        const size_t syms0 = probe_syms_.size();   // (a probed solver: what the captured rounds launch, for every replay's report)
         hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
         int rc = CGO_OK;
         if (e == hipSuccess) {
@@ -627,9 +641,11 @@ int HipBackend::pipe_launch_graph(int rounds) {
         e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
         if (e != hipSuccess) { set_error(std::string("hipGraphInstantiate failed: ") + hipGetErrorString(e)); return CGO_EHIP; }
-        graphs_.push_back(PipeGraph{exec, rounds, pipe_npts_, xc_, uc_, obj_->p[0].p, obj_->n_local});
+        graphs_.push_back(PipeGraph{exec, rounds, pipe_npts_, xc_, uc_, obj_->p[0].p, obj_->n_local, {}});
         g = &graphs_.back();
+        if (probe_) { g->syms = probe_syms_.substr(syms0 ? syms0 + 3 : 0); probe_syms_.resize(syms0); }
     }
+    if (probe_ && !g->syms.empty()) { if (!probe_syms_.empty()) probe_syms_ += " + "; probe_syms_ += g->syms; }
     HIPCHK(hipGraphLaunch((hipGraphExec_t)g->exec, ctx_->stream));
     for (int r = 0; r < rounds; ++r) {
         pipe_prof_[(int)(pipe_enq_ % PIPE_RING)] = {-1, prof_gen_};
@@ -1022,6 +1038,91 @@ int HipBackend::probe_launch_stored(int kk, int variant, double a_acc, double be
     *sums_len = probe_len_;
     if (probe_len_ > sums_cap) { set_error("probe: sums_cap smaller than the launch's rows"); return CGO_EINVAL; }
     if (probe_len_) std::memcpy(sums, probe_row_, sizeof(double) * probe_len_);
+    return CGO_OK;
+}
+
+// ---- a batch of controller-armed rounds on host vectors (cgo_solver_probe_armed) --------------------------------------------
+// What accept_dir_trial_ctl does when it arms a batch — k_ctl_init from the caller's state, pipe_enqueue, pipe_wait per round —
+// with every record handed out whole instead of being replayed into the host state machine, then the device block itself.
+// Form 2 launches the controller kernel of an un-fused round alone (pipe_finalize_ctl) on a row the caller supplies.
+static_assert(sizeof(cgo_ctl_state) == sizeof(CtlState) && sizeof(cgo_ctl_args) == sizeof(CtlArgs) && sizeof(cgo_ctl_record) == sizeof(CtlRecord),
+              "include/cgo.h repeats the controller's blocks word for word");
+static_assert(offsetof(cgo_ctl_state, npts) == offsetof(CtlState, npts) && offsetof(cgo_ctl_state, it) == offsetof(CtlState, it) &&
+              offsetof(cgo_ctl_args, go) == offsetof(CtlArgs, go) && offsetof(cgo_ctl_record, a_acc) == offsetof(CtlRecord, a_acc) &&
+              offsetof(cgo_ctl_record, npts) == offsetof(CtlRecord, npts) && offsetof(cgo_ctl_record, xwait) == offsetof(CtlRecord, xwait),
+              "include/cgo.h repeats the controller's blocks word for word");
+
+int HipBackend::probe_armed(const cgo_cg_config &cfg, const cgo_ls_config &ls, cgo_armed_probe &p, const double *x, const double *u,
+                            double *x_out, double *u_out) {
+    p.symbol[0] = 0;
+    if (ctx_->world() != 1) { set_error("probe: a single-rank solver"); return CGO_EINVAL; }
+    if (ctl_depth() <= 0) { set_error("probe: this solver's engine arms no rounds (controller depth 0)"); return CGO_EINVAL; }
+    if (p.form < 0 || p.form > 2 || p.rounds < 1 || p.rounds > CGO_ARMED_PROBE_MAX_ROUNDS || (p.form == 2 && p.rounds != 1)) {
+        set_error("probe: form 0 | 1 | 2, 1 ≤ rounds ≤ 32, the controller alone (form 2) runs one round"); return CGO_EINVAL;
+    }
+    if (p.st.npts < 0 || p.st.npts > CTL_MAXP) { set_error("probe: 0 ≤ npts ≤ 7 trial steps"); return CGO_EINVAL; }
+    if (p.form != 2 && !(x && u)) { set_error("probe: armed rounds read x and u"); return CGO_EINVAL; }
+    if (int rc = probe_prepare()) return rc;
+    if (int rc = pipe_drain()) return rc;
+    if (int rc = pipe_alloc()) return rc;
+    HIPCHK(hipSetDevice(ctx_->device));
+    hipStream_t st = ctx_->stream;
+    const size_t nb = (size_t)obj_->n_local * sizeof(double);
+    CtlConfig cc;
+    cc.ls = ls; cc.eps = p.use_eps ? p.eps : cfg.eps; cc.mu = cfg.beta.mu;
+    cc.beta_kind = cfg.beta.kind; cc.maxp = max_points();
+    cc.max_iters = p.max_iters;
+    CtlState s0;
+    std::memcpy(&s0, &p.st, sizeof s0);
+    const int ns = rows_for(cc.maxp);
+    if (x) HIPCHK(hipMemcpyAsync(xc_, x, nb, hipMemcpyHostToDevice, st));
+    if (u) HIPCHK(hipMemcpyAsync(uc_, u, nb, hipMemcpyHostToDevice, st));
+    if (p.form == 2) HIPCHK(hipMemcpyAsync(ctx_->partials, p.row, sizeof(double) * ns, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    u_lag_ = false; rep_n_ = 0;
+    pipe_npts_ = cc.maxp;
+    probe_syms_.clear();
+    const unsigned long long first = pipe_enq_;
+    k_ctl_init<<<1, 1, 0, st>>>((CtlDev *)ctl_dev_, cc, s0, pipe_enq_);
+    HIPCHK(hipGetLastError());
+    pipe_stopped_ = false;
+    int rc = CGO_OK;
+    if (p.form == 2) {
+        pipe_checked_ = false;   // k_finalize_ctl releases the plain sequence number
+        rc = pipe_finalize_ctl(ctx_->partials, 1, ns);
+        if (!rc) { pipe_prof_[(int)(pipe_enq_ % PIPE_RING)] = {-1, prof_gen_}; pipe_enq_++; }
+    } else {
+        const bool graph0 = graph_on_;
+        graph_on_ = p.form == 1;
+        rc = pipe_enqueue(p.rounds);
+        graph_on_ = graph0;
+    }
+    for (unsigned long long id = first; !rc && id < pipe_enq_; ++id) {
+        CtlRecord rec;
+        rc = pipe_wait(id, rec);
+        if (!rc) { std::memcpy(&p.rec[id - first], &rec, sizeof rec); pipe_done_++; }
+    }
+    if (rc) {   // nothing is retried: the stream is left to finish what it holds, the pipe counts as drained
+        (void)hipStreamSynchronize(st);
+        pipe_done_ = pipe_enq_;
+        return rc == CGO_EINVAL ? rc : CGO_ESTATE;
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    CtlDev d;
+    double od[CTL_NSUMS] = {};
+    HIPCHK(hipMemcpyAsync(&d, ctl_dev_, sizeof d, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(od, ctx_->out_dev, sizeof(double) * ns, hipMemcpyDeviceToHost, st));
+    if (x_out) HIPCHK(hipMemcpyAsync(x_out, xc_, nb, hipMemcpyDeviceToHost, st));
+    if (u_out) HIPCHK(hipMemcpyAsync(u_out, uc_, nb, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::memcpy(&p.st_out, &d.st, sizeof d.st);
+    std::memcpy(&p.args_out, &d.args, sizeof d.args);
+    p.round_out = d.round;
+    std::memcpy(p.out_dev, od, sizeof od);
+    p.width = ns; p.maxp = cc.maxp;
+    if (int rc2 = probe_slack_intact()) return rc2;
+    if (probe_syms_.size() >= sizeof p.symbol) { set_error("probe: the symbol list does not fit"); return CGO_ESTATE; }
+    std::snprintf(p.symbol, sizeof p.symbol, "%s", probe_syms_.c_str());
     return CGO_OK;
 }
 

@@ -675,7 +675,7 @@ int cgo_solver_set_x0_fill(cgo_solver *s, int32_t kind, uint64_t seed, double lo
 int cgo_solver_start(cgo_solver *s) {
     API_GUARD_BEGIN
     REQUIRE(s, "null argument");
-    if (s->be->probed()) { set_error("a solver that a probe (cgo_solver_probe_launch / _lbfgs / _resident) has used is for probing only"); return CGO_ESTATE; }
+    if (s->be->probed()) { set_error("a solver that a probe (cgo_solver_probe_launch / _lbfgs / _resident / _armed) has used is for probing only"); return CGO_ESTATE; }
     return s->sv->start();
     API_GUARD_END
 }
@@ -683,7 +683,7 @@ int cgo_solver_start(cgo_solver *s) {
 int cgo_solver_iterate(cgo_solver *s, int64_t iters, int32_t *finished) {
     API_GUARD_BEGIN
     REQUIRE(s, "null argument");
-    if (s->be->probed()) { set_error("a solver that a probe (cgo_solver_probe_launch / _lbfgs / _resident) has used is for probing only"); return CGO_ESTATE; }
+    if (s->be->probed()) { set_error("a solver that a probe (cgo_solver_probe_launch / _lbfgs / _resident / _armed) has used is for probing only"); return CGO_ESTATE; }
     bool fin = false;
     int rc = s->sv->iterate(iters, fin);
     if (rc == CGO_ESTATE) set_error("cgo_solver_iterate before cgo_solver_start");
@@ -1041,6 +1041,14 @@ int cgo_solver_probe_resident(cgo_solver *s, cgo_resident_probe *p, const double
     API_GUARD_BEGIN
     REQUIRE(s && p && x && u && rows && rows_cap >= 0, "bad argument");
     return s->be->probe_resident(s->sv->config(), s->sv->linesearch(), *p, x, u, rows, rows_cap, x_out, u_out);
+    API_GUARD_END
+}
+
+int cgo_solver_probe_armed(cgo_solver *s, cgo_armed_probe *p, const double *x, const double *u, double *x_out, double *u_out) {
+    API_GUARD_BEGIN
+    REQUIRE(s && p, "null argument");
+    REQUIRE(!s->sv->is_sys(), "probe: armed rounds belong to minimizeobjective's line searches");
+    return s->be->probe_armed(s->sv->config(), s->sv->linesearch(), *p, x, u, x_out, u_out);
     API_GUARD_END
 }
 

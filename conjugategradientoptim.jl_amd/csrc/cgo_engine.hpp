@@ -227,6 +227,7 @@ class Solver {
     VecBackend *backend() { return be_; }
     const cgo_cg_config &config() const { return cfg_; }
     const cgo_ls_config &linesearch() const { return ls_; }
+    bool is_sys() const { return sys_; }
 
   private:
     // evalϕdϕ! (cg_utils.jl:4-23).  h1/h2: the (at most two) steps the line search can ask for

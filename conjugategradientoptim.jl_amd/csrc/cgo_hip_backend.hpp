@@ -232,6 +232,11 @@ class HipBackend : public VecBackend {
     int probe_resident(const cgo_cg_config &cfg, const cgo_ls_config &ls, cgo_resident_probe &p, const double *x, const double *u,
                        double *rows, int64_t rows_cap, double *x_out, double *u_out);
 
+    // Test entry point (cgo_solver_probe_armed): a batch of controller-armed rounds on host vectors through k_ctl_init,
+    // pipe_enqueue and pipe_wait — every record whole, the device block and the vectors back.
+    int probe_armed(const cgo_cg_config &cfg, const cgo_ls_config &ls, cgo_armed_probe &p, const double *x, const double *u,
+                    double *x_out, double *u_out);
+
     // raw single-launch helpers used by the kernel-level C entry points
     static int run_dir(HipCtx *ctx, double *u_host, const double *g_host, double beta, int64_t n,
                        double *out2);
@@ -336,10 +341,11 @@ class HipBackend : public VecBackend {
     unsigned prof_gen_ = 0;
     int pipe_alloc();
     int pipe_round_kernels();
+    int pipe_finalize_ctl(const double *src, int nrows, int ns);
     int pipe_enqueue_round();
     int pipe_launch_graph(int rounds);
     int pipe_enqueue(int64_t count);
-    struct PipeGraph { void *exec; int rounds, npts; double *x, *u; const double *p0; int64_t n; };   // (armed rounds: built-in objectives, one slot)
+    struct PipeGraph { void *exec; int rounds, npts; double *x, *u; const double *p0; int64_t n; std::string syms; };   // (armed rounds: built-in objectives, one slot)
     std::vector<PipeGraph> graphs_;      // instantiated hipGraphs of 2 / 4 / 8 controller rounds
     bool graph_on_ = false;              // CGO_CTL_GRAPH=1: batches of armed rounds replay from instantiated hipGraphs (measured 3–8 % slower than kernel-by-kernel enqueue)
     bool capturing_ = false;

@@ -531,7 +531,7 @@ int cgo_kernel_trial(cgo_objective *obj, const double *x, const double *u, doubl
  * parameter vector is the OBJECTIVE's: its old buffer is freed, so the objective of a probed solver must not be shared with
  * another solver in use (one that has started, or keeps a captured graph or a resident slice on it).
  * CGO_EINVAL for every other kind (the L-BFGS passes: cgo_solver_probe_lbfgs; the resident solver: cgo_solver_probe_resident;
- * armed rounds — the on-device controller's finisher — have no probe and remain outside: they are what is left unprobed).
+ * armed rounds — the on-device controller's finisher, k_cg_armed and k_finalize_ctl — cgo_solver_probe_armed).
  *
  * A solver of the stored-gradient family (k_fused: β = LBFGS(m) on an element-wise objective, a host-closure objective,
  * policy.stored_gradient) is probed through the same entry point, single rank only, one trial step (k = 1) where the kind
@@ -653,6 +653,56 @@ typedef struct cgo_resident_probe {
 } cgo_resident_probe;
 int cgo_solver_probe_resident(cgo_solver *s, cgo_resident_probe *p, const double *x, const double *u,
                               double *rows, int64_t rows_cap, double *x_out, double *u_out);
+/* A batch of CONTROLLER-ARMED rounds (csrc/cgo_ctl.hpp) of a single-rank solver on host vectors, through the
+ * engine's own path: k_ctl_init writes the device block from `st` and the solver's configuration (line search, β kind, μ and the
+ * row layout — trial points per launch — are the solver's; max_iters, and eps where use_eps is set, are given here), the rounds
+ * are enqueued as the engine enqueues them, and every record is awaited with the engine's bounded wait.  The solver's policy
+ * and its context's tail setting pick the form of a round: ONE launch (k_cg_armed, whose finisher runs the controller) where
+ * the fused tail applies, else k_cg reading its scalars from the device block + k_finalize_t above 64 rows + k_finalize_ctl.
+ *   form 0  rounds launched one by one
+ *        1  as captured graphs, the engine's own split into batches of 8, 4 and 2 rounds (a remaining round goes by itself)
+ *        2  the controller alone: `row` is placed as a single row of partials and k_finalize_ctl<width> is launched on it,
+ *           rounds = 1, no vector is read or written (x, u may be NULL) — for sums no vector data produces on demand
+ * 1 ≤ rounds ≤ CGO_ARMED_PROBE_MAX_ROUNDS.  The three structs below are the controller's own (CtlState, CtlArgs, CtlRecord),
+ * word for word.  Out: rec[0..rounds) whole; st_out, args_out, round_out = the device block after the last round (round
+ * counts on from probe to probe); out_dev = the device copy of the last reduced row (width slots, +0.0 behind them); x_out /
+ * u_out (may be NULL) the vectors after the last round; symbol = every instantiation launched, in order, joined by " + ", e.g.
+ * "k_cg_armed<ObjQuadDiag, 7>" or "k_cg<ObjBooth, 7, 3, false> + k_finalize_ctl<24>".  As with cgo_solver_probe_launch the
+ * first probe gives every buffer NaN slack, every call checks it and drains the controller's pipe before it returns, and the
+ * solver is for probing only.  A record that does not validate, or the bounded wait running out: CGO_ESTATE, never a hang.
+ * CGO_EINVAL where the engine would arm no round (controller depth 0: multi-rank without device mailboxes, two-phase and
+ * stencil objectives, the stored-gradient family), for a multi-rank solver, and for bad arguments. */
+#define CGO_ARMED_PROBE_MAX_ROUNDS 32
+typedef struct cgo_ctl_state {
+    double f_x, gg, a_acc, beta, a[7];
+    int32_t npts, go;
+    int64_t it;
+} cgo_ctl_state;
+typedef struct cgo_ctl_args {
+    double a_acc, beta, a[7];
+    int64_t go;
+} cgo_ctl_args;
+typedef struct cgo_ctl_record {
+    double sums[56], a_acc, beta, a[7];
+    int32_t npts, accepted;
+    int64_t xwait;
+} cgo_ctl_record;
+typedef struct cgo_armed_probe {
+    int32_t rounds, form, use_eps, reserved;
+    int64_t max_iters;
+    double eps;
+    cgo_ctl_state st;
+    double row[56];                                       /* form 2 */
+    /* out */
+    int32_t width, maxp;
+    uint64_t round_out;
+    cgo_ctl_state st_out;
+    cgo_ctl_args args_out;
+    double out_dev[56];
+    cgo_ctl_record rec[CGO_ARMED_PROBE_MAX_ROUNDS];
+    char symbol[4096];
+} cgo_armed_probe;
+int cgo_solver_probe_armed(cgo_solver *s, cgo_armed_probe *p, const double *x, const double *u, double *x_out, double *u_out);
 /* device-resident micro-benchmark of the fused kernels: allocates vectors of
  * n doubles on the ctx, runs `reps` launches of `kernel_kind`, returns the mean
  * HIP-event time per launch (ms) and the algorithmic bytes per launch */

@@ -739,4 +739,13 @@ double sim_beta_from_scalars(const cgo_beta_config *b, const double *t7, double 
 
 const char *sim_status_name(int s) { return status_name(s); }
 
+// ctl_step (csrc/cgo_ctl.hpp) as the host compiles it, on blocks passed as bytes: the reference the device-compiled controller
+// (tail_ctl, k_finalize_ctl) is held to word for word.  `state` is advanced in place, `rec` receives the whole record, both
+// zeroed first where the structs have padding; returns 1 where the round armed the next one.  sizes: sizeof of the three blocks.
+int sim_ctl_step(const CtlConfig *cfg, CtlState *state, const double *row56, CtlRecord *rec) {
+    std::memset((void *)rec, 0, sizeof *rec);
+    return ctl_step(*cfg, *state, row56, *rec) ? 1 : 0;
+}
+void sim_ctl_sizes(int64_t *out3) { out3[0] = sizeof(CtlConfig); out3[1] = sizeof(CtlState); out3[2] = sizeof(CtlRecord); }
+
 }  // extern "C"

@@ -56,6 +56,30 @@ int main(void){
     assert [int(v) for v in l3.split()] == [20, 7, 3]
 
 
+def test_armed_probe_struct_layout_matches_header(cgo, tmp_path):
+    """cgo_armed_probe and the controller blocks it carries (cgo_ctl_state, cgo_ctl_args, cgo_ctl_record): sizeof and the
+    offsets of the fields behind every change of alignment, header against ctypes."""
+    from cgo_amd import _lib
+    fields = {"cgo_ctl_state": ("a", "npts", "go", "it"), "cgo_ctl_args": ("a", "go"), "cgo_ctl_record": ("a_acc", "a", "npts", "accepted", "xwait"),
+              "cgo_armed_probe": ("max_iters", "eps", "st", "row", "width", "round_out", "st_out", "args_out", "out_dev", "rec", "symbol")}
+    ct = {"cgo_ctl_state": _lib.CtlStateC, "cgo_ctl_args": _lib.CtlArgsC, "cgo_ctl_record": _lib.CtlRecordC, "cgo_armed_probe": _lib.ArmedProbeC}
+    lines = []
+    for t, fs in fields.items():
+        lines.append(f' printf("%zu", sizeof({t}));')
+        lines += [f' printf(" %zu", offsetof({t}, {f}));' for f in fs]
+        lines.append(' printf("\\n");')
+    prog = tmp_path / "armed_layout.c"
+    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "cgo.h"\nint main(void){\n' + "\n".join(lines) +
+                    '\n printf("%d\\n", CGO_ARMED_PROBE_MAX_ROUNDS);\n return 0; }\n')
+    exe = tmp_path / "armed_layout"
+    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.strip().splitlines()
+    for line, (t, fs) in zip(out, fields.items()):
+        assert [int(v) for v in line.split()] == [C.sizeof(ct[t])] + [getattr(ct[t], f).offset for f in fs], t
+    assert int(out[-1]) == 32 == _lib.ArmedProbeC.rec.size // C.sizeof(_lib.CtlRecordC)
+    assert C.sizeof(_lib.CtlStateC) == 104 and C.sizeof(_lib.CtlArgsC) == 80 and C.sizeof(_lib.CtlRecordC) == 536   # csrc/cgo_ctl.hpp
+
+
 def test_status_names_are_the_reference_symbols(cgo):
     from cgo_amd import _lib
     from oracle import oracle as O
