@@ -93,6 +93,18 @@ struct ObjQuadDiag {  // f = ½ Σ D_i x_i²
         g = p * x;
         f += 0.5 * (g * x);
     }
+    // f = kFScale · Σ raw terms (ObjFScale below): the same g, the terms D_i x_i² without the factor
+    static constexpr double kFScale = 0.5;
+    __device__ static inline void eval2_raw(d2 x, d2 p, double, double &f, d2 &g) {
+        g.x = p.x * x.x;
+        g.y = p.y * x.y;
+        f += g.x * x.x;
+        f += g.y * x.y;
+    }
+    __device__ static inline void eval1_raw(double x, double p, double, double &f, double &g) {
+        g = p * x;
+        f += g * x;
+    }
 };
 
 struct ObjRosenPaired {  // f = Σ_j 100 (x_{2j+1} − x_{2j}²)² + (1 − x_{2j})²   (0-based)
@@ -144,7 +156,25 @@ template <class Obj> __device__ inline void obj_eval1(double x, const PS<Obj> &p
     if constexpr (ObjParams<Obj>::array) Obj::eval1(x, p.v, s0, f, g);
     else Obj::eval1(x, p.v[0], s0, f, g);
 }
-// Slot J of an argument block that carries p0 … p3.  J is a compile-time constant at every use: a run-time index into the
+// Late scaling.  A functor may declare `static constexpr double kFScale = c`, c a power of two, together with eval2_raw / eval1_raw
+// (the scalar-`p` signatures): they form g exactly as eval2 / eval1 do and add the objective's terms to f WITHOUT the factor c, so
+// that f = c · Σ raw terms.  Scaling by a power of two commutes with rounding — fl(c·a + c·b) = c · fl(a + b) — while no term or
+// partial sum is subnormal and the unscaled sum stays finite, so a launch may accumulate the raw terms and scale each lane's sum
+// once (the lean rows of k_cg: LateF, cgo_kernels_cg.hip.hpp).  Declared by ObjQuadDiag only.
+template <class Obj, class = void> struct ObjFScale { static constexpr bool declared = false; static constexpr double scale = 1.0; };
+template <class Obj> struct ObjFScale<Obj, decltype((void)Obj::kFScale)> {
+    static constexpr bool declared = true; static constexpr double scale = Obj::kFScale;
+    static_assert(!ObjParams<Obj>::array, "eval2_raw / eval1_raw take the scalar-p signatures");
+};
+template <class Obj, bool RAW> __device__ inline void obj_term2(d2 x, const PV<Obj> &p, double s0, double &f, d2 &g) {
+    if constexpr (RAW) Obj::eval2_raw(x, p.v[0], s0, f, g);
+    else obj_eval2<Obj>(x, p, s0, f, g);
+}
+template <class Obj, bool RAW> __device__ inline void obj_term1(double x, const PS<Obj> &p, double s0, double &f, double &g) {
+    if constexpr (RAW) Obj::eval1_raw(x, p.v[0], s0, f, g);
+    else obj_eval1<Obj>(x, p, s0, f, g);
+}
+// Slot J of an argument block that carries p0 … p3. J is a compile-time constant at every use: a run-time index into the
 // argument copy would send the whole block to scratch (the note at cg_launch's reduction tail, cgo_kernels_cg.hip.hpp).
 template <int J, class A> __device__ inline const double *param_slot(const A &P) {
     static_assert(J >= 0 && J < MAX_PARAM_SLOTS, "no such slot");

@@ -589,6 +589,18 @@ __device__ inline void store_partials_n(double (&acc)[N], double *partials, cons
 
 template <int NPTS> struct RW { static constexpr int W = (NPTS == 1) ? NR1 : (NPTS == 3 ? NR : (NPTS == 5 ? NR5 : NR7)); static constexpr int GU = RS_PER_POINT * NPTS, UU = GU + 1; };
 
+// Late scaling of f (ObjFScale, cgo_kernels.hip.hpp): on exactly where the objective declares a scale AND the launch
+// is a lean row.  The R_TRIAL block then adds the raw terms and cg_launch scales each lane's NPTS f accumulators once, before the
+// reduction: NPTS multiplications per lane instead of 2·NPTS per element pair.  No mode bit of its own — a lean row IS "no unread
+// sums, and f scaled late".  -DCGO_LEAN_SCALE_EARLY restores per-term scaling in the lean rows (A/B).
+template <class Obj, int MODE> struct LateF {
+#ifdef CGO_LEAN_SCALE_EARLY
+    static constexpr bool on = false;
+#else
+    static constexpr bool on = ObjFScale<Obj>::declared && (MODE & R_LEAN) != 0;
+#endif
+};
+
 template <class Obj, int MODE, int NPTS>
 __device__ inline void cg_pair(const RParams &P, d2 &x, d2 &u, const PV<Obj> &p, double (&acc)[RW<NPTS>::W], bool &wx, bool &wu, d2 &gout) {
     constexpr int R_GU = RW<NPTS>::GU, R_UU = RW<NPTS>::UU;
@@ -679,7 +691,7 @@ __device__ inline void cg_pair(const RParams &P, d2 &x, d2 &u, const PV<Obj> &p,
             d2 xp, gt;
             xp.x = x.x + P.a[j] * u.x;
             xp.y = x.y + P.a[j] * u.y;
-            obj_eval2<Obj>(xp, p, P.s0, acc[b + RS_F], gt);
+            obj_term2<Obj, LateF<Obj, MODE>::on>(xp, p, P.s0, acc[b + RS_F], gt);
             const double y0 = gt.x - g.x, y1 = gt.y - g.y;
             acc[b + RS_GTU] = dsum(acc[b + RS_GTU], gt.x, u.x);   acc[b + RS_GTU] = dsum(acc[b + RS_GTU], gt.y, u.y);
             acc[b + RS_GTGT] = dsum(acc[b + RS_GTGT], gt.x, gt.x); acc[b + RS_GTGT] = dsum(acc[b + RS_GTGT], gt.y, gt.y);
@@ -745,7 +757,7 @@ __device__ inline void cg_single(const RParams &P, long long i, double (&acc)[RW
             const int b = RS_PER_POINT * j;
             const double xp = x + P.a[j] * u;
             double gt;
-            obj_eval1<Obj>(xp, p, P.s0, acc[b + RS_F], gt);
+            obj_term1<Obj, LateF<Obj, MODE>::on>(xp, p, P.s0, acc[b + RS_F], gt);
             const double y = gt - g;
             acc[b + RS_GTU] = dsum(acc[b + RS_GTU], gt, u); acc[b + RS_GTGT] = dsum(acc[b + RS_GTGT], gt, gt);
             if (!(MODE & R_NOGTG)) acc[b + RS_GTG] = dsum(acc[b + RS_GTG], gt, g);
@@ -838,6 +850,11 @@ __device__ inline void cg_launch(const RParams &Pin) {
         if (proj) stg2<BIG>(P.x2, i, ga);
     }
     if ((P.n & 1) && blockIdx.x == 0 && threadIdx.x == 0) cg_single<Obj, MODE, NPTS>(P, P.n - 1, acc);
+    if constexpr (LateF<Obj, MODE>::on) {  // the lane's sums of raw terms → its f sums, once (lean rows carry R_TRIAL: the only writer of these slots)
+        static_assert((MODE & R_TRIAL) && !(MODE & (R_INIT | R_PROJ)), "only the trial block of a lean row adds raw terms");
+#pragma unroll
+        for (int j = 0; j < NPTS; ++j) acc[RS_PER_POINT * j + RS_F] *= ObjFScale<Obj>::scale;
+    }
     if (MODE == R_ACCEPT || MODE == R_GRAD || MODE == R_GRADT || MODE == R_ULAG || MODE == R_REPLAY) return;  // no sums
 #if defined(CGO_STAMPS) && !defined(CGO_RTC)
     const unsigned long long st1 = (unsigned long long)wall_clock64();
