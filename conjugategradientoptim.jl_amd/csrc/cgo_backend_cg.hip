@@ -15,34 +15,10 @@ using namespace dev;
 // ---- gradient-free multi-point CG family (cgo_kernels_cg.hip.hpp) ---------------------------
 double bytes_r(int obj_kind, int mode, int64_t n, int n_params) {
     const int p = std::max(obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0, n_params);
-    int v = 0;
-    mode &= ~R_LEAN;   // lean sums drop arithmetic, not bytes
-    if (mode == R_INIT) v = 1 + p + 1;
-    else if (mode == R_TRIAL) v = 2 + p;
-    else if (mode == (R_ACCEPT | R_DIR | R_TRIAL)) v = 2 + p + 2;
-    else if (mode == (R_ACCEPT | R_DIR)) v = 2 + p + 2;
-    else if (mode == R_ACCEPT) v = 2 + 1;
-    else if (mode == R_RESET) v = 1 + p + 1;
-    else if (mode == R_UPG) v = 2 + p;
-    else if (mode == R_GRAD) v = 1 + p + 1;
-    else if (mode == R_GRADT) v = 2 + p + 1;
-    else if (mode == R_DIR || mode == (R_DIR | R_TRIAL)) v = 2 + p + 1;
-    else if (mode == R_PROJ) v = 3 + p + 1;
-    else if (mode == R_EDGES) v = 0;
-    // lazy direction: A reads x, u, D and writes x; B is the plain launch on the lagged pair; a trial in the lagged state
-    // writes nothing; the materialise pass writes u
-    else if (mode == (R_ACCEPT | R_DIR | R_TRIAL | R_NOWU)) v = 2 + p + 1;
-    else if (mode == (R_ULAG | R_ACCEPT | R_DIR | R_TRIAL)) v = 2 + p + 2;
-    else if (mode == (R_ULAG | R_TRIAL)) v = 2 + p;
-    else if (mode == R_ULAG) v = 2 + p + 1;
-    // replay: N reads x, u, D and writes nothing; S is the plain launch on the replayed pair; a trial with steps outstanding
-    // writes nothing; the materialise pass writes x and u
-    else if (mode == (R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL | R_NOWU | R_NOWX)) v = 2 + p;
-    else if (mode == (R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL)) v = 2 + p + 2;
-    else if (mode == (R_REPLAY | R_TRIAL)) v = 2 + p;
-    else if (mode == R_REPLAY) v = 2 + p + 2;
-    return 8.0 * (double)n * (double)v;
+    return 8.0 * (double)n * (double)r_vectors(mode, p);   // reads + writes of the mode (cgo_modes.hpp): a new row needs no edit here
 }
+// pure-HBM streaming: the rows that exist in that form only, or above the threshold for what the mode does
+static inline bool launch_is_big(const HipBackend &be, int mode, double bytes) { return r_big_only(mode) || bytes > be.big_bytes(r_read_only(mode)); }
 
 // The point ladder, written once: f(Pts<N>) for the odd N ≤ MAXPTS a launch of `npts` points takes.  A count that is none of
 // them takes the largest where that is 7 (k_cg), 1 otherwise (k_chain: anything but 3).
@@ -91,9 +67,16 @@ static inline bool lean_row(int mode) {
 }
 int HipBackend::lean_for(int mode) const { return (lean_bits_ && lean_row(mode | lean_bits_)) ? lean_bits_ : 0; }
 
-// Row width of a CG launch: 7 sums per trial point + 2 direction sums, padded (10 or 24).
-static inline int rows_for(int npts) { return npts == 1 ? NR1 : (npts == 3 ? NR : (npts == 5 ? NR5 : NR7)); }
-static inline int npts_for(int k) { return k <= 1 ? 1 : (k <= 3 ? 3 : (k <= 5 ? 5 : 7)); }  // kernel variant for k trial steps
+// a row of an `npts`-point launch (0: npts_for(k)) → the scalars of its first k trial points and, with `dir`, the direction sums
+void unpack_r(const double *s, int k, Scal *out, bool dir, int npts) {
+    if (npts == 0) npts = npts_for(k);
+    for (int j = 0; j < k; ++j) {
+        const double *q = s + RS_PER_POINT * j;
+        out[j].f = q[RS_F]; out[j].gtu = q[RS_GTU]; out[j].gtgt = q[RS_GTGT]; out[j].gtg = q[RS_GTG];
+        out[j].yy = q[RS_YY]; out[j].uy = q[RS_UY]; out[j].ygt = q[RS_YGT];
+    }
+    if (dir) { out[0].gu = s[RS_PER_POINT * npts]; out[0].uu = s[RS_PER_POINT * npts + 1]; }
+}
 
 // stencil launches carry one or three trial points: three only where the mode evaluates trials at all
 static inline int chain_npts(int mode, int npts) { return ((mode & R_TRIAL) && npts >= 3) ? 3 : 1; }
@@ -106,7 +89,7 @@ int HipBackend::launch_r(int kk, int mode, double a_acc, double beta, const doub
     // u without reading it (R_INIT, R_RESET) simply ends the lag.  (accept_dir_trial / trial choose the lag modes; a probe
     // never meets the flag.)
     if (u_lag_ && !(mode & R_ULAG)) {
-        if (mode & (R_ACCEPT | R_DIR | R_TRIAL | R_UPG | R_GRADT | R_PROJ)) { if (int rc = materialize_u()) return rc; }
+        if (r_reads_u(mode)) { if (int rc = materialize_u()) return rc; }
         else if (mode & (R_INIT | R_RESET)) u_lag_ = false;
     }
     // Steps outstanding (replay): x lags too, and every launch reads x — R_RESET and R_INIT included.  Any launch but N / S / T
@@ -116,7 +99,7 @@ int HipBackend::launch_r(int kk, int mode, double a_acc, double beta, const doub
     const int npts = npts_for(k);
     if (int rc = launch_r_kernel(kk, mode, a_acc, beta, a, k, npts, nullptr, &grid)) return rc;
     total_launches_++;
-    const bool has_sums = (mode != R_ACCEPT && mode != R_GRAD && mode != R_GRADT && mode != R_ULAG && mode != R_REPLAY);
+    const bool has_sums = r_has_sums(mode);
     const bool fused = has_sums && tail_fused(grid);   // the launch's last workgroup already left the sums (finish_tail)
     if (has_sums && chain()) {   // 24- or 32-slot rows: the sums + this rank's eight edge values (cgo_kernels_chain.hip.hpp)
         const bool three = chain_npts(mode, npts) == 3;
@@ -153,7 +136,11 @@ int HipBackend::launch_r(int kk, int mode, double a_acc, double beta, const doub
 // trial launch and the plain trial launch of this solver have to be BIG ones (same partition, same order of additions).
 bool HipBackend::lazy_eligible() const {
     if (!lazy_on_ || !rmode_ || chain() || sys_on_ || probe_ || pingpong_ == 1) return false;
-    if (obj_->kind != CGO_OBJ_QUAD_DIAG && obj_->kind != CGO_OBJ_ROSENBROCK_PAIRED && obj_->kind != CGO_OBJ_BOOTH) return false;
+    bool aot = false;   // the objectives with ahead-of-time kernels
+#define ROW(KIND, T) aot = aot || obj_->kind == KIND;
+    CGO_OBJ_ROWS(ROW)
+#undef ROW
+    if (!aot) return false;
     if (const char *e = getenv("CGO_PINGPONG")) { if (e[0] == '1') return false; }
     if (ctl_depth() > 0) return false;
     const int64_t n = obj_->n_local;
@@ -265,10 +252,9 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
     if (obj_->unset_slot() >= 0) return param_unset_error(obj_->unset_slot());
     const int64_t n = obj_->n_local;
     if (mode & (R_GRAD | R_GRADT)) { if (int rc = ensure_ga()) return rc; }
-    const bool has_sums = (mode != R_ACCEPT && mode != R_GRAD && mode != R_GRADT && mode != R_ULAG && mode != R_REPLAY);
+    const bool has_sums = r_has_sums(mode);
     if (chain()) {
-        const double bytes = bytes_r(obj_->kind, mode, n, false);
-        const bool big = bytes > big_bytes(mode == R_TRIAL || mode == R_UPG);
+        const bool big = launch_is_big(*this, mode, bytes_r(obj_->kind, mode, n, 0));
         const int grid = big ? GRID_BIG : grid_cg(n, 1);
         *grid_out = grid;
         last_mode_ = mode; last_npts_ = chain_npts(mode, npts); last_big_ = big;
@@ -286,9 +272,7 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
     P.ctl = ctl;
     P.x2 = xn_;
     for (int j = 0; j < MAXP; ++j) P.a[j] = (a && j < k) ? a[j] : ((a && k > 0) ? a[k - 1] : 0.0);
-    const double bytes = bytes_r(obj_->kind, mode, n, obj_->nparams());
-    const bool lag = (mode & (R_ULAG | R_NOWU | R_REPLAY | R_NOWX)) != 0;   // BIG instantiations only (lazy_eligible)
-    const bool big = lag || bytes > big_bytes(mode == R_TRIAL || mode == R_UPG);
+    const bool big = launch_is_big(*this, mode, bytes_r(obj_->kind, mode, n, obj_->nparams()));
     const int grid = big ? GRID_BIG : grid_cg(n, npts);
     *grid_out = grid;
     last_mode_ = mode; last_npts_ = npts; last_big_ = big;
@@ -303,8 +287,7 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
         }
     }
     if (P.tail.tickets) P.partials = ctx_->partials_f;
-    const bool wr_x = ((mode & R_ACCEPT) != 0 && !(mode & R_NOWX)) || mode == R_REPLAY;
-    const bool wr_u = ((mode & (R_DIR | R_INIT | R_RESET)) != 0 && !(mode & R_NOWU)) || mode == R_ULAG || mode == R_REPLAY;
+    const bool wr_x = r_writes_x(mode), wr_u = r_writes_u(mode);
     const bool pp = big && !ctl && (wr_x || wr_u) && !(mode & R_PROJ) && pingpong_ready();
     if (pp && wr_x) P.xo = xalt_;
     if (pp && wr_u) P.uo = ualt_;
@@ -318,7 +301,7 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
 #undef ROW
     case CGO_OBJ_USER:
         if (!obj_->rtc) { set_error("user objective has no compiled module"); return CGO_EINVAL; }
-        if (lag) break;   // built-in objectives only: r stays −2
+        if (r_big_only(mode)) break;   // built-in objectives only: r stays −2
         if (int rc = launch_module(obj_->rtc->cg(mode, npts, big), &P, grid, st)) return rc;
         r = 0;
         break;
@@ -353,7 +336,7 @@ int HipBackend::launch_chain_kernel(int mode, double a_acc, double beta, const d
     // the global vector ends where this rank's shard touches its ends
     P.has_left = obj_->offset > 0 ? 1 : 0;
     P.has_right = obj_->offset + obj_->n_local < obj_->n_global ? 1 : 0;
-    const bool wr_x = (mode & R_ACCEPT) != 0, wr_u = (mode & (R_DIR | R_INIT | R_RESET)) != 0;
+    const bool wr_x = r_writes_x(mode), wr_u = r_writes_u(mode);
     if (wr_x) P.xo = xalt_;
     if (wr_u) P.uo = ualt_;
     const int r = big ? launch_chain<true>(mode, npts, P, grid, ctx_->stream) : launch_chain<false>(mode, npts, P, grid, ctx_->stream);
@@ -396,7 +379,7 @@ std::string HipBackend::kernel_symbol(int kk) const {
         case KK_SYS_PROJECT: mode = R_PROJ; break;
         default: return "";
         }
-        const bool big = (mode & (R_ULAG | R_NOWU | R_REPLAY | R_NOWX)) != 0 || bytes_r(obj_->kind, mode, n, hp) > big_bytes(mode == R_TRIAL || mode == R_UPG);
+        const bool big = launch_is_big(*this, mode, bytes_r(obj_->kind, mode, n, hp));
         if ((mode & R_REPLAY) && (mode & R_ACCEPT)) mode |= lean_for(mode);   // N and S: the lean row where that is what runs
         return r_symbol(mode, chain() ? chain_npts(mode, npts) : npts, big);
     }
@@ -452,10 +435,7 @@ __global__ void k_ctl_init(CtlDev *d, const CtlConfig cfg, const CtlState st, un
     d->cfg = cfg;
     d->st = st;
     d->round = round;
-    CtlArgs a;
-    a.a_acc = st.a_acc; a.beta = st.beta; a.go = st.go;
-    for (int j = 0; j < CTL_MAXP; ++j) a.a[j] = st.a[j];
-    d->args = a;
+    d->args = ctl_args_of(st);
 }
 
 // Final reduction stage of a controller-armed launch + the controller itself: rows → sums →
@@ -503,16 +483,8 @@ __global__ __launch_bounds__(THREADS) void k_finalize_ctl(const double *partials
     if (tid == 0) {
         if (go) {
             ctl_step(sd.cfg, sd.st, fin, sr);
-            CtlArgs a;
-            a.a_acc = sd.st.a_acc; a.beta = sd.st.beta; a.go = sd.st.go;
-            for (int j = 0; j < CTL_MAXP; ++j) a.a[j] = sd.st.a[j];
-            sd.args = a;
-        } else {
-            for (int i = 0; i < CTL_NSUMS; ++i) sr.sums[i] = 0.0;
-            sr.a_acc = 0.0; sr.beta = 0.0;
-            for (int j = 0; j < CTL_MAXP; ++j) sr.a[j] = 0.0;
-            sr.npts = -1; sr.accepted = 0; sr.xwait = 0;
-        }
+            sd.args = ctl_args_of(sd.st);
+        } else ctl_idle_record(sr);
         sd.round = round + 1;
     }
     __syncthreads();
@@ -731,13 +703,7 @@ int HipBackend::accept_dir_trial_ctl(const CtlConfig &cc, const CtlState &s0, in
         set_error("internal: the on-device controller and the host state machine disagree on a launch");
         return CGO_ESTATE;
     }
-    const int np = pipe_npts_;
-    for (int j = 0; j < s0.npts; ++j) {
-        const double *q = rec.sums + RS_PER_POINT * j;
-        out[j].f = q[RS_F]; out[j].gtu = q[RS_GTU]; out[j].gtgt = q[RS_GTGT]; out[j].gtg = q[RS_GTG];
-        out[j].yy = q[RS_YY]; out[j].uy = q[RS_UY]; out[j].ygt = q[RS_YGT];
-    }
-    out[0].gu = rec.sums[RS_PER_POINT * np]; out[0].uu = rec.sums[RS_PER_POINT * np + 1];
+    unpack_r(rec.sums, s0.npts, out, true, pipe_npts_);
     total_launches_++;
     pipe_served_++;
     pipe_streak_++;
@@ -769,15 +735,6 @@ int HipBackend::accept_dir_trial_keep_streak(const CtlState &s0, Scal *out) {
     return rc;
 }
 
-void unpack_r(const double *s, int k, Scal *out, bool dir) {
-    const int npts = npts_for(k);
-    for (int j = 0; j < k; ++j) {
-        const double *q = s + RS_PER_POINT * j;
-        out[j].f = q[RS_F]; out[j].gtu = q[RS_GTU]; out[j].gtgt = q[RS_GTGT]; out[j].gtg = q[RS_GTG];
-        out[j].yy = q[RS_YY]; out[j].uy = q[RS_UY]; out[j].ygt = q[RS_YGT];
-    }
-    if (dir) { out[0].gu = s[RS_PER_POINT * npts]; out[0].uu = s[RS_PER_POINT * npts + 1]; }
-}
 
 // ---- one launch on host vectors (cgo_solver_probe_launch) ------------------------------------------------------------
 // Every buffer a launch of this solver can touch — x, u, their ping-pong partners, both gradient buffers (the second one is
@@ -879,7 +836,7 @@ int HipBackend::probe_launch(int kk, int variant, double a_acc, double beta, con
         }
         if (mode > 0 && (mode & (R_TRIAL | R_GRADT | R_PROJ)) && k < 1) mode = -1;
         if (mode > 0 && chain() && k > 3) mode = -1;
-        if (mode > 0 && (mode & (R_ULAG | R_NOWU | R_REPLAY | R_NOWX)) && (chain() || obj_->kind == CGO_OBJ_USER)) mode = -1;
+        if (mode > 0 && r_big_only(mode) && (chain() || obj_->kind == CGO_OBJ_USER)) mode = -1;
     }
     if (mode < 0) { set_error("probe: kernel kind / variant / trial steps not a launch this solver's engine issues"); return CGO_EINVAL; }
     if (int rc = probe_prepare()) return rc;

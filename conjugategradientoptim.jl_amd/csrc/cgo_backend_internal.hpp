@@ -57,7 +57,7 @@ bool is_big(int obj_kind, int mode, int64_t n, int n_params, double forced);
 int grid_cg(int64_t n, int npts = 1);
 // ALGORITHMIC bytes of a k_cg / k_chain launch (cgo_backend_cg.hip)
 double bytes_r(int obj_kind, int mode, int64_t n, int n_params);
-void unpack_r(const double *s, int k, Scal *out, bool dir);
+void unpack_r(const double *s, int k, Scal *out, bool dir, int npts = 0);
 // host side of the publish protocols (cgo_hip_backend.hip)
 int launch_module(hipFunction_t f, void *params, int grid, hipStream_t st);
 int wait_word(HipCtx *ctx, unsigned long long *word, unsigned long long want);

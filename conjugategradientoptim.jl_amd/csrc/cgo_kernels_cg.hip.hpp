@@ -29,6 +29,7 @@
 #pragma once
 
 #include "cgo_kernels.hip.hpp"
+#include "cgo_modes.hpp"   // mode bits (RMode), and what a mode reads, writes and sums
 #ifndef CGO_RTC   // the run-time compiled copies of these kernels (user objectives) carry no controller
 #include "cgo_ctl.hpp"
 #endif
@@ -42,43 +43,13 @@ constexpr int NR5 = 40;  // row width of 5-point launches (35 trial sums + 2 dir
 constexpr int NR7 = 56;  // row width of 7-point launches (49 + 2, padded)
 constexpr int MAXP = 7;  // most trial points one launch evaluates
 enum RSlot : int { RS_F = 0, RS_GTU, RS_GTGT, RS_GTG, RS_YY, RS_UY, RS_YGT, RS_PER_POINT };
-
-enum RMode : int {
-    R_ACCEPT = 1,  // x ← x + a_acc·u                       optim.jl:136,140
-    R_DIR = 2,     // u ← −g + β·u ; Σ g·u, Σ u·u            cg_flavours.jl:10-12, nocedal.jl:56, wolfe.jl:240
-    R_TRIAL = 4,   // NPTS × { xp = x + a_j·u ; g⁺ = ∇f(xp) ; all trial sums }   cg_utils.jl:4-23
-    R_INIT = 8,    // u = −∇f(x) ; Σ f, Σ g·g                 optim.jl:25-26, cg_flavours.jl:29
-    R_RESET = 16,  // u = −∇f(x) ; Σ g·u, Σ u·u               wolfe.jl:129
-    R_UPG = 32,    // Σ (u + ∇f(x))²                          wolfe.jl:123
-    R_GRAD = 64,   // gout = ∇f(x)                            (materialise for Results.gradient)
-    R_GRADT = 128, // gout = ∇f(x + a_0·u)                    (rare: LinearAlgebra.norm scaled path on g⁺)
-    R_PROJ = 256,  // solvesystem: x2 ← x2 + m·∇f(x + a_0·u) ; g⁺ = ∇f(x2) ; trial sums of g⁺ against ∇f(x), u
-                   //                                          solve_system.jl:169-177,199-204,239-253  (m = P.beta)
-    // (512: R_EDGES of the stencil launches, cgo_kernels_chain.hip.hpp)
-    // Lazy direction: the direction is recoverable from the stored iterate one step later, so every second
-    // accept + direction + trial launch leaves the OLD u in memory and the next launch forms the new one itself.
-    R_ULAG = 1024, // on load, before anything else: u ← −∇f(x) + β_prev·u — memory holds (x_{k+1}, u_k), β_prev = β_k; no sums
-                   // (those of this direction were formed by the launch that did not store it).  Alone: store that u.
-    R_NOWU = 2048, // R_DIR without the store of u: registers, sums and trials use the new direction, memory keeps the old one
-    // Replay: x may lag as well.  Memory holds (x_k, u_k) and the host the scalars (a*_k, β_k), (a*_{k+1}, β_{k+1}), …
-    // of the steps accepted since; a launch rebuilds the current pair in registers from them.
-    R_REPLAY = 4096, // on load, before anything else, for j < nrep: x ← x + ra[j]·u ; u ← −∇f(x) + rb[j]·u — the R_ACCEPT and R_DIR
-                     // expressions; no sums (they belonged to the launches that first formed these directions).  Alone: store x and u.
-    R_NOWX = 8192,   // R_ACCEPT without the store of x (always together with R_NOWU)
-    // Lean sums: trial sums the solver's β flavour never reads (beta_unread_sums, cgo_ctl.hpp) are not formed —
-    // compile-time only, no branch in the loop.  Row width and slot positions stay; a dropped slot leaves the tail as +0.0, the
-    // others keep their accumulator chains bit for bit.  R_TRIAL block only.
-    R_NOGTG = 16384,   // no Σ g⁺·g
-    R_NOYY = 32768,    // no Σ y·y
-    R_NOUY = 65536,    // no Σ u·y
-    R_NOYGT = 131072   // no Σ y·g⁺
-};
-constexpr int R_LEAN = R_NOGTG | R_NOYY | R_NOUY | R_NOYGT;   // transparent to every decision taken on a mode but the row that runs
+constexpr int RMAX = 7;  // most replayed steps (replay depth up to 8)
+// Row width of a CG launch: 7 sums per trial point + 2 direction sums, padded; and the kernel variant for k trial steps.
+constexpr int rows_for(int npts) { return npts == 1 ? NR1 : (npts == 3 ? NR : (npts == 5 ? NR5 : NR7)); }
+constexpr int npts_for(int k) { return k <= 1 ? 1 : (k <= 3 ? 3 : (k <= 5 ? 5 : 7)); }
 #ifndef CGO_RTC
 static_assert(CTL_NOGTG == R_NOGTG && CTL_NOYY == R_NOYY && CTL_NOUY == R_NOUY && CTL_NOYGT == R_NOYGT, "beta_unread_sums speaks in these bits");
 #endif
-constexpr int RMAX = 7;  // most replayed steps (replay depth up to 8)
-
 // Launch scalars kept in device memory for launches armed by the on-device controller
 // (cgo_ctl.hpp): written by the controller after launch k, read by launch k+1 — no host in between.
 struct CtlArgs {
@@ -94,6 +65,19 @@ struct CtlArgs {
 struct CtlDev { CtlConfig cfg; CtlState st; CtlArgs args; unsigned long long round; };
 constexpr int PIPE_RING = 64;   // records in flight
 static_assert(sizeof(CtlDev) % 8 == 0 && sizeof(CtlRecord) % 8 == 0, "controller blocks are copied as 8-byte words");
+// the next armed launch's arguments, from the controller's state; the record of a round that found the controller stopped
+__device__ inline CtlArgs ctl_args_of(const CtlState &st) {
+    CtlArgs a;
+    a.a_acc = st.a_acc; a.beta = st.beta; a.go = st.go;
+    for (int j = 0; j < CTL_MAXP; ++j) a.a[j] = st.a[j];
+    return a;
+}
+__device__ inline void ctl_idle_record(CtlRecord &sr) {
+    for (int i = 0; i < CTL_NSUMS; ++i) sr.sums[i] = 0.0;
+    sr.a_acc = 0.0; sr.beta = 0.0;
+    for (int j = 0; j < CTL_MAXP; ++j) sr.a[j] = 0.0;
+    sr.npts = -1; sr.accepted = 0; sr.xwait = 0;
+}
 #endif
 
 struct RParams {
@@ -303,10 +287,7 @@ __device__ inline void tail_ctl(const Tail &T, double v) {
     if (tid == 0) {
         ctl_decide(sd.cfg, sd.st, fin, sr);
         sr.xwait = xticks;
-        CtlArgs a;
-        a.a_acc = sd.st.a_acc; a.beta = sd.st.beta; a.go = sd.st.go;
-        for (int j = 0; j < CTL_MAXP; ++j) a.a[j] = sd.st.a[j];
-        sd.args = a;
+        sd.args = ctl_args_of(sd.st);
         sd.round = round + 1;
     }
     __syncthreads();
@@ -325,10 +306,7 @@ __device__ inline void tail_ctl_idle(const Tail &T) {
     CtlDev *d = reinterpret_cast<CtlDev *>(T.ctl);
     if (tid == 0) {
         round_s = d->round;
-        for (int i = 0; i < CTL_NSUMS; ++i) sr.sums[i] = 0.0;
-        sr.a_acc = 0.0; sr.beta = 0.0;
-        for (int j = 0; j < CTL_MAXP; ++j) sr.a[j] = 0.0;
-        sr.npts = -1; sr.accepted = 0; sr.xwait = 0;
+        ctl_idle_record(sr);
         d->round = round_s + 1;
     }
     __syncthreads();
@@ -587,7 +565,7 @@ __device__ inline void store_partials_n(double (&acc)[N], double *partials, cons
     else if (tid < N) partials[(size_t)blockIdx.x * N + tid] = own;
 }
 
-template <int NPTS> struct RW { static constexpr int W = (NPTS == 1) ? NR1 : (NPTS == 3 ? NR : (NPTS == 5 ? NR5 : NR7)); static constexpr int GU = RS_PER_POINT * NPTS, UU = GU + 1; };
+template <int NPTS> struct RW { static constexpr int W = rows_for(NPTS); static constexpr int GU = RS_PER_POINT * NPTS, UU = GU + 1; };
 
 // Late scaling of f (ObjFScale, cgo_kernels.hip.hpp): on exactly where the objective declares a scale AND the launch
 // is a lean row.  The R_TRIAL block then adds the raw terms and cg_launch scales each lane's NPTS f accumulators once, before the
@@ -609,7 +587,7 @@ __device__ inline void cg_pair(const RParams &P, d2 &x, d2 &u, const PV<Obj> &p,
     if (MODE & R_ULAG) {  // the direction the previous launch formed and did not store: same expression, same operands as R_DIR
         obj_eval2<Obj>(x, p, P.s0, f00, g0);
         u.x = -g0.x + P.beta_prev * u.x; u.y = -g0.y + P.beta_prev * u.y;
-        if (MODE == R_ULAG) wu = true;
+        if (!(MODE & R_DIR) && r_writes_u(MODE)) wu = true;   // the materialise pass (with R_DIR: decided below)
     }
     if (MODE & R_REPLAY) {  // the steps accepted since (x, u) was stored.  Compile-time slot indices under a wave-uniform guard: a
         // run-time index into the modifiable copy of the arguments would send the whole block to scratch (see cg_launch)
@@ -624,12 +602,13 @@ __device__ inline void cg_pair(const RParams &P, d2 &x, d2 &u, const PV<Obj> &p,
                 u.x = -gr.x + P.rb[j] * u.x; u.y = -gr.y + P.rb[j] * u.y;
             }
         }
-        if (MODE == R_REPLAY) { wx = true; wu = true; }
+        if (!(MODE & R_ACCEPT) && r_writes_x(MODE)) wx = true;   // the materialise pass (with R_ACCEPT / R_DIR: decided below)
+        if (!(MODE & R_DIR) && r_writes_u(MODE)) wu = true;
     }
     if (MODE & R_ACCEPT) {
         x.x = x.x + P.a_acc * u.x;
         x.y = x.y + P.a_acc * u.y;
-        wx = (MODE & R_NOWX) == 0;
+        wx = r_writes_x(MODE);
     }
     d2 g;
     double f0 = 0.0;
@@ -644,7 +623,7 @@ __device__ inline void cg_pair(const RParams &P, d2 &x, d2 &u, const PV<Obj> &p,
         acc[RS_GTGT] = dsum(acc[RS_GTGT], g.x, g.x);
         acc[RS_GTGT] = dsum(acc[RS_GTGT], g.y, g.y);
         u.x = -g.x; u.y = -g.y;
-        wu = true;
+        wu = r_writes_u(MODE);
     }
     if (MODE & (R_DIR | R_RESET)) {
         d2 un;
@@ -653,7 +632,7 @@ __device__ inline void cg_pair(const RParams &P, d2 &x, d2 &u, const PV<Obj> &p,
         acc[R_GU] = dsum(acc[R_GU], g.x, un.x); acc[R_GU] = dsum(acc[R_GU], g.y, un.y);
         acc[R_UU] = dsum(acc[R_UU], un.x, un.x); acc[R_UU] = dsum(acc[R_UU], un.y, un.y);
         u = un;
-        wu = (MODE & R_NOWU) == 0;
+        wu = r_writes_u(MODE);
     }
     if (MODE & R_UPG) {
         const double t0 = u.x + g.x, t1 = u.y + g.y;
@@ -708,13 +687,13 @@ template <class Obj, int MODE, int NPTS>
 __device__ inline void cg_single(const RParams &P, long long i, double (&acc)[RW<NPTS>::W]) {
     constexpr int R_GU = RW<NPTS>::GU, R_UU = RW<NPTS>::UU;
     double x = P.x[i];
-    double u = (MODE & (R_ACCEPT | R_DIR | R_TRIAL | R_UPG | R_GRADT | R_PROJ | R_ULAG | R_REPLAY)) ? P.u[i] : 0.0;
+    double u = r_reads_u(MODE) ? P.u[i] : 0.0;
     const PS<Obj> p = ps_load<Obj>(P, i);
     if (MODE & R_ULAG) {
         double g0 = 0.0, f00 = 0.0;
         obj_eval1<Obj>(x, p, P.s0, f00, g0);
         u = -g0 + P.beta_prev * u;
-        if (MODE == R_ULAG) P.uo[i] = u;
+        if (!(MODE & R_DIR) && r_writes_u(MODE)) P.uo[i] = u;   // the materialise pass (with R_DIR: stored below)
     }
     if (MODE & R_REPLAY) {
 #pragma unroll
@@ -726,16 +705,17 @@ __device__ inline void cg_single(const RParams &P, long long i, double (&acc)[RW
                 u = -gr + P.rb[j] * u;
             }
         }
-        if (MODE == R_REPLAY) { P.xo[i] = x; P.uo[i] = u; }
+        if (!(MODE & R_ACCEPT) && r_writes_x(MODE)) P.xo[i] = x;   // the materialise pass (with R_ACCEPT / R_DIR: stored below)
+        if (!(MODE & R_DIR) && r_writes_u(MODE)) P.uo[i] = u;
     }
-    if (MODE & R_ACCEPT) { x = x + P.a_acc * u; if (!(MODE & R_NOWX)) P.xo[i] = x; }
+    if (MODE & R_ACCEPT) { x = x + P.a_acc * u; if (r_writes_x(MODE)) P.xo[i] = x; }
     double g = 0.0, f0 = 0.0;
     obj_eval1<Obj>(x, p, P.s0, f0, g);
-    if (MODE & R_INIT) { acc[RS_F] += f0; acc[RS_GTGT] = dsum(acc[RS_GTGT], g, g); P.uo[i] = -g; }
+    if (MODE & R_INIT) { acc[RS_F] += f0; acc[RS_GTGT] = dsum(acc[RS_GTGT], g, g); if (r_writes_u(MODE)) P.uo[i] = -g; }
     if (MODE & (R_DIR | R_RESET)) {
         const double un = (MODE & R_DIR) ? (-g + P.beta * u) : -g;
         acc[R_GU] = dsum(acc[R_GU], g, un); acc[R_UU] = dsum(acc[R_UU], un, un);
-        if (!(MODE & R_NOWU)) P.uo[i] = un;
+        if (r_writes_u(MODE)) P.uo[i] = un;
         u = un;
     }
     if (MODE & R_UPG) { const double t = u + g; acc[R_UU] = dsum(acc[R_UU], t, t); }
@@ -798,8 +778,7 @@ __device__ inline void cg_launch(const RParams &Pin) {
     double acc[W];
 #pragma unroll
     for (int s = 0; s < W; ++s) acc[s] = 0.0;
-    constexpr bool rd_u = (MODE & (R_ACCEPT | R_DIR | R_TRIAL | R_UPG | R_GRADT | R_PROJ | R_ULAG | R_REPLAY)) != 0;
-    constexpr bool wr_g = (MODE & (R_GRAD | R_GRADT)) != 0;
+    constexpr bool rd_u = r_reads_u(MODE), wr_g = r_writes_g(MODE);
     constexpr bool proj = (MODE & R_PROJ) != 0;  // the gout argument of cg_pair carries x2
     const long long n2 = P.n >> 1;
     long long i, hi, step;
@@ -855,7 +834,7 @@ __device__ inline void cg_launch(const RParams &Pin) {
 #pragma unroll
         for (int j = 0; j < NPTS; ++j) acc[RS_PER_POINT * j + RS_F] *= ObjFScale<Obj>::scale;
     }
-    if (MODE == R_ACCEPT || MODE == R_GRAD || MODE == R_GRADT || MODE == R_ULAG || MODE == R_REPLAY) return;  // no sums
+    if (!r_has_sums(MODE)) return;
 #if defined(CGO_STAMPS) && !defined(CGO_RTC)
     const unsigned long long st1 = (unsigned long long)wall_clock64();
 #endif

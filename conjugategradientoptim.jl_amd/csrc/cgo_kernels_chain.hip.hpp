@@ -32,7 +32,6 @@ constexpr int NRC = 24;        // row width of a 1-point chain launch (shares k_
 constexpr int RC_EDGE = 10;    // slots 10–13: x_new, u_new of the first two elements; 14–17: of the last two
 constexpr int NRC3 = 32;       // row width of a 3-point chain launch: sums as in a 3-point k_cg row (0–22) …
 constexpr int RC3_EDGE = 24;   // … edge values in slots 24–31
-constexpr int R_EDGES = 512;   // mode bit: publish the edge values of the CURRENT x, u only (after set_x0)
 template <int NPTS> struct ChainRow {
     static constexpr int W = NPTS == 1 ? NRC : NRC3, EDGE = NPTS == 1 ? RC_EDGE : RC3_EDGE;
     static constexpr int GU = RS_PER_POINT * NPTS, UU = GU + 1;   // Σ g·u_new, Σ u_new·u_new behind the trial sums
@@ -144,9 +143,8 @@ __global__ __launch_bounds__(BLOCK) void k_chain(const ChainParams P) {
     double acc[W];
 #pragma unroll
     for (int s = 0; s < W; ++s) acc[s] = 0.0;
-    constexpr bool need_u = (MODE & (R_ACCEPT | R_DIR | R_TRIAL | R_UPG | R_GRADT | R_EDGES)) != 0;
-    constexpr bool wr_x = (MODE & R_ACCEPT) != 0;
-    constexpr bool wr_u = (MODE & (R_DIR | R_INIT | R_RESET)) != 0;
+    constexpr bool need_u = r_reads_u(MODE) || (MODE & R_EDGES) != 0;   // (R_EDGES: the edge lanes publish their u)
+    constexpr bool wr_x = r_writes_x(MODE), wr_u = r_writes_u(MODE);
     const long long n2 = P.n >> 1;
     long long i, hi, step;
     if (BIG) {
@@ -193,14 +191,14 @@ __global__ __launch_bounds__(BLOCK) void k_chain(const ChainParams P) {
         }
         d2 xn2, un2, g2 = d2{0.0, 0.0};
         chain_window<MODE, NPTS, W>(X, U, E, P.a_acc, P.beta, a3, acc, xn2, un2, g2);
-        if (MODE & (R_GRAD | R_GRADT)) stg2<false>(P.gout, i, g2);
+        if (r_writes_g(MODE)) stg2<false>(P.gout, i, g2);
         if (wr_x) stg2<false>(P.xo, i, xn2);
         if (wr_u) stg2<false>(P.uo, i, un2);
         // this rank's edge values AFTER the launch, for the neighbours' next window (exactly one lane owns each)
         if (first) { acc[EDGE + 0] = xn2.x; acc[EDGE + 1] = xn2.y; acc[EDGE + 2] = un2.x; acc[EDGE + 3] = un2.y; }
         if (last) { acc[EDGE + 4] = xn2.x; acc[EDGE + 5] = xn2.y; acc[EDGE + 6] = un2.x; acc[EDGE + 7] = un2.y; }
     }
-    if (MODE == R_ACCEPT || MODE == R_GRAD || MODE == R_GRADT) return;   // no sums (an accept-only launch ends the solve)
+    if (!r_has_sums(MODE)) return;
     store_partials_n<W>(acc, P.partials, P.tail);
 }
 

@@ -205,6 +205,8 @@ def sim_lib():
         L.sim_set_resident.argtypes = [C.c_int, C.c_int64]
         L.sim_resident_stats.restype = None
         L.sim_resident_stats.argtypes = [i64p, i64p, i64p]
+        L.sim_launch_mode.restype = None
+        L.sim_launch_mode.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.sim_beta_from_scalars.restype = C.c_double
         L.sim_beta_from_scalars.argtypes = [C.POINTER(_lib.BetaConfig), dp, C.c_double, C.c_double,
                                             C.c_double]

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../conjugategradientoptim.jl_amd/csrc/cgo_engine.hpp"
+#include "../../conjugategradientoptim.jl_amd/csrc/cgo_modes.hpp"
 
 using namespace cgo;
 
@@ -747,5 +748,16 @@ int sim_ctl_step(const CtlConfig *cfg, CtlState *state, const double *row56, Ctl
     return ctl_step(*cfg, *state, row56, *rec) ? 1 : 0;
 }
 void sim_ctl_sizes(int64_t *out3) { out3[0] = sizeof(CtlConfig); out3[1] = sizeof(CtlState); out3[2] = sizeof(CtlRecord); }
+
+// What a launch of the k_cg / k_chain family streams and leaves (csrc/cgo_modes.hpp), as a plain host compiler sees the header
+// the kernels and the backend ask: out7 = vectors of n doubles (the p of bytes_r), reads u, writes x, writes u, writes g,
+// has sums, BIG-only.
+void sim_launch_mode(int mode, int obj_kind, int n_params, int *out7) {
+    namespace d = cgo::dev;
+    const int p = std::max(obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0, n_params);
+    out7[0] = d::r_vectors(mode, p);
+    out7[1] = d::r_reads_u(mode); out7[2] = d::r_writes_x(mode); out7[3] = d::r_writes_u(mode); out7[4] = d::r_writes_g(mode);
+    out7[5] = d::r_has_sums(mode); out7[6] = d::r_big_only(mode);
+}
 
 }  // extern "C"

@@ -236,7 +236,7 @@ def test_row_lists_are_unchanged(monkeypatch):
     assert I.rows("CG_LEAN") == [(LEAN_N, 7), (LEAN_S, 7)] == [(129031, 7), (118791, 7)]
     assert len(I.mode_points("CG_LEAN")) * len(I.rows("OBJ")) == 24
     assert (len(I.rows("CG")), len(I.rows("CG_LAG")), len(I.rows("CG_REPLAY"))) == (12, 4, 4)
-    hdr = open(os.path.join(I.CSRC, "cgo_kernels_cg.hip.hpp")).read()
+    hdr = open(os.path.join(I.CSRC, "cgo_modes.hpp")).read()
     assert not re.search(r"R_\w+ = 262144\b", hdr), "no new mode bit"
 
 

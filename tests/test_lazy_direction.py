@@ -352,7 +352,7 @@ def test_lag_rows_parse_and_are_what_the_backend_alternates_between(monkeypatch)
     assert I.rows("CG_LAG") == [(ADT | R_NOWU, 7), (R_ULAG | ADT, 7), (R_ULAG | R_TRIAL, 7), (R_ULAG, 1)]
     assert not {m for m, _ in I.rows("CG_LAG")} & {m for m, _ in I.rows("CG")}       # the pinned list is untouched
     assert I.stray_uses() == []
-    hdr = open(os.path.join(I.CSRC, "cgo_kernels_cg.hip.hpp")).read()
+    hdr = open(os.path.join(I.CSRC, "cgo_modes.hpp")).read()
     assert re.search(r"R_ULAG = 1024\b", hdr) and re.search(r"R_NOWU = 2048\b", hdr)
 
 

@@ -402,7 +402,7 @@ def test_lean_rows_parse_and_are_disjoint_from_the_pinned_lists(monkeypatch):
         assert not lean & {m for m, _ in I.rows(fam)}, fam
     assert (len(I.rows("CG")), len(I.rows("CG_LAG")), len(I.rows("CG_REPLAY"))) == (12, 4, 4)
     assert I.stray_uses() == []
-    hdr = open(os.path.join(I.CSRC, "cgo_kernels_cg.hip.hpp")).read()
+    hdr = open(os.path.join(I.CSRC, "cgo_modes.hpp")).read()
     for name, bit in (("R_NOGTG", 16384), ("R_NOYY", 32768), ("R_NOUY", 65536), ("R_NOYGT", 131072)):
         assert re.search(r"\b%s = %d\b" % (name, bit), hdr), name
     assert "CGO_CG_LEAN_ROWS" not in open(os.path.join(I.CSRC, "cgo_rtc.hip")).read()      # built-in objectives only

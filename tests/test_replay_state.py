@@ -442,7 +442,7 @@ def test_replay_rows_parse_and_are_disjoint_from_the_pinned_lists(monkeypatch):
     assert not replay & {m for m, _ in I.rows("CG")} and not replay & {m for m, _ in I.rows("CG_LAG")}
     assert len(I.rows("CG")) == 12 and len(I.rows("CG_LAG")) == 4
     assert I.stray_uses() == []
-    hdr = open(os.path.join(I.CSRC, "cgo_kernels_cg.hip.hpp")).read()
+    hdr = open(os.path.join(I.CSRC, "cgo_modes.hpp")).read()
     assert re.search(r"R_REPLAY = 4096\b", hdr) and re.search(r"R_NOWX = 8192\b", hdr)
     assert "CGO_CG_REPLAY_ROWS" not in open(os.path.join(I.CSRC, "cgo_rtc.hip")).read()      # built-in objectives only
 
