@@ -17,8 +17,6 @@ double bytes_r(int obj_kind, int mode, int64_t n, int n_params) {
     const int p = std::max(obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0, n_params);
     return 8.0 * (double)n * (double)r_vectors(mode, p);   // reads + writes of the mode (cgo_modes.hpp): a new row needs no edit here
 }
-// pure-HBM streaming: the rows that exist in that form only, or above the threshold for what the mode does
-static inline bool launch_is_big(const HipBackend &be, int mode, double bytes) { return r_big_only(mode) || bytes > be.big_bytes(r_read_only(mode)); }
 
 // The point ladder, written once: f(Pts<N>) for the odd N ≤ MAXPTS a launch of `npts` points takes.  A count that is none of
 // them takes the largest where that is 7 (k_cg), 1 otherwise (k_chain: anything but 3).
@@ -81,6 +79,15 @@ void unpack_r(const double *s, int k, Scal *out, bool dir, int npts) {
 // stencil launches carry one or three trial points: three only where the mode evaluates trials at all
 static inline int chain_npts(int mode, int npts) { return ((mode & R_TRIAL) && npts >= 3) ? 3 : 1; }
 
+// What a launch of (mode, npts) is for this solver — decided HERE for the launch, its profile entry and kernel_symbol.  Pure-HBM: the
+// rows that exist in that form only, or above the threshold for what the mode does.  (The stencil objective has no parameter slots.)
+RPlan HipBackend::r_plan(int mode, int npts) const {
+    const double bytes = bytes_r(obj_->kind, mode, obj_->n_local, obj_->nparams());
+    const bool big = r_big_only(mode) || bytes > big_bytes(r_read_only(mode));
+    return {big, big ? GRID_BIG : grid_cg(obj_->n_local, chain() ? 1 : npts), chain() ? chain_npts(mode, npts) : npts, bytes};
+}
+bool HipBackend::adt_is_big() const { return bytes_r(obj_->kind, R_ADT, obj_->n_local, obj_->nparams()) > big_bytes(false); }
+
 int HipBackend::launch_r(int kk, int mode, double a_acc, double beta, const double *a, int k, bool fetch,
                          double *sums) {
     if (int rc = pipe_drain()) return rc;
@@ -95,14 +102,15 @@ int HipBackend::launch_r(int kk, int mode, double a_acc, double beta, const doub
     // Steps outstanding (replay): x lags too, and every launch reads x — R_RESET and R_INIT included.  Any launch but N / S / T
     // gets both vectors stored first.
     if (rep_n_ > 0 && !(mode & R_REPLAY)) { if (int rc = materialize_lag()) return rc; }
-    int grid = 0;
+    RPlan plan;
     const int npts = npts_for(k);
-    if (int rc = launch_r_kernel(kk, mode, a_acc, beta, a, k, npts, nullptr, &grid)) return rc;
+    if (int rc = launch_r_kernel(kk, mode, a_acc, beta, a, k, npts, nullptr, &plan)) return rc;
+    const int grid = plan.grid;
     total_launches_++;
     const bool has_sums = r_has_sums(mode);
     const bool fused = has_sums && tail_fused(grid);   // the launch's last workgroup already left the sums (finish_tail)
     if (has_sums && chain()) {   // 24- or 32-slot rows: the sums + this rank's eight edge values (cgo_kernels_chain.hip.hpp)
-        const bool three = chain_npts(mode, npts) == 3;
+        const bool three = plan.npts == 3;
         const int W = three ? NRC3 : NRC, edge = three ? RC3_EDGE : RC_EDGE, nsums = three ? NR : NR1;
         if (!fused) { if (int rc = finalize_rows(ctx_, grid, W, true)) return rc; }
         const int Wd = ctx_->world(), me = ctx_->rank();
@@ -126,7 +134,7 @@ int HipBackend::launch_r(int kk, int mode, double a_acc, double beta, const doub
         }
         if (probe_ && fetch) { std::memcpy(probe_row_, sums, sizeof(double) * rows_for(npts)); probe_len_ = rows_for(npts); }
     }
-    if (prof_on_) prof_commit(kk, bytes_r(obj_->kind, mode, obj_->n_local, obj_->nparams()));
+    if (prof_on_) prof_commit(kk, plan.bytes);
     return CGO_OK;
 }
 
@@ -143,9 +151,7 @@ bool HipBackend::lazy_eligible() const {
     if (!aot) return false;
     if (const char *e = getenv("CGO_PINGPONG")) { if (e[0] == '1') return false; }
     if (ctl_depth() > 0) return false;
-    const int64_t n = obj_->n_local;
-    const int hp = obj_->nparams();
-    return bytes_r(obj_->kind, R_ACCEPT | R_DIR | R_TRIAL, n, hp) > big_bytes(false) && bytes_r(obj_->kind, R_TRIAL, n, hp) > big_bytes(true);
+    return adt_is_big() && r_plan(R_TRIAL, 1).big;
 }
 
 // Every reader of the stored direction other than the lag launches: store u_{k+1} = −∇f(x_{k+1}) + β_k·u_k now.  Not a launch
@@ -153,7 +159,7 @@ bool HipBackend::lazy_eligible() const {
 int HipBackend::materialize_u() {
     if (!u_lag_) return CGO_OK;
     const int64_t asked = total_launches_;
-    const int rc = launch_r(KK_MATERIALIZE_U, R_ULAG, 0.0, 0.0, nullptr, 0, false, nullptr);
+    const int rc = launch_rk(KK_MATERIALIZE_U, 0.0, 0.0, nullptr, 0, false, nullptr);
     total_launches_ = asked;
     if (rc) return rc;
     u_lag_ = false;
@@ -167,7 +173,7 @@ int HipBackend::materialize_lag() {
     if (int rc = materialize_u()) return rc;
     if (rep_n_ == 0) return CGO_OK;
     const int64_t asked = total_launches_;
-    const int rc = launch_r(KK_MATERIALIZE_XU, R_REPLAY, 0.0, 0.0, nullptr, 0, false, nullptr);
+    const int rc = launch_rk(KK_MATERIALIZE_XU, 0.0, 0.0, nullptr, 0, false, nullptr);
     total_launches_ = asked;
     if (rc) return rc;
     rep_n_ = 0;
@@ -189,35 +195,35 @@ void HipBackend::set_probe_replay(int nrep, const double *a, const double *beta)
 // accept + direction + trial and trial of the k_cg family.  Where eligible: depth d ≥ 2 — d − 1 launches that store nothing
 // (N), then one that replays them and stores both vectors (S); depth 1 — alternating between the two lag launches.
 int HipBackend::accept_dir_trial_r(double a_acc, double beta, const double *a, int k, double *s) {
-    if (!lazy_eligible()) return launch_r(KK_ACCEPT_DIR_TRIAL, R_ACCEPT | R_DIR | R_TRIAL, a_acc, beta, a, k, true, s);
+    if (!lazy_eligible()) return launch_rk(KK_ACCEPT_DIR_TRIAL, a_acc, beta, a, k, true, s);
     if (replay_depth_ >= 2) {
         if (int rc = materialize_u()) return rc;
         if (rep_n_ < replay_depth_ - 1 && rep_n_ < RMAX) {   // launch N: the new pair in registers only
-            const int mode_n = R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL | R_NOWU | R_NOWX;
+            const int mode_n = r_mode_of(KK_ACCEPT_TRIAL_NOSTORE);
             if (int rc = launch_r(KK_ACCEPT_TRIAL_NOSTORE, mode_n | lean_for(mode_n), a_acc, beta, a, k, true, s)) return rc;
             rep_a_[rep_n_] = a_acc; rep_b_[rep_n_] = beta; rep_n_++;
             return CGO_OK;
         }
         // launch S: replays the outstanding steps, then today's launch
-        const int mode_s = R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL;
+        const int mode_s = R_REPLAY | R_ADT;
         if (int rc = launch_r(KK_ACCEPT_DIR_TRIAL, mode_s | lean_for(mode_s), a_acc, beta, a, k, true, s)) return rc;
         rep_n_ = 0;
         return CGO_OK;
     }
     if (!u_lag_) {   // launch A: x ← x + a·u, the new direction in registers only
-        if (int rc = launch_r(KK_ACCEPT_TRIAL_LAZY, R_ACCEPT | R_DIR | R_TRIAL | R_NOWU, a_acc, beta, a, k, true, s)) return rc;
+        if (int rc = launch_rk(KK_ACCEPT_TRIAL_LAZY, a_acc, beta, a, k, true, s)) return rc;
         u_lag_ = true; beta_lag_ = beta;
         return CGO_OK;
     }
     // launch B: rebuilds the direction A left unstored, then today's launch
-    if (int rc = launch_r(KK_ACCEPT_DIR_TRIAL, R_ULAG | R_ACCEPT | R_DIR | R_TRIAL, a_acc, beta, a, k, true, s)) return rc;
+    if (int rc = launch_r(KK_ACCEPT_DIR_TRIAL, R_ULAG | R_ADT, a_acc, beta, a, k, true, s)) return rc;
     u_lag_ = false;
     return CGO_OK;
 }
 int HipBackend::trial_r(const double *a, int k, double *s) {
     if (rep_n_ > 0 && lazy_eligible()) return launch_r(KK_TRIAL, R_REPLAY | R_TRIAL, 0, 0, a, k, true, s);   // 24 B: nothing stored, steps still outstanding
     if (u_lag_ && lazy_eligible()) return launch_r(KK_TRIAL, R_ULAG | R_TRIAL, 0, 0, a, k, true, s);   // 24 B: nothing stored, still lagged
-    return launch_r(KK_TRIAL, R_TRIAL, 0, 0, a, k, true, s);
+    return launch_rk(KK_TRIAL, 0, 0, a, k, true, s);
 }
 
 // Fused reduction tail (finish_tail): a host-driven launch of the k_cg / k_chain family takes the next sequence number
@@ -247,19 +253,18 @@ Tail HipBackend::make_tail(bool on) {
 
 // the k_cg launch itself (bracketed by the profiling events); `ctl` non-null = controller-armed
 int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, const double *a, int k, int npts,
-                                const CtlArgs *ctl, int *grid_out) {
+                                const CtlArgs *ctl, RPlan *plan_out) {
     HIPCHK(hipSetDevice(ctx_->device));
     if (obj_->unset_slot() >= 0) return param_unset_error(obj_->unset_slot());
     const int64_t n = obj_->n_local;
     if (mode & (R_GRAD | R_GRADT)) { if (int rc = ensure_ga()) return rc; }
     const bool has_sums = r_has_sums(mode);
+    const RPlan plan = *plan_out = r_plan(mode, npts);
+    const bool big = plan.big; const int grid = plan.grid;
+    last_mode_ = mode; last_npts_ = plan.npts; last_big_ = big;
     if (chain()) {
-        const bool big = launch_is_big(*this, mode, bytes_r(obj_->kind, mode, n, 0));
-        const int grid = big ? GRID_BIG : grid_cg(n, 1);
-        *grid_out = grid;
-        last_mode_ = mode; last_npts_ = chain_npts(mode, npts); last_big_ = big;
         if (int rc = prof_begin(kk)) return rc;
-        if (int rc = launch_chain_kernel(mode, a_acc, beta, a, k, chain_npts(mode, npts), big, grid, make_tail(has_sums && !ctl && tail_fused(grid)))) return rc;
+        if (int rc = launch_chain_kernel(mode, a_acc, beta, a, k, plan.npts, big, grid, make_tail(has_sums && !ctl && tail_fused(grid)))) return rc;
         return prof_end();
     }
     RParams P;
@@ -272,10 +277,6 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
     P.ctl = ctl;
     P.x2 = xn_;
     for (int j = 0; j < MAXP; ++j) P.a[j] = (a && j < k) ? a[j] : ((a && k > 0) ? a[k - 1] : 0.0);
-    const bool big = launch_is_big(*this, mode, bytes_r(obj_->kind, mode, n, obj_->nparams()));
-    const int grid = big ? GRID_BIG : grid_cg(n, npts);
-    *grid_out = grid;
-    last_mode_ = mode; last_npts_ = npts; last_big_ = big;
     P.tail = make_tail(has_sums && !ctl && tail_fused(grid));
     if (ctl && pipe_fused(grid)) {
         P.tail.partials2 = ctx_->partials2_f; P.tail.tickets = ctx_->tickets; P.tail.out = ctx_->out_dev;
@@ -355,73 +356,27 @@ std::string HipBackend::r_symbol(int mode, int npts, bool big) const {
     return buf;
 }
 
-// The instantiation a launch of kind `kk` uses under the current policy, as rocprofv3 prints it minus namespaces.
+// The instantiation a launch of kind `kk` uses under the current policy, as rocprofv3 prints it minus namespaces: the kind's mode and point
+// rule (cgo_launch_kinds.hpp), the plan the launch itself asks for (r_plan) and, next to them, which lazy / replay kinds this solver issues.
 std::string HipBackend::kernel_symbol(int kk) const {
-    const char *on = obj_tname();
-    const int64_t n = obj_->n_local;
-    const int hp = obj_->nparams();
-    char buf[160];
-    if (rmode_) {
-        int mode = -1, npts = 1;
-        switch (kk) {
-        case KK_INIT: mode = R_INIT; break;
-        case KK_TRIAL: mode = R_TRIAL; npts = npts_for(std::min(max_points(), 3)); break;
-        case KK_ACCEPT_DIR_TRIAL: mode = (lazy_eligible() ? (replay_depth_ >= 2 ? R_REPLAY : R_ULAG) : 0) | R_ACCEPT | R_DIR | R_TRIAL; npts = npts_for(max_points()); break;
-        case KK_ACCEPT_TRIAL_LAZY: if (!lazy_eligible() || replay_depth_ >= 2) return ""; mode = R_ACCEPT | R_DIR | R_TRIAL | R_NOWU; npts = npts_for(max_points()); break;
-        case KK_MATERIALIZE_U: if (!lazy_eligible() || replay_depth_ >= 2) return ""; mode = R_ULAG; break;
-        case KK_ACCEPT_TRIAL_NOSTORE: if (!lazy_eligible() || replay_depth_ < 2) return ""; mode = R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL | R_NOWU | R_NOWX; npts = npts_for(max_points()); break;
-        case KK_MATERIALIZE_XU: if (!lazy_eligible() || replay_depth_ < 2) return ""; mode = R_REPLAY; break;
-        case KK_ACCEPT_DIR: mode = R_ACCEPT | R_DIR; break;
-        case KK_ACCEPT_ONLY: mode = R_ACCEPT; break;
-        case KK_RESET_DIR: mode = R_RESET; break;
-        case KK_UPG_NORM: mode = R_UPG; break;
-        case KK_DIR_TRIAL: mode = R_DIR | R_TRIAL; npts = npts_for(max_points()); break;
-        case KK_SYS_PROJECT: mode = R_PROJ; break;
-        default: return "";
-        }
-        const bool big = launch_is_big(*this, mode, bytes_r(obj_->kind, mode, n, hp));
-        if ((mode & R_REPLAY) && (mode & R_ACCEPT)) mode |= lean_for(mode);   // N and S: the lean row where that is what runs
-        return r_symbol(mode, chain() ? chain_npts(mode, npts) : npts, big);
+    if (!rmode_) {
+        if (obj_->two_phase() || kk == KK_LBFGS_PUSH || kk == KK_LBFGS_LOOP || kk == KK_LBFGS_FINAL) return lbfgs_symbol(kk);
+        const int mode = fused_mode(kk);
+        return mode < 0 ? "" : fused_symbol(obj_tname(), mode, is_big(obj_->kind, mode, obj_->n_local, obj_->nparams(), pol_.hbm_stream_bytes));
     }
-    if (obj_->two_phase()) {
-        if (kk == KK_LSE_STATS) return "k_lse_stats";
-        if (kk == KK_LSE_GRAD) return "k_lse_grad";
-        const bool big_ring = 8.0 * (double)n * (3.0 + 2.0 * std::max(qn_m_ - 1, 0)) > big_bytes();
-        if (kk == KK_LBFGS_FINAL && qn_m_ > 0) {   // the L-BFGS passes of the log-sum-exp objective (a full ring assumed for the policy bit)
-            if (spec_on_ && qn_m_ - 1 <= SPEC_MAXC) { snprintf(buf, sizeof buf, "k_lbfgs_combine_spec<ObjLse, %s, %s>", big_ring ? "true" : "false", spec_fuse_push_ ? "true" : "false"); return buf; }
-            if (gram_on_) { snprintf(buf, sizeof buf, "k_lbfgs_combine_lse<%s>", big_ring ? "true" : "false"); return buf; }
-            return "k_lbfgs_loop";
-        }
-        if (kk == KK_LBFGS_PUSH && qn_m_ > 0) {
-            if (spec_on_ && qn_m_ - 1 <= SPEC_MAXC && !spec_fuse_push_) { snprintf(buf, sizeof buf, "k_lbfgs_push_lite<ObjLse, %s>", 8.0 * (double)n * 7.0 > big_bytes() ? "true" : "false"); return buf; }
-            if (gram_on_) { snprintf(buf, sizeof buf, fuse_grad_ && x2_.p ? "k_lbfgs_push_gram_lse<%s>" : "k_lbfgs_push_gram<%s>", big_ring ? "true" : "false"); return buf; }
-            return "k_lbfgs_push";
-        }
-        return "";
-    }
-    int mode = -1;
+    const RKind *rk = r_kind(kk);
+    if (!rk) return "";
+    int mode = rk->mode;
+    const bool lazy = lazy_eligible();
     switch (kk) {
-    case KK_INIT: mode = M_INIT; break;
-    case KK_TRIAL: mode = need_beta_ ? (M_TRIAL | M_BETA) : M_TRIAL; break;
-    case KK_ACCEPT_DIR_TRIAL: mode = M_ACCEPT | M_DIR | M_TRIAL | M_BETA; break;
-    case KK_ACCEPT_DIR: mode = M_ACCEPT | M_DIR; break;
-    case KK_ACCEPT_ONLY: mode = M_ACCEPT; break;
-    case KK_RESET_DIR: mode = M_RESET; break;
-    case KK_UPG_NORM: mode = M_UPG; break;
-    case KK_LBFGS_PUSH: return gram_on_ ? "k_lbfgs_push_gram" : "k_lbfgs_push";
-    case KK_LBFGS_LOOP: return "k_lbfgs_loop";
-    case KK_LBFGS_FINAL:
-        if (spec_on_ && qn_m_ > 0 && qn_m_ - 1 <= SPEC_MAXC) {   // the one-pass form (a full ring assumed for the policy bit)
-            snprintf(buf, sizeof buf, "k_lbfgs_combine_spec<%s, %s, %s>", on, 8.0 * (double)n * (3.0 + (double)hp + 2.0 * (qn_m_ - 1)) > big_bytes() ? "true" : "false",
-                     spec_fuse_push_ ? "true" : "false");
-            return buf;
-        }
-        return gram_on_ ? "k_lbfgs_combine" : "k_lbfgs_loop";
-    default: return "";
+    case KK_ACCEPT_DIR_TRIAL: if (lazy) mode |= replay_depth_ >= 2 ? R_REPLAY : R_ULAG; break;   // launch S / launch B
+    case KK_ACCEPT_TRIAL_LAZY: case KK_MATERIALIZE_U: if (!lazy || replay_depth_ >= 2) return ""; break;
+    case KK_ACCEPT_TRIAL_NOSTORE: case KK_MATERIALIZE_XU: if (!lazy || replay_depth_ < 2) return ""; break;
+    default: break;
     }
-    const bool objective_mode = (mode & (M_TRIAL | M_INIT)) != 0;
-    snprintf(buf, sizeof buf, "k_fused<%s, %d, %s>", objective_mode ? on : "ObjQuadDiag", mode, is_big(obj_->kind, mode, n, hp, pol_.hbm_stream_bytes) ? "true" : "false");
-    return buf;
+    const RPlan plan = r_plan(mode, rk->pts == PTS_ONE ? 1 : npts_for(rk->pts == PTS_MAX ? max_points() : std::min(max_points(), 3)));
+    if ((mode & R_REPLAY) && (mode & R_ACCEPT)) mode |= lean_for(mode);   // N and S: the lean row where that is what runs
+    return r_symbol(mode, plan.npts, plan.big);
 }
 
 // ---- on-device controller (cgo_ctl.hpp) ------------------------------------------------------
@@ -504,8 +459,7 @@ int HipBackend::ctl_depth() const {
     if (!(rmode_ && ctx_->host_publish && !obj_->two_phase())) return 0;
     if (ctx_->single()) return ctl_depth_;
     if (!ctx_->dev_exchange() || ctx_->force_gather) return 0;
-    const bool big = bytes_r(obj_->kind, R_ACCEPT | R_DIR | R_TRIAL, obj_->n_local, obj_->nparams()) > big_bytes(false);
-    return (!big && pipe_fused(grid_cg(obj_->n_local, policy_points()))) ? ctl_depth_ : 0;
+    return (!adt_is_big() && pipe_fused(grid_cg(obj_->n_local, policy_points()))) ? ctl_depth_ : 0;
 }
 
 int HipBackend::pipe_alloc() {
@@ -541,10 +495,11 @@ int HipBackend::prepare_controller() {
 // No argument depends on the round (record slot and sequence number come from CtlDev::round), so the same launches can
 // be captured into a hipGraph.
 int HipBackend::pipe_round_kernels() {
-    int grid = 0;
+    RPlan plan;
     const int npts = pipe_npts_, ns = rows_for(npts);
     CtlDev *d = (CtlDev *)ctl_dev_;
-    if (int rc = launch_r_kernel(KK_ACCEPT_DIR_TRIAL, R_ACCEPT | R_DIR | R_TRIAL, 0.0, 0.0, nullptr, 0, npts, &d->args, &grid)) return rc;
+    if (int rc = launch_r_kernel(KK_ACCEPT_DIR_TRIAL, R_ADT, 0.0, 0.0, nullptr, 0, npts, &d->args, &plan)) return rc;
+    const int grid = plan.grid;
     pipe_checked_ = pipe_fused(grid) && !ctx_->tail_strict;
     if (pipe_fused(grid)) {   // the launch's own finisher reduced, ran the controller and published the record
         if (probe_) probe_note(nullptr, 0, "k_cg_armed<%s, %d>", obj_tname(), last_npts_);
@@ -710,7 +665,7 @@ int HipBackend::accept_dir_trial_ctl(const CtlConfig &cc, const CtlState &s0, in
     const auto &pp = pipe_prof_[(int)(id % PIPE_RING)];
     if (prof_on_) {
         prof_cnt_[KK_ACCEPT_DIR_TRIAL]++;
-        prof_bytes_[KK_ACCEPT_DIR_TRIAL] = bytes_r(obj_->kind, R_ACCEPT | R_DIR | R_TRIAL, obj_->n_local, obj_->nparams());
+        prof_bytes_[KK_ACCEPT_DIR_TRIAL] = bytes_r(obj_->kind, R_ADT, obj_->n_local, obj_->nparams());
         if (pp.first >= 0 && pp.second == prof_gen_ && pp.first < ring_used_) {
             ring_[pp.first].kk = KK_ACCEPT_DIR_TRIAL;
             ring_[pp.first].bytes = prof_bytes_[KK_ACCEPT_DIR_TRIAL];
@@ -812,27 +767,16 @@ int HipBackend::probe_launch(int kk, int variant, double a_acc, double beta, con
         if (kk == KK_LSE_STATS && mode != LM_NOU && k < 1) mode = -1;
         if (kk == KK_LSE_GRAD && mode != 2 && k < 1) mode = -1;
     } else {
-        auto pick = [&](int dflt, std::initializer_list<int> ok) { const int m = variant ? variant : dflt; for (int o : ok) if (o == m) return m; return -1; };
-        switch (kk) {
-        case KK_INIT: mode = chain() ? pick(R_INIT, {R_INIT, R_GRAD, R_EDGES}) : pick(R_INIT, {R_INIT, R_GRAD}); break;
-        case KK_TRIAL: mode = pick(R_TRIAL, {R_TRIAL, R_ULAG | R_TRIAL, R_REPLAY | R_TRIAL}); break;
-        case KK_ACCEPT_DIR_TRIAL:
-            if (variant & R_LEAN) { mode = (lean_row(variant) && (variant & ~R_LEAN) == (R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL)) ? variant : -1; break; }   // lean S
-            mode = pick(R_ACCEPT | R_DIR | R_TRIAL, {R_ACCEPT | R_DIR | R_TRIAL, R_ULAG | R_ACCEPT | R_DIR | R_TRIAL, R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL}); break;
-        case KK_ACCEPT_TRIAL_NOSTORE:
-            if (variant & R_LEAN) { mode = (lean_row(variant) && (variant & ~R_LEAN) == (R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL | R_NOWU | R_NOWX)) ? variant : -1; break; }   // lean N
-            mode = pick(R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL | R_NOWU | R_NOWX, {R_REPLAY | R_ACCEPT | R_DIR | R_TRIAL | R_NOWU | R_NOWX}); break;
-        case KK_MATERIALIZE_XU: mode = pick(R_REPLAY, {R_REPLAY}); break;
-        case KK_ACCEPT_TRIAL_LAZY: mode = pick(R_ACCEPT | R_DIR | R_TRIAL | R_NOWU, {R_ACCEPT | R_DIR | R_TRIAL | R_NOWU}); break;
-        case KK_MATERIALIZE_U: mode = pick(R_ULAG, {R_ULAG}); break;
-        case KK_ACCEPT_DIR: mode = pick(R_ACCEPT | R_DIR, {R_ACCEPT | R_DIR}); break;
-        case KK_ACCEPT_ONLY: mode = pick(R_ACCEPT, {R_ACCEPT}); break;
-        case KK_RESET_DIR: mode = pick(R_RESET, {R_RESET}); break;
-        case KK_UPG_NORM: mode = pick(R_UPG, {R_UPG}); break;
-        case KK_DIR_TRIAL: mode = pick(R_DIR | R_TRIAL, {R_DIR, R_DIR | R_TRIAL}); break;
-        case KK_SYS_PROJECT: mode = pick(R_PROJ, {R_PROJ}); break;
-        case KK_SCALED_NORM: mode = pick(R_GRAD, {R_GRAD, R_GRADT}); break;
-        default: break;
+        // the kind's default mode, or one of those its row allows (cgo_launch_kinds.hpp); beside the table: the lean rows of launches
+        // N and S, the stencil objective's edge pass, and scaled_norm_parts' two materialise passes (a kind kernel_symbol does not name)
+        static constexpr RKind norm_passes{KK_SCALED_NORM, R_GRAD, PTS_ONE, {R_GRADT, 0}};
+        const RKind *rk = kk == KK_SCALED_NORM ? &norm_passes : r_kind(kk);
+        if (rk && (variant & R_LEAN)) {
+            const int full = kk == KK_ACCEPT_DIR_TRIAL ? (R_REPLAY | R_ADT) : (kk == KK_ACCEPT_TRIAL_NOSTORE ? rk->mode : -1);
+            if (lean_row(variant) && (variant & ~R_LEAN) == full) mode = variant;
+        } else if (rk) {
+            const int m = variant ? variant : rk->mode;
+            if (r_kind_allows(*rk, m) || (kk == KK_INIT && chain() && m == R_EDGES)) mode = m;
         }
         if (mode > 0 && (mode & (R_TRIAL | R_GRADT | R_PROJ)) && k < 1) mode = -1;
         if (mode > 0 && chain() && k > 3) mode = -1;
@@ -921,22 +865,12 @@ int HipBackend::probe_launch_stored(int kk, int variant, double a_acc, double be
                                     double *u_out, double *g_out, std::string &symbol) {
     if (ctx_->world() != 1) { set_error("probe: a single-rank solver"); return CGO_EINVAL; }
     const bool host = obj_->host_closure();
-    auto pick = [&](int dflt, std::initializer_list<int> ok) { const int m = variant ? variant : dflt; for (int o : ok) if (o == m) return m; return -1; };
     int mode = -1;
-    switch (kk) {
-    case KK_INIT: mode = host ? pick(M_BETAONLY, {M_BETAONLY}) : pick(M_INIT, {M_INIT}); break;
-    case KK_TRIAL:
-        mode = host ? pick(M_BETAONLY, {M_BETAONLY}) : pick(need_beta_ ? (M_TRIAL | M_BETA) : M_TRIAL, {M_TRIAL, M_TRIAL | M_BETA});
-        break;
-    case KK_ACCEPT_DIR_TRIAL:
-        mode = host ? pick(M_ACCEPT | M_DIR, {M_ACCEPT | M_DIR}) : pick(M_ACCEPT | M_DIR | M_TRIAL | M_BETA, {M_ACCEPT | M_DIR | M_TRIAL | M_BETA});
-        break;
-    case KK_ACCEPT_DIR: mode = pick(M_ACCEPT | M_DIR, {M_ACCEPT | M_DIR}); break;
-    case KK_ACCEPT_ONLY: mode = pick(M_ACCEPT, {M_ACCEPT}); break;
-    case KK_RESET_DIR: mode = pick(M_RESET, {M_RESET}); break;
-    case KK_UPG_NORM: mode = pick(M_UPG, {M_UPG}); break;
-    case KK_SCALED_NORM: mode = (variant == 0 || variant == 1 || variant == 3 || variant == 4) ? variant : -1; break;
-    default: break;
+    if (const MKind *mk = m_kind(kk)) {   // the mode this solver's entry point launches, or the other one of the kind's row
+        const int m = variant ? variant : (host ? mk->host : fused_mode(kk));
+        if (host ? m == mk->host : (m == mk->mode || (mk->alt && m == mk->alt))) mode = m;
+    } else if (kk == KK_SCALED_NORM) {
+        mode = (variant == 0 || variant == 1 || variant == 3 || variant == 4) ? variant : -1;
     }
     const bool trial_step = kk == KK_TRIAL || kk == KK_ACCEPT_DIR_TRIAL;
     if (mode >= 0 && trial_step && k != 1) mode = -1;   // one trial step per launch in this family
@@ -966,12 +900,12 @@ int HipBackend::probe_launch_stored(int kk, int variant, double a_acc, double be
     switch (kk) {
     case KK_INIT: {
         double s[NS];
-        rc = host ? host_trial(0.0, true, o[0]) : launch(KK_INIT, M_INIT, 0, 0, 0, true, s);
+        rc = host ? host_trial(0.0, true, o[0]) : launch_k(KK_INIT, 0, 0, 0, true, s);
         break;
     }
     case KK_TRIAL: {
         const bool nb0 = need_beta_;
-        need_beta_ = mode == (M_TRIAL | M_BETA);
+        need_beta_ = mode == m_mode_of(KK_TRIAL);
         rc = trial(a, 1, o);
         need_beta_ = nb0;
         break;

@@ -54,6 +54,7 @@ static inline bool with_width(int ns, bool or_last, F f) {
 double big_bytes_for(double forced, bool read_only = false);
 double env_big_bytes();
 bool is_big(int obj_kind, int mode, int64_t n, int n_params, double forced);
+std::string fused_symbol(const char *obj_tname, int mode, bool big);   // a k_fused instantiation as rocprofv3 prints it minus namespaces
 int grid_cg(int64_t n, int npts = 1);
 // ALGORITHMIC bytes of a k_cg / k_chain launch (cgo_backend_cg.hip)
 double bytes_r(int obj_kind, int mode, int64_t n, int n_params);

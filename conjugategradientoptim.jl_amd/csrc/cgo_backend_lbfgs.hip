@@ -10,6 +10,16 @@ namespace cgo {
 
 using namespace dev;
 
+// ---- what a pass streams, in n-long double vectors: each formula once, for the launch and for the symbol that names it -----------
+static inline double ring_pass_vectors(int count) { return 3.0 + 2.0 * count; }   // g, x, the ring / u
+static inline double push_lite_vectors(int hp) { return 7.0 + hp; }
+// g, x, the ring / u — and with the state update: u_old / x, g, s, y, less the two reads of the pair formed in registers
+static inline double spec_pass_vectors(int hp, int count, bool push, int new_in_list) { return 3.0 + hp + 2.0 * count + (push ? 5.0 - 2.0 * new_in_list : 0.0); }
+constexpr double LOOP_VECTORS = 4.0;   // lbfgs_direction's geometry: every step of the two-loop recursion runs on it
+static inline double vec_bytes(int64_t n, double vectors) { return 8.0 * (double)n * vectors; }
+struct Path { bool big; int grid; };   // streaming path and grid of a light launch that moves `bytes`
+static inline Path path_for(const HipBackend &be, double bytes, bool read_only = false) { const bool big = bytes > be.big_bytes(read_only); return {big, big ? GRID_BIG : grid_for(be.n_local())}; }
+
 // ---- two-phase objective (log-sum-exp) --------------------------------------------------
 template <int MODE>
 static int launch_lse_stats(const LseParams &P, bool big, bool ref, int grid, hipStream_t st) {
@@ -38,8 +48,7 @@ int HipBackend::lse_stats(int mode, double a_acc, double beta, double a_trial, S
     if (ref) P.M = Mr;
     const double nvec = (mode == LM_NOU) ? 1.0 : (mode == 0 ? 2.0 : 5.0);
     const double bytes = 8.0 * (double)n * nvec;
-    const bool big = bytes > big_bytes(mode == 0 || mode == LM_NOU);
-    const int grid = big ? GRID_BIG : grid_for(n);
+    const auto [big, grid] = path_for(*this, bytes, mode == 0 || mode == LM_NOU);
     last_mode_ = mode; last_big_ = big; last_npts_ = ref ? 1 : 0;   // (probe_launch's symbol; npts = the REF form)
     hipStream_t st = ctx_->stream;
     if (int rc = prof_begin(KK_LSE_STATS)) return rc;
@@ -86,8 +95,7 @@ int HipBackend::lse_grad(bool init, double a, Scal &out) {
     P.partials = ctx_->partials;
     const bool beta = need_beta_ && !init;
     const double bytes = 8.0 * (double)n * (init ? 3.0 : (beta ? 4.0 : 3.0));
-    const bool big = bytes > big_bytes();
-    const int grid = big ? GRID_BIG : grid_for(n);
+    const auto [big, grid] = path_for(*this, bytes);
     last_mode_ = init ? 2 : (beta ? 1 : 0); last_big_ = big;   // (probe_launch's symbol)
     hipStream_t st = ctx_->stream;
     if (int rc = prof_begin(KK_LSE_GRAD)) return rc;
@@ -185,8 +193,7 @@ int HipBackend::lbfgs_push_gram(double a_x, double a_s, int slot, const int *pre
         L.xo = push_xo_; L.gt_out = gt_; L.M = lse_M_; L.S = lse_S_; L.lambda = obj_->s0;
     }
     const double bytes = 8.0 * (double)n * (7.0 + 2.0 * count);   // fused: R x,u,g + ring, W x',s,y,g⁺ — the same count, g⁺ written instead of read
-    const bool big = bytes > big_bytes();
-    const int grid = big ? GRID_BIG : grid_for(n);
+    const auto [big, grid] = path_for(*this, bytes);
     hipStream_t st = ctx_->stream;
     if (int rc = prof_begin(KK_LBFGS_PUSH)) return rc;
     if (fused) {
@@ -236,8 +243,7 @@ int HipBackend::lbfgs_direction_gram(const int *slots, const double *cy, const d
         P.cs[j] = j < count ? cs[j] : 0.0;
     }
     const double bytes = 8.0 * (double)n * (2.0 + 2.0 * count);
-    const bool big = bytes > big_bytes();
-    const int grid = big ? GRID_BIG : grid_for(n);
+    const auto [big, grid] = path_for(*this, bytes);
     hipStream_t st = ctx_->stream;
     if (int rc = prof_begin(KK_LBFGS_FINAL)) return rc;
     if (big) k_lbfgs_combine<true><<<grid, BLOCK, 0, st>>>(P);
@@ -277,9 +283,8 @@ int HipBackend::lbfgs_direction_gram_trial(const int *slots, const double *cy, c
         P.cy[j] = j < count ? cy[j] : 0.0;
         P.cs[j] = j < count ? cs[j] : 0.0;
     }
-    const double bytes = 8.0 * (double)n * (3.0 + 2.0 * count);   // g, x, the ring / u
-    const bool big = bytes > big_bytes();
-    const int grid = big ? GRID_BIG : grid_for(n);
+    const double bytes = vec_bytes(n, ring_pass_vectors(count));
+    const auto [big, grid] = path_for(*this, bytes);
     hipStream_t st = ctx_->stream;
     if (int rc = prof_begin(KK_LBFGS_FINAL)) return rc;
     if (big) k_lbfgs_combine_lse<true><<<grid, BLOCK, 0, st>>>(P, xc_, a_trial);
@@ -339,7 +344,6 @@ int HipBackend::lbfgs_direction_spec(const int *slots, const double *cy, const d
     const double Mr = lse ? lse_M_ + std::log(lse_S_) : 0.0, Sr = 1.0;
     SpecParams Q{Mr, 1.0 / Sr, obj_->s0, nullptr, nullptr, nullptr, nullptr};
     obj_->param_args(Q);
-    const double hp = (double)obj_->nparams();
     // the state update of the accepted speculated trial, if it was left to this pass (lbfgs_push_commit(direction_follows))
     const bool push = lite_deferred_;
     lite_deferred_ = false;
@@ -351,10 +355,8 @@ int HipBackend::lbfgs_direction_spec(const int *slots, const double *cy, const d
         push_counts_[0]++;
         qn_sgt_slot_ = -1;
     }
-    // g, x, the ring / u — and with the state update: u_old / x, g, s, y, less the two reads of the pair formed in registers
-    const double bytes = 8.0 * (double)n * (3.0 + hp + 2.0 * count + (push ? 5.0 - 2.0 * U.new_in_list : 0.0));
-    const bool big = bytes > big_bytes();
-    const int grid = big ? GRID_BIG : grid_for(n);
+    const double bytes = vec_bytes(n, spec_pass_vectors(obj_->nparams(), count, push, U.new_in_list));
+    const auto [big, grid] = path_for(*this, bytes);
     hipStream_t st = ctx_->stream;
     if (int rc = prof_begin(KK_LBFGS_FINAL)) return rc;
     switch (obj_->kind) {
@@ -478,9 +480,8 @@ int HipBackend::lbfgs_push_lite() {
     HIPCHK(hipSetDevice(ctx_->device));
     const int64_t n = obj_->n_local;
     double *sn = qn_S_.p + (size_t)lite_slot_ * ring_ld(n), *yn = qn_Y_.p + (size_t)lite_slot_ * ring_ld(n);
-    const double bytes = 8.0 * (double)n * (7.0 + (double)obj_->nparams());
-    const bool big = bytes > big_bytes();
-    const int grid = big ? GRID_BIG : grid_for(n);
+    const double bytes = vec_bytes(n, push_lite_vectors(obj_->nparams()));
+    const auto [big, grid] = path_for(*this, bytes);
     hipStream_t st = ctx_->stream;
     if (int rc = prof_begin(KK_LBFGS_PUSH)) return rc;
     switch (obj_->kind) {
@@ -554,8 +555,7 @@ int HipBackend::lbfgs_push(double a_x, double a_s, int slot, double &sy, double 
     P.s = qn_S_.p + (size_t)slot * ring_ld(n); P.y = qn_Y_.p + (size_t)slot * ring_ld(n);
     P.n = n; P.a = a_x; P.a_s = a_s; P.partials = ctx_->partials;
     const double bytes = 8.0 * (double)n * 7.0;
-    const bool big = bytes > big_bytes();
-    const int grid = big ? GRID_BIG : grid_for(n);
+    const auto [big, grid] = path_for(*this, bytes);
     if (int rc = prof_begin(KK_LBFGS_PUSH)) return rc;
     if (big) k_lbfgs_push<true><<<grid, BLOCK, 0, ctx_->stream>>>(P);
     else k_lbfgs_push<false><<<grid, BLOCK, 0, ctx_->stream>>>(P);
@@ -578,15 +578,14 @@ int HipBackend::lbfgs_direction(const int *slots, const double *rho, int count, 
     HIPCHK(hipSetDevice(ctx_->device));
     if (count == 0) return reset_dir(out);  // no curvature pairs yet: u = −g
     const int64_t n = obj_->n_local;
-    const double bytes = 8.0 * (double)n * 4.0;
-    const bool big = bytes > big_bytes();
-    const int grid = big ? GRID_BIG : grid_for(n);
+    const Path path = path_for(*this, vec_bytes(n, LOOP_VECTORS));
+    const int grid = path.grid;
     auto S = [&](int slot) { return qn_S_.p + (size_t)slot * ring_ld(n); };
     auto Y = [&](int slot) { return qn_Y_.p + (size_t)slot * ring_ld(n); };
     LoopParams P;
     std::memset(&P, 0, sizeof(P));
     P.n = n; P.partials = ctx_->partials; P.alpha = qn_alpha_dev_; P.dot_stride = NS; P.dot_slot = S_GU;
-    auto launch = [&](int kk, double nvec) { return launch_loop(P, kk, nvec, big, grid); };
+    auto launch = [&](int kk, double nvec) { return launch_loop(P, kk, nvec, path.big, grid); };
     // first dot  s_newest · g : already reduced by the push of this very pair, else one dot-only launch
     if (slots[0] == qn_sgt_slot_) {
         P.dot_ptr = nullptr; P.dot_count = 0; P.dot_host = qn_sgt_;
@@ -619,6 +618,28 @@ int HipBackend::lbfgs_direction(const int *slots, const double *rho, int count, 
     if (int rc = fetch_sums(ctx_, s)) return rc;
     out.gu = s[S_GU]; out.uu = s[S_UU];
     return CGO_OK;
+}
+
+// kernel_symbol's half for the stored-gradient L-BFGS passes and the log-sum-exp objective.  The policy bit of a ring pass is
+// that of a full ring with no state update riding in it: count = m − 1, push = false, through the formulas the launches use.
+std::string HipBackend::lbfgs_symbol(int kk) const {
+    const int hp = obj_->nparams(), full = std::max(qn_m_ - 1, 0);
+    const bool lse = obj_->two_phase(), spec = spec_on_ && qn_m_ > 0 && qn_m_ - 1 <= SPEC_MAXC;
+    auto big = [&](double vectors) { return path_for(*this, vec_bytes(obj_->n_local, vectors)).big ? "true" : "false"; };
+    char buf[160] = "";
+    if (lse && (kk == KK_LSE_STATS || kk == KK_LSE_GRAD)) return kk == KK_LSE_STATS ? "k_lse_stats" : "k_lse_grad";
+    if (lse && qn_m_ <= 0) return "";
+    if (kk == KK_LBFGS_LOOP && !lse) return "k_lbfgs_loop";
+    if (kk == KK_LBFGS_FINAL) {   // (log-sum-exp: no parameter slots, the one-pass and the ring-pass formula agree)
+        if (spec) snprintf(buf, sizeof buf, "k_lbfgs_combine_spec<%s, %s, %s>", obj_tname(), big(spec_pass_vectors(hp, full, false, 0)), spec_fuse_push_ ? "true" : "false");
+        else if (lse && gram_on_) snprintf(buf, sizeof buf, "k_lbfgs_combine_lse<%s>", big(ring_pass_vectors(full)));
+        else return gram_on_ ? "k_lbfgs_combine" : "k_lbfgs_loop";
+    } else if (kk == KK_LBFGS_PUSH) {
+        if (lse && spec && !spec_fuse_push_) snprintf(buf, sizeof buf, "k_lbfgs_push_lite<ObjLse, %s>", big(push_lite_vectors(hp)));
+        else if (lse && gram_on_) snprintf(buf, sizeof buf, fuse_grad_ && x2_.p ? "k_lbfgs_push_gram_lse<%s>" : "k_lbfgs_push_gram<%s>", big(ring_pass_vectors(full)));
+        else return gram_on_ ? "k_lbfgs_push_gram" : "k_lbfgs_push";
+    }
+    return buf;
 }
 
 // ---- one L-BFGS pass on host vectors (cgo_solver_probe_lbfgs) ----------------------------------------------------------
@@ -777,8 +798,7 @@ int HipBackend::probe_lbfgs(int m, cgo_lbfgs_probe &p, const double *x, const do
         L.mode = p.loop_mode; L.k = p.k; L.rho = p.rho; L.scale = p.scale; L.apply_scale = p.apply_scale; L.final_step = p.final_step;
         L.qin = p.q_from_g ? ga_.p : u_.p; L.qout = u_.p; L.v = vec(p.v_ring, p.v_slot); L.w = vec(p.w_ring, p.w_slot);
         L.dot_host = p.dot_host; L.dot_ptr = p.dot_count ? dots.p : nullptr; L.dot_count = p.dot_count;
-        const bool big = 8.0 * (double)n * 4.0 > big_bytes();   // lbfgs_direction's geometry
-        const int grid = big ? GRID_BIG : grid_for((int64_t)n);
+        const auto [big, grid] = path_for(*this, vec_bytes((int64_t)n, LOOP_VECTORS));   // lbfgs_direction's geometry
         rc = launch_loop(L, p.final_step ? KK_LBFGS_FINAL : KK_LBFGS_LOOP, 4.0, big, grid);
         if (!rc) rc = finalize_rows(ctx_, grid, NS);
         double s[NS];

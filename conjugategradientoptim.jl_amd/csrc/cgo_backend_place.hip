@@ -47,8 +47,6 @@ int HipBackend::tune_placement() {
     const int np = obj_->nparams();
     const bool hp = np > 0;
     static const bool dbg = getenv("CGO_DEBUG_PLACE") != nullptr;
-    if (dbg) fprintf(stderr, "[cgo place] on=%d rmode=%d chain=%d bytes=%.3g big=%.3g\n", (int)on, (int)rmode_, (int)chain(),
-                     bytes_r(obj_->kind, R_ACCEPT | R_DIR | R_TRIAL, n, np), big_bytes(false));
     // Searched for the pure-HBM (BIG) launches only.  Round 3 measured the grid-stride launches that exceed the 256 MiB
     // Infinity Cache as well (CGO_PLACE_MIN_BYTES=2.7e8; the 8-GPU shard of config 5, n/8 = 1.25e7, and config 3 at
     // n = 1e7): there the bare mix on the launch's own policy differs by 3–5 % between triples, with no
@@ -56,10 +54,11 @@ int HipBackend::tune_placement() {
     // does not move at all (87.0 vs 87.2 µs, 53.7 vs 54.6 µs; scripts/r03_shard.sh) — at those sizes the launch is 20 µs above
     // its own mix for other reasons (two waves per SIMD do not hide the FP64 work behind the stream).  Not worth 24 spare
     // buffers and 30–40 ms per solver: off by default below the BIG threshold.
-    const double launch_bytes = bytes_r(obj_->kind, R_ACCEPT | R_DIR | R_TRIAL, n, np);
+    const double launch_bytes = bytes_r(obj_->kind, R_ADT, n, np);
+    if (dbg) fprintf(stderr, "[cgo place] on=%d rmode=%d chain=%d bytes=%.3g big=%.3g\n", (int)on, (int)rmode_, (int)chain(), launch_bytes, big_bytes(false));
     static const double min_env = [] { const char *e = getenv("CGO_PLACE_MIN_BYTES"); double v = e ? atof(e) : 0.0; return v > 0.0 ? v : 0.0; }();   // (experiments: the search below the pure-HBM threshold)
     const double min_bytes = min_env > 0.0 ? min_env : big_bytes(false);
-    const bool big = launch_bytes > big_bytes(false);
+    const bool big = adt_is_big();
     const int mix_grid = big ? GRID_BIG : grid_cg(n, policy_points());
     // (the mix that is timed has three streams — x, u and ONE parameter vector: an objective with more slots is not searched)
     if (!on || !rmode_ || chain() || np > 1 || launch_bytes <= min_bytes) return CGO_OK;

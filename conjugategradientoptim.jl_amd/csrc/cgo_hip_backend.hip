@@ -154,8 +154,12 @@ int param_unset_error(int slot) {
     return CGO_ESTATE;
 }
 bool is_big(int obj_kind, int mode, int64_t n, int hp, double forced) {
-    const bool ro = (mode == M_UPG || mode == M_BETAONLY);
-    return bytes_for(obj_kind, mode, n, hp) > big_bytes_for(forced, ro);
+    return bytes_for(obj_kind, mode, n, hp) > big_bytes_for(forced, m_read_only(mode));
+}
+std::string fused_symbol(const char *obj_tname, int mode, bool big) {   // objective-free modes run as ObjQuadDiag's instantiation (launch_any)
+    char buf[160];
+    snprintf(buf, sizeof buf, "k_fused<%s, %d, %s>", m_evaluates(mode) ? obj_tname : "ObjQuadDiag", mode, big ? "true" : "false");
+    return buf;
 }
 
 static int grid_capped(int64_t n, int cap) {
@@ -193,18 +197,7 @@ int grid_cg(int64_t n, int npts) {
 // ALGORITHMIC bytes of one launch: 8·n·(distinct n-vectors read + written)
 double bytes_for(int obj_kind, int mode, int64_t n, int n_params) {
     const int p = std::max(obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0, n_params);
-    int v = 0;
-    if (mode == M_INIT) v = 1 + p + 2;
-    else if (mode == (M_TRIAL | M_BETA)) v = 3 + p + 1;
-    else if (mode == M_TRIAL) v = 2 + p + 1;
-    else if (mode == (M_ACCEPT | M_DIR | M_TRIAL | M_BETA)) v = 3 + p + 3;
-    else if (mode == (M_ACCEPT | M_DIR)) v = 3 + 2;
-    else if (mode == M_ACCEPT) v = 2 + 1;
-    else if (mode == M_DIR) v = 2 + 1;
-    else if (mode == M_RESET) v = 1 + 1;
-    else if (mode == M_UPG) v = 2;
-    else if (mode == M_BETAONLY) v = 3;
-    return 8.0 * (double)n * (double)v;
+    return 8.0 * (double)n * (double)m_vectors(mode, p);   // reads + writes of the mode (cgo_modes.hpp): a new row needs no edit here
 }
 
 // the rows of cgo_instances.def; -1: no such mode, -2: no such objective
@@ -252,8 +245,7 @@ int launch_fused(HipCtx *ctx, int obj_kind, int mode, const void *kparams, int64
     hipStream_t st = ctx->stream;
     if (timed) HIPCHK(hipEventRecord(e0, st));
     int r;
-    const bool objective_mode = (mode & (M_TRIAL | M_INIT)) != 0;
-    if (obj_kind == CGO_OBJ_USER && objective_mode) {
+    if (obj_kind == CGO_OBJ_USER && m_evaluates(mode)) {
         if (!obj || !obj->rtc) { set_error("user objective has no compiled module"); return CGO_EINVAL; }
         KParams Pc = P;
         if (int rc = launch_module(obj->rtc->fused(mode, big), &Pc, grid, st)) return rc;
@@ -265,8 +257,7 @@ int launch_fused(HipCtx *ctx, int obj_kind, int mode, const void *kparams, int64
     if (r == -2) { set_error("objective kind not implemented on the device yet"); return CGO_EINVAL; }
     if (r) { set_error("internal: kernel mode not instantiated"); return CGO_EINVAL; }
     HIPCHK(hipGetLastError());
-    const bool has_sums = mode != M_ACCEPT;
-    if (has_sums) {
+    if (m_has_sums(mode)) {
         if (int rc = finalize_rows(ctx, grid, NS)) return rc;
     }
     return CGO_OK;
@@ -776,7 +767,7 @@ void HipBackend::profile_get(int kind, int64_t *launches, double *ms, double *by
 int HipBackend::launch(int kk, int mode, double a_acc, double beta, double a_trial, bool fetch,
                        double *sums) {
     HIPCHK(hipSetDevice(ctx_->device));
-    if (obj_->unset_slot() >= 0 && (mode & (M_TRIAL | M_INIT))) return param_unset_error(obj_->unset_slot());
+    if (obj_->unset_slot() >= 0 && m_evaluates(mode)) return param_unset_error(obj_->unset_slot());
     KParams P;
     P.x = xc_; P.u = u_.p; P.g = g_; P.gt = gt_; obj_->param_args(P);
     P.n = obj_->n_local; P.offset = obj_->offset;
@@ -791,9 +782,7 @@ int HipBackend::launch(int kk, int mode, double a_acc, double beta, double a_tri
         if (int rc = fetch_sums(ctx_, sums)) return rc;
     }
     if (probe_stored_) {   // cgo_solver_probe_launch: the instantiation launch_fused dispatched, and the row
-        const bool objective_mode = (mode & (M_TRIAL | M_INIT)) != 0;
-        probe_note(nullptr, 0, "k_fused<%s, %d, %s>", objective_mode ? obj_tname() : "ObjQuadDiag", mode,
-                   is_big(obj_->kind, mode, obj_->n_local, obj_->nparams(), pol_.hbm_stream_bytes) ? "true" : "false");
+        probe_note(nullptr, 0, "%s", fused_symbol(obj_tname(), mode, is_big(obj_->kind, mode, obj_->n_local, obj_->nparams(), pol_.hbm_stream_bytes)).c_str());
         if (fetch) probe_append(sums, NS);
     }
     if (prof_on_) prof_commit(kk, bytes_for(obj_->kind, mode, obj_->n_local, obj_->nparams()));
@@ -815,7 +804,7 @@ int HipBackend::init_eval(Scal &out) {
         if (chain() && !ctx_->single()) {   // the neighbours' edge elements of x0, before the first gradient
             if (int rc = launch_r(KK_INIT, R_EDGES, 0, 0, nullptr, 0, true, s)) return rc;
         }
-        if (int rc = launch_r(KK_INIT, R_INIT, 0, 0, nullptr, 0, true, s)) return rc;
+        if (int rc = launch_rk(KK_INIT, 0, 0, nullptr, 0, true, s)) return rc;
         out = Scal();
         out.f = s[RS_F]; out.gtgt = s[RS_GTGT];
         return CGO_OK;
@@ -831,7 +820,7 @@ int HipBackend::init_eval(Scal &out) {
         return CGO_OK;
     }
     double s[NS];
-    if (int rc = launch(KK_INIT, M_INIT, 0, 0, 0, true, s)) return rc;
+    if (int rc = launch_k(KK_INIT, 0, 0, 0, true, s)) return rc;
     std::swap(g_, gt_);  // the gradient just written becomes the current one
     out = Scal();
     out.f = s[S_F];
@@ -851,8 +840,7 @@ int HipBackend::trial(const double *a, int k, Scal *out) {
     if (int rc = flush_lite()) return rc;
     spec_valid_ = false; spec_unmat_ = false;   // this launch writes g⁺ of ITS step: whatever the direction pass speculated on is no longer the last trial
     double s[NS];
-    const int mode = need_beta_ ? (M_TRIAL | M_BETA) : M_TRIAL;
-    if (int rc = launch(KK_TRIAL, mode, 0, 0, a[0], true, s)) return rc;
+    if (int rc = launch_k(KK_TRIAL, 0, 0, a[0], true, s)) return rc;
     unpack(s, out[0], true, false);
     return CGO_OK;
 }
@@ -874,8 +862,7 @@ int HipBackend::accept_dir_trial(double a_acc, double beta, const double *a, int
     }
     std::swap(g_, gt_);  // g ← g⁺ (optim.jl:139) without moving a byte
     if (obj_->two_phase()) return lse_stats(LM_ACCEPT | LM_DIR, a_acc, beta, a[0], out[0], true);
-    if (int rc = launch(KK_ACCEPT_DIR_TRIAL, M_ACCEPT | M_DIR | M_TRIAL | M_BETA, a_acc, beta, a[0], true, s))
-        return rc;
+    if (int rc = launch_k(KK_ACCEPT_DIR_TRIAL, a_acc, beta, a[0], true, s)) return rc;
     unpack(s, out[0], true, true);
     return CGO_OK;
 }
@@ -883,33 +870,33 @@ int HipBackend::accept_dir_trial(double a_acc, double beta, const double *a, int
 int HipBackend::accept_dir(double a_acc, double beta, Scal &out) {
     if (rmode_) {
         double s[NR7];
-        if (int rc = launch_r(KK_ACCEPT_DIR, R_ACCEPT | R_DIR, a_acc, beta, nullptr, 0, true, s)) return rc;
+        if (int rc = launch_rk(KK_ACCEPT_DIR, a_acc, beta, nullptr, 0, true, s)) return rc;
         out.gu = s[RS_PER_POINT]; out.uu = s[RS_PER_POINT + 1];
         return CGO_OK;
     }
     double s[NS];
     std::swap(g_, gt_);
-    if (int rc = launch(KK_ACCEPT_DIR, M_ACCEPT | M_DIR, a_acc, beta, 0, true, s)) return rc;
+    if (int rc = launch_k(KK_ACCEPT_DIR, a_acc, beta, 0, true, s)) return rc;
     unpack(s, out, false, true);
     return CGO_OK;
 }
 
 int HipBackend::accept_only(double a_acc) {
-    if (rmode_) return launch_r(KK_ACCEPT_ONLY, R_ACCEPT, a_acc, 0, nullptr, 0, false, nullptr);
+    if (rmode_) return launch_rk(KK_ACCEPT_ONLY, a_acc, 0, nullptr, 0, false, nullptr);
     std::swap(g_, gt_);
-    return launch(KK_ACCEPT_ONLY, M_ACCEPT, a_acc, 0, 0, false, nullptr);
+    return launch_k(KK_ACCEPT_ONLY, a_acc, 0, 0, false, nullptr);
 }
 
 int HipBackend::reset_dir(Scal &out) {
     if (int rc = flush_lite()) return rc;
     if (rmode_) {
         double s[NR7];
-        if (int rc = launch_r(KK_RESET_DIR, R_RESET, 0, 0, nullptr, 0, true, s)) return rc;
+        if (int rc = launch_rk(KK_RESET_DIR, 0, 0, nullptr, 0, true, s)) return rc;
         out.gu = s[RS_PER_POINT]; out.uu = s[RS_PER_POINT + 1];
         return CGO_OK;
     }
     double s[NS];
-    if (int rc = launch(KK_RESET_DIR, M_RESET, 0, 0, 0, true, s)) return rc;
+    if (int rc = launch_k(KK_RESET_DIR, 0, 0, 0, true, s)) return rc;
     unpack(s, out, false, true);
     return CGO_OK;
 }
@@ -917,12 +904,12 @@ int HipBackend::reset_dir(Scal &out) {
 int HipBackend::upg_sumsq(double &out) {
     if (rmode_) {
         double s[NR7];
-        if (int rc = launch_r(KK_UPG_NORM, R_UPG, 0, 0, nullptr, 0, true, s)) return rc;
+        if (int rc = launch_rk(KK_UPG_NORM, 0, 0, nullptr, 0, true, s)) return rc;
         out = s[RS_PER_POINT + 1];
         return CGO_OK;
     }
     double s[NS];
-    if (int rc = launch(KK_UPG_NORM, M_UPG, 0, 0, 0, true, s)) return rc;
+    if (int rc = launch_k(KK_UPG_NORM, 0, 0, 0, true, s)) return rc;
     out = s[S_UU];
     return CGO_OK;
 }
@@ -942,7 +929,7 @@ int HipBackend::sys_begin() {
 int HipBackend::sys_project(double a, double m, Scal &out) {
     double s[NR7];
     const double a1[1] = {a};
-    if (int rc = launch_r(KK_SYS_PROJECT, R_PROJ, 0.0, m, a1, 1, true, s)) return rc;
+    if (int rc = launch_rk(KK_SYS_PROJECT, 0.0, m, a1, 1, true, s)) return rc;
     unpack_r(s, 1, &out, false);
     return CGO_OK;
 }
@@ -956,7 +943,7 @@ int HipBackend::dir_trial(double beta, const double *a, int k, Scal *out) {
         out[0].gu = s[RS_PER_POINT]; out[0].uu = s[RS_PER_POINT + 1];
         return CGO_OK;
     }
-    if (int rc = launch_r(KK_DIR_TRIAL, R_DIR | R_TRIAL, 0.0, beta, a, k, true, s)) return rc;
+    if (int rc = launch_rk(KK_DIR_TRIAL, 0.0, beta, a, k, true, s)) return rc;
     unpack_r(s, k, out, true);
     return CGO_OK;
 }
@@ -1248,19 +1235,9 @@ int HipBackend::bench_kernel(HipCtx *ctx, HipObjective *obj, int kernel_kind, in
                              double *ms, double *bytes) {
     HIPCHK(hipSetDevice(ctx->device));
     if (n < 2 || reps < 1) { set_error("bench_kernel: n ≥ 2 and reps ≥ 1 required"); return CGO_EINVAL; }
-    int mode = 0;
-    switch (kernel_kind) {
-    case KK_INIT: mode = M_INIT; break;
-    case KK_TRIAL: mode = M_TRIAL | M_BETA; break;
-    case KK_ACCEPT_DIR_TRIAL: mode = M_ACCEPT | M_DIR | M_TRIAL | M_BETA; break;
-    case KK_ACCEPT_DIR: mode = M_ACCEPT | M_DIR; break;
-    case KK_ACCEPT_ONLY: mode = M_ACCEPT; break;
-    case KK_RESET_DIR: mode = M_RESET; break;
-    case KK_UPG_NORM: mode = M_UPG; break;
-    case 100: mode = M_DIR; break;       // the 24 B/elt updatedir!+dots kernel
-    case 101: mode = M_BETAONLY; break;  // the 24 B/elt getβ partial-sum kernel
-    default: set_error("bench_kernel: unknown kernel kind"); return CGO_EINVAL;
-    }
+    // the kind's k_fused mode (cgo_launch_kinds.hpp); 100: the 24 B/elt updatedir!+dots kernel, 101: the 24 B/elt getβ partial-sum kernel
+    const int mode = kernel_kind == 100 ? M_DIR : (kernel_kind == 101 ? M_BETAONLY : m_mode_of(kernel_kind));
+    if (mode < 0) { set_error("bench_kernel: unknown kernel kind"); return CGO_EINVAL; }
     const int okind = obj ? obj->kind : CGO_OBJ_ROSENBROCK_PAIRED;
     if (obj && obj->uses_param() && (obj->unset_slot() >= 0 || obj->n_local < n)) {
         set_error("bench_kernel: objective parameter vector missing or shorter than n");

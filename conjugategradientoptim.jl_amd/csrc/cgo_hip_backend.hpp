@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "cgo_engine.hpp"
+#include "cgo_launch_kinds.hpp"
 #include "cgo_rtc.hpp"
 
 namespace cgo {
@@ -102,6 +103,8 @@ struct HipObjective {
     template <class A> void param_args(A &P) const { P.p0 = p[0].p; P.p1 = p[1].p; P.p2 = p[2].p; P.p3 = p[3].p; }   // KParams, RParams, SpecParams, ResParams
     bool two_phase() const { return kind == CGO_OBJ_LSE; }
 };
+
+struct RPlan { bool big; int grid, npts; double bytes; };   // a k_cg / k_chain launch: streaming path, grid, points as launched, algorithmic bytes
 
 class HipBackend : public VecBackend {
   public:
@@ -252,6 +255,7 @@ class HipBackend : public VecBackend {
   private:
     int launch(int kk, int mode, double a_acc, double beta, double a_trial, bool fetch,
                double *sums /*[NS] global*/);
+    int launch_k(int kk, double a_acc, double beta, double a_trial, bool fetch, double *sums) { return launch(kk, fused_mode(kk), a_acc, beta, a_trial, fetch, sums); }
     HipCtx *ctx_;
     HipObjective *obj_;
     DevBuf x_, u_, ga_, gb_;
@@ -308,6 +312,12 @@ class HipBackend : public VecBackend {
     int64_t multi7_min_n_ = INT64_MAX;
     int64_t band3_lo_ = 0, band3_hi_ = 0;  // sizes inside [lo, hi) stay at three points
     int launch_r(int kk, int mode, double a_acc, double beta, const double *a, int k, bool fetch, double *sums);
+    int launch_rk(int kk, double a_acc, double beta, const double *a, int k, bool fetch, double *sums) { return launch_r(kk, r_mode_of(kk), a_acc, beta, a, k, fetch, sums); }
+    RPlan r_plan(int mode, int npts) const;   // asked by the launch itself, its byte accounting and kernel_symbol
+    bool adt_is_big() const;                  // is this solver's accept + direction + trial launch a pure-HBM one?
+    // the k_fused mode this solver's entry point of kind kk launches (−1: none): a trial whose β sums nobody reads takes the row without them
+    int fused_mode(int kk) const { const MKind *mk = m_kind(kk); return !mk ? -1 : ((kk == KK_TRIAL && !need_beta_) ? mk->alt : mk->mode); }
+    std::string lbfgs_symbol(int kk) const;   // kernel_symbol's half for the L-BFGS and log-sum-exp launches (cgo_backend_lbfgs.hip)
     // lazy direction: memory holds (x_{k+1}, u_k) while u_lag_ is set, and beta_lag_ = β_k rebuilds u_{k+1} from them
     bool lazy_on_ = false, u_lag_ = false;
     double beta_lag_ = 0.0, probe_beta_prev_ = 0.0;
@@ -322,7 +332,7 @@ class HipBackend : public VecBackend {
     int accept_dir_trial_r(double a_acc, double beta, const double *a, int k, double *s);
     int trial_r(const double *a, int k, double *s);
     int launch_r_kernel(int kk, int mode, double a_acc, double beta, const double *a, int k, int npts,
-                        const struct dev::CtlArgs *ctl, int *grid_out);
+                        const struct dev::CtlArgs *ctl, RPlan *plan_out);
     // on-device controller (cgo_ctl.hpp): rounds armed on the device ahead of the host
     int ctl_depth_ = 0;  // set by the C API per objective class / CGO_CTL_DEPTH
     unsigned long long epoch_ = 0;          // this solver's number on its context (device-mailbox block numbers carry it)

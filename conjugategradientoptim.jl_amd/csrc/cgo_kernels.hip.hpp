@@ -44,6 +44,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #endif
+#include "cgo_modes.hpp"   // M_*: the mode bits, and what a mode loads and stores
 
 namespace cgo {
 namespace dev {
@@ -57,11 +58,6 @@ constexpr int BLOCK = 256;      // 4 wavefronts of 64
 constexpr int GRID_SMALL = 1024;  // grid-stride path: 256 CUs × 4 workgroups
 constexpr int GRID_BIG = 4096;    // contiguous-chunk path
 constexpr int MAX_GRID = 4096;    // partial-row capacity
-
-enum Mode : int {
-    M_ACCEPT = 1, M_DIR = 2, M_TRIAL = 4, M_BETA = 8, M_INIT = 16, M_RESET = 32, M_UPG = 64,
-    M_BETAONLY = 128
-};
 
 struct KParams {
     double *x;          // current iterate (updated in place by M_ACCEPT)
@@ -347,14 +343,7 @@ static __global__ void k_publish(const double *src, int count, double *host_out,
 }
 
 // ---- the fused body ---------------------------------------------------------
-template <int MODE> struct Needs {
-    static constexpr bool x = (MODE & (M_ACCEPT | M_TRIAL | M_INIT)) != 0;
-    static constexpr bool u = (MODE & (M_ACCEPT | M_DIR | M_TRIAL | M_UPG | M_BETAONLY)) != 0;
-    static constexpr bool g = (MODE & (M_DIR | M_BETA | M_RESET | M_UPG | M_BETAONLY)) != 0;
-    static constexpr bool gt_in = (MODE & M_BETAONLY) != 0;
-    static constexpr bool p = (MODE & (M_TRIAL | M_INIT)) != 0;
-};
-
+// (which vectors a MODE loads: m_reads_x / _u / _g / _gt and m_evaluates, cgo_modes.hpp)
 template <class Obj> struct Lanes { d2 x, u, g, gt; PV<Obj> p; };
 
 template <bool NT> __device__ inline d2 ldg2(const double *base, long long i) {
@@ -392,11 +381,11 @@ template <class Obj, class A> __device__ inline PS<Obj> ps_load(const A &P, long
 
 template <class Obj, int MODE, bool NT>
 __device__ inline void load2(const KParams &P, long long i, Lanes<Obj> &v) {
-    if (Needs<MODE>::x) v.x = ldg2<NT>(P.x, i);
-    if (Needs<MODE>::u) v.u = ldg2<NT>(P.u, i);
-    if (Needs<MODE>::g) v.g = ldg2<NT>(P.g, i);
-    if (Needs<MODE>::gt_in) v.gt = ldg2<NT>(P.gt, i);
-    if (Needs<MODE>::p && obj_nparams<Obj>() > 0) v.p = pv_load<Obj, NT>(P, i);
+    if (m_reads_x(MODE)) v.x = ldg2<NT>(P.x, i);
+    if (m_reads_u(MODE)) v.u = ldg2<NT>(P.u, i);
+    if (m_reads_g(MODE)) v.g = ldg2<NT>(P.g, i);
+    if (m_reads_gt(MODE)) v.gt = ldg2<NT>(P.gt, i);
+    if (m_evaluates(MODE) && obj_nparams<Obj>() > 0) v.p = pv_load<Obj, NT>(P, i);
 }
 
 template <class Obj, int MODE, bool NT>
@@ -476,12 +465,12 @@ __device__ inline void body2(const KParams &P, long long i, Lanes<Obj> &v, doubl
 // odd tail element (never taken for pair-only objectives: host validates n even)
 template <class Obj, int MODE>
 __device__ inline void body1(const KParams &P, long long i, double (&acc)[NS]) {
-    double x = Needs<MODE>::x ? P.x[i] : 0.0;
-    double u = Needs<MODE>::u ? P.u[i] : 0.0;
-    const double g = Needs<MODE>::g ? P.g[i] : 0.0;
+    double x = m_reads_x(MODE) ? P.x[i] : 0.0;
+    double u = m_reads_u(MODE) ? P.u[i] : 0.0;
+    const double g = m_reads_g(MODE) ? P.g[i] : 0.0;
     PS<Obj> p;
     p.v[0] = 0.0;
-    if (Needs<MODE>::p && obj_nparams<Obj>() > 0) p = ps_load<Obj>(P, i);
+    if (m_evaluates(MODE) && obj_nparams<Obj>() > 0) p = ps_load<Obj>(P, i);
     if (MODE & M_ACCEPT) { x = x + P.a_acc * u; P.x[i] = x; }
     if (MODE & (M_DIR | M_RESET)) {
         const double un = (MODE & M_DIR) ? (-g + P.beta * u) : -g;

@@ -1,7 +1,8 @@
-// cgo_modes.hpp — what a launch of the gradient-free CG family (k_cg, k_cg_armed, k_chain) does, as a function of its mode: the
-// mode bits, and which vectors a mode reads, writes and sums.  Plain C++, constexpr only: the kernels (on their template argument),
-// the backend's launches and byte accounting, the run-time compiled module and the CPU tests all ask HERE.  (The row layout —
-// widths, slots, RW — stays with the kernels that fill the rows: cgo_kernels_cg.hip.hpp.)
+// cgo_modes.hpp — what a launch of the gradient-free CG family (k_cg, k_cg_armed, k_chain: R_*, r_*) and of the stored-gradient
+// family (k_fused: M_*, m_*) does, as a function of its mode: the mode bits, and which vectors a mode reads, writes and sums.
+// Plain C++, constexpr only: the kernels (on their template argument), the backend's launches and byte accounting, the run-time
+// compiled module and the CPU tests all ask HERE.  (The row layouts — widths, slots, RW, NS — stay with the kernels that fill the
+// rows: cgo_kernels_cg.hip.hpp, cgo_kernels.hip.hpp.)
 #pragma once
 
 namespace cgo {
@@ -59,6 +60,25 @@ constexpr int r_vectors(int mode, int p) {
     if (r_base(mode) == R_EDGES) return 0;
     return 1 + (r_reads_u(mode) ? 1 : 0) + (r_evaluates(mode) ? p : 0) + ((mode & R_PROJ) ? 2 : 0)
            + (r_writes_x(mode) ? 1 : 0) + (r_writes_u(mode) ? 1 : 0) + (r_writes_g(mode) ? 1 : 0);
+}
+
+// ---- the stored-gradient family (k_fused, cgo_kernels.hip.hpp; what each bit computes is told there) -----------------------------
+enum Mode : int { M_ACCEPT = 1, M_DIR = 2, M_TRIAL = 4, M_BETA = 8, M_INIT = 16, M_RESET = 32, M_UPG = 64, M_BETAONLY = 128 };
+// the facts about a mode, written for the CGO_FUSED_* rows of cgo_instances.def: what it loads …
+constexpr bool m_reads_x(int mode) { return (mode & (M_ACCEPT | M_TRIAL | M_INIT)) != 0; }
+constexpr bool m_reads_u(int mode) { return (mode & (M_ACCEPT | M_DIR | M_TRIAL | M_UPG | M_BETAONLY)) != 0; }
+constexpr bool m_reads_g(int mode) { return (mode & (M_DIR | M_BETA | M_RESET | M_UPG | M_BETAONLY)) != 0; }
+constexpr bool m_reads_gt(int mode) { return (mode & M_BETAONLY) != 0; }
+// … ∇f: streams the parameter vectors and takes an objective-specific instantiation (the other modes run as ObjQuadDiag's) …
+constexpr bool m_evaluates(int mode) { return (mode & (M_TRIAL | M_INIT)) != 0; }
+constexpr bool m_writes_x(int mode) { return (mode & M_ACCEPT) != 0; }   // … what it stores …
+constexpr bool m_writes_u(int mode) { return (mode & (M_DIR | M_RESET | M_INIT)) != 0; }
+constexpr bool m_writes_gt(int mode) { return m_evaluates(mode); }
+constexpr bool m_has_sums(int mode) { return mode != M_ACCEPT; }   // … a row of sums, unless the launch ends the solve …
+constexpr bool m_read_only(int mode) { return mode == M_UPG || mode == M_BETAONLY; }   // … the read-only streaming threshold applies
+constexpr int m_vectors(int mode, int p) {   // n-long double vectors the launch streams, for an objective of p parameter vectors
+    return (m_reads_x(mode) ? 1 : 0) + (m_reads_u(mode) ? 1 : 0) + (m_reads_g(mode) ? 1 : 0) + (m_reads_gt(mode) ? 1 : 0)
+           + (m_evaluates(mode) ? p : 0) + (m_writes_x(mode) ? 1 : 0) + (m_writes_u(mode) ? 1 : 0) + (m_writes_gt(mode) ? 1 : 0);
 }
 }  // namespace dev
 }  // namespace cgo

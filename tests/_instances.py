@@ -5,10 +5,11 @@ import os
 import re
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "conjugategradientoptim.jl_amd", "csrc")
-BITS = dict(M_ACCEPT=1, M_DIR=2, M_TRIAL=4, M_BETA=8, M_INIT=16, M_RESET=32, M_UPG=64, M_BETAONLY=128)
-# the R_* mode bits of the k_cg / k_chain family: as csrc/cgo_modes.hpp declares them (`R_NAME = number`)
-BITS.update((m.group(1), int(m.group(2))) for m in re.finditer(r"\b(R_[A-Z]+) = (\d+)\b", open(os.path.join(CSRC, "cgo_modes.hpp")).read()))
+# the mode bits of the k_cg / k_chain family (R_*) and of k_fused (M_*): as csrc/cgo_modes.hpp declares them (`NAME = number`)
+BITS = {m.group(1): int(m.group(2)) for m in re.finditer(r"\b([RM]_[A-Z]+) = (\d+)\b", open(os.path.join(CSRC, "cgo_modes.hpp")).read())}
 assert BITS["R_ACCEPT"] == 1 and BITS["R_EDGES"] == 512 and len([k for k in BITS if k.startswith("R_")]) == 18, BITS
+assert {k: v for k, v in BITS.items() if k.startswith("M_")} == dict(M_ACCEPT=1, M_DIR=2, M_TRIAL=4, M_BETA=8, M_INIT=16, M_RESET=32, M_UPG=64,
+                                                                     M_BETAONLY=128), BITS   # the run-time compiled module's names carry these numbers
 
 
 def _value(field):

@@ -15,6 +15,7 @@
 
 #include "../../conjugategradientoptim.jl_amd/csrc/cgo_engine.hpp"
 #include "../../conjugategradientoptim.jl_amd/csrc/cgo_modes.hpp"
+#include "../../conjugategradientoptim.jl_amd/csrc/cgo_launch_kinds.hpp"
 
 using namespace cgo;
 
@@ -758,6 +759,26 @@ void sim_launch_mode(int mode, int obj_kind, int n_params, int *out7) {
     out7[0] = d::r_vectors(mode, p);
     out7[1] = d::r_reads_u(mode); out7[2] = d::r_writes_x(mode); out7[3] = d::r_writes_u(mode); out7[4] = d::r_writes_g(mode);
     out7[5] = d::r_has_sums(mode); out7[6] = d::r_big_only(mode);
+}
+
+// The same for the stored-gradient family (k_fused): out11 = vectors (the p of bytes_for), reads x, u, g, g⁺, evaluates the
+// objective, writes x, u, g⁺, has sums, read-only.
+void sim_fused_mode(int mode, int obj_kind, int n_params, int *out11) {
+    namespace d = cgo::dev;
+    const int p = std::max(obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0, n_params);
+    out11[0] = d::m_vectors(mode, p);
+    out11[1] = d::m_reads_x(mode); out11[2] = d::m_reads_u(mode); out11[3] = d::m_reads_g(mode); out11[4] = d::m_reads_gt(mode);
+    out11[5] = d::m_evaluates(mode); out11[6] = d::m_writes_x(mode); out11[7] = d::m_writes_u(mode); out11[8] = d::m_writes_gt(mode);
+    out11[9] = d::m_has_sums(mode); out11[10] = d::m_read_only(mode);
+}
+
+// The rows of csrc/cgo_launch_kinds.hpp, five ints each (k_cg family: kind, mode, point rule, the two other modes a probe may ask
+// for; k_fused: kind, mode, the other mode, the host-closure mode, 0); returns the number of rows.
+int sim_launch_kinds(int fused, int *out, int cap_rows) {
+    int n = 0;
+    if (fused) { for (const MKind &r : M_KINDS) { if (n < cap_rows) { int *o = out + 5 * n; o[0] = r.kk; o[1] = r.mode; o[2] = r.alt; o[3] = r.host; o[4] = 0; } ++n; } }
+    else { for (const RKind &r : R_KINDS) { if (n < cap_rows) { int *o = out + 5 * n; o[0] = r.kk; o[1] = r.mode; o[2] = r.pts; o[3] = r.alt[0]; o[4] = r.alt[1]; } ++n; } }
+    return n;
 }
 
 }  // extern "C"
