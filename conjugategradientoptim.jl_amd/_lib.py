@@ -47,6 +47,13 @@ class ResultsC(C.Structure):
                 ("total_launches", C.c_int64)]
 
 
+class BatchResultsC(C.Structure):  # cgo_batch_results (include/cgo.h)
+    _fields_ = [("objective", dp), ("iters_ran", i64p), ("status", C.POINTER(C.c_int32)), ("total_fdf_evals", i64p),
+                ("minimizer", dp), ("gradient", dp), ("trace_objective", dp), ("trace_grad_norm", dp),
+                ("trace_step_size", dp), ("trace_objective_evals", i64p), ("launches", C.c_int64),
+                ("handed_back", C.c_int64)]
+
+
 class SolverPolicyC(C.Structure):  # cgo_solver_policy (include/cgo.h)
     _fields_ = [("size", C.c_int32), ("points", C.c_int32), ("resident", C.c_int32), ("controller_depth", C.c_int32),
                 ("controller_graph", C.c_int32), ("controller_fused", C.c_int32), ("stored_gradient", C.c_int32),
@@ -185,6 +192,10 @@ SIGNATURES = {
     "cgo_minimize_rerun": (C.c_int, [_vp, _vp, dp, C.POINTER(CGConfigC), C.POINTER(LSConfigC),
                                      C.POINTER(CGConfigC), C.POINTER(LSConfigC), C.c_int32,
                                      C.POINTER(ResultsC), C.POINTER(C.c_int32)]),
+    "cgo_minimize_batch": (C.c_int, [_vp, C.c_int32, C.c_int64, C.c_int64, dp, dp, C.POINTER(CGConfigC), C.POINTER(LSConfigC),
+                                     C.c_int64, C.POINTER(BatchResultsC)]),
+    "cgo_batch_max_n": (C.c_int64, [_vp, C.c_int32]),
+    "cgo_stop_status": (C.c_int32, [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, i64p]),
     "cgo_kernel_dir": (C.c_int, [_vp, dp, dp, C.c_double, C.c_int64, dp]),
     "cgo_kernel_beta_partials": (C.c_int, [_vp, dp, dp, dp, C.c_int64, dp]),
     "cgo_getbeta": (C.c_int, [_vp, C.POINTER(BetaConfig), dp, dp, dp, C.c_int64, dp]),

@@ -1071,6 +1071,71 @@ def minimizeobjective(fdf, x_initial: Sequence[float], config: CGConfig,
             own.close()
 
 
+class BatchResults(list):
+    """The `Results` of a batched solve, one per problem, plus the two counters of the call: `launches` (k_batch launches)
+    and `handed_back` (problems the host engine finished)."""
+    launches: int = 0
+    handed_back: int = 0
+
+
+def batch_max_n(kind: str, ctx: Optional[Context] = None) -> int:
+    """Largest n of one problem of a batched solve: what one workgroup's LDS holds of x, u and the parameter vector."""
+    ctx = ctx or default_context()
+    return int(_lib.lib().cgo_batch_max_n(ctx._h, OBJ_KINDS[kind]))
+
+
+def minimizeobjectivebatch(kind: str, X0, config: CGConfig, linesearch_config: LineSearchConfig, D=None,
+                           ctx: Optional[Context] = None, slice_iters: int = 0) -> BatchResults:
+    """`batch` independent minimizeobjective problems in ONE launch sequence, a workgroup each: X0 is [batch, n], `kind` one of
+    "quad_diag" (D: [batch, n], the rows of the diagonal), "rosenbrock_paired" (n even) or "booth" (n = 2); one config and one
+    line search for all.  Returns a list of `Results`, one per problem — what minimizeobjective returns for it — with the
+    counters `launches` and `handed_back` as attributes.  Problems whose next iteration the device loop does not run are
+    finished by the ordinary engine; anything the batched form does not cover raises CgoError (no loop of solves behind it).
+    slice_iters: outer iterations per problem and launch (0: the library's policy)."""
+    if kind not in OBJ_KINDS:
+        raise ValueError(f"unknown objective kind {kind!r}")
+    X0 = np.ascontiguousarray(np.asarray(X0, dtype=np.float64))
+    if X0.ndim != 2:
+        raise ValueError("X0 must be [batch, n]")
+    batch, n = X0.shape
+    Dc = None
+    if D is not None:
+        Dc = np.ascontiguousarray(np.asarray(D, dtype=np.float64))
+        if Dc.shape != X0.shape:
+            raise ValueError("D must have the shape of X0")
+    ctx = ctx or default_context()
+    trace = isinstance(config.trace_status, EnableTrace)
+    cap = max(config.max_iters, 1)
+    f = np.zeros(batch)
+    it = np.zeros(batch, dtype=np.int64)
+    st = np.zeros(batch, dtype=np.int32)
+    ev = np.zeros(batch, dtype=np.int64)
+    x, g = np.zeros((batch, n)), np.zeros((batch, n))
+    r = _lib.BatchResultsC()
+    r.objective, r.iters_ran = f.ctypes.data_as(dp), it.ctypes.data_as(i64p)
+    r.status, r.total_fdf_evals = st.ctypes.data_as(C.POINTER(C.c_int32)), ev.ctypes.data_as(i64p)
+    r.minimizer, r.gradient = x.ctypes.data_as(dp), g.ctypes.data_as(dp)
+    if trace:
+        to, tg, ts = np.zeros((batch, cap)), np.zeros((batch, cap)), np.zeros((batch, cap))
+        te = np.zeros((batch, cap), dtype=np.int64)
+        r.trace_objective, r.trace_grad_norm = to.ctypes.data_as(dp), tg.ctypes.data_as(dp)
+        r.trace_step_size, r.trace_objective_evals = ts.ctypes.data_as(dp), te.ctypes.data_as(i64p)
+    cfg, ls = config._c(), linesearch_config._c()
+    check(_lib.lib().cgo_minimize_batch(ctx._h, OBJ_KINDS[kind], n, batch, X0.ctypes.data_as(dp),
+                                        Dc.ctypes.data_as(dp) if Dc is not None else None, C.byref(cfg), C.byref(ls),
+                                        int(slice_iters), C.byref(r)))
+    out = BatchResults()
+    out.launches, out.handed_back = int(r.launches), int(r.handed_back)
+    empty, empty_i = np.zeros(0), np.zeros(0, dtype=np.int64)
+    for b in range(batch):
+        k = max(int(it[b]), 0) if trace else 0
+        tr = (TraceContainer(to[b, :k].copy(), tg[b, :k].copy(), ts[b, :k].copy(), te[b, :k].copy(), config.trace_status) if trace
+              else TraceContainer(empty.copy(), empty.copy(), empty.copy(), empty_i.copy(), config.trace_status))
+        out.append(Results(float(f[b]), x[b].copy(), g[b].copy(), int(it[b]), _lib.lib().cgo_status_name(int(st[b])).decode(), tr,
+                           int(ev[b]), int(r.launches)))
+    return out
+
+
 class UndefVarError(RuntimeError):
     """What the reference raises when solvesystem's line search finds no step (solve_system.jl:55 reads
     the loop variable `i` outside the loop)."""

@@ -953,6 +953,138 @@ int cgo_minimize_rerun(cgo_ctx *ctx, cgo_objective *obj, const double *x0, const
     API_GUARD_END
 }
 
+// ---- batched solves: many small problems in one launch, a workgroup each (k_batch) ----------------------------------------
+static bool batch_kind(int32_t k) { return k == CGO_OBJ_QUAD_DIAG || k == CGO_OBJ_ROSENBROCK_PAIRED || k == CGO_OBJ_BOOTH; }
+
+int64_t cgo_batch_max_n(cgo_ctx *ctx, int32_t obj_kind) {
+    if (!ctx || !batch_kind(obj_kind)) return 0;
+    const int64_t m = HipBackend::batch_max_n(&ctx->c, obj_kind);
+    return obj_kind == CGO_OBJ_BOOTH ? std::min<int64_t>(m, 2) : m;
+}
+
+int32_t cgo_stop_status(int64_t it, int64_t max_iters, double f_x, double grad_norm, double eps, double f_x0, int64_t *iters_ran) {
+    int64_t ran = 0;
+    const int st = stop_status(it, max_iters, f_x, grad_norm, eps, f_x0, ran);
+    if (iters_ran) *iters_ran = ran;
+    return st;
+}
+
+int cgo_minimize_batch(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
+                       const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out) {
+    API_GUARD_BEGIN
+    REQUIRE(ctx && x0 && cfg && ls && out, "null argument");
+    out->launches = 0; out->handed_back = 0;
+    REQUIRE(batch_kind(obj_kind), "batched solves: the objective must be CGO_OBJ_QUAD_DIAG, CGO_OBJ_ROSENBROCK_PAIRED or CGO_OBJ_BOOTH");
+    {
+        std::string why;
+        if (int rc = check_cg_config(cfg, why)) { set_error(why); return rc; }
+        if (int rc = check_ls_config(ls, why)) { set_error(why); return rc; }
+        if (int rc = check_batch_config(*cfg, *ls, why)) { set_error(why); return rc; }
+    }
+    REQUIRE(ctx->c.world() == 1, "batched solves: a multi-rank context is not supported (one rank only)");
+    REQUIRE(batch >= 1, "batched solves: batch must be ≥ 1");
+    REQUIRE(batch <= 0x7FFFFFFF, "batched solves: batch exceeds the largest grid");
+    REQUIRE(slice_iters >= 0, "batched solves: slice_iters must be ≥ 0 (0 = the library's policy)");
+    REQUIRE(n >= 1, "batched solves: n must be ≥ 1");
+    if (obj_kind == CGO_OBJ_ROSENBROCK_PAIRED) REQUIRE(n % 2 == 0, "batched solves: paired Rosenbrock needs an even n");
+    if (obj_kind == CGO_OBJ_BOOTH) REQUIRE(n == 2, "batched solves: Booth is 2-dimensional (n = 2)");
+    if (obj_kind == CGO_OBJ_QUAD_DIAG) REQUIRE(param0, "batched solves: the quadratic needs param0, the [batch*n] rows of D");
+    HIPCHK2(hipSetDevice(ctx->c.device));
+    {
+        const int64_t max_n = cgo_batch_max_n(ctx, obj_kind);
+        if (n > max_n) { set_error("batched solves: n = " + std::to_string(n) + " exceeds what one workgroup's LDS holds (cgo_batch_max_n = " + std::to_string(max_n) + ")"); return CGO_EINVAL; }
+    }
+    cgo_solver_policy pol;
+    { std::string pw; if (int rc = resolve_policy(ctx, nullptr, pol, pw)) { set_error(pw); return rc; } }
+    // the concatenated problems: ONE objective and backend whose x, u and parameter vector are the [batch][ld] rows
+    const int64_t ld = n + (n & 1);
+    HipObjective cat;
+    cat.ctx = &ctx->c; cat.kind = obj_kind; cat.n_global = cat.n_local = batch * ld; cat.offset = 0;
+    if (cat.uses_param()) { if (int rc = cat.p[0].alloc((size_t)(batch * ld))) return rc; }
+    HipBackend be(&ctx->c, &cat);
+    be.set_policy(pol);
+    be.set_rmode(true);
+    if (int rc = be.alloc()) return rc;
+    if (int rc = be.batch_begin(batch, n, x0, param0, cfg->max_iters, cfg->trace_enabled != 0)) return rc;
+    BatchRun run;
+    if (int rc = run_batch(&be, *cfg, *ls, batch, slice_iters, run)) { if (rc == CGO_ESTATE) set_error("internal: a batched launch left a problem in a state the driver does not know"); return rc; }
+    out->launches = run.launches;
+    // finished on the device: the status follows from the state (stop_status); minimizer and gradient of EVERY row from one
+    // download — the rows the host engine finishes below are overwritten with its own
+    if (int rc = be.batch_results(out->minimizer, out->gradient)) return rc;
+    const bool trace = cfg->trace_enabled != 0;
+    const int64_t mi = cfg->max_iters;
+    std::vector<ResRecord> recs;
+    const bool want_trace = trace && (out->trace_objective || out->trace_grad_norm || out->trace_step_size || out->trace_objective_evals);
+    if (want_trace) { if (int rc = be.batch_records(-1, 1, recs)) return rc; }
+    const int64_t stride = be.batch_rec_stride();
+    for (int64_t b = 0; b < batch; ++b) {
+        const ResState &s = run.st[(size_t)b];
+        if (s.reason != RES_STOP) continue;
+        int64_t ran = 0;
+        const int st = stop_status(s.it, mi, s.f_x, s.norm, cfg->eps, run.f_x0[(size_t)b], ran);
+        if (st == CGO_INCOMPLETE) { set_error("internal: a batched problem stopped on the device in a state that does not stop"); return CGO_ESTATE; }
+        if (out->objective) out->objective[b] = s.f_x;
+        if (out->iters_ran) out->iters_ran[b] = ran;
+        if (out->status) out->status[b] = st;
+        if (out->total_fdf_evals) out->total_fdf_evals[b] = 1 + run.evals[(size_t)b];
+        if (want_trace)
+            for (int64_t i = 0; i < s.it; ++i) {
+                const ResRecord &r = recs[(size_t)(b * stride + i)];
+                if (out->trace_objective) out->trace_objective[b * mi + i] = r.f;
+                if (out->trace_grad_norm) out->trace_grad_norm[b * mi + i] = r.norm;
+                if (out->trace_step_size) out->trace_step_size[b * mi + i] = r.a;
+                if (out->trace_objective_evals) out->trace_objective_evals[b * mi + i] = r.evals;
+            }
+    }
+    // handed back: the iteration at st.it + 1 is the host engine's — ONE ordinary solver (no resident slices), reused
+    cgo_objective *hobj = nullptr;
+    cgo_solver *hs = nullptr;
+    int rc = CGO_OK;
+    for (int64_t b = 0; b < batch && !rc; ++b) {
+        const ResState &s = run.st[(size_t)b];
+        if (s.reason != RES_HOST) continue;
+        if (!hs) {
+            if ((rc = cgo_objective_create(ctx, obj_kind, n, 0, n, &hobj))) break;
+            cgo_solver_policy hp;
+            cgo_solver_policy_init(&hp);
+            hp.resident = 0;
+            if ((rc = make_solver(ctx, hobj, cfg, ls, nullptr, &hp, &hs))) break;
+        }
+        if (s.it == 0) {   // nothing completed: the problem's own start, as a single solve has it
+            if ((rc = be.batch_export_row(b, *hs->be, false))) break;
+            if ((rc = hs->sv->start())) break;
+        } else {
+            if ((rc = be.batch_export_row(b, *hs->be, true))) break;
+            std::vector<ResRecord> prefix;
+            if ((rc = be.batch_records(b, s.it, prefix))) break;
+            hs->sv->resume(run.f_x0[(size_t)b], run.evals[(size_t)b], s, prefix.data());
+        }
+        bool fin = false;
+        while (!rc && !fin) rc = hs->sv->iterate(INT64_MAX / 2, fin);
+        if (rc) break;
+        cgo_results r{};
+        r.minimizer = out->minimizer ? out->minimizer + b * n : nullptr;
+        r.gradient = out->gradient ? out->gradient + b * n : nullptr;
+        r.trace_objective = out->trace_objective ? out->trace_objective + b * mi : nullptr;
+        r.trace_grad_norm = out->trace_grad_norm ? out->trace_grad_norm + b * mi : nullptr;
+        r.trace_step_size = out->trace_step_size ? out->trace_step_size + b * mi : nullptr;
+        r.trace_objective_evals = out->trace_objective_evals ? out->trace_objective_evals + b * mi : nullptr;
+        if ((rc = cgo_solver_results(hs, &r))) break;
+        if (out->objective) out->objective[b] = r.objective;
+        if (out->iters_ran) out->iters_ran[b] = r.iters_ran;
+        if (out->status) out->status[b] = r.status;
+        if (out->total_fdf_evals) out->total_fdf_evals[b] = r.total_fdf_evals;
+        out->handed_back++;
+    }
+    std::string keep = get_error();
+    if (hs) cgo_solver_destroy(hs);
+    if (hobj) cgo_objective_destroy(hobj);
+    if (rc) set_error(keep);
+    return rc;
+    API_GUARD_END
+}
+
 // ---- kernel-level entry points --------------------------------------------------
 int cgo_kernel_dir(cgo_ctx *ctx, double *u, const double *g, double beta, int64_t n, double *out2) {
     API_GUARD_BEGIN

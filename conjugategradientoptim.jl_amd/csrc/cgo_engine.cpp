@@ -393,17 +393,24 @@ int Solver::run_resident(int64_t cap, int64_t &done, int &reason) {
     for (int j = 0; j < s.ncache; ++j) { s.ca[j] = cache_[j].a; s.cs[j] = trial_sums(cache_[j].s); }
     if (int rc = be_->resident_run(c, s, cap, res_recs_, res_log_)) return rc;
     done = s.done; reason = s.reason;
-    if (s.done > 0) {
+    if (s.done > 0) adopt(s, res_recs_.data(), res_log_.data());
+    return CGO_OK;
+}
+
+// The s.done iterations a device loop completed (k_resident's slice, k_batch's launches) become this engine's: loop state, the
+// trace records, the trial log, and the trial sums waiting in the cache.
+void Solver::adopt(const ResState &s, const ResRecord *recs, const ResLog *log) {
+    {
         f_x_ = s.f_x; gg_ = s.gg; norm_df_x_ = s.norm; dphi0_ = s.dphi0; uu_ = s.uu; a_initial_ = s.a_initial;
         it_ = s.it; dir_is_neg_grad_ = s.dir_neg != 0;
         last_eval_a_ = s.last_a;
         total_evals_ += s.evals;
         if (cfg_.trace_enabled)
             for (int64_t i = 0; i < s.done; ++i) {
-                const ResRecord &r = res_recs_[(size_t)i];
+                const ResRecord &r = recs[(size_t)i];
                 tr_f_.push_back(r.f); tr_g_.push_back(r.norm); tr_a_.push_back(r.a); tr_e_.push_back(r.evals);
             }
-        if (log_on_) for (int64_t i = 0; i < s.log_len; ++i) log_.push_back({res_log_[(size_t)i].a, res_log_[(size_t)i].phi, res_log_[(size_t)i].dphi});
+        if (log_on_) for (int64_t i = 0; i < s.log_len; ++i) log_.push_back({log[(size_t)i].a, log[(size_t)i].phi, log[(size_t)i].dphi});
         // the trial sums of the pass that accepted the last step wait in the cache, for this engine or the next slice
         ncache_ = s.ncache;
         for (int j = 0; j < s.ncache; ++j) {
@@ -413,7 +420,22 @@ int Solver::run_resident(int64_t cap, int64_t &done, int &reason) {
             cache_[j] = {s.ca[j], q};
         }
     }
-    return CGO_OK;
+}
+
+// A solve whose start (optim.jl:25-47) and first s.it > 0 iterations ran in a batched launch continues here: the engine as
+// start() leaves it — minus the initial evaluation, which the device did — then the completed iterations.  The backend already
+// holds the problem's x and u.  `evals`: evalϕdϕ! calls of those iterations; recs: their records (read when the trace is on).
+void Solver::resume(double f_x0, int64_t evals, const ResState &s, const ResRecord *recs) {
+    total_evals_ = 1;
+    f_x0_ = f_x0;
+    iters_ran_ = 0; status_ = CGO_INCOMPLETE;
+    ncache_ = 0; finished_ = false; started_ = true;
+    qn_trial_done_ = false;
+    res_fail_streak_ = 0; res_backoff_ = 0;
+    tr_f_.clear(); tr_g_.clear(); tr_a_.clear(); tr_e_.clear(); log_.clear();
+    ResState t = s;
+    t.done = s.it; t.evals = evals; t.log_len = 0;
+    adopt(t, recs, nullptr);
 }
 
 // optim.jl:50-160
@@ -425,10 +447,10 @@ int Solver::iterate(int64_t iters, bool &finished) {
     bool host_next = false;
     for (int64_t budget = iters; budget > 0 && !finished_; --budget) {
         const int64_t n = it_ + 1;
-        if (n > cfg_.max_iters) { finish(cfg_.max_iters, CGO_MAX_ITERS_REACHED); break; }  // optim.jl:162-169
-        if (std::isfinite(f_x_) && std::isfinite(norm_df_x_) && norm_df_x_ < cfg_.eps) {    // optim.jl:53-80
-            finish(n - 1, f_x_ <= f_x0_ ? CGO_SUCCESS : CGO_INCREASING_OBJECTIVE);
-            break;
+        {   // optim.jl:162-169, 53-80 (stop_status, cgo_resident.hpp: the rule batched solves apply to a state the device finished)
+            int64_t ran = 0;
+            const int st = stop_status(it_, cfg_.max_iters, f_x_, norm_df_x_, cfg_.eps, f_x0_, ran);
+            if (st != CGO_INCOMPLETE) { finish(ran, st); break; }
         }
         if (resident && !host_next && res_backoff_ == 0 && be_->resident_ready(cfg_, ls_)) {   // (re-asked: a backend can take itself off the resident path)   // as many whole iterations as the slice allows in ONE launch; what it cannot do comes back here
             int64_t done = 0;
@@ -590,6 +612,41 @@ int Solver::iterate(int64_t iters, bool &finished) {
         }
     }
     finished = finished_;
+    return CGO_OK;
+}
+
+// ---- batched solves -----------------------------------------------------------------------------------------------------
+// What res_iterate does not run has no batched form: there is no loop of single solves behind this entry point.
+int check_batch_config(const cgo_cg_config &cfg, const cgo_ls_config &ls, std::string &why) {
+    if (cfg.beta.kind == CGO_BETA_LBFGS) { why = "batched solves: β = L-BFGS is not supported (CG flavours only)"; return CGO_EINVAL; }
+    if (cfg.beta.kind == CGO_BETA_BROYDEN_FAMILY) { why = "batched solves: β = Broyden family is not supported (CG flavours only)"; return CGO_EINVAL; }
+    if (ls.kind == CGO_LS_BACKTRACKING) { why = "batched solves: the Backtracking line search is not supported (StrongWolfeBisection or WolfeBisection)"; return CGO_EINVAL; }
+    return CGO_OK;
+}
+
+int run_batch(VecBackend *be, const cgo_cg_config &cfg, const cgo_ls_config &ls, int64_t batch, int64_t slice_iters, BatchRun &out) {
+    ResConfig c{};
+    c.ls = ls; c.eps = cfg.eps; c.mu = cfg.beta.mu; c.beta_kind = cfg.beta.kind;
+    c.npts = 3; c.max_iters = cfg.max_iters; c.log_on = 0;
+    const int64_t budget = slice_iters > 0 ? slice_iters : 64;
+    out.evals.assign((size_t)batch, 0);
+    out.launches = 0;
+    std::vector<char> live((size_t)batch, 1);
+    for (;;) {
+        if (int rc = be->batch_launch(c, budget, out.st, out.f_x0)) return rc;
+        out.launches++;
+        if ((int64_t)out.st.size() != batch || (int64_t)out.f_x0.size() != batch) return CGO_ESTATE;
+        bool any = false;
+        for (int64_t b = 0; b < batch; ++b) {
+            if (!live[(size_t)b]) continue;   // (a finished problem's workgroup returned at once: its state is as it was)
+            const ResState &s = out.st[(size_t)b];
+            out.evals[(size_t)b] += s.evals;
+            if (s.reason == RES_STOP || s.reason == RES_HOST) live[(size_t)b] = 0;
+            else if (s.reason == RES_BUDGET && s.done > 0) any = true;   // (a slice that ends on its budget has completed it)
+            else return CGO_ESTATE;
+        }
+        if (!any) break;
+    }
     return CGO_OK;
 }
 

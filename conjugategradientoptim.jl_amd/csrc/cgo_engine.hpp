@@ -115,6 +115,11 @@ struct VecBackend {
     // shard).  resident_run advances `s` by up to `budget` iterations and returns their records (and trial log).
     virtual bool resident_ready(const cgo_cg_config &, const cgo_ls_config &) const { return false; }
     virtual int resident_run(const ResConfig &, ResState &, int64_t /*budget*/, std::vector<ResRecord> &, std::vector<ResLog> &) { return CGO_EINVAL; }
+    // Batched solves (run_batch below; k_batch, cgo_kernels_batch.hip.hpp): this backend holds [batch] independent problems,
+    // one row of x, u and the parameter vector each.  ONE launch advances every unfinished problem by up to `budget` outer
+    // iterations — a problem that has not started gets its initial evaluation first — then st[b] is problem b's loop state
+    // (reason: RES_BUDGET, RES_STOP or RES_HOST; evals, done: of this launch) and f_x0[b] its f(x_initial).
+    virtual int batch_launch(const ResConfig &, int64_t /*budget*/, std::vector<ResState> & /*st*/, std::vector<double> & /*f_x0*/) { return CGO_EINVAL; }
     // solvesystem (solve_system.jl:64-253).  The second iterate buffer `x_next` (:82) lives in the backend.
     virtual bool sys_supported() const { return false; }
     virtual int sys_begin() { return CGO_EINVAL; }                      // x_next ← x
@@ -228,8 +233,12 @@ class Solver {
     const cgo_cg_config &config() const { return cfg_; }
     const cgo_ls_config &linesearch() const { return ls_; }
     bool is_sys() const { return sys_; }
+    // A solve a batched launch started and advanced by s.it > 0 iterations continues on this engine (its backend holds the
+    // problem's x and u): in place of start().  evals: evalϕdϕ! calls of those iterations; recs: their s.it records.
+    void resume(double f_x0, int64_t evals, const ResState &s, const ResRecord *recs);
 
   private:
+    void adopt(const ResState &s, const ResRecord *recs, const ResLog *log);   // s.done iterations a device loop completed → this engine
     // evalϕdϕ! (cg_utils.jl:4-23).  h1/h2: the (at most two) steps the line search can ask for
     // next, whatever this trial's outcome — evaluated speculatively in the same launch.
     // h3/h4: likelier grandchildren, used by 5-point launches; evaln: any number of hints (solvesystem).
@@ -289,5 +298,18 @@ class Solver {
     std::vector<TrialRecord> log_;
     bool log_on_ = false;
 };
+
+// Batched solves: `batch` independent problems under ONE cfg and ls, a workgroup each (VecBackend::batch_launch), launched until
+// every problem's reason is RES_STOP — finished on the device: stop_status() of its state is its result — or RES_HOST: the
+// iteration at st.it + 1 is the host engine's, which the caller runs one problem at a time (Solver::start for st.it == 0,
+// Solver::resume otherwise).  slice_iters: outer iterations per problem and launch (0: the library's 64).
+struct BatchRun {
+    std::vector<ResState> st;       // [batch] final states
+    std::vector<double> f_x0;       // [batch]
+    std::vector<int64_t> evals;     // [batch] evalϕdϕ! calls of the iterations completed on the device
+    int64_t launches = 0;
+};
+int check_batch_config(const cgo_cg_config &cfg, const cgo_ls_config &ls, std::string &why);
+int run_batch(VecBackend *be, const cgo_cg_config &cfg, const cgo_ls_config &ls, int64_t batch, int64_t slice_iters, BatchRun &out);
 
 }  // namespace cgo

@@ -593,6 +593,9 @@ HipBackend::~HipBackend() {
     if (res_pr_script_) (void)hipFree(res_pr_script_);
     if (res_pr_out_) (void)hipFree(res_pr_out_);
     if (res_pr_rows_) (void)hipFree(res_pr_rows_);
+    if (bat_st_) (void)hipFree(bat_st_);
+    if (bat_recs_) (void)hipFree(bat_recs_);
+    if (bat_fx0_) (void)hipFree(bat_fx0_);
     for (auto &r : ring_) { if (r.e0) (void)hipEventDestroy(r.e0); if (r.e1) (void)hipEventDestroy(r.e1); }
 }
 

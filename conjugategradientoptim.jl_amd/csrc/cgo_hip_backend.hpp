@@ -156,6 +156,16 @@ class HipBackend : public VecBackend {
     int64_t resident_iters() const { return res_iters_; }
     int64_t resident_slices() const { return res_slices_; }
     int64_t resident_gave_up() const { return res_gave_up_; }
+    // Batched solves (cgo_backend_batch.hip; k_batch, cgo_kernels_batch.hip.hpp).  The backend's objective spans the
+    // CONCATENATED problems — n_local = batch · ld, ld = n + (n & 1) — so that x, u and the parameter vector are the
+    // [batch][ld] rows and the ordinary gradient launch (download) serves every problem at once.
+    static int64_t batch_max_n(HipCtx *ctx, int obj_kind);    // largest n one workgroup's LDS holds (res_plan's arithmetic); 0: no kernel
+    int batch_begin(int64_t batch, int64_t n, const double *x0, const double *param0, int64_t max_iters, bool trace);
+    int batch_launch(const ResConfig &c, int64_t budget, std::vector<ResState> &st, std::vector<double> &f_x0) override;
+    int batch_records(int64_t b, int64_t count, std::vector<ResRecord> &out);     // the trace records of problem b's first `count` iterations (b < 0: every row)
+    int64_t batch_rec_stride() const { return bat_rec_stride_; }
+    int batch_export_row(int64_t b, HipBackend &dst, bool with_u);                // row b of x (u), and of the parameter vector → dst
+    int batch_results(double *x /*[batch·n]*/, double *g /*[batch·n]*/);          // dense rows; each may be nullptr
     int64_t push_count(int kind) const { return push_counts_[kind]; }   // 0 speculated, 1 fused (g⁺ formed in the push), 2 plain
     bool sys_supported() const override { return rmode_; }
     int sys_begin() override;
@@ -392,6 +402,13 @@ class HipBackend : public VecBackend {
     double *res_pr_rows_ = nullptr;
     bool res_pr_ready_ = false;
     int64_t res_iters_ = 0, res_slices_ = 0, res_gave_up_ = 0;
+    // batched solves
+    int64_t bat_count_ = 0, bat_n_ = 0, bat_ld_ = 0, bat_rec_stride_ = 0;
+    bool bat_trace_ = false;
+    size_t bat_lds_ = 0;
+    ResState *bat_st_ = nullptr;             // device [batch]
+    ResRecord *bat_recs_ = nullptr;          // device [batch][bat_rec_stride_]
+    double *bat_fx0_ = nullptr;              // device [batch]
     bool prof_on_ = false;
     struct ProfSlot { hipEvent_t e0 = nullptr, e1 = nullptr; int kk = -1; double bytes = 0; };
     std::vector<ProfSlot> ring_;

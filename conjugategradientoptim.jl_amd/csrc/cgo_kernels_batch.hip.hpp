@@ -1,0 +1,119 @@
+// cgo_kernels_batch.hip.hpp — k_batch: MANY small problems in one launch, a workgroup each, finished on the device.
+//
+// One small problem (BASELINE config 1: n = 1000) is latency-bound on the resident solver: one workgroup on one CU, the other
+// 255 idle.  A user with n ≈ 1e3 has many of them — a parameter sweep, multi-start, one fit per pixel — and
+// here blockIdx.x says WHICH PROBLEM, not which chunk:
+//
+//   * workgroup b loads row b of x, u and the parameter vector ([batch][ld], ld = n + (n & 1)) into LDS and its own ResState
+//     from st[b]; a problem that is already finished (RES_STOP, RES_HOST) costs its workgroup one load and a return;
+//   * a problem that has not started (RES_FRESH) gets optim.jl:25-47 here: pass<R_INIT, 1> → u = −g, f_x, g·g;
+//   * then res_iterate (cgo_resident.hpp) — the loop k_resident runs — over ResDev in its SOLO form: the passes, trial and
+//     accept_dir_trial are ResDev's own (cgo_kernels_resident.hip.hpp), the workgroup's row is the total, its lane 0 the leader;
+//   * when the slice ends: x, u back in place if an iteration completed, the state to st[b], the records of the completed
+//     iterations (written by the leader as they completed) in recs[b].
+//
+// Workgroups never wait for one another: no atomics, no polling, no read of another problem's rows.  More workgroups than CUs
+// simply queue.  A launch is bounded by `budget` outer iterations per problem, each by the line search's own limits.
+#pragma once
+
+#include "cgo_kernels_resident.hip.hpp"
+
+namespace cgo {
+namespace dev {
+
+struct BatchParams {
+    double *x; double *u; const double *p0;   // [batch][ld]; the padding element of an odd n is never read by a pass
+    ResState *st;                             // [batch]
+    ResRecord *recs;                          // [batch][rec_stride]
+    double *f_x0;                             // [batch]: f(x_initial), written with the initial evaluation (optim.jl:31)
+    long long n, ld, rec_stride;
+    int rec_abs;                              // 1: record of iteration it lives at [it − 1] (the trace); 0: at [its number in this slice]
+    double s0;
+    ResConfig cfg;
+    long long budget;
+};
+
+template <class Obj, int NPTS>
+__global__ __launch_bounds__(BLOCK, 1) void k_batch(const BatchParams B) {
+    extern __shared__ __attribute__((aligned(16))) double res_lds[];
+    __shared__ double tot[RES_WMAX];
+    __shared__ double fs[BLOCK];
+    __shared__ ResState s_out;
+    const int tid = threadIdx.x;
+    const long long b = blockIdx.x, lo = b * B.ld;
+    ResState s = B.st[b];
+    if (s.reason == RES_STOP || s.reason == RES_HOST) return;   // finished, on the device or for the host (the whole workgroup alike)
+    double *xs = res_lds, *us = res_lds + B.ld, *ps = res_lds + 2 * B.ld;
+    // (both row loops below have a UNIFORM trip count and a per-lane guard inside: a loop that lanes leave one by one ends with
+    //  no lane active, and a per-lane value the register allocator parks right there — the row offset, kept for the write-back —
+    //  is then never parked at all)
+    for (long long i0 = 0; i0 < B.ld; i0 += BLOCK) {
+        const long long i = i0 + tid;
+        if (i < B.ld) {
+            xs[i] = B.x[lo + i];
+            us[i] = B.u[lo + i];
+            if constexpr (obj_nparams<Obj>() > 0) ps[i] = B.p0[lo + i];
+        }
+    }
+    __syncthreads();
+    ResParams Q{};   // what ResDev reads of it in its SOLO form: the stride of the parameter slots, the objective's scalar, no clocks
+    Q.n = B.n; Q.chunk = B.ld; Q.s0 = B.s0; Q.timing = 0;
+    ResDev<Obj, NPTS, false, true> v{Q, xs, us, ps, (int)(B.n >> 1), (B.n & 1) != 0, 0ull, tot, fs, 0, 0, 0};
+    ResConfig cfg = B.cfg;
+    // (as k_resident: the loop state is FP64 arithmetic throughout — into VGPRs once, opaquely; see the note there)
+#define RES_V(x) asm volatile("" : "+v"(x))
+    RES_V(s.f_x); RES_V(s.gg); RES_V(s.norm); RES_V(s.dphi0); RES_V(s.uu); RES_V(s.a_initial); RES_V(s.last_a); RES_V(s.last_beta);
+#pragma unroll
+    for (int j = 0; j < RES_MAXP; ++j) {
+        RES_V(s.ca[j]); RES_V(s.cs[j].f); RES_V(s.cs[j].gtu); RES_V(s.cs[j].gtgt); RES_V(s.cs[j].gtg); RES_V(s.cs[j].yy); RES_V(s.cs[j].uy); RES_V(s.cs[j].ygt);
+    }
+    RES_V(cfg.ls.c1); RES_V(cfg.ls.c2); RES_V(cfg.ls.a_max_growth_factor); RES_V(cfg.ls.delta1); RES_V(cfg.ls.max_step_size);
+    RES_V(cfg.ls.discount_factor); RES_V(cfg.eps); RES_V(cfg.mu);
+#undef RES_V
+    bool go = true;
+    if (s.reason == RES_FRESH) {   // optim.jl:25-47: f_x = fdf!(df_x, x); u = −df_x
+        double sums[RW<1>::W];
+        v.template pass<R_INIT, 1>(0.0, 0.0, nullptr, 0, sums);
+        s.f_x = sums[RS_F]; s.gg = sums[RS_GTGT];
+        s.dphi0 = -s.gg; s.uu = s.gg; s.dir_neg = 1;
+        s.it = 0; s.ncache = 0;
+        s.done = 0; s.log_len = 0; s.evals = 0; s.passes = 1;
+        if (v.leader()) B.f_x0[b] = s.f_x;
+        // LinearAlgebra.norm: sqrt(Σg²) in range; 0 when g IS the zero vector (u = −g lies in LDS: every element ±0 — a sum of
+        // exactly 0 alone could be the underflow of tiny squares); everything else is the rare path, the host's from iteration 0
+        int nz = 0;
+        if (s.gg == 0.0) {
+            for (long long i0 = 0; i0 < B.n; i0 += BLOCK) {
+                const long long i = i0 + tid;
+                if (i < B.n) nz |= (us[i] != 0.0);
+            }
+        }
+        nz = __syncthreads_or(nz);
+        if (sumsq_in_range(s.gg)) s.norm = __builtin_sqrt(s.gg);
+        else if (s.gg == 0.0 && nz == 0) s.norm = 0.0;
+        else { s.reason = RES_HOST; go = false; }
+    }
+    if (go) {
+        ResRecord *recs = B.recs + b * B.rec_stride + (B.rec_abs ? s.it : 0);
+        res_iterate(cfg, s, v, (int64_t)B.budget, recs, nullptr, 0);
+    }
+    s.t_total = 0; s.t_compute = 0; s.t_reduce = 0; s.t_exchange = 0; s.t_cycles = 0;
+    __syncthreads();
+    if (s.done > 0) {   // x, u of the last completed iteration (an iteration handed back never touched them)
+        for (long long i0 = 0; i0 < B.n; i0 += BLOCK) {
+            const long long i = i0 + tid;
+            if (i < B.n) {
+                B.x[lo + i] = xs[i];
+                B.u[lo + i] = us[i];
+            }
+        }
+    }
+    constexpr int WS = sizeof(ResState) / 8;
+    static_assert(sizeof(ResState) % 8 == 0 && WS <= BLOCK, "the state goes out as 8-byte words, one lane each");
+    if (tid == 0) s_out = s;
+    __syncthreads();
+    if (tid < WS) reinterpret_cast<unsigned long long *>(B.st + b)[tid] = reinterpret_cast<const unsigned long long *>(&s_out)[tid];
+}
+
+}  // namespace dev
+}  // namespace cgo

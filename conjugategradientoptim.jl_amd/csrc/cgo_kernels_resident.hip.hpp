@@ -74,7 +74,9 @@ struct ResParams {
     const double *p1, *p2, *p3;               // parameter slots 1–3 (run-time compiled objectives with kParams > 1 only)
 };
 
-template <class Obj, int NPTS, bool PROBE = false>
+// SOLO (k_batch, cgo_kernels_batch.hip.hpp): the workgroup IS the whole problem whatever the grid — blockIdx.x names a problem, not a
+// chunk — so its own row is the total (the G == 1 branch of the exchange, no polling) and its lane 0 is the leader.
+template <class Obj, int NPTS, bool PROBE = false, bool SOLO = false>
 struct ResDev {
     const ResParams &P;
     double *xs, *us, *ps;      // LDS (ps: one chunk per parameter slot, P.chunk apart)
@@ -86,7 +88,7 @@ struct ResDev {
     int pr_pass = 0;           // PROBE: passes completed
 
     static constexpr int kNpts = NPTS;
-    __device__ __forceinline__ bool leader() const { return blockIdx.x == 0 && threadIdx.x == 0; }
+    __device__ __forceinline__ bool leader() const { return (SOLO || blockIdx.x == 0) && threadIdx.x == 0; }
     // (a clock read is an s_memrealtime round trip of ≈ 0.2 µs: with ≈ 30 of them per outer iteration the instrumentation
     //  itself cost a third of a small slice — only with CGO_RES_TIMING=1)
     __device__ __forceinline__ long long clock() const { return P.timing ? wall_clock64() : 0; }
@@ -132,7 +134,7 @@ struct ResDev {
     template <int W>
     __device__ __forceinline__ int exchange(double own) {
         static_assert(BLOCK / W >= 4, "poll_rows keeps at most four rows per lane");
-        const int G = gridDim.x, tid = threadIdx.x;
+        const int G = SOLO ? 1 : (int)gridDim.x, tid = threadIdx.x;
         if (G == 1) {
             if (tid < W) tot[tid] = own;
             __syncthreads();
@@ -245,6 +247,43 @@ struct ResDev {
     }
 
     static __device__ TrialSums ts(const double *q) { return TrialSums{q[0], q[1], q[2], q[3], q[4], q[5], q[6]}; }
+
+    // res_iterate asks this when Σg⁺² of the accepted trial is exactly 0 (res_trial_gradient_is_zero, cgo_resident.hpp) — SOLO only:
+    // is ∇f(x + a·u) the zero vector, element by element?  Then its norm IS 0 and the iteration stays on the device; if the sum
+    // is the underflow of tiny squares it is the host's scaled norm, as before.  The gradient is the R_GRADT body's, the one the
+    // host's rare path launches for the same question (scaled_norm_parts); nothing is written.  (Uniform trip count: k_batch's note.)
+    static constexpr bool kZeroCheck = SOLO;
+    __device__ __forceinline__ bool trial_gradient_is_zero(double a) {
+        const int tid = threadIdx.x;
+        RParams rp;
+        rp.a_acc = 0.0; rp.beta = 0.0; rp.s0 = P.s0; rp.n = 0;
+#pragma unroll
+        for (int j = 0; j < MAXP; ++j) rp.a[j] = (j == 0) ? a : 0.0;
+        const d2 *x2 = reinterpret_cast<const d2 *>(xs), *u2 = reinterpret_cast<const d2 *>(us);
+        const ParamPtrs pl{ps, ps + P.chunk, ps + 2 * P.chunk, ps + 3 * P.chunk};
+        int nz = 0;
+        for (int i0 = 0; i0 < npairs; i0 += BLOCK) {
+            const int i = i0 + tid;
+            if (i < npairs) {
+                d2 xa = x2[i], ua = u2[i];
+                const PV<Obj> pa = pv_load<Obj, false>(pl, i);
+                double acc[RW<1>::W] = {};
+                bool wx = false, wu = false;
+                d2 g = d2{0.0, 0.0};
+                cg_pair<Obj, R_GRADT, 1>(rp, xa, ua, pa, acc, wx, wu, g);
+                nz |= (g.x != 0.0) | (g.y != 0.0);   // (a NaN counts as nonzero)
+            }
+        }
+        if (odd && tid == 0) {   // the odd tail element, as cg_single's R_GRADT line forms it
+            rp.x = xs; rp.u = us; rp.p0 = pl.p0; rp.p1 = pl.p1; rp.p2 = pl.p2; rp.p3 = pl.p3; rp.xo = xs; rp.uo = us; rp.gout = nullptr; rp.x2 = nullptr;
+            const long long i = 2LL * npairs;
+            const PS<Obj> p = ps_load<Obj>(rp, i);
+            double fd = 0.0, gg = 0.0;
+            obj_eval1<Obj>(xs[i] + a * us[i], p, P.s0, fd, gg);
+            nz |= (gg != 0.0);
+        }
+        return __syncthreads_or(nz) == 0;
+    }
 
     __device__ __forceinline__ int trial(const double *a, int k, TrialSums *out) {
         constexpr int NT = NPTS < 3 ? NPTS : 3;

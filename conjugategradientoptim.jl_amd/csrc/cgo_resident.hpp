@@ -44,8 +44,18 @@ enum ResReason : int32_t {
     RES_STOP = 1,      // the stop test at the top of an iteration fired (optim.jl:53-80,162-169): the host finishes
     RES_HOST = 2,      // the iteration at s.it + 1 needs the host; x, u are those of iteration s.it
     RES_LOG_FULL = 3,  // the trial log must be drained first
-    RES_ERROR = 4      // the exchange between workgroups gave up (state unusable)
+    RES_ERROR = 4,     // the exchange between workgroups gave up (state unusable)
+    RES_FRESH = 5      // batched solves only (k_batch): the problem has not had its initial evaluation yet (optim.jl:25-47)
 };
+
+// The stop test at the top of iteration it + 1 (optim.jl:53-80,162-169) as a function of the loop state: the terminal status
+// and Results.iters_ran, or CGO_INCOMPLETE when the iteration runs.  ONE statement of the rule for the host engine
+// (Solver::iterate) and for the problems a batched solve finishes on the device (RES_STOP is exactly "this test fired").
+CGO_HD inline int stop_status(int64_t it, int64_t max_iters, double f_x, double norm, double eps, double f_x0, int64_t &iters_ran) {
+    if (it + 1 > max_iters) { iters_ran = max_iters; return CGO_MAX_ITERS_REACHED; }
+    if (hd_isfinite(f_x) && hd_isfinite(norm) && norm < eps) { iters_ran = it; return f_x <= f_x0 ? CGO_SUCCESS : CGO_INCREASING_OBJECTIVE; }
+    return CGO_INCOMPLETE;
+}
 
 struct ResState {
     // the loop state of optim.jl:25-47,136-145 between two outer iterations
@@ -346,6 +356,24 @@ CGO_HD inline int res_trial_points(const cgo_ls_config &ls, double a0, int maxp,
     return k;
 }
 
+// LinearAlgebra.norm's rare path has ONE case a V may settle itself: Σg⁺² is exactly 0 because g⁺ = ∇f(x + a·u) IS the zero
+// vector — then the norm is 0, exactly what the scaled form returns (Solver::robust_norm: max|g⁺| = 0 → 0) — and not the
+// underflow of squares of |g⁺_i| < 2e-162, which stays the host's.  A V that can tell declares `kZeroCheck` and answers
+// `trial_gradient_is_zero(a)` (the batched solves' ResDev); every other V (the resident solver's, the test double's) compiles to
+// `false`, i.e. to the hand-back it always was.
+template <class V, class = void> struct ResZeroCheck {
+    static CGO_HD RES_EV_INLINE bool yes(V &, double) { return false; }
+};
+template <class V> struct ResZeroCheck<V, decltype((void)V::kZeroCheck)> {
+    static CGO_HD RES_EV_INLINE bool yes(V &v, double a) {
+        if constexpr (V::kZeroCheck) return v.trial_gradient_is_zero(a);
+        else return false;
+    }
+};
+template <class V> CGO_HD RES_EV_INLINE bool res_trial_gradient_is_zero(V &v, double gtgt, double a) {
+    return gtgt == 0.0 && ResZeroCheck<V>::yes(v, a);
+}
+
 // Up to `budget` outer iterations of minimizeobjective (optim.jl:50-160).  Every caller thread passes identical arguments
 // and V returns identical sums to all of them.  recs[0 … s.done) and log[0 … s.log_len) are written by V's leader only.
 template <class V>
@@ -383,7 +411,7 @@ CGO_HD inline void res_iterate(const ResConfig &c, ResState &s, V &v, int64_t bu
         if (rc == 9) { s.reason = RES_ERROR; break; }
         if (rc != 0 || o.status != CGO_SUCCESS || ev.evals == 0 || ev.overflow) { s.reason = RES_HOST; break; }   // optim.jl:93-104 → host
         const TrialSums t = ev.last;            // info.xp / df_xp: the LAST evaluated trial = the accepted one (both bisection searches)
-        if (!sumsq_in_range(t.gtgt)) { s.reason = RES_HOST; break; }                                   // LinearAlgebra.norm rare path
+        if (!sumsq_in_range(t.gtgt) && !res_trial_gradient_is_zero(v, t.gtgt, ev.last_a)) { s.reason = RES_HOST; break; }   // LinearAlgebra.norm rare path
         const double norm_xp = __builtin_sqrt(t.gtgt);                                                // optim.jl:107
         if (!hd_isfinite(o.phi) || !hd_isfinite(norm_xp)) { s.reason = RES_HOST; break; }              // optim.jl:108-121
         if (!beta_norms_fast_ok(c.beta_kind, t, s.uu)) { s.reason = RES_HOST; break; }

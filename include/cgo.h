@@ -494,6 +494,35 @@ int cgo_minimize_rerun(cgo_ctx *ctx, cgo_objective *obj, const double *x0_local,
                        const cgo_cg_config *rerun_cfgs, const cgo_ls_config *rerun_ls,
                        int32_t npairs, cgo_results *outs, int32_t *nouts);
 
+/* ---- batched solves: many small problems in one launch, a workgroup each ---------------------------------
+ * `batch` independent minimizeobjective problems of the same objective kind and size n under ONE config and line search: a
+ * parameter sweep, multi-start, one small fit per pixel.  Each problem occupies one workgroup (k_batch), which runs the
+ * reference's outer loop and line search on the device until its stop test fires; a problem whose next iteration the device
+ * loop does not run (any line-search outcome other than :success, non-finite values, a rare-path norm, WolfeBisection's
+ * bracket collapse) is finished by the ordinary engine, one at a time, with the reference's status and iters_ran.
+ * Objectives: CGO_OBJ_QUAD_DIAG (param0 = the [batch*n] rows of D), CGO_OBJ_ROSENBROCK_PAIRED (n even), CGO_OBJ_BOOTH (n = 2).
+ * CGO_EINVAL, with a message naming the reason, for any other objective, β = L-BFGS / Broyden, Backtracking, a multi-rank
+ * context, batch < 1, n > cgo_batch_max_n, and a missing param0 — there is no fallback to a loop of solves. */
+typedef struct cgo_batch_results {      /* every pointer caller-allocated, each may be NULL */
+    double  *objective;                 /* [batch] */
+    int64_t *iters_ran;                 /* [batch] */
+    int32_t *status;                    /* [batch] */
+    int64_t *total_fdf_evals;           /* [batch] */
+    double  *minimizer, *gradient;      /* [batch * n], row-major, dense */
+    double  *trace_objective, *trace_grad_norm, *trace_step_size;   /* [batch * max_iters], row b valid in [0, iters_ran[b]) */
+    int64_t *trace_objective_evals;
+    int64_t launches, handed_back;      /* out: k_batch launches; problems the host engine finished */
+} cgo_batch_results;
+int cgo_minimize_batch(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch,
+                       const double *x0 /* [batch*n] */, const double *param0 /* [batch*n]; NULL unless the objective has a parameter vector */,
+                       const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters /* 0 = library policy */,
+                       cgo_batch_results *out);
+int64_t cgo_batch_max_n(cgo_ctx *ctx, int32_t obj_kind);   /* largest n one workgroup's LDS holds (same arithmetic as the resident plan); 0: none */
+/* The stop test at the top of iteration it + 1 (optim.jl:53-80,162-169) as a function of the loop state — the one rule the
+ * engine and the problems a batch finishes on the device share: the terminal status (CGO_INCOMPLETE: the iteration runs) and
+ * Results.iters_ran. */
+int32_t cgo_stop_status(int64_t it, int64_t max_iters, double f_x, double grad_norm, double eps, double f_x0, int64_t *iters_ran);
+
 /* ---- kernel-level entry points on host vectors (KATs / micro-benchmarks)
  *      each: H2D, ONE fused launch, D2H ---------------------------------- */
 /* updatedir!(u, df_x, β) (cg_flavours.jl:2-15) fused with the next dϕ₀ = g·u
