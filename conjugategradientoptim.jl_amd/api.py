@@ -1078,31 +1078,54 @@ class BatchResults(list):
     handed_back: int = 0
 
 
-def batch_max_n(kind: str, ctx: Optional[Context] = None) -> int:
-    """Largest n of one problem of a batched solve: what one workgroup's LDS holds of x, u and the parameter vector."""
+def batch_max_n(obj_or_kind, ctx: Optional[Context] = None) -> int:
+    """Largest n of one problem of a batched solve: what one workgroup's LDS holds of x, u and the parameter vectors.  A kind
+    name for the built-in objectives; a run-time compiled `DeviceObjective` (kind "user") for its own — the first call on its
+    compiled module compiles the batch program."""
+    if isinstance(obj_or_kind, DeviceObjective):
+        return int(_lib.lib().cgo_batch_max_n_obj(obj_or_kind._h))
     ctx = ctx or default_context()
-    return int(_lib.lib().cgo_batch_max_n(ctx._h, OBJ_KINDS[kind]))
+    return int(_lib.lib().cgo_batch_max_n(ctx._h, OBJ_KINDS[obj_or_kind]))
 
 
-def minimizeobjectivebatch(kind: str, X0, config: CGConfig, linesearch_config: LineSearchConfig, D=None,
+def minimizeobjectivebatch(obj_or_kind, X0, config: CGConfig, linesearch_config: LineSearchConfig, D=None, params=None,
                            ctx: Optional[Context] = None, slice_iters: int = 0) -> BatchResults:
-    """`batch` independent minimizeobjective problems in ONE launch sequence, a workgroup each: X0 is [batch, n], `kind` one of
-    "quad_diag" (D: [batch, n], the rows of the diagonal), "rosenbrock_paired" (n even) or "booth" (n = 2); one config and one
-    line search for all.  Returns a list of `Results`, one per problem — what minimizeobjective returns for it — with the
-    counters `launches` and `handed_back` as attributes.  Problems whose next iteration the device loop does not run are
-    finished by the ordinary engine; anything the batched form does not cover raises CgoError (no loop of solves behind it).
-    slice_iters: outer iterations per problem and launch (0: the library's policy)."""
-    if kind not in OBJ_KINDS:
-        raise ValueError(f"unknown objective kind {kind!r}")
+    """`batch` independent minimizeobjective problems in ONE launch sequence, a workgroup each: X0 is [batch, n]; one config and
+    one line search for all.  `obj_or_kind` is either one of "quad_diag" (D: [batch, n], the rows of the diagonal),
+    "rosenbrock_paired" (n even) or "booth" (n = 2), or a run-time compiled `DeviceObjective` (ElementwiseObjective) of size n —
+    the MODEL: its source, scalar and cost class are every problem's, its own parameter vectors are not touched — with `params`,
+    a sequence of its n_params arrays [batch, n], the rows of slot 0, 1, ….  The first batched solve on a compiled source
+    compiles its batch program (seconds); later ones find it.  Returns a list of `Results`, one per problem — what
+    minimizeobjective returns for it — with the counters `launches` and `handed_back` as attributes.  Problems whose next
+    iteration the device loop does not run are finished by the ordinary engine; anything the batched form does not cover
+    raises CgoError (no loop of solves behind it).  slice_iters: outer iterations per problem and launch (0: the library's
+    policy)."""
+    model = obj_or_kind if isinstance(obj_or_kind, DeviceObjective) else None
+    if model is None and obj_or_kind not in OBJ_KINDS:
+        raise ValueError(f"unknown objective kind {obj_or_kind!r}")
     X0 = np.ascontiguousarray(np.asarray(X0, dtype=np.float64))
     if X0.ndim != 2:
         raise ValueError("X0 must be [batch, n]")
     batch, n = X0.shape
     Dc = None
     if D is not None:
+        if model is not None:
+            raise ValueError("D belongs to the built-in quadratic: an objective takes params, one array per slot")
         Dc = np.ascontiguousarray(np.asarray(D, dtype=np.float64))
         if Dc.shape != X0.shape:
             raise ValueError("D must have the shape of X0")
+    Pc = []
+    if params is not None:
+        if model is None:
+            raise ValueError("params belongs to a run-time compiled objective: the built-in quadratic takes D")
+        for j, v in enumerate(params):
+            Pc.append(None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.float64)))
+            if Pc[-1] is not None and Pc[-1].shape != X0.shape:
+                raise ValueError(f"params[{j}] must have the shape of X0")
+    if model is not None:
+        if n != model.n_global:
+            raise ValueError(f"X0 must be [batch, {model.n_global}], the size of the model objective")
+        ctx = ctx or model.ctx
     ctx = ctx or default_context()
     trace = isinstance(config.trace_status, EnableTrace)
     cap = max(config.max_iters, 1)
@@ -1121,9 +1144,14 @@ def minimizeobjectivebatch(kind: str, X0, config: CGConfig, linesearch_config: L
         r.trace_objective, r.trace_grad_norm = to.ctypes.data_as(dp), tg.ctypes.data_as(dp)
         r.trace_step_size, r.trace_objective_evals = ts.ctypes.data_as(dp), te.ctypes.data_as(i64p)
     cfg, ls = config._c(), linesearch_config._c()
-    check(_lib.lib().cgo_minimize_batch(ctx._h, OBJ_KINDS[kind], n, batch, X0.ctypes.data_as(dp),
-                                        Dc.ctypes.data_as(dp) if Dc is not None else None, C.byref(cfg), C.byref(ls),
-                                        int(slice_iters), C.byref(r)))
+    if model is not None:
+        rows = (dp * max(len(Pc), 1))(*[v.ctypes.data_as(dp) if v is not None else None for v in Pc])
+        check(_lib.lib().cgo_minimize_batch_obj(ctx._h, model._h, batch, X0.ctypes.data_as(dp), rows, len(Pc), C.byref(cfg),
+                                                C.byref(ls), int(slice_iters), C.byref(r)))
+    else:
+        check(_lib.lib().cgo_minimize_batch(ctx._h, OBJ_KINDS[obj_or_kind], n, batch, X0.ctypes.data_as(dp),
+                                            Dc.ctypes.data_as(dp) if Dc is not None else None, C.byref(cfg), C.byref(ls),
+                                            int(slice_iters), C.byref(r)))
     out = BatchResults()
     out.launches, out.handed_back = int(r.launches), int(r.handed_back)
     empty, empty_i = np.zeros(0), np.zeros(0, dtype=np.int64)

@@ -1,7 +1,8 @@
 // cgo_backend_batch.hip — the host side of batched solves: many small problems in one launch, a workgroup each (k_batch,
-// cgo_kernels_batch.hip.hpp).  The backend's objective spans the concatenated problems (n_local = batch · ld), so x, u and the
-// parameter vector ARE the [batch][ld] rows; the loop over launches is the engine's (run_batch, cgo_engine.cpp), the hand-back
-// of a problem the device loop does not finish is the C API's (cgo_minimize_batch), through batch_export_row below.
+// cgo_kernels_batch.hip.hpp).  The backend's objective spans the concatenated problems (n_local = batch · ld), so x, u and every
+// parameter slot ARE the [batch][ld] rows; the loop over launches is the engine's (run_batch, cgo_engine.cpp), the hand-back
+// of a problem the device loop does not finish is the C API's (cgo_minimize_batch[_obj]), through batch_export_row below.
+// A run-time compiled objective (CGO_OBJ_USER) brings its own k_batch, the batch program of its module (cgo_rtc_batch.hip).
 #include "cgo_backend_internal.hpp"
 #include "cgo_kernels_batch.hip.hpp"
 
@@ -26,47 +27,65 @@ static const void *batch_kernel_for(int obj_kind, int npts) {
     default: return nullptr;
     }
 }
-static int batch_vecs(int obj_kind) { return 2 + (obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0); }   // x, u and the parameter vector
+static int batch_vecs(int nparams) { return 2 + nparams; }   // x, u and the parameter slots
 
 // res_plan's arithmetic for ONE workgroup that holds a whole problem: what the device gives a block, minus the kernel's static
 // LDS, minus the same 512 bytes of slack, over 8 bytes × the vectors, rounded down to an even count (ld is even).
-int64_t HipBackend::batch_max_n(HipCtx *ctx, int obj_kind) {
+// `rtc`: the module of a CGO_OBJ_USER objective, its batch program loaded (rtc_compile_batch).
+int64_t HipBackend::batch_max_n(HipCtx *ctx, int obj_kind, const RtcModule *rtc) {
     const void *fn = batch_kernel_for(obj_kind, 3);
-    if (!fn) return 0;
+    const hipFunction_t mf = (obj_kind == CGO_OBJ_USER && rtc) ? rtc->batch(3) : nullptr;
+    if (!fn && !mf) return 0;
     if (hipSetDevice(ctx->device) != hipSuccess) { (void)hipGetLastError(); return 0; }
     int max_lds = 0;
     if (hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, fn) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    const int64_t avail = (int64_t)max_lds - (int64_t)fa.sharedSizeBytes - 512;
-    const int64_t ld_max = (avail / (8 * batch_vecs(obj_kind))) & ~1LL;
+    int64_t static_lds = 0;
+    if (fn) {
+        hipFuncAttributes fa;
+        if (hipFuncGetAttributes(&fa, fn) != hipSuccess) { (void)hipGetLastError(); return 0; }
+        static_lds = (int64_t)fa.sharedSizeBytes;
+    } else {
+        int v = 0;
+        if (hipFuncGetAttribute(&v, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, mf) != hipSuccess) { (void)hipGetLastError(); return 0; }
+        static_lds = v;
+    }
+    const int nparams = fn ? (obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0) : rtc->n_params;
+    const int64_t avail = (int64_t)max_lds - static_lds - 512;
+    const int64_t ld_max = (avail / (8 * batch_vecs(nparams))) & ~1LL;
     return ld_max < 2 ? 0 : ld_max;
 }
 
-int HipBackend::batch_begin(int64_t batch, int64_t n, const double *x0, const double *param0, int64_t max_iters, bool trace) {
+int HipBackend::batch_begin(int64_t batch, int64_t n, const double *x0, const double *const *params, int64_t max_iters, bool trace) {
     const int64_t ld = n + (n & 1);
     if (batch < 1 || n < 1 || obj_->n_local != batch * ld || !rmode_) { set_error("internal: batched solve on a backend of another shape"); return CGO_ESTATE; }
     HIPCHK(hipSetDevice(ctx_->device));
     bat_count_ = batch; bat_n_ = n; bat_ld_ = ld; bat_trace_ = trace;
     bat_rec_stride_ = trace ? std::max<int64_t>(max_iters, 1) : 0;   // (no trace: one slice's worth, sized by the first launch)
-    bat_lds_ = (size_t)ld * 8 * (size_t)batch_vecs(obj_->kind);
-    // rows padded to ld: the padding element is zero in x, u and the parameter vector — no pass reads it (the odd tail is the
-    // workgroup's own element n − 1), and the gradient launch over the concatenated rows gets ∇f = D·x = 0 there
+    bat_lds_ = (size_t)ld * 8 * (size_t)batch_vecs(obj_->nparams());
+    // rows padded to ld.  No pass reads the padding element (the odd tail is the workgroup's own element n − 1); the ONE
+    // gradient launch over the concatenated rows (batch_results) does evaluate it.  Built-in objectives: zero in x, u and the
+    // parameter vector, ∇f = D·x = 0 there.  A user's body is never evaluated on data the user did not supply — log(p), 1/p at
+    // a zero would put a NaN into that launch — so there the padding of x and of every slot repeats element n − 1 of its row
+    // (u stays zero).
+    const bool user = obj_->kind == CGO_OBJ_USER;
     std::vector<double> rows((size_t)batch * (size_t)ld, 0.0);
     const size_t nb = rows.size() * sizeof(double);
-    for (int64_t b = 0; b < batch; ++b) std::memcpy(rows.data() + (size_t)b * ld, x0 + (size_t)b * n, sizeof(double) * (size_t)n);
+    auto fill_rows = [&](const double *src) {
+        for (int64_t b = 0; b < batch; ++b) {
+            std::memcpy(rows.data() + (size_t)b * ld, src + (size_t)b * n, sizeof(double) * (size_t)n);
+            if (ld > n) rows[(size_t)b * ld + n] = user ? src[(size_t)b * n + n - 1] : 0.0;
+        }
+    };
+    fill_rows(x0);
     HIPCHK(hipMemcpyAsync(xc_, rows.data(), nb, hipMemcpyHostToDevice, ctx_->stream));
     HIPCHK(hipMemsetAsync(uc_, 0, nb, ctx_->stream));
     HIPCHK(hipStreamSynchronize(ctx_->stream));
-    if (obj_->uses_param()) {
-        if (!param0) { set_error("internal: batched solve without its parameter rows"); return CGO_ESTATE; }
-        for (int64_t b = 0; b < batch; ++b) {
-            std::memcpy(rows.data() + (size_t)b * ld, param0 + (size_t)b * n, sizeof(double) * (size_t)n);
-            if (ld > n) rows[(size_t)b * ld + n] = 0.0;
-        }
-        HIPCHK(hipMemcpyAsync(obj_->p[0].p, rows.data(), nb, hipMemcpyHostToDevice, ctx_->stream));
+    for (int j = 0; j < obj_->nparams(); ++j) {
+        if (!params || !params[j]) { set_error("internal: batched solve without its parameter rows"); return CGO_ESTATE; }
+        fill_rows(params[j]);
+        HIPCHK(hipMemcpyAsync(obj_->p[j].p, rows.data(), nb, hipMemcpyHostToDevice, ctx_->stream));
         HIPCHK(hipStreamSynchronize(ctx_->stream));
-        obj_->p_set[0] = true;
+        obj_->p_set[j] = true;
     }
     std::vector<ResState> st((size_t)batch);
     for (auto &s : st) { std::memset(&s, 0, sizeof s); s.a_initial = NAN; s.reason = RES_FRESH; }   // optim.jl:47
@@ -75,6 +94,10 @@ int HipBackend::batch_begin(int64_t batch, int64_t n, const double *x0, const do
     HIPCHK(hipMemcpy(bat_st_, st.data(), sizeof(ResState) * (size_t)batch, hipMemcpyHostToDevice));
     HIPCHK(hipMemset(bat_fx0_, 0, sizeof(double) * (size_t)batch));
     if (trace) HIPCHK(hipMalloc((void **)&bat_recs_, sizeof(ResRecord) * (size_t)batch * (size_t)bat_rec_stride_));
+    if (user) {   // (a module's kernel takes its dynamic LDS as launched, as the resident solver's does)
+        if (!obj_->rtc || !obj_->rtc->batch(3)) { set_error("internal: batched solve before the objective's batch program was compiled"); return CGO_ESTATE; }
+        return CGO_OK;
+    }
     const void *fn = batch_kernel_for(obj_->kind, 3);
     if (!fn) { set_error("batched solves: no k_batch instantiation for this objective"); return CGO_EINVAL; }
     if (bat_lds_ > 48 * 1024) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bat_lds_));
@@ -90,15 +113,21 @@ int HipBackend::batch_launch(const ResConfig &c, int64_t budget, std::vector<Res
         if (!bat_recs_) { bat_rec_stride_ = budget; HIPCHK(hipMalloc((void **)&bat_recs_, sizeof(ResRecord) * (size_t)bat_count_ * (size_t)budget)); }
     }
     BatchParams B{};
-    B.x = xc_; B.u = uc_; B.p0 = obj_->p[0].p;
+    B.x = xc_; B.u = uc_; B.p0 = obj_->p[0].p; B.p1 = obj_->p[1].p; B.p2 = obj_->p[2].p; B.p3 = obj_->p[3].p;
     B.st = bat_st_; B.recs = bat_recs_; B.f_x0 = bat_fx0_;
     B.n = bat_n_; B.ld = bat_ld_; B.rec_stride = bat_rec_stride_; B.rec_abs = bat_trace_ ? 1 : 0;
     B.s0 = obj_->s0;
     B.cfg = c; B.cfg.npts = 3; B.cfg.log_on = 0;
     B.budget = budget;
-    const void *fn = batch_kernel_for(obj_->kind, 3);
     void *args[] = {&B};
-    HIPCHK(hipLaunchKernel(fn, dim3((unsigned)bat_count_), dim3(BLOCK), args, bat_lds_, ctx_->stream));
+    if (obj_->kind == CGO_OBJ_USER) {
+        const hipFunction_t mf = obj_->rtc ? obj_->rtc->batch(3) : nullptr;
+        if (!mf) { set_error("internal: kernel missing from the run-time compiled objective module"); return CGO_EINVAL; }
+        HIPCHK(hipModuleLaunchKernel(mf, (unsigned)bat_count_, 1, 1, BLOCK, 1, 1, (unsigned)bat_lds_, ctx_->stream, args, nullptr));
+    } else {
+        const void *fn = batch_kernel_for(obj_->kind, 3);
+        HIPCHK(hipLaunchKernel(fn, dim3((unsigned)bat_count_), dim3(BLOCK), args, bat_lds_, ctx_->stream));
+    }
     total_launches_++;
     st.resize((size_t)bat_count_); f_x0.resize((size_t)bat_count_);
     HIPCHK(hipMemcpyAsync(st.data(), bat_st_, sizeof(ResState) * (size_t)bat_count_, hipMemcpyDeviceToHost, ctx_->stream));
@@ -124,9 +153,10 @@ int HipBackend::batch_export_row(int64_t b, HipBackend &dst, bool with_u) {
     if (int rc = dst.set_x0_device(xc_ + (size_t)b * (size_t)bat_ld_)) return rc;   // (ends whatever the last problem left pending there)
     const size_t nb = sizeof(double) * (size_t)bat_n_;
     if (with_u) HIPCHK(hipMemcpyAsync(dst.uc_, uc_ + (size_t)b * (size_t)bat_ld_, nb, hipMemcpyDeviceToDevice, ctx_->stream));
-    if (obj_->uses_param()) {
-        HIPCHK(hipMemcpyAsync(dst.obj_->p[0].p, obj_->p[0].p + (size_t)b * (size_t)bat_ld_, nb, hipMemcpyDeviceToDevice, ctx_->stream));
-        dst.obj_->p_set[0] = true;
+    if (dst.obj_->nparams() != obj_->nparams()) { set_error("internal: batch_export_row to an objective of other parameter slots"); return CGO_ESTATE; }
+    for (int j = 0; j < obj_->nparams(); ++j) {
+        HIPCHK(hipMemcpyAsync(dst.obj_->p[j].p, obj_->p[j].p + (size_t)b * (size_t)bat_ld_, nb, hipMemcpyDeviceToDevice, ctx_->stream));
+        dst.obj_->p_set[j] = true;
     }
     HIPCHK(hipStreamSynchronize(ctx_->stream));
     return CGO_OK;

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <vector>
 
@@ -969,12 +970,9 @@ int32_t cgo_stop_status(int64_t it, int64_t max_iters, double f_x, double grad_n
     return st;
 }
 
-int cgo_minimize_batch(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
-                       const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out) {
-    API_GUARD_BEGIN
-    REQUIRE(ctx && x0 && cfg && ls && out, "null argument");
-    out->launches = 0; out->handed_back = 0;
-    REQUIRE(batch_kind(obj_kind), "batched solves: the objective must be CGO_OBJ_QUAD_DIAG, CGO_OBJ_ROSENBROCK_PAIRED or CGO_OBJ_BOOTH");
+// What both entry points refuse alike: a config the device loop does not run, a multi-rank context, a batch, a slice or a size
+// out of range.
+static int check_batch_call(cgo_ctx *ctx, const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t n, int64_t batch, int64_t slice_iters) {
     {
         std::string why;
         if (int rc = check_cg_config(cfg, why)) { set_error(why); return rc; }
@@ -986,26 +984,23 @@ int cgo_minimize_batch(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch,
     REQUIRE(batch <= 0x7FFFFFFF, "batched solves: batch exceeds the largest grid");
     REQUIRE(slice_iters >= 0, "batched solves: slice_iters must be ≥ 0 (0 = the library's policy)");
     REQUIRE(n >= 1, "batched solves: n must be ≥ 1");
-    if (obj_kind == CGO_OBJ_ROSENBROCK_PAIRED) REQUIRE(n % 2 == 0, "batched solves: paired Rosenbrock needs an even n");
-    if (obj_kind == CGO_OBJ_BOOTH) REQUIRE(n == 2, "batched solves: Booth is 2-dimensional (n = 2)");
-    if (obj_kind == CGO_OBJ_QUAD_DIAG) REQUIRE(param0, "batched solves: the quadratic needs param0, the [batch*n] rows of D");
-    HIPCHK2(hipSetDevice(ctx->c.device));
-    {
-        const int64_t max_n = cgo_batch_max_n(ctx, obj_kind);
-        if (n > max_n) { set_error("batched solves: n = " + std::to_string(n) + " exceeds what one workgroup's LDS holds (cgo_batch_max_n = " + std::to_string(max_n) + ")"); return CGO_EINVAL; }
-    }
+    return CGO_OK;
+}
+
+// The concatenated problems: ONE objective `cat` (n_local = batch · ld, its parameter slots allocated) and backend whose x, u and
+// parameter slots are the [batch][ld] rows — launched until every problem is finished or handed back, then everything after
+// the launch loop: statuses from stop_status, traces, and the hand-back of the problems the device loop does not finish to ONE
+// ordinary solver on `make_hobj`'s objective of size n (created on the first hand-back).
+static int run_batch_on(cgo_ctx *ctx, HipObjective &cat, int64_t n, int64_t batch, const double *x0, const double *const *params,
+                        const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out,
+                        const std::function<int(cgo_objective **)> &make_hobj) {
     cgo_solver_policy pol;
     { std::string pw; if (int rc = resolve_policy(ctx, nullptr, pol, pw)) { set_error(pw); return rc; } }
-    // the concatenated problems: ONE objective and backend whose x, u and parameter vector are the [batch][ld] rows
-    const int64_t ld = n + (n & 1);
-    HipObjective cat;
-    cat.ctx = &ctx->c; cat.kind = obj_kind; cat.n_global = cat.n_local = batch * ld; cat.offset = 0;
-    if (cat.uses_param()) { if (int rc = cat.p[0].alloc((size_t)(batch * ld))) return rc; }
     HipBackend be(&ctx->c, &cat);
     be.set_policy(pol);
     be.set_rmode(true);
     if (int rc = be.alloc()) return rc;
-    if (int rc = be.batch_begin(batch, n, x0, param0, cfg->max_iters, cfg->trace_enabled != 0)) return rc;
+    if (int rc = be.batch_begin(batch, n, x0, params, cfg->max_iters, cfg->trace_enabled != 0)) return rc;
     BatchRun run;
     if (int rc = run_batch(&be, *cfg, *ls, batch, slice_iters, run)) { if (rc == CGO_ESTATE) set_error("internal: a batched launch left a problem in a state the driver does not know"); return rc; }
     out->launches = run.launches;
@@ -1045,7 +1040,7 @@ int cgo_minimize_batch(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch,
         const ResState &s = run.st[(size_t)b];
         if (s.reason != RES_HOST) continue;
         if (!hs) {
-            if ((rc = cgo_objective_create(ctx, obj_kind, n, 0, n, &hobj))) break;
+            if ((rc = make_hobj(&hobj))) break;
             cgo_solver_policy hp;
             cgo_solver_policy_init(&hp);
             hp.resident = 0;
@@ -1082,6 +1077,83 @@ int cgo_minimize_batch(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch,
     if (hobj) cgo_objective_destroy(hobj);
     if (rc) set_error(keep);
     return rc;
+}
+
+int cgo_minimize_batch(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
+                       const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out) {
+    API_GUARD_BEGIN
+    REQUIRE(ctx && x0 && cfg && ls && out, "null argument");
+    out->launches = 0; out->handed_back = 0;
+    REQUIRE(batch_kind(obj_kind), "batched solves: the objective must be CGO_OBJ_QUAD_DIAG, CGO_OBJ_ROSENBROCK_PAIRED or CGO_OBJ_BOOTH");
+    if (int rc = check_batch_call(ctx, cfg, ls, n, batch, slice_iters)) return rc;
+    if (obj_kind == CGO_OBJ_ROSENBROCK_PAIRED) REQUIRE(n % 2 == 0, "batched solves: paired Rosenbrock needs an even n");
+    if (obj_kind == CGO_OBJ_BOOTH) REQUIRE(n == 2, "batched solves: Booth is 2-dimensional (n = 2)");
+    if (obj_kind == CGO_OBJ_QUAD_DIAG) REQUIRE(param0, "batched solves: the quadratic needs param0, the [batch*n] rows of D");
+    HIPCHK2(hipSetDevice(ctx->c.device));
+    {
+        const int64_t max_n = cgo_batch_max_n(ctx, obj_kind);
+        if (n > max_n) { set_error("batched solves: n = " + std::to_string(n) + " exceeds what one workgroup's LDS holds (cgo_batch_max_n = " + std::to_string(max_n) + ")"); return CGO_EINVAL; }
+    }
+    const int64_t ld = n + (n & 1);
+    HipObjective cat;
+    cat.ctx = &ctx->c; cat.kind = obj_kind; cat.n_global = cat.n_local = batch * ld; cat.offset = 0;
+    if (cat.uses_param()) { if (int rc = cat.p[0].alloc((size_t)(batch * ld))) return rc; }
+    const double *params[1] = {param0};
+    return run_batch_on(ctx, cat, n, batch, x0, params, cfg, ls, slice_iters, out,
+                        [&](cgo_objective **h) { return cgo_objective_create(ctx, obj_kind, n, 0, n, h); });
+    API_GUARD_END
+}
+
+// The model's batch program (k_batch<UserObjective, …>, cgo_rtc_batch.hip): compiled on the first batched use of its module
+static int batch_program(cgo_objective *model) {
+    std::string log;
+    if (int rc = rtc_compile_batch(*model->o.rtc, log)) { set_error("user objective: the batch program did not compile:\n" + log); return rc; }
+    return CGO_OK;
+}
+static bool batch_model_whole(const cgo_objective *m) { return m->o.offset == 0 && m->o.n_local == m->o.n_global && m->o.ctx->world() == 1; }
+
+int64_t cgo_batch_max_n_obj(cgo_objective *model) {
+    try {
+        if (!model || model->o.kind != CGO_OBJ_USER || !model->o.rtc || !batch_model_whole(model)) return 0;
+        if (batch_program(model)) return 0;
+        return HipBackend::batch_max_n(model->o.ctx, CGO_OBJ_USER, model->o.rtc.get());
+    } catch (...) { return 0; }
+}
+
+int cgo_minimize_batch_obj(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *x0, const double *const *params,
+                           int32_t n_params, const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters,
+                           cgo_batch_results *out) {
+    API_GUARD_BEGIN
+    REQUIRE(ctx && model && x0 && cfg && ls && out, "null argument");
+    out->launches = 0; out->handed_back = 0;
+    REQUIRE(model->o.kind == CGO_OBJ_USER && model->o.rtc,
+            "batched solves: the model must be a run-time compiled objective (cgo_objective_create_from_source[_ex]); built-in objectives: cgo_minimize_batch");
+    REQUIRE(model->o.ctx == &ctx->c, "batched solves: the model belongs to another context");
+    REQUIRE(batch_model_whole(model), "batched solves: a sharded or multi-rank model is not supported (n_global = n_local = the size of ONE problem, one rank only)");
+    const int64_t n = model->o.n_local;
+    if (int rc = check_batch_call(ctx, cfg, ls, n, batch, slice_iters)) return rc;
+    const int K = model->o.nparams();
+    if (n_params != K) { set_error("batched solves: n_params = " + std::to_string(n_params) + ", the model reads " + std::to_string(K) + " parameter slots"); return CGO_EINVAL; }
+    REQUIRE(K == 0 || params, "batched solves: params is null, the model reads parameter slots");
+    for (int j = 0; j < K; ++j)
+        if (!params[j]) { set_error("batched solves: params[" + std::to_string(j) + "] is null (the [batch*n] rows of slot " + std::to_string(j) + ")"); return CGO_EINVAL; }
+    HIPCHK2(hipSetDevice(ctx->c.device));
+    if (int rc = batch_program(model)) return rc;
+    {
+        const int64_t max_n = HipBackend::batch_max_n(&ctx->c, CGO_OBJ_USER, model->o.rtc.get());
+        if (n > max_n) { set_error("batched solves: n = " + std::to_string(n) + " exceeds what one workgroup's LDS holds (cgo_batch_max_n_obj = " + std::to_string(max_n) + ")"); return CGO_EINVAL; }
+    }
+    const int64_t ld = n + (n & 1);
+    HipObjective cat;   // shares the model's compiled module, its scalar and its cost class; the slots are its own [batch][ld] rows
+    cat.ctx = &ctx->c; cat.kind = CGO_OBJ_USER; cat.n_global = cat.n_local = batch * ld; cat.offset = 0;
+    cat.rtc = model->o.rtc; cat.user_nparams = K; cat.s0 = model->o.s0; cat.user_cheap = model->o.user_cheap;
+    for (int j = 0; j < K; ++j) { if (int rc = cat.p[j].alloc((size_t)(batch * ld))) return rc; }
+    return run_batch_on(ctx, cat, n, batch, x0, params, cfg, ls, slice_iters, out, [&](cgo_objective **h) {
+        // (the module cache makes this free while the model lives: same device, text and n_params)
+        if (int rc = cgo_objective_create_from_source_ex(ctx, model->o.rtc->user_source.c_str(), K, n, 0, n, h)) return rc;
+        (*h)->o.s0 = model->o.s0; (*h)->o.user_cheap = model->o.user_cheap;
+        return (int)CGO_OK;
+    });
     API_GUARD_END
 }
 

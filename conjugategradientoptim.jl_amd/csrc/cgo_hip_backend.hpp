@@ -157,14 +157,16 @@ class HipBackend : public VecBackend {
     int64_t resident_slices() const { return res_slices_; }
     int64_t resident_gave_up() const { return res_gave_up_; }
     // Batched solves (cgo_backend_batch.hip; k_batch, cgo_kernels_batch.hip.hpp).  The backend's objective spans the
-    // CONCATENATED problems — n_local = batch · ld, ld = n + (n & 1) — so that x, u and the parameter vector are the
+    // CONCATENATED problems — n_local = batch · ld, ld = n + (n & 1) — so that x, u and every parameter slot are the
     // [batch][ld] rows and the ordinary gradient launch (download) serves every problem at once.
-    static int64_t batch_max_n(HipCtx *ctx, int obj_kind);    // largest n one workgroup's LDS holds (res_plan's arithmetic); 0: no kernel
-    int batch_begin(int64_t batch, int64_t n, const double *x0, const double *param0, int64_t max_iters, bool trace);
+    // largest n one workgroup's LDS holds of x, u and the slots (res_plan's arithmetic); 0: no kernel.  CGO_OBJ_USER: `rtc` with its batch program
+    static int64_t batch_max_n(HipCtx *ctx, int obj_kind, const RtcModule *rtc = nullptr);
+    // params[j], j < nparams(): the [batch·n] rows of slot j
+    int batch_begin(int64_t batch, int64_t n, const double *x0, const double *const *params, int64_t max_iters, bool trace);
     int batch_launch(const ResConfig &c, int64_t budget, std::vector<ResState> &st, std::vector<double> &f_x0) override;
     int batch_records(int64_t b, int64_t count, std::vector<ResRecord> &out);     // the trace records of problem b's first `count` iterations (b < 0: every row)
     int64_t batch_rec_stride() const { return bat_rec_stride_; }
-    int batch_export_row(int64_t b, HipBackend &dst, bool with_u);                // row b of x (u), and of the parameter vector → dst
+    int batch_export_row(int64_t b, HipBackend &dst, bool with_u);                // row b of x (u), and of every parameter slot → dst
     int batch_results(double *x /*[batch·n]*/, double *g /*[batch·n]*/);          // dense rows; each may be nullptr
     int64_t push_count(int kind) const { return push_counts_[kind]; }   // 0 speculated, 1 fused (g⁺ formed in the push), 2 plain
     bool sys_supported() const override { return rmode_; }

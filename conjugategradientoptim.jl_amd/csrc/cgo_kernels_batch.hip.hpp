@@ -4,8 +4,8 @@
 // 255 idle.  A user with n ≈ 1e3 has many of them — a parameter sweep, multi-start, one fit per pixel — and
 // here blockIdx.x says WHICH PROBLEM, not which chunk:
 //
-//   * workgroup b loads row b of x, u and the parameter vector ([batch][ld], ld = n + (n & 1)) into LDS and its own ResState
-//     from st[b]; a problem that is already finished (RES_STOP, RES_HOST) costs its workgroup one load and a return;
+//   * workgroup b loads row b of x, u and of every parameter slot the objective reads ([batch][ld] each, ld = n + (n & 1)) into
+//     LDS — slot j at ps + j·ld, where ResDev looks for it — and its own ResState from st[b]; a problem that is already finished (RES_STOP, RES_HOST) costs its workgroup one load and a return;
 //   * a problem that has not started (RES_FRESH) gets optim.jl:25-47 here: pass<R_INIT, 1> → u = −g, f_x, g·g;
 //   * then res_iterate (cgo_resident.hpp) — the loop k_resident runs — over ResDev in its SOLO form: the passes, trial and
 //     accept_dir_trial are ResDev's own (cgo_kernels_resident.hip.hpp), the workgroup's row is the total, its lane 0 the leader;
@@ -31,6 +31,7 @@ struct BatchParams {
     double s0;
     ResConfig cfg;
     long long budget;
+    const double *p1, *p2, *p3;               // [batch][ld]: parameter slots 1–3 (run-time compiled objectives with kParams > 1 only)
 };
 
 template <class Obj, int NPTS>
@@ -52,7 +53,11 @@ __global__ __launch_bounds__(BLOCK, 1) void k_batch(const BatchParams B) {
         if (i < B.ld) {
             xs[i] = B.x[lo + i];
             us[i] = B.u[lo + i];
-            if constexpr (obj_nparams<Obj>() > 0) ps[i] = B.p0[lo + i];
+            constexpr int K = obj_nparams<Obj>();
+            if constexpr (K > 0) ps[i] = B.p0[lo + i];
+            if constexpr (K > 1) ps[B.ld + i] = B.p1[lo + i];
+            if constexpr (K > 2) ps[2 * B.ld + i] = B.p2[lo + i];
+            if constexpr (K > 3) ps[3 * B.ld + i] = B.p3[lo + i];
         }
     }
     __syncthreads();

@@ -26,6 +26,7 @@ using namespace dev;
 RtcModule::~RtcModule() {
     if (mod) (void)hipModuleUnload(mod);
     if (probe_mod) (void)hipModuleUnload(probe_mod);
+    if (batch_mod) (void)hipModuleUnload(batch_mod);
 }
 
 static std::string key_cg(int mode, int npts, bool big) {
@@ -60,7 +61,7 @@ hipFunction_t RtcModule::fused(int mode, bool big) const {
 }
 
 // the embedded kernel templates + the user's objective as one translation unit
-static std::string rtc_program_source(const std::string &source, int n_params) {
+std::string rtc_program_source(const std::string &source, int n_params) {
     const bool has_param = n_params > 0;
     const std::string K = std::to_string(n_params);
     std::string src;
@@ -106,9 +107,8 @@ static std::string rtc_program_source(const std::string &source, int n_params) {
 
 // One program → one loaded module: compiles `src` for the name expressions of `wants`, loads the code object as `mod` and
 // files every kernel in `fn` under its key.  On failure `mod` is unloaded again and `fn` is as it was.
-struct Want { std::string key, expr; };
-static int rtc_build(const std::string &src, const char *name, const std::vector<Want> &wants, hipModule_t &mod,
-                     std::map<std::string, hipFunction_t> &fn, std::string &log) {
+int rtc_build(const std::string &src, const char *name, const std::vector<Want> &wants, hipModule_t &mod,
+              std::map<std::string, hipFunction_t> &fn, std::string &log) {
     hiprtcProgram prog;
     if (hiprtcCreateProgram(&prog, src.c_str(), name, 0, nullptr, nullptr) != HIPRTC_SUCCESS) { log = "hiprtcCreateProgram failed"; return CGO_EHIP; }
     for (auto &w : wants) hiprtcAddNameExpression(prog, w.expr.c_str());

@@ -6,6 +6,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <vector>
 
 namespace cgo {
 
@@ -22,6 +23,10 @@ struct RtcModule {
     // what it did before the probe existed
     hipFunction_t resident_probe(int npts) const;
     hipModule_t probe_mod = nullptr;
+    // k_batch<UserObjective, npts> (batched solves, cgo_rtc_batch.hip): a program of its own as well, compiled on the first
+    // batched solve on the objective (rtc_compile_batch) — an objective that never batches does not pay for it
+    hipFunction_t batch(int npts) const;
+    hipModule_t batch_mod = nullptr;
     std::string user_source;
     int n_params = 0;   // parameter slots the objective was created with (0 … CGO_MAX_PARAM_SLOTS)
     int device = 0;
@@ -37,5 +42,15 @@ int rtc_compile_objective(int device, const std::string &source, int n_params,
                           std::shared_ptr<RtcModule> &out, std::string &log);
 // the PROBE form of the module's resident kernel, compiled and loaded on first use; CGO_OK if it is there already
 int rtc_compile_resident_probe(RtcModule &m, std::string &log);
+// k_batch for the module's objective, one kernel per row of CGO_BATCH_ROWS, compiled and loaded on first use (cgo_rtc_batch.hip)
+int rtc_compile_batch(RtcModule &m, std::string &log);
+
+// What a further program of a module is built from (cgo_rtc.hip): the embedded kernel templates + the user's objective as one
+// translation unit, and one program → one loaded module: compiles `src` for the name expressions of `wants`, loads the code
+// object as `mod` and files every kernel in `fn` under its key.  On failure `mod` is unloaded again and `fn` is as it was.
+struct Want { std::string key, expr; };
+std::string rtc_program_source(const std::string &source, int n_params);
+int rtc_build(const std::string &src, const char *name, const std::vector<Want> &wants, hipModule_t &mod,
+              std::map<std::string, hipFunction_t> &fn, std::string &log);
 
 }  // namespace cgo

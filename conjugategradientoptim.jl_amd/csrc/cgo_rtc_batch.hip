@@ -1,0 +1,39 @@
+// cgo_rtc_batch.hip — batched solves on a run-time compiled objective: k_batch<UserObjective, NPTS> (cgo_kernels_batch.hip.hpp,
+// embedded with the other kernel templates) for the rows of CGO_BATCH_ROWS, as a SECOND program of the objective's module.
+//
+// k_batch is a 512-VGPR kernel that takes hiprtc about as long as k_resident: it is not part of the program every user
+// objective compiles at creation (cgo_rtc.hip), but compiled from the kept source on the first batched solve and kept on
+// the RtcModule — as the PROBE form of the resident kernel is (rtc_compile_resident_probe).  While one objective of the same
+// text lives, every later batched solve finds it there.
+#include "cgo_rtc.hpp"
+
+#include <mutex>
+
+#include "cgo_hip_backend.hpp"
+#include "cgo_instances.def"
+
+namespace cgo {
+
+hipFunction_t RtcModule::batch(int npts) const {
+    // the last row with NPTS ≤ npts, the first row below that (the rule of the ahead-of-time dispatch, cgo_backend_batch.hip)
+    hipFunction_t f = nullptr;
+#define ROW(NPTS) \
+    if (!f || npts >= NPTS) { auto it = fn.find("batch:" #NPTS); if (it != fn.end()) f = it->second; }
+    CGO_BATCH_ROWS(ROW)
+#undef ROW
+    return f;
+}
+
+int rtc_compile_batch(RtcModule &m, std::string &log) {
+    static std::mutex mu;   // (objectives of one text share the module: two first batched solves must not both build it)
+    std::lock_guard<std::mutex> lock(mu);
+    if (m.batch_mod) return CGO_OK;
+    if (hipSetDevice(m.device) != hipSuccess) { log = "hipSetDevice failed"; return CGO_EHIP; }
+    std::vector<Want> wants;
+#define ROW(NPTS) wants.push_back({"batch:" #NPTS, "cgo::dev::k_batch<cgo::dev::UserObjective, " #NPTS ">"});
+    CGO_BATCH_ROWS(ROW)
+#undef ROW
+    return rtc_build(rtc_program_source(m.user_source, m.n_params), "cgo_user_objective_batch.hip", wants, m.batch_mod, m.fn, log);
+}
+
+}  // namespace cgo

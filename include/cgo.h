@@ -518,6 +518,25 @@ int cgo_minimize_batch(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch,
                        const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters /* 0 = library policy */,
                        cgo_batch_results *out);
 int64_t cgo_batch_max_n(cgo_ctx *ctx, int32_t obj_kind);   /* largest n one workgroup's LDS holds (same arithmetic as the resident plan); 0: none */
+/* The same for a RUN-TIME COMPILED objective: the caller's own element-wise body or `struct UserObjective`, with its up to
+ * CGO_MAX_PARAM_SLOTS per-element data vectors given per problem.
+ * `model`: an objective from cgo_objective_create_from_source[_ex] on a single-rank ctx whose n_global = n_local = n is the size of
+ * ONE problem; it supplies the compiled source, n_params, scalar slot 0 (shared by all problems) and the cost class.  Its own
+ * parameter slots are neither read nor written.  params[j] (j < n_params) = the [batch*n] rows of slot j.
+ * The kernel (k_batch for the model's objective) is a second program of the model's compiled module: the first batched call on
+ * a module — cgo_batch_max_n_obj included — compiles it (seconds), every later one on an objective of the same text finds it.
+ * One workgroup holds 2 + n_params vectors of a problem: cgo_batch_max_n_obj shrinks with the slots.  A `struct
+ * UserObjective` with kPairOnly = true needs an even n; that stays the caller's matter, as for a single solve.  Where n is odd
+ * the rows are padded by one element on the device; that element of x and of every slot repeats element n − 1 of its row, so
+ * the body is never evaluated on data the caller did not supply.
+ * CGO_EINVAL, with a message naming the reason, for a model that is not run-time compiled (those: cgo_minimize_batch), a
+ * sharded or multi-rank model, n_params other than the model's, a null params[j], n > cgo_batch_max_n_obj, and everything
+ * cgo_minimize_batch refuses of a config. */
+int cgo_minimize_batch_obj(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *x0 /* [batch*n] */,
+                           const double *const *params, int32_t n_params,
+                           const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters /* 0 = library policy */,
+                           cgo_batch_results *out);
+int64_t cgo_batch_max_n_obj(cgo_objective *model);   /* 0: none */
 /* The stop test at the top of iteration it + 1 (optim.jl:53-80,162-169) as a function of the loop state — the one rule the
  * engine and the problems a batch finishes on the device share: the terminal status (CGO_INCOMPLETE: the iteration runs) and
  * Results.iters_ran. */
