@@ -198,6 +198,10 @@ SIGNATURES = {
     "cgo_minimize_batch_obj": (C.c_int, [_vp, _vp, C.c_int64, dp, C.POINTER(dp), C.c_int32, C.POINTER(CGConfigC), C.POINTER(LSConfigC),
                                          C.c_int64, C.POINTER(BatchResultsC)]),
     "cgo_batch_max_n_obj": (C.c_int64, [_vp]),
+    "cgo_batch_open": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(dp), C.c_int32, C.POINTER(_vp)]),
+    "cgo_batch_solve": (C.c_int, [_vp, dp, dp, C.POINTER(C.c_uint8), C.POINTER(CGConfigC), C.POINTER(LSConfigC), C.c_int64,
+                                  C.POINTER(BatchResultsC)]),
+    "cgo_batch_close": (C.c_int, [_vp]),
     "cgo_stop_status": (C.c_int32, [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, i64p]),
     "cgo_kernel_dir": (C.c_int, [_vp, dp, dp, C.c_double, C.c_int64, dp]),
     "cgo_kernel_beta_partials": (C.c_int, [_vp, dp, dp, dp, C.c_int64, dp]),

@@ -1088,8 +1088,54 @@ def batch_max_n(obj_or_kind, ctx: Optional[Context] = None) -> int:
     return int(_lib.lib().cgo_batch_max_n(ctx._h, OBJ_KINDS[obj_or_kind]))
 
 
+class _BatchOut:
+    """The caller-allocated arrays of a `cgo_batch_results` for [batch] problems of size n under `config`, and what they become."""
+
+    def __init__(self, batch: int, n: int, config: CGConfig):
+        self.batch, self.config = batch, config
+        self.trace = isinstance(config.trace_status, EnableTrace)
+        cap = max(config.max_iters, 1)
+        self.f = np.zeros(batch)
+        self.it = np.zeros(batch, dtype=np.int64)
+        self.st = np.zeros(batch, dtype=np.int32)
+        self.ev = np.zeros(batch, dtype=np.int64)
+        self.x, self.g = np.zeros((batch, n)), np.zeros((batch, n))
+        r = self.c = _lib.BatchResultsC()
+        r.objective, r.iters_ran = self.f.ctypes.data_as(dp), self.it.ctypes.data_as(i64p)
+        r.status, r.total_fdf_evals = self.st.ctypes.data_as(C.POINTER(C.c_int32)), self.ev.ctypes.data_as(i64p)
+        r.minimizer, r.gradient = self.x.ctypes.data_as(dp), self.g.ctypes.data_as(dp)
+        if self.trace:
+            self.to, self.tg, self.ts = np.zeros((batch, cap)), np.zeros((batch, cap)), np.zeros((batch, cap))
+            self.te = np.zeros((batch, cap), dtype=np.int64)
+            r.trace_objective, r.trace_grad_norm = self.to.ctypes.data_as(dp), self.tg.ctypes.data_as(dp)
+            r.trace_step_size, r.trace_objective_evals = self.ts.ctypes.data_as(dp), self.te.ctypes.data_as(i64p)
+
+    def results(self, active=None) -> "BatchResults":
+        r, config, trace = self.c, self.config, self.trace
+        out = BatchResults()
+        out.launches, out.handed_back = int(r.launches), int(r.handed_back)
+        empty, empty_i = np.zeros(0), np.zeros(0, dtype=np.int64)
+        for b in range(self.batch):
+            if active is not None and not active[b]:
+                out.append(None)
+                continue
+            k = max(int(self.it[b]), 0) if trace else 0
+            tr = (TraceContainer(self.to[b, :k].copy(), self.tg[b, :k].copy(), self.ts[b, :k].copy(), self.te[b, :k].copy(), config.trace_status)
+                  if trace else TraceContainer(empty.copy(), empty.copy(), empty.copy(), empty_i.copy(), config.trace_status))
+            out.append(Results(float(self.f[b]), self.x[b].copy(), self.g[b].copy(), int(self.it[b]),
+                               _lib.lib().cgo_status_name(int(self.st[b])).decode(), tr, int(self.ev[b]), int(r.launches)))
+        return out
+
+
+def _batch_rows(name: str, v, shape) -> np.ndarray:
+    a = np.ascontiguousarray(np.asarray(v, dtype=np.float64))
+    if a.shape != tuple(shape):
+        raise ValueError(f"{name} must be {list(shape)}")
+    return a
+
+
 def minimizeobjectivebatch(obj_or_kind, X0, config: CGConfig, linesearch_config: LineSearchConfig, D=None, params=None,
-                           ctx: Optional[Context] = None, slice_iters: int = 0) -> BatchResults:
+                           ctx: Optional[Context] = None, slice_iters: int = 0, scalars=None) -> BatchResults:
     """`batch` independent minimizeobjective problems in ONE launch sequence, a workgroup each: X0 is [batch, n]; one config and
     one line search for all.  `obj_or_kind` is either one of "quad_diag" (D: [batch, n], the rows of the diagonal),
     "rosenbrock_paired" (n even) or "booth" (n = 2), or a run-time compiled `DeviceObjective` (ElementwiseObjective) of size n —
@@ -1099,7 +1145,8 @@ def minimizeobjectivebatch(obj_or_kind, X0, config: CGConfig, linesearch_config:
     minimizeobjective returns for it — with the counters `launches` and `handed_back` as attributes.  Problems whose next
     iteration the device loop does not run are finished by the ordinary engine; anything the batched form does not cover
     raises CgoError (no loop of solves behind it).  slice_iters: outer iterations per problem and launch (0: the library's
-    policy)."""
+    policy).  scalars: a [batch] array, every problem's OWN `s0` in place of the model's (a model only: the built-in kinds
+    read no scalar) — one `Batch.solve`; a `Batch` kept open serves many such calls on the same data."""
     model = obj_or_kind if isinstance(obj_or_kind, DeviceObjective) else None
     if model is None and obj_or_kind not in OBJ_KINDS:
         raise ValueError(f"unknown objective kind {obj_or_kind!r}")
@@ -1107,6 +1154,8 @@ def minimizeobjectivebatch(obj_or_kind, X0, config: CGConfig, linesearch_config:
     if X0.ndim != 2:
         raise ValueError("X0 must be [batch, n]")
     batch, n = X0.shape
+    if scalars is not None and model is None:
+        raise ValueError(f"scalars belongs to a run-time compiled objective: {obj_or_kind} reads no scalar")
     Dc = None
     if D is not None:
         if model is not None:
@@ -1126,42 +1175,82 @@ def minimizeobjectivebatch(obj_or_kind, X0, config: CGConfig, linesearch_config:
         if n != model.n_global:
             raise ValueError(f"X0 must be [batch, {model.n_global}], the size of the model objective")
         ctx = ctx or model.ctx
+    if scalars is not None:
+        scalars = _batch_rows("scalars", scalars, (batch,))
+        with Batch(model, Pc, batch) as B:
+            return B.solve(X0, config, linesearch_config, scalars=scalars, slice_iters=slice_iters)
     ctx = ctx or default_context()
-    trace = isinstance(config.trace_status, EnableTrace)
-    cap = max(config.max_iters, 1)
-    f = np.zeros(batch)
-    it = np.zeros(batch, dtype=np.int64)
-    st = np.zeros(batch, dtype=np.int32)
-    ev = np.zeros(batch, dtype=np.int64)
-    x, g = np.zeros((batch, n)), np.zeros((batch, n))
-    r = _lib.BatchResultsC()
-    r.objective, r.iters_ran = f.ctypes.data_as(dp), it.ctypes.data_as(i64p)
-    r.status, r.total_fdf_evals = st.ctypes.data_as(C.POINTER(C.c_int32)), ev.ctypes.data_as(i64p)
-    r.minimizer, r.gradient = x.ctypes.data_as(dp), g.ctypes.data_as(dp)
-    if trace:
-        to, tg, ts = np.zeros((batch, cap)), np.zeros((batch, cap)), np.zeros((batch, cap))
-        te = np.zeros((batch, cap), dtype=np.int64)
-        r.trace_objective, r.trace_grad_norm = to.ctypes.data_as(dp), tg.ctypes.data_as(dp)
-        r.trace_step_size, r.trace_objective_evals = ts.ctypes.data_as(dp), te.ctypes.data_as(i64p)
+    o = _BatchOut(batch, n, config)
     cfg, ls = config._c(), linesearch_config._c()
     if model is not None:
         rows = (dp * max(len(Pc), 1))(*[v.ctypes.data_as(dp) if v is not None else None for v in Pc])
         check(_lib.lib().cgo_minimize_batch_obj(ctx._h, model._h, batch, X0.ctypes.data_as(dp), rows, len(Pc), C.byref(cfg),
-                                                C.byref(ls), int(slice_iters), C.byref(r)))
+                                                C.byref(ls), int(slice_iters), C.byref(o.c)))
     else:
         check(_lib.lib().cgo_minimize_batch(ctx._h, OBJ_KINDS[obj_or_kind], n, batch, X0.ctypes.data_as(dp),
                                             Dc.ctypes.data_as(dp) if Dc is not None else None, C.byref(cfg), C.byref(ls),
-                                            int(slice_iters), C.byref(r)))
-    out = BatchResults()
-    out.launches, out.handed_back = int(r.launches), int(r.handed_back)
-    empty, empty_i = np.zeros(0), np.zeros(0, dtype=np.int64)
-    for b in range(batch):
-        k = max(int(it[b]), 0) if trace else 0
-        tr = (TraceContainer(to[b, :k].copy(), tg[b, :k].copy(), ts[b, :k].copy(), te[b, :k].copy(), config.trace_status) if trace
-              else TraceContainer(empty.copy(), empty.copy(), empty.copy(), empty_i.copy(), config.trace_status))
-        out.append(Results(float(f[b]), x[b].copy(), g[b].copy(), int(it[b]), _lib.lib().cgo_status_name(int(st[b])).decode(), tr,
-                           int(ev[b]), int(r.launches)))
-    return out
+                                            int(slice_iters), C.byref(o.c)))
+    return o.results()
+
+
+class Batch:
+    """`batch` problems of one run-time compiled objective that STAY ON THE DEVICE between solves (cgo_batch_open): `model` as
+    in minimizeobjectivebatch, `params` its n_params arrays [batch, n], uploaded once.  `solve` then runs the batch any number
+    of times — each call from its own X0, under its own config and line search, optionally with a scalar per problem and with
+    only some of the problems.  A context manager; `close` frees the device rows."""
+
+    def __init__(self, model: DeviceObjective, params, batch: int):
+        self._h = None
+        if not isinstance(model, DeviceObjective) or model.kind != "user":
+            raise ValueError("Batch: the model must be a run-time compiled objective (ElementwiseObjective)")
+        self.model, self.batch, self.n = model, int(batch), int(model.n_global)
+        if self.batch < 1:
+            raise ValueError("Batch: batch must be ≥ 1")
+        Pc = [_batch_rows(f"params[{j}]", v, (self.batch, self.n)) for j, v in enumerate(params or [])]
+        rows = (dp * max(len(Pc), 1))(*[v.ctypes.data_as(dp) for v in Pc])
+        h = C.c_void_p()
+        ctx_h = model.ctx._h if model.ctx is not None else None
+        check(_lib.lib().cgo_batch_open(ctx_h, model._h, self.batch, rows, len(Pc), C.byref(h)))
+        self._h = h
+
+    def solve(self, X0, config: CGConfig, linesearch_config: LineSearchConfig, scalars=None, active=None,
+              slice_iters: int = 0) -> BatchResults:
+        """One batched solve from X0 ([batch, n]).  scalars: [batch], every problem's own `s0` (None: the model's for all — then
+        every number is what minimizeobjectivebatch returns).  active: [batch] booleans, the problems that run (None: all); the
+        entry of an inactive problem in the returned list is None."""
+        if self._h is None:
+            raise ValueError("Batch: closed")
+        X0 = _batch_rows("X0", X0, (self.batch, self.n))
+        sc = None if scalars is None else _batch_rows("scalars", scalars, (self.batch,))
+        ac = None
+        if active is not None:
+            ac = np.ascontiguousarray(np.asarray(active).astype(bool).astype(np.uint8))
+            if ac.shape != (self.batch,):
+                raise ValueError(f"active must be [{self.batch}]")
+        o = _BatchOut(self.batch, self.n, config)
+        cfg, ls = config._c(), linesearch_config._c()
+        check(_lib.lib().cgo_batch_solve(self._h, X0.ctypes.data_as(dp), sc.ctypes.data_as(dp) if sc is not None else None,
+                                         ac.ctypes.data_as(C.POINTER(C.c_uint8)) if ac is not None else None, C.byref(cfg),
+                                         C.byref(ls), int(slice_iters), C.byref(o.c)))
+        return o.results(ac)
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            _lib.lib().cgo_batch_close(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class UndefVarError(RuntimeError):
@@ -1234,9 +1323,10 @@ class BoxConstraints:
     `lb`, `ub` are floats (one interval for every variable: the bounds are constants of the generated source) or
     length-D arrays (`lbs::Vector{T}`, `ubs::Vector{T}` of examples/constrained.jl:22-31: every variable its own
     interval; the bounds travel as the objective's last two parameter vectors).  One float and one array: the float
-    is the same for every variable."""
+    is the same for every variable.  Every problem of a batch its own box: BatchBoxConstraints."""
     lb: Union[float, Sequence[float], np.ndarray]
     ub: Union[float, Sequence[float], np.ndarray]
+    _NDIM = (1,)   # (a class attribute, not a field: the dimensions an array bound may have)
 
     def __post_init__(self):
         for name in ("lb", "ub"):
@@ -1245,14 +1335,24 @@ class BoxConstraints:
                 setattr(self, name, float(v))
             else:
                 a = np.ascontiguousarray(v, dtype=np.float64)
-                assert a.ndim == 1, f"BoxConstraints.{name}: a float or a one-dimensional array"
+                assert a.ndim in self._NDIM, f"BoxConstraints.{name}: a float or a one-dimensional array"
                 setattr(self, name, a)
         if self.per_variable and np.ndim(self.lb) == 1 and np.ndim(self.ub) == 1:
             assert self.lb.size == self.ub.size, "BoxConstraints: lb and ub differ in length"
 
     @property
     def per_variable(self) -> bool:
-        return np.ndim(self.lb) == 1 or np.ndim(self.ub) == 1
+        return np.ndim(self.lb) >= 1 or np.ndim(self.ub) >= 1
+
+    def rows(self, batch: int, D: int):
+        """(lbs, ubs) as [batch, D] arrays (primalbarriermethodbatch): a float or a length-D array is every problem's."""
+        out = []
+        for name in ("lb", "ub"):
+            v = getattr(self, name)
+            assert np.ndim(v) == 0 or v.shape in ((D,), (batch, D)), \
+                f"BoxConstraints.{name} has shape {np.shape(v)} for {batch} problems of {D} variables"
+            out.append(np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (batch, D))))
+        return out[0], out[1]
 
     def vectors(self, D: int):
         """(lbs, ubs) as length-D arrays; AssertionError if an array bound has another length."""
@@ -1267,6 +1367,13 @@ class BoxConstraints:
 
     def n_constraints(self, D: int) -> int:
         return 2 * D
+
+
+@dataclass
+class BatchBoxConstraints(BoxConstraints):
+    """BoxConstraints for primalbarriermethodbatch whose array bounds may also be [batch, D]: every problem its own set of bounds
+    (a float or a length-D array is every problem's, as in BoxConstraints)."""
+    _NDIM = (1, 2)
 
 
 _BUILTIN_BASE_PARAMS = {"ObjQuadDiag": 1, "ObjRosenPaired": 0, "ObjBooth": 0}
@@ -1445,6 +1552,108 @@ def primalbarriermethod(constraints: BoxConstraints, f0df0: str, x_initial: Sequ
             t = bc.barrier_growth_factor * t                        # :240
         return assemble("max_iters_reached", bc.max_iters, t)
     finally:
+        obj.close()
+
+
+def _refuse_unbatched(config: CGConfig, linesearch_config: LineSearchConfig):
+    """What the batched device loop does not run, in the library's words (check_batch_config) — before any work is done."""
+    if isinstance(config.β_config, LBFGS):
+        raise _lib.CgoError(1, "batched solves: β = L-BFGS is not supported (CG flavours only)")
+    if isinstance(config.β_config, BroydenFamily):
+        raise _lib.CgoError(1, "batched solves: β = Broyden family is not supported (CG flavours only)")
+    if isinstance(linesearch_config, Backtracking):
+        raise _lib.CgoError(1, "batched solves: the Backtracking line search is not supported (StrongWolfeBisection or WolfeBisection)")
+
+
+def primalbarriermethodbatch(constraints: BoxConstraints, f0df0: str, X_initial, centering_config: CGConfig,
+                             linesearch_config: LineSearchConfig, barrier_config: PrimalBarrierConfig, *rerun_config_tuples,
+                             params=None, ctx: Optional[Context] = None) -> List[PrimalBarrierResults]:
+    """primalbarriermethod for `batch` problems at once: X_initial is [batch, D], `params` the base objective's own [batch, D]
+    rows (one array per slot), `constraints` one box for all (floats), one set of bounds for all (length-D arrays) or every
+    problem's own ([batch, D] arrays: a BatchBoxConstraints).  The loop of primal_barrier.jl:156-255 with every scalar a [batch] array: t (verifyt0
+    from ONE batched evaluation of f0), the status of the last stage, the stop tests.  Every stage of every centering step is
+    ONE batched solve (`Batch.solve`) with scalars = t and active = the problems still running (for a rerun stage: those whose
+    last status is not "success", from the previous stage's minimizers); `X_initial` is never updated, as in the reference.
+    Returns what primalbarriermethod returns for each problem.  Configs the batched device loop does not run raise CgoError
+    before any work (no loop of single solves)."""
+    X0 = np.ascontiguousarray(np.asarray(X_initial, dtype=np.float64))
+    if X0.ndim != 2:
+        raise ValueError("X_initial must be [batch, D]")
+    batch, D = X0.shape
+    _refuse_unbatched(centering_config, linesearch_config)
+    for tup in rerun_config_tuples:
+        _refuse_unbatched(tup[0], tup[1])
+    own = [_batch_rows(f"params[{j}]", v, (batch, D)) for j, v in enumerate(params or [])]
+    bar_rows = list(own)
+    if constraints.per_variable:
+        assert len(own) + 2 <= MAX_PARAM_SLOTS, f"{len(own)} parameter vectors of the base objective leave no two slots for the bounds"
+        lbs, ubs = constraints.rows(batch, D)
+        bar_rows += [lbs, ubs]
+    else:
+        lbs, ubs = constraints.rows(batch, D)
+    bc = barrier_config
+    mu = bc.barrier_growth_factor
+    stages = [(centering_config, linesearch_config)] + [(t[0], t[1]) for t in rerun_config_tuples]
+    rets: List[List[List[Results]]] = [[] for _ in range(batch)]     # [problem][centering step][stage]
+
+    def assemble(b, status, it, t):                                   # assembleresults!  (:9-35)
+        total = sum(int(e) for rr in rets[b][:it] for r in rr for e in r.trace.objective_evals)
+        return PrimalBarrierResults(rets[b][:it], status, it, float(t), total)
+
+    out: List[Optional[PrimalBarrierResults]] = [None] * batch
+    running = np.ones(batch, dtype=bool)
+    infeasible = np.any(X0 - ubs >= 0.0, axis=1) | np.any(lbs - X0 >= 0.0, axis=1)      # :178-191
+    for b in np.flatnonzero(infeasible):
+        out[b] = assemble(b, "infeasible_start", 0, bc.t_initial)
+        running[b] = False
+    if not running.any():
+        return out
+    # (the models' own parameter vectors are never read by a batched solve: their slots stay reserved and unset)
+    obj = ElementwiseObjective(D, barrier_objective_source(f0df0, constraints), param=[None] * len(bar_rows) if bar_rows else None, ctx=ctx)
+    B = None
+    try:
+        t = np.full(batch, float(bc.t_initial))
+        if not math.isfinite(bc.t_initial) or bc.t_initial < 0.0:     # verifyt0  (:259-276): f0(x_initial) of every problem, one launch
+            base = ElementwiseObjective(D, _base_objective_source(f0df0), param=[None] * len(own) if own else None, ctx=ctx)
+            try:
+                with Batch(base, own, batch) as B0:   # max_iters = 0: the initial evaluation (optim.jl:31) and nothing after it
+                    c0 = CGConfig(centering_config.ϵ, centering_config.β_config, 0, False, DisableTrace())
+                    r0 = B0.solve(np.where(running[:, None], X0, X0[np.flatnonzero(running)[0]]), c0, linesearch_config)
+                f_x0 = np.array([r.objective for r in r0])
+            finally:
+                base.close()
+            t = (f_x0 - bc.inf_f0_lb) * mu
+        B = Batch(obj, bar_rows, batch)
+        for i in range(1, bc.max_iters + 1):                          # :208
+            step: List[List[Results]] = [[] for _ in range(batch)]
+            act, X = running.copy(), X0
+            for k, (cfg_k, ls_k) in enumerate(stages):                # minimizeobjectivererun  (optim.jl:173-208)
+                if k > 0:
+                    act = act & np.array([bool(step[b]) and step[b][-1].status != "success" for b in range(batch)])
+                    if not act.any():
+                        break
+                    X = np.array([step[b][-1].minimizer if act[b] else X0[b] for b in range(batch)])
+                rs = B.solve(X, cfg_k, ls_k, scalars=np.where(running, t, 1.0), active=act)
+                for b in np.flatnonzero(act):
+                    step[b].append(rs[b])
+            for b in np.flatnonzero(running):
+                rets[b].append(step[b])
+                if step[b][-1].status != "success":
+                    out[b] = assemble(b, "centering_step_issue", i, t[b])   # :215-223
+                elif constraints.n_constraints(D) / t[b] < bc.barrier_tol:   # :229
+                    out[b] = assemble(b, "success", i, t[b])
+                else:
+                    t[b] = mu * t[b]                                  # :240
+                    continue
+                running[b] = False
+            if not running.any():
+                break
+        for b in np.flatnonzero(running):
+            out[b] = assemble(b, "max_iters_reached", bc.max_iters, t[b])
+        return out
+    finally:
+        if B is not None:
+            B.close()
         obj.close()
 
 

@@ -27,6 +27,14 @@ static const void *batch_kernel_for(int obj_kind, int npts) {
     default: return nullptr;
     }
 }
+static const void *batch_grad_kernel_for(int obj_kind) {
+    switch (obj_kind) {
+#define ROW(KIND, T) case KIND: return (const void *)k_batch_grad<T>;
+    CGO_OBJ_ROWS(ROW)
+#undef ROW
+    default: return nullptr;
+    }
+}
 static int batch_vecs(int nparams) { return 2 + nparams; }   // x, u and the parameter slots
 
 // res_plan's arithmetic for ONE workgroup that holds a whole problem: what the device gives a block, minus the kernel's static
@@ -55,46 +63,31 @@ int64_t HipBackend::batch_max_n(HipCtx *ctx, int obj_kind, const RtcModule *rtc)
     return ld_max < 2 ? 0 : ld_max;
 }
 
-int HipBackend::batch_begin(int64_t batch, int64_t n, const double *x0, const double *const *params, int64_t max_iters, bool trace) {
+// "allocate + slots": the rows of every parameter slot go up ONCE; the states, f_x0 and (where scalars per problem will come) s0v
+// are allocated.  batch_reset below starts a solve on them, any number of times.
+int HipBackend::batch_alloc(int64_t batch, int64_t n, const double *const *params) {
     const int64_t ld = n + (n & 1);
-    if (batch < 1 || n < 1 || obj_->n_local != batch * ld || !rmode_) { set_error("internal: batched solve on a backend of another shape"); return CGO_ESTATE; }
+    if (batch < 1 || n < 1 || obj_->n_local != batch * ld || !rmode_ || bat_st_) { set_error("internal: batched solve on a backend of another shape"); return CGO_ESTATE; }
     HIPCHK(hipSetDevice(ctx_->device));
-    bat_count_ = batch; bat_n_ = n; bat_ld_ = ld; bat_trace_ = trace;
-    bat_rec_stride_ = trace ? std::max<int64_t>(max_iters, 1) : 0;   // (no trace: one slice's worth, sized by the first launch)
+    bat_count_ = batch; bat_n_ = n; bat_ld_ = ld;
     bat_lds_ = (size_t)ld * 8 * (size_t)batch_vecs(obj_->nparams());
     // rows padded to ld.  No pass reads the padding element (the odd tail is the workgroup's own element n − 1); the ONE
     // gradient launch over the concatenated rows (batch_results) does evaluate it.  Built-in objectives: zero in x, u and the
     // parameter vector, ∇f = D·x = 0 there.  A user's body is never evaluated on data the user did not supply — log(p), 1/p at
     // a zero would put a NaN into that launch — so there the padding of x and of every slot repeats element n − 1 of its row
     // (u stays zero).
-    const bool user = obj_->kind == CGO_OBJ_USER;
     std::vector<double> rows((size_t)batch * (size_t)ld, 0.0);
     const size_t nb = rows.size() * sizeof(double);
-    auto fill_rows = [&](const double *src) {
-        for (int64_t b = 0; b < batch; ++b) {
-            std::memcpy(rows.data() + (size_t)b * ld, src + (size_t)b * n, sizeof(double) * (size_t)n);
-            if (ld > n) rows[(size_t)b * ld + n] = user ? src[(size_t)b * n + n - 1] : 0.0;
-        }
-    };
-    fill_rows(x0);
-    HIPCHK(hipMemcpyAsync(xc_, rows.data(), nb, hipMemcpyHostToDevice, ctx_->stream));
-    HIPCHK(hipMemsetAsync(uc_, 0, nb, ctx_->stream));
-    HIPCHK(hipStreamSynchronize(ctx_->stream));
     for (int j = 0; j < obj_->nparams(); ++j) {
         if (!params || !params[j]) { set_error("internal: batched solve without its parameter rows"); return CGO_ESTATE; }
-        fill_rows(params[j]);
+        batch_fill_rows(rows, params[j]);
         HIPCHK(hipMemcpyAsync(obj_->p[j].p, rows.data(), nb, hipMemcpyHostToDevice, ctx_->stream));
         HIPCHK(hipStreamSynchronize(ctx_->stream));
         obj_->p_set[j] = true;
     }
-    std::vector<ResState> st((size_t)batch);
-    for (auto &s : st) { std::memset(&s, 0, sizeof s); s.a_initial = NAN; s.reason = RES_FRESH; }   // optim.jl:47
     HIPCHK(hipMalloc((void **)&bat_st_, sizeof(ResState) * (size_t)batch));
     HIPCHK(hipMalloc((void **)&bat_fx0_, sizeof(double) * (size_t)batch));
-    HIPCHK(hipMemcpy(bat_st_, st.data(), sizeof(ResState) * (size_t)batch, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(bat_fx0_, 0, sizeof(double) * (size_t)batch));
-    if (trace) HIPCHK(hipMalloc((void **)&bat_recs_, sizeof(ResRecord) * (size_t)batch * (size_t)bat_rec_stride_));
-    if (user) {   // (a module's kernel takes its dynamic LDS as launched, as the resident solver's does)
+    if (obj_->kind == CGO_OBJ_USER) {   // (a module's kernel takes its dynamic LDS as launched, as the resident solver's does)
         if (!obj_->rtc || !obj_->rtc->batch(3)) { set_error("internal: batched solve before the objective's batch program was compiled"); return CGO_ESTATE; }
         return CGO_OK;
     }
@@ -104,19 +97,75 @@ int HipBackend::batch_begin(int64_t batch, int64_t n, const double *x0, const do
     return CGO_OK;
 }
 
+void HipBackend::batch_fill_rows(std::vector<double> &rows, const double *src) const {
+    const bool user = obj_->kind == CGO_OBJ_USER;
+    for (int64_t b = 0; b < bat_count_; ++b) {
+        std::memcpy(rows.data() + (size_t)b * bat_ld_, src + (size_t)b * bat_n_, sizeof(double) * (size_t)bat_n_);
+        if (bat_ld_ > bat_n_) rows[(size_t)b * bat_ld_ + bat_n_] = user ? src[(size_t)b * bat_n_ + bat_n_ - 1] : 0.0;
+    }
+}
+
+// "reset for a solve": x ← x0, u ← 0, every ACTIVE problem's state fresh (optim.jl:47) and its f_x0 zero; an inactive problem
+// (active[b] == 0) is preset RES_STOP, so that its workgroup returns at once and nothing of it is read afterwards.  scalars:
+// every problem's own objective scalar for this solve (null: the objective's s0 for all).
+int HipBackend::batch_reset(const double *x0, const double *scalars, const unsigned char *active, int64_t max_iters, bool trace) {
+    if (!bat_st_) { set_error("internal: batch_reset before batch_alloc"); return CGO_ESTATE; }
+    HIPCHK(hipSetDevice(ctx_->device));
+    const int64_t batch = bat_count_;
+    bat_trace_ = trace;
+    if (trace) {   // (no trace: one slice's worth, sized by the first launch)
+        const int64_t stride = std::max<int64_t>(max_iters, 1);
+        if (int rc = batch_recs_reserve(stride)) return rc;
+    }
+    std::vector<double> rows((size_t)batch * (size_t)bat_ld_, 0.0);
+    const size_t nb = rows.size() * sizeof(double);
+    batch_fill_rows(rows, x0);
+    HIPCHK(hipMemcpyAsync(xc_, rows.data(), nb, hipMemcpyHostToDevice, ctx_->stream));
+    HIPCHK(hipMemsetAsync(uc_, 0, nb, ctx_->stream));
+    HIPCHK(hipStreamSynchronize(ctx_->stream));
+    std::vector<ResState> st((size_t)batch);
+    for (int64_t b = 0; b < batch; ++b) {
+        ResState &s = st[(size_t)b];
+        std::memset(&s, 0, sizeof s);
+        s.a_initial = NAN;   // optim.jl:47
+        s.reason = (!active || active[b]) ? RES_FRESH : RES_STOP;
+    }
+    HIPCHK(hipMemcpy(bat_st_, st.data(), sizeof(ResState) * (size_t)batch, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(bat_fx0_, 0, sizeof(double) * (size_t)batch));
+    bat_s0v_on_ = scalars != nullptr;
+    if (scalars) {
+        if (!bat_s0v_) HIPCHK(hipMalloc((void **)&bat_s0v_, sizeof(double) * (size_t)batch));
+        HIPCHK(hipMemcpy(bat_s0v_, scalars, sizeof(double) * (size_t)batch, hipMemcpyHostToDevice));
+    }
+    return CGO_OK;
+}
+
+// the records: [batch][stride], grown when a solve needs a longer row
+int HipBackend::batch_recs_reserve(int64_t stride) {
+    const size_t need = (size_t)bat_count_ * (size_t)stride;
+    if (bat_recs_ && bat_recs_cap_ < need) { HIPCHK(hipFree(bat_recs_)); bat_recs_ = nullptr; bat_recs_cap_ = 0; }
+    if (!bat_recs_) { HIPCHK(hipMalloc((void **)&bat_recs_, sizeof(ResRecord) * need)); bat_recs_cap_ = need; }
+    bat_rec_stride_ = stride;
+    return CGO_OK;
+}
+
+int HipBackend::batch_begin(int64_t batch, int64_t n, const double *x0, const double *const *params, int64_t max_iters, bool trace) {
+    if (int rc = batch_alloc(batch, n, params)) return rc;
+    return batch_reset(x0, nullptr, nullptr, max_iters, trace);
+}
+
 int HipBackend::batch_launch(const ResConfig &c, int64_t budget, std::vector<ResState> &st, std::vector<double> &f_x0) {
     if (!bat_st_) { set_error("internal: batch_launch before batch_begin"); return CGO_ESTATE; }
     HIPCHK(hipSetDevice(ctx_->device));
     if (budget < 1) budget = 1;
     if (!bat_trace_) {   // nobody reads the records: the leader still writes one per completed iteration of the slice
-        if (bat_recs_ && bat_rec_stride_ < budget) { HIPCHK(hipFree(bat_recs_)); bat_recs_ = nullptr; }
-        if (!bat_recs_) { bat_rec_stride_ = budget; HIPCHK(hipMalloc((void **)&bat_recs_, sizeof(ResRecord) * (size_t)bat_count_ * (size_t)budget)); }
+        if (int rc = batch_recs_reserve(budget)) return rc;
     }
     BatchParams B{};
     B.x = xc_; B.u = uc_; B.p0 = obj_->p[0].p; B.p1 = obj_->p[1].p; B.p2 = obj_->p[2].p; B.p3 = obj_->p[3].p;
     B.st = bat_st_; B.recs = bat_recs_; B.f_x0 = bat_fx0_;
     B.n = bat_n_; B.ld = bat_ld_; B.rec_stride = bat_rec_stride_; B.rec_abs = bat_trace_ ? 1 : 0;
-    B.s0 = obj_->s0;
+    B.s0 = obj_->s0; B.s0v = bat_s0v_on_ ? bat_s0v_ : nullptr;
     B.cfg = c; B.cfg.npts = 3; B.cfg.log_on = 0;
     B.budget = budget;
     void *args[] = {&B};
@@ -162,12 +211,41 @@ int HipBackend::batch_export_row(int64_t b, HipBackend &dst, bool with_u) {
     return CGO_OK;
 }
 
-int HipBackend::batch_results(double *x, double *g) {
+// ∇f of every row with its problem's own scalar → ga_ (k_batch_grad): what the R_GRAD launch of download() is without them
+int HipBackend::batch_grad_rows() {
+    if (int rc = ensure_ga()) return rc;
+    BatchGradParams G{};
+    G.x = xc_; G.g = ga_.p; G.p0 = obj_->p[0].p; G.p1 = obj_->p[1].p; G.p2 = obj_->p[2].p; G.p3 = obj_->p[3].p;
+    G.s0v = bat_s0v_; G.n = bat_n_; G.ld = bat_ld_;
+    void *args[] = {&G};
+    if (obj_->kind == CGO_OBJ_USER) {
+        const hipFunction_t mf = obj_->rtc ? obj_->rtc->batch_grad() : nullptr;
+        if (!mf) { set_error("internal: kernel missing from the run-time compiled objective module"); return CGO_EINVAL; }
+        HIPCHK(hipModuleLaunchKernel(mf, (unsigned)bat_count_, 1, 1, BLOCK, 1, 1, 0, ctx_->stream, args, nullptr));
+    } else {
+        const void *fn = batch_grad_kernel_for(obj_->kind);
+        if (!fn) { set_error("batched solves: no k_batch_grad instantiation for this objective"); return CGO_EINVAL; }
+        HIPCHK(hipLaunchKernel(fn, dim3((unsigned)bat_count_), dim3(BLOCK), args, 0, ctx_->stream));
+    }
+    total_launches_++;
+    return CGO_OK;
+}
+
+int HipBackend::batch_results(double *x, double *g, const unsigned char *active) {
     if (!x && !g) return CGO_OK;
     const size_t rows = (size_t)bat_count_ * (size_t)bat_ld_;
     std::vector<double> xr(x ? rows : 0), gr(g ? rows : 0);
-    if (int rc = download(x ? xr.data() : nullptr, g ? gr.data() : nullptr)) return rc;   // ONE gradient launch over every row
+    if (bat_s0v_on_) {   // a scalar per problem: a workgroup per row, each with its own
+        HIPCHK(hipSetDevice(ctx_->device));
+        if (g) { if (int rc = batch_grad_rows()) return rc; }
+        if (x) HIPCHK(hipMemcpyAsync(xr.data(), xc_, sizeof(double) * rows, hipMemcpyDeviceToHost, ctx_->stream));
+        if (g) HIPCHK(hipMemcpyAsync(gr.data(), ga_.p, sizeof(double) * rows, hipMemcpyDeviceToHost, ctx_->stream));
+        HIPCHK(hipStreamSynchronize(ctx_->stream));
+    } else {
+        if (int rc = download(x ? xr.data() : nullptr, g ? gr.data() : nullptr)) return rc;   // ONE gradient launch over every row
+    }
     for (int64_t b = 0; b < bat_count_; ++b) {
+        if (active && !active[b]) continue;   // an inactive problem's rows of the output stay as the caller left them
         if (x) std::memcpy(x + (size_t)b * bat_n_, xr.data() + (size_t)b * bat_ld_, sizeof(double) * (size_t)bat_n_);
         if (g) std::memcpy(g + (size_t)b * bat_n_, gr.data() + (size_t)b * bat_ld_, sizeof(double) * (size_t)bat_n_);
     }

@@ -988,25 +988,30 @@ static int check_batch_call(cgo_ctx *ctx, const cgo_cg_config *cfg, const cgo_ls
 }
 
 // The concatenated problems: ONE objective `cat` (n_local = batch · ld, its parameter slots allocated) and backend whose x, u and
-// parameter slots are the [batch][ld] rows — launched until every problem is finished or handed back, then everything after
-// the launch loop: statuses from stop_status, traces, and the hand-back of the problems the device loop does not finish to ONE
-// ordinary solver on `make_hobj`'s objective of size n (created on the first hand-back).
-static int run_batch_on(cgo_ctx *ctx, HipObjective &cat, int64_t n, int64_t batch, const double *x0, const double *const *params,
-                        const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out,
-                        const std::function<int(cgo_objective **)> &make_hobj) {
+// parameter slots are the [batch][ld] rows.  batch_backend_on makes the backend and uploads the slot rows; batch_solve_on starts
+// a solve on it — launched until every active problem is finished or handed back, then everything after the launch loop:
+// statuses from stop_status, traces, and the hand-back of the problems the device loop does not finish to ONE ordinary solver on
+// `make_hobj`'s objective of size n (created on the first hand-back), which takes the problem's own scalar where the call has them.
+static int batch_backend_on(cgo_ctx *ctx, HipObjective &cat, int64_t n, int64_t batch, const double *const *params, HipBackend &be) {
     cgo_solver_policy pol;
     { std::string pw; if (int rc = resolve_policy(ctx, nullptr, pol, pw)) { set_error(pw); return rc; } }
-    HipBackend be(&ctx->c, &cat);
     be.set_policy(pol);
     be.set_rmode(true);
     if (int rc = be.alloc()) return rc;
-    if (int rc = be.batch_begin(batch, n, x0, params, cfg->max_iters, cfg->trace_enabled != 0)) return rc;
+    return be.batch_alloc(batch, n, params);
+}
+
+static int batch_solve_on(cgo_ctx *ctx, HipBackend &be, int64_t n, int64_t batch, const double *x0, const double *scalars,
+                          const unsigned char *active, const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters,
+                          cgo_batch_results *out, const std::function<int(cgo_objective **)> &make_hobj) {
+    auto on = [&](int64_t b) { return !active || active[b] != 0; };
+    if (int rc = be.batch_reset(x0, scalars, active, cfg->max_iters, cfg->trace_enabled != 0)) return rc;
     BatchRun run;
     if (int rc = run_batch(&be, *cfg, *ls, batch, slice_iters, run)) { if (rc == CGO_ESTATE) set_error("internal: a batched launch left a problem in a state the driver does not know"); return rc; }
     out->launches = run.launches;
     // finished on the device: the status follows from the state (stop_status); minimizer and gradient of EVERY row from one
     // download — the rows the host engine finishes below are overwritten with its own
-    if (int rc = be.batch_results(out->minimizer, out->gradient)) return rc;
+    if (int rc = be.batch_results(out->minimizer, out->gradient, active)) return rc;
     const bool trace = cfg->trace_enabled != 0;
     const int64_t mi = cfg->max_iters;
     std::vector<ResRecord> recs;
@@ -1015,7 +1020,7 @@ static int run_batch_on(cgo_ctx *ctx, HipObjective &cat, int64_t n, int64_t batc
     const int64_t stride = be.batch_rec_stride();
     for (int64_t b = 0; b < batch; ++b) {
         const ResState &s = run.st[(size_t)b];
-        if (s.reason != RES_STOP) continue;
+        if (s.reason != RES_STOP || !on(b)) continue;
         int64_t ran = 0;
         const int st = stop_status(s.it, mi, s.f_x, s.norm, cfg->eps, run.f_x0[(size_t)b], ran);
         if (st == CGO_INCOMPLETE) { set_error("internal: a batched problem stopped on the device in a state that does not stop"); return CGO_ESTATE; }
@@ -1038,7 +1043,7 @@ static int run_batch_on(cgo_ctx *ctx, HipObjective &cat, int64_t n, int64_t batc
     int rc = CGO_OK;
     for (int64_t b = 0; b < batch && !rc; ++b) {
         const ResState &s = run.st[(size_t)b];
-        if (s.reason != RES_HOST) continue;
+        if (s.reason != RES_HOST || !on(b)) continue;
         if (!hs) {
             if ((rc = make_hobj(&hobj))) break;
             cgo_solver_policy hp;
@@ -1046,6 +1051,7 @@ static int run_batch_on(cgo_ctx *ctx, HipObjective &cat, int64_t n, int64_t batc
             hp.resident = 0;
             if ((rc = make_solver(ctx, hobj, cfg, ls, nullptr, &hp, &hs))) break;
         }
+        if (scalars) { if ((rc = cgo_objective_set_scalar(hobj, 0, scalars[b]))) break; }   // (the call's own objective, never the model)
         if (s.it == 0) {   // nothing completed: the problem's own start, as a single solve has it
             if ((rc = be.batch_export_row(b, *hs->be, false))) break;
             if ((rc = hs->sv->start())) break;
@@ -1077,6 +1083,14 @@ static int run_batch_on(cgo_ctx *ctx, HipObjective &cat, int64_t n, int64_t batc
     if (hobj) cgo_objective_destroy(hobj);
     if (rc) set_error(keep);
     return rc;
+}
+
+static int run_batch_on(cgo_ctx *ctx, HipObjective &cat, int64_t n, int64_t batch, const double *x0, const double *const *params,
+                        const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out,
+                        const std::function<int(cgo_objective **)> &make_hobj) {
+    HipBackend be(&ctx->c, &cat);
+    if (int rc = batch_backend_on(ctx, cat, n, batch, params, be)) return rc;
+    return batch_solve_on(ctx, be, n, batch, x0, nullptr, nullptr, cfg, ls, slice_iters, out, make_hobj);
 }
 
 int cgo_minimize_batch(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
@@ -1120,18 +1134,18 @@ int64_t cgo_batch_max_n_obj(cgo_objective *model) {
     } catch (...) { return 0; }
 }
 
-int cgo_minimize_batch_obj(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *x0, const double *const *params,
-                           int32_t n_params, const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters,
-                           cgo_batch_results *out) {
-    API_GUARD_BEGIN
-    REQUIRE(ctx && model && x0 && cfg && ls && out, "null argument");
-    out->launches = 0; out->handed_back = 0;
+// What every entry point on a model refuses of it, and what it builds from it: the concatenated objective `cat` — it shares the
+// model's compiled module, its scalar and its cost class; the slots are its own [batch][ld] rows — and the objective of size n a
+// handed-back problem is finished on.
+static int check_batch_model(cgo_ctx *ctx, cgo_objective *model) {
     REQUIRE(model->o.kind == CGO_OBJ_USER && model->o.rtc,
             "batched solves: the model must be a run-time compiled objective (cgo_objective_create_from_source[_ex]); built-in objectives: cgo_minimize_batch");
     REQUIRE(model->o.ctx == &ctx->c, "batched solves: the model belongs to another context");
     REQUIRE(batch_model_whole(model), "batched solves: a sharded or multi-rank model is not supported (n_global = n_local = the size of ONE problem, one rank only)");
+    return CGO_OK;
+}
+static int batch_model_cat(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *const *params, int32_t n_params, HipObjective &cat) {
     const int64_t n = model->o.n_local;
-    if (int rc = check_batch_call(ctx, cfg, ls, n, batch, slice_iters)) return rc;
     const int K = model->o.nparams();
     if (n_params != K) { set_error("batched solves: n_params = " + std::to_string(n_params) + ", the model reads " + std::to_string(K) + " parameter slots"); return CGO_EINVAL; }
     REQUIRE(K == 0 || params, "batched solves: params is null, the model reads parameter slots");
@@ -1144,16 +1158,98 @@ int cgo_minimize_batch_obj(cgo_ctx *ctx, cgo_objective *model, int64_t batch, co
         if (n > max_n) { set_error("batched solves: n = " + std::to_string(n) + " exceeds what one workgroup's LDS holds (cgo_batch_max_n_obj = " + std::to_string(max_n) + ")"); return CGO_EINVAL; }
     }
     const int64_t ld = n + (n & 1);
-    HipObjective cat;   // shares the model's compiled module, its scalar and its cost class; the slots are its own [batch][ld] rows
     cat.ctx = &ctx->c; cat.kind = CGO_OBJ_USER; cat.n_global = cat.n_local = batch * ld; cat.offset = 0;
     cat.rtc = model->o.rtc; cat.user_nparams = K; cat.s0 = model->o.s0; cat.user_cheap = model->o.user_cheap;
     for (int j = 0; j < K; ++j) { if (int rc = cat.p[j].alloc((size_t)(batch * ld))) return rc; }
-    return run_batch_on(ctx, cat, n, batch, x0, params, cfg, ls, slice_iters, out, [&](cgo_objective **h) {
+    return CGO_OK;
+}
+static std::function<int(cgo_objective **)> batch_model_hobj(cgo_ctx *ctx, cgo_objective *model) {
+    return [ctx, model](cgo_objective **h) {
         // (the module cache makes this free while the model lives: same device, text and n_params)
-        if (int rc = cgo_objective_create_from_source_ex(ctx, model->o.rtc->user_source.c_str(), K, n, 0, n, h)) return rc;
+        const int64_t n = model->o.n_local;
+        if (int rc = cgo_objective_create_from_source_ex(ctx, model->o.rtc->user_source.c_str(), model->o.nparams(), n, 0, n, h)) return rc;
         (*h)->o.s0 = model->o.s0; (*h)->o.user_cheap = model->o.user_cheap;
         return (int)CGO_OK;
-    });
+    };
+}
+
+int cgo_minimize_batch_obj(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *x0, const double *const *params,
+                           int32_t n_params, const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters,
+                           cgo_batch_results *out) {
+    API_GUARD_BEGIN
+    REQUIRE(ctx && model && x0 && cfg && ls && out, "null argument");
+    out->launches = 0; out->handed_back = 0;
+    if (int rc = check_batch_model(ctx, model)) return rc;
+    const int64_t n = model->o.n_local;
+    if (int rc = check_batch_call(ctx, cfg, ls, n, batch, slice_iters)) return rc;
+    HipObjective cat;
+    if (int rc = batch_model_cat(ctx, model, batch, params, n_params, cat)) return rc;
+    return run_batch_on(ctx, cat, n, batch, x0, params, cfg, ls, slice_iters, out, batch_model_hobj(ctx, model));
+    API_GUARD_END
+}
+
+// ---- a batch that stays on the device between solves ---------------------------------------------------------------------------
+// The concatenated objective, its backend and the uploaded slot rows of cgo_minimize_batch_obj, kept: every cgo_batch_solve is
+// then "reset for a solve" (HipBackend::batch_reset) and the launch loop, hand-backs and result assembly of the one-shot call.
+struct cgo_batch {
+    cgo_ctx *ctx = nullptr;
+    cgo_objective *model = nullptr;   // a reference is held: its scalar and cost class are read at every solve
+    int64_t n = 0, batch = 0;
+    HipObjective cat;
+    HipBackend *be = nullptr;
+    ~cgo_batch() { delete be; }
+};
+
+int cgo_batch_open(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *const *params, int32_t n_params, cgo_batch **handle) {
+    API_GUARD_BEGIN
+    REQUIRE(ctx && model && handle, "null argument");
+    *handle = nullptr;
+    if (int rc = check_batch_model(ctx, model)) return rc;
+    const int64_t n = model->o.n_local;
+    REQUIRE(ctx->c.world() == 1, "batched solves: a multi-rank context is not supported (one rank only)");
+    REQUIRE(batch >= 1, "batched solves: batch must be ≥ 1");
+    REQUIRE(batch <= 0x7FFFFFFF, "batched solves: batch exceeds the largest grid");
+    REQUIRE(n >= 1, "batched solves: n must be ≥ 1");
+    std::unique_ptr<cgo_batch> h(new cgo_batch);
+    h->ctx = ctx; h->n = n; h->batch = batch;
+    if (int rc = batch_model_cat(ctx, model, batch, params, n_params, h->cat)) return rc;
+    h->be = new HipBackend(&ctx->c, &h->cat);
+    if (int rc = batch_backend_on(ctx, h->cat, n, batch, params, *h->be)) return rc;
+    h->model = model; model->refs++;
+    *handle = h.release();
+    return CGO_OK;
+    API_GUARD_END
+}
+
+int cgo_batch_solve(cgo_batch *h, const double *x0, const double *scalars, const unsigned char *active, const cgo_cg_config *cfg,
+                    const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out) {
+    API_GUARD_BEGIN
+    REQUIRE(h && x0 && cfg && ls && out, "null argument");
+    out->launches = 0; out->handed_back = 0;
+    if (int rc = check_batch_call(h->ctx, cfg, ls, h->n, h->batch, slice_iters)) return rc;
+    if (scalars)
+        for (int64_t b = 0; b < h->batch; ++b)
+            if (!std::isfinite(scalars[b])) { set_error("batched solves: scalars[" + std::to_string(b) + "] is not finite"); return CGO_EINVAL; }
+    if (active) {
+        bool any = false;
+        for (int64_t b = 0; b < h->batch && !any; ++b) any = active[b] != 0;
+        REQUIRE(any, "batched solves: active selects no problem");
+    }
+    HIPCHK2(hipSetDevice(h->ctx->c.device));
+    h->cat.s0 = h->model->o.s0; h->cat.user_cheap = h->model->o.user_cheap;
+    return batch_solve_on(h->ctx, *h->be, h->n, h->batch, x0, scalars, active, cfg, ls, slice_iters, out, batch_model_hobj(h->ctx, h->model));
+    API_GUARD_END
+}
+
+int cgo_batch_close(cgo_batch *h) {
+    API_GUARD_BEGIN
+    if (!h) return CGO_OK;
+    cgo_ctx *c = h->ctx;
+    cgo_objective *m = h->model;
+    if (c) (void)hipSetDevice(c->c.device);
+    delete h;            // (the backend before the model: its objective shares the model's module)
+    obj_unref(m);
+    return CGO_OK;
     API_GUARD_END
 }
 

@@ -163,11 +163,18 @@ class HipBackend : public VecBackend {
     static int64_t batch_max_n(HipCtx *ctx, int obj_kind, const RtcModule *rtc = nullptr);
     // params[j], j < nparams(): the [batch·n] rows of slot j
     int batch_begin(int64_t batch, int64_t n, const double *x0, const double *const *params, int64_t max_iters, bool trace);
+    // … in its two halves, for a batch that stays on the device between solves (cgo_batch_open / cgo_batch_solve): the slot rows
+    // once; then per solve x0, the states, and optionally a scalar per problem (scalars, [batch]) and which problems run
+    // (active, [batch] bytes; null: all — an inactive problem's workgroup returns at once)
+    int batch_alloc(int64_t batch, int64_t n, const double *const *params);
+    int batch_reset(const double *x0, const double *scalars, const unsigned char *active, int64_t max_iters, bool trace);
     int batch_launch(const ResConfig &c, int64_t budget, std::vector<ResState> &st, std::vector<double> &f_x0) override;
     int batch_records(int64_t b, int64_t count, std::vector<ResRecord> &out);     // the trace records of problem b's first `count` iterations (b < 0: every row)
     int64_t batch_rec_stride() const { return bat_rec_stride_; }
     int batch_export_row(int64_t b, HipBackend &dst, bool with_u);                // row b of x (u), and of every parameter slot → dst
-    int batch_results(double *x /*[batch·n]*/, double *g /*[batch·n]*/);          // dense rows; each may be nullptr
+    // dense rows; each may be nullptr; rows of inactive problems are not written.  With a scalar per problem the gradient is
+    // k_batch_grad's (a workgroup per row), otherwise the ordinary gradient launch over the concatenated rows
+    int batch_results(double *x /*[batch·n]*/, double *g /*[batch·n]*/, const unsigned char *active = nullptr);
     int64_t push_count(int kind) const { return push_counts_[kind]; }   // 0 speculated, 1 fused (g⁺ formed in the push), 2 plain
     bool sys_supported() const override { return rmode_; }
     int sys_begin() override;
@@ -411,6 +418,12 @@ class HipBackend : public VecBackend {
     ResState *bat_st_ = nullptr;             // device [batch]
     ResRecord *bat_recs_ = nullptr;          // device [batch][bat_rec_stride_]
     double *bat_fx0_ = nullptr;              // device [batch]
+    double *bat_s0v_ = nullptr;              // device [batch]: the scalars of the solve under way (bat_s0v_on_)
+    bool bat_s0v_on_ = false;
+    size_t bat_recs_cap_ = 0;                // records allocated
+    void batch_fill_rows(std::vector<double> &rows, const double *src) const;
+    int batch_recs_reserve(int64_t stride);
+    int batch_grad_rows();
     bool prof_on_ = false;
     struct ProfSlot { hipEvent_t e0 = nullptr, e1 = nullptr; int kk = -1; double bytes = 0; };
     std::vector<ProfSlot> ring_;

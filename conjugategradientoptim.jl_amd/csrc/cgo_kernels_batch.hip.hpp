@@ -11,6 +11,8 @@
 //     accept_dir_trial are ResDev's own (cgo_kernels_resident.hip.hpp), the workgroup's row is the total, its lane 0 the leader;
 //   * when the slice ends: x, u back in place if an iteration completed, the state to st[b], the records of the completed
 //     iterations (written by the leader as they completed) in recs[b].
+// The objective's scalar is the launch's (s0) or the problem's own (s0v[b]): a barrier weight, a regularisation strength, a
+// temperature per problem.  With scalars per problem the results' gradient is k_batch_grad's (below), a workgroup per row too.
 //
 // Workgroups never wait for one another: no atomics, no polling, no read of another problem's rows.  More workgroups than CUs
 // simply queue.  A launch is bounded by `budget` outer iterations per problem, each by the line search's own limits.
@@ -32,6 +34,7 @@ struct BatchParams {
     ResConfig cfg;
     long long budget;
     const double *p1, *p2, *p3;               // [batch][ld]: parameter slots 1–3 (run-time compiled objectives with kParams > 1 only)
+    const double *s0v;                        // [batch]: every problem's own objective scalar; null: s0 is every problem's
 };
 
 template <class Obj, int NPTS>
@@ -62,7 +65,7 @@ __global__ __launch_bounds__(BLOCK, 1) void k_batch(const BatchParams B) {
     }
     __syncthreads();
     ResParams Q{};   // what ResDev reads of it in its SOLO form: the stride of the parameter slots, the objective's scalar, no clocks
-    Q.n = B.n; Q.chunk = B.ld; Q.s0 = B.s0; Q.timing = 0;
+    Q.n = B.n; Q.chunk = B.ld; Q.s0 = B.s0v ? B.s0v[b] : B.s0; Q.timing = 0;
     ResDev<Obj, NPTS, false, true> v{Q, xs, us, ps, (int)(B.n >> 1), (B.n & 1) != 0, 0ull, tot, fs, 0, 0, 0};
     ResConfig cfg = B.cfg;
     // (as k_resident: the loop state is FP64 arithmetic throughout — into VGPRs once, opaquely; see the note there)
@@ -118,6 +121,52 @@ __global__ __launch_bounds__(BLOCK, 1) void k_batch(const BatchParams B) {
     if (tid == 0) s_out = s;
     __syncthreads();
     if (tid < WS) reinterpret_cast<unsigned long long *>(B.st + b)[tid] = reinterpret_cast<const unsigned long long *>(&s_out)[tid];
+}
+
+// ∇f of every problem at its x, with the problem's own scalar: Results.gradient of a batched solve whose problems differ in
+// s0 (without scalars per problem it is ONE ordinary R_GRAD launch over the concatenated rows, batch_results).  blockIdx.x = the
+// problem; row b of x and of every slot the objective reads comes straight from HBM, row b of g goes back; the pair and odd-tail
+// bodies are those of the R_GRAD launch (cg_pair, cg_single's line).  The padding element of an odd n is neither read nor written.
+struct BatchGradParams {
+    const double *x; double *g;               // [batch][ld]
+    const double *p0, *p1, *p2, *p3;          // [batch][ld], the slots the objective reads
+    const double *s0v;                        // [batch]
+    long long n, ld;
+};
+
+template <class Obj>
+__global__ __launch_bounds__(BLOCK) void k_batch_grad(const BatchGradParams G) {
+    const int tid = threadIdx.x;
+    const long long b = blockIdx.x, lo = b * G.ld;
+    const double s0 = G.s0v[b];
+    RParams rp;
+    rp.a_acc = 0.0; rp.beta = 0.0; rp.s0 = s0; rp.n = 0; rp.nrep = 0;
+#pragma unroll
+    for (int j = 0; j < MAXP; ++j) rp.a[j] = 0.0;
+    constexpr int K = obj_nparams<Obj>();
+    const ParamPtrs pl{K > 0 ? G.p0 + lo : nullptr, K > 1 ? G.p1 + lo : nullptr, K > 2 ? G.p2 + lo : nullptr, K > 3 ? G.p3 + lo : nullptr};
+    const double *xr = G.x + lo;
+    double *gr = G.g + lo;
+    const long long npairs = G.n >> 1;
+    for (long long i0 = 0; i0 < npairs; i0 += BLOCK) {   // (uniform trip count, per-lane guard: k_batch's note)
+        const long long i = i0 + tid;
+        if (i < npairs) {
+            d2 xa = ldg2<false>(xr, i), ua = d2{0.0, 0.0};
+            const PV<Obj> pa = pv_load<Obj, false>(pl, i);
+            double acc[RW<1>::W] = {};
+            bool wx = false, wu = false;
+            d2 g = d2{0.0, 0.0};
+            cg_pair<Obj, R_GRAD, 1>(rp, xa, ua, pa, acc, wx, wu, g);
+            stg2<false>(gr, i, g);
+        }
+    }
+    if ((G.n & 1) && tid == 0) {   // the odd tail element, as cg_single's R_GRAD line forms it
+        const long long i = G.n - 1;
+        const PS<Obj> p = ps_load<Obj>(pl, i);
+        double f0 = 0.0, g = 0.0;
+        obj_eval1<Obj>(xr[i], p, s0, f0, g);
+        gr[i] = g;
+    }
 }
 
 }  // namespace dev

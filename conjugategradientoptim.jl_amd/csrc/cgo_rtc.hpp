@@ -26,6 +26,7 @@ struct RtcModule {
     // k_batch<UserObjective, npts> (batched solves, cgo_rtc_batch.hip): a program of its own as well, compiled on the first
     // batched solve on the objective (rtc_compile_batch) — an objective that never batches does not pay for it
     hipFunction_t batch(int npts) const;
+    hipFunction_t batch_grad() const;         // k_batch_grad<UserObjective>, in the same program
     hipModule_t batch_mod = nullptr;
     std::string user_source;
     int n_params = 0;   // parameter slots the objective was created with (0 … CGO_MAX_PARAM_SLOTS)

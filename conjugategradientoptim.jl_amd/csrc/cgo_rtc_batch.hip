@@ -1,5 +1,6 @@
 // cgo_rtc_batch.hip — batched solves on a run-time compiled objective: k_batch<UserObjective, NPTS> (cgo_kernels_batch.hip.hpp,
-// embedded with the other kernel templates) for the rows of CGO_BATCH_ROWS, as a SECOND program of the objective's module.
+// embedded with the other kernel templates) for the rows of CGO_BATCH_ROWS, and k_batch_grad<UserObjective> beside them, as a
+// SECOND program of the objective's module.
 //
 // k_batch is a 512-VGPR kernel that takes hiprtc about as long as k_resident: it is not part of the program every user
 // objective compiles at creation (cgo_rtc.hip), but compiled from the kept source on the first batched solve and kept on
@@ -24,6 +25,11 @@ hipFunction_t RtcModule::batch(int npts) const {
     return f;
 }
 
+hipFunction_t RtcModule::batch_grad() const {
+    auto it = fn.find("batch:grad");
+    return it != fn.end() ? it->second : nullptr;
+}
+
 int rtc_compile_batch(RtcModule &m, std::string &log) {
     static std::mutex mu;   // (objectives of one text share the module: two first batched solves must not both build it)
     std::lock_guard<std::mutex> lock(mu);
@@ -33,6 +39,7 @@ int rtc_compile_batch(RtcModule &m, std::string &log) {
 #define ROW(NPTS) wants.push_back({"batch:" #NPTS, "cgo::dev::k_batch<cgo::dev::UserObjective, " #NPTS ">"});
     CGO_BATCH_ROWS(ROW)
 #undef ROW
+    wants.push_back({"batch:grad", "cgo::dev::k_batch_grad<cgo::dev::UserObjective>"});   // the results' gradient with a scalar per problem
     return rtc_build(rtc_program_source(m.user_source, m.n_params), "cgo_user_objective_batch.hip", wants, m.batch_mod, m.fn, log);
 }
 

@@ -597,6 +597,45 @@ function evalbacktrackcondition(condition::Armijo{Float64}, ϕ_a::Float64, a::Fl
     return v[] != 0
 end
 
+# ---- a batch that stays on the device between solves (cgo_batch_open / _solve / _close, include/cgo.h) -----------
+# ccall wrappers only: no batched driver on this side.  Rows are the library's `[batch][n]`, i.e. n × batch matrices here
+# (column-major): column b is problem b.  `out` is the caller's cgo_batch_results — every pointer caller-allocated, C_NULL allowed.
+mutable struct CBatchResults
+    objective::Ptr{Float64}
+    iters_ran::Ptr{Int64}
+    status::Ptr{Int32}
+    total_fdf_evals::Ptr{Int64}
+    minimizer::Ptr{Float64}
+    gradient::Ptr{Float64}
+    trace_objective::Ptr{Float64}
+    trace_grad_norm::Ptr{Float64}
+    trace_step_size::Ptr{Float64}
+    trace_objective_evals::Ptr{Int64}
+    launches::Int64
+    handed_back::Int64
+end
+function batch_open(model::DeviceObjective, params::Vector{Matrix{Float64}}, batch::Integer)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    rows = Ptr{Float64}[pointer(p) for p in params]
+    GC.@preserve params begin
+        check(ccall((:cgo_batch_open, libcgo), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}, Int32, Ref{Ptr{Cvoid}}),
+                    model.ctx.h, model.h, batch, rows, length(params), r))
+    end
+    return r[]
+end
+function batch_solve!(out::CBatchResults, handle::Ptr{Cvoid}, x0::Matrix{Float64}, config::CGConfig, linesearch_config::LineSearchConfig;
+                      scalars::Union{Nothing,Vector{Float64}} = nothing, active::Union{Nothing,Vector{UInt8}} = nothing, slice_iters::Integer = 0)
+    s = scalars === nothing ? Ptr{Float64}(C_NULL) : pointer(scalars)
+    a = active === nothing ? Ptr{UInt8}(C_NULL) : pointer(active)
+    GC.@preserve x0 scalars active begin
+        check(ccall((:cgo_batch_solve, libcgo), Cint,
+                    (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ref{CCGConfig}, Ref{CLSConfig}, Int64, Ref{CBatchResults}),
+                    handle, x0, s, a, ccfg(config), cls(linesearch_config), slice_iters, out))
+    end
+    return out
+end
+batch_close(handle::Ptr{Cvoid}) = check(ccall((:cgo_batch_close, libcgo), Cint, (Ptr{Cvoid},), handle))
+
 # ---- kernel-level generics (src/cg_flavours.jl:2-15, 46-170; src/cg_utils.jl:4-23) ---------------------
 function updatedir!(u::Vector{Float64}, df_x::Vector{Float64}, β::Float64; ctx::Context = defaultcontext())
     @assert length(u) == length(df_x)

@@ -537,6 +537,24 @@ int cgo_minimize_batch_obj(cgo_ctx *ctx, cgo_objective *model, int64_t batch, co
                            const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters /* 0 = library policy */,
                            cgo_batch_results *out);
 int64_t cgo_batch_max_n_obj(cgo_objective *model);   /* 0: none */
+/* A batch that STAYS ON THE DEVICE between solves: the concatenated problems of cgo_minimize_batch_obj, their slot rows uploaded
+ * once, solved any number of times — each time from its own x0, under its own config and line search, optionally with
+ *   scalars [batch]: every problem's OWN scalar slot 0 for this solve (a barrier weight t, a regularisation strength per
+ *                    problem) — NULL: the model's, for all, and every number is what cgo_minimize_batch_obj returns;
+ *   active  [batch] bytes: nonzero = the problem runs.  An inactive problem costs its workgroup one load and a return, and its
+ *                    entries of every array of `out` are left untouched — NULL: all run.
+ * The model's scalar and cost class are read at every solve; the handle holds a reference on the model.  With scalars,
+ * Results.gradient comes from a kernel of the batch program that evaluates every row with its own scalar (k_batch_grad), and a
+ * problem the host engine finishes is finished under its own scalar.
+ * cgo_batch_open refuses what cgo_minimize_batch_obj refuses of a model, a batch and params; cgo_batch_solve what it refuses of a
+ * config, and a non-finite entry of scalars and an `active` that selects no problem (CGO_EINVAL, the reason in the message). */
+typedef struct cgo_batch cgo_batch;
+int cgo_batch_open(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *const *params, int32_t n_params,
+                   cgo_batch **handle);
+int cgo_batch_solve(cgo_batch *handle, const double *x0 /* [batch*n] */, const double *scalars /* [batch] or NULL */,
+                    const unsigned char *active /* [batch] or NULL */, const cgo_cg_config *cfg, const cgo_ls_config *ls,
+                    int64_t slice_iters /* 0 = library policy */, cgo_batch_results *out);
+int cgo_batch_close(cgo_batch *handle);
 /* The stop test at the top of iteration it + 1 (optim.jl:53-80,162-169) as a function of the loop state — the one rule the
  * engine and the problems a batch finishes on the device share: the terminal status (CGO_INCOMPLETE: the iteration runs) and
  * Results.iters_ran. */
