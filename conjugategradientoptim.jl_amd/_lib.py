@@ -54,6 +54,10 @@ class BatchResultsC(C.Structure):  # cgo_batch_results (include/cgo.h)
                 ("handed_back", C.c_int64)]
 
 
+class BatchPolicyC(C.Structure):  # cgo_batch_policy (include/cgo.h)
+    _fields_ = [("size", C.c_int32), ("rows", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
 class SolverPolicyC(C.Structure):  # cgo_solver_policy (include/cgo.h)
     _fields_ = [("size", C.c_int32), ("points", C.c_int32), ("resident", C.c_int32), ("controller_depth", C.c_int32),
                 ("controller_graph", C.c_int32), ("controller_fused", C.c_int32), ("stored_gradient", C.c_int32),
@@ -202,6 +206,16 @@ SIGNATURES = {
     "cgo_batch_solve": (C.c_int, [_vp, dp, dp, C.POINTER(C.c_uint8), C.POINTER(CGConfigC), C.POINTER(LSConfigC), C.c_int64,
                                   C.POINTER(BatchResultsC)]),
     "cgo_batch_close": (C.c_int, [_vp]),
+    "cgo_batch_policy_init": (None, [C.POINTER(BatchPolicyC)]),
+    "cgo_minimize_batch_ex": (C.c_int, [_vp, C.c_int32, C.c_int64, C.c_int64, dp, dp, C.POINTER(CGConfigC), C.POINTER(LSConfigC),
+                                        C.c_int64, C.POINTER(BatchPolicyC), C.POINTER(BatchResultsC), C.POINTER(C.c_int32)]),
+    "cgo_minimize_batch_obj_ex": (C.c_int, [_vp, _vp, C.c_int64, dp, C.POINTER(dp), C.c_int32, C.POINTER(CGConfigC), C.POINTER(LSConfigC),
+                                            C.c_int64, C.POINTER(BatchPolicyC), C.POINTER(BatchResultsC), C.POINTER(C.c_int32)]),
+    "cgo_batch_open_ex": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(dp), C.c_int32, C.POINTER(BatchPolicyC), C.POINTER(_vp)]),
+    "cgo_batch_rows": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
+    "cgo_batch_max_n_ex": (C.c_int64, [_vp, C.c_int32, C.POINTER(BatchPolicyC)]),
+    "cgo_batch_max_n_obj_ex": (C.c_int64, [_vp, C.POINTER(BatchPolicyC)]),
+    "cgo_batch_rows_shape": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cgo_stop_status": (C.c_int32, [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, i64p]),
     "cgo_kernel_dir": (C.c_int, [_vp, dp, dp, C.c_double, C.c_int64, dp]),
     "cgo_kernel_beta_partials": (C.c_int, [_vp, dp, dp, dp, C.c_int64, dp]),

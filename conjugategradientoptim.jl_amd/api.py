@@ -1072,20 +1072,48 @@ def minimizeobjective(fdf, x_initial: Sequence[float], config: CGConfig,
 
 
 class BatchResults(list):
-    """The `Results` of a batched solve, one per problem, plus the two counters of the call: `launches` (k_batch launches)
-    and `handed_back` (problems the host engine finished)."""
+    """The `Results` of a batched solve, one per problem, plus the counters of the call: `launches` (k_batch launches),
+    `handed_back` (problems the host engine finished) and `rows`, the tier that ran ("lds" or "device")."""
     launches: int = 0
     handed_back: int = 0
+    rows: str = "lds"
 
 
-def batch_max_n(obj_or_kind, ctx: Optional[Context] = None) -> int:
-    """Largest n of one problem of a batched solve: what one workgroup's LDS holds of x, u and the parameter vectors.  A kind
-    name for the built-in objectives; a run-time compiled `DeviceObjective` (kind "user") for its own — the first call on its
-    compiled module compiles the batch program."""
+BATCH_ROWS = {"lds": 0, "device": 1, "auto": 2}      # CGO_BATCH_ROWS_*
+_BATCH_ROWS_NAMES = {v: k for k, v in BATCH_ROWS.items()}
+
+
+def _batch_policy(rows) -> Optional["_lib.BatchPolicyC"]:
+    """`rows` as a cgo_batch_policy — None for "lds", the calls without a policy.  An unknown value raises before any
+    library call."""
+    if not isinstance(rows, str) or rows not in BATCH_ROWS:
+        raise ValueError(f"rows must be one of 'lds', 'device', 'auto', not {rows!r}")
+    if rows == "lds":
+        return None
+    pol = _lib.BatchPolicyC()
+    _lib.lib().cgo_batch_policy_init(C.byref(pol))
+    pol.rows = BATCH_ROWS[rows]
+    return pol
+
+
+def batch_rows_shape():
+    """(lanes per workgroup, pairs of elements per lane and trip) of the streaming loop of rows="device"."""
+    blk, u = C.c_int32(0), C.c_int32(0)
+    _lib.lib().cgo_batch_rows_shape(C.byref(blk), C.byref(u))
+    return int(blk.value), int(u.value)
+
+
+def batch_max_n(obj_or_kind, ctx: Optional[Context] = None, rows: str = "lds") -> int:
+    """Largest n of one problem of a batched solve.  rows="lds": what one workgroup's LDS holds of x, u and the parameter
+    vectors; "device" / "auto": the index range of a pass over rows in device memory (memory is the other limit, checked by
+    the call).  A kind name for the built-in objectives; a run-time compiled `DeviceObjective` (kind "user") for its own — with
+    rows="lds" the first call on its compiled module compiles the batch program."""
+    pol = _batch_policy(rows)
+    polp = C.byref(pol) if pol is not None else None
     if isinstance(obj_or_kind, DeviceObjective):
-        return int(_lib.lib().cgo_batch_max_n_obj(obj_or_kind._h))
+        return int(_lib.lib().cgo_batch_max_n_obj_ex(obj_or_kind._h, polp))
     ctx = ctx or default_context()
-    return int(_lib.lib().cgo_batch_max_n(ctx._h, OBJ_KINDS[obj_or_kind]))
+    return int(_lib.lib().cgo_batch_max_n_ex(ctx._h, OBJ_KINDS[obj_or_kind], polp))
 
 
 class _BatchOut:
@@ -1110,10 +1138,10 @@ class _BatchOut:
             r.trace_objective, r.trace_grad_norm = self.to.ctypes.data_as(dp), self.tg.ctypes.data_as(dp)
             r.trace_step_size, r.trace_objective_evals = self.ts.ctypes.data_as(dp), self.te.ctypes.data_as(i64p)
 
-    def results(self, active=None) -> "BatchResults":
+    def results(self, active=None, rows_used: int = 0) -> "BatchResults":
         r, config, trace = self.c, self.config, self.trace
         out = BatchResults()
-        out.launches, out.handed_back = int(r.launches), int(r.handed_back)
+        out.launches, out.handed_back, out.rows = int(r.launches), int(r.handed_back), _BATCH_ROWS_NAMES[int(rows_used)]
         empty, empty_i = np.zeros(0), np.zeros(0, dtype=np.int64)
         for b in range(self.batch):
             if active is not None and not active[b]:
@@ -1135,7 +1163,7 @@ def _batch_rows(name: str, v, shape) -> np.ndarray:
 
 
 def minimizeobjectivebatch(obj_or_kind, X0, config: CGConfig, linesearch_config: LineSearchConfig, D=None, params=None,
-                           ctx: Optional[Context] = None, slice_iters: int = 0, scalars=None) -> BatchResults:
+                           ctx: Optional[Context] = None, slice_iters: int = 0, scalars=None, rows: str = "lds") -> BatchResults:
     """`batch` independent minimizeobjective problems in ONE launch sequence, a workgroup each: X0 is [batch, n]; one config and
     one line search for all.  `obj_or_kind` is either one of "quad_diag" (D: [batch, n], the rows of the diagonal),
     "rosenbrock_paired" (n even) or "booth" (n = 2), or a run-time compiled `DeviceObjective` (ElementwiseObjective) of size n —
@@ -1146,7 +1174,12 @@ def minimizeobjectivebatch(obj_or_kind, X0, config: CGConfig, linesearch_config:
     iteration the device loop does not run are finished by the ordinary engine; anything the batched form does not cover
     raises CgoError (no loop of solves behind it).  slice_iters: outer iterations per problem and launch (0: the library's
     policy).  scalars: a [batch] array, every problem's OWN `s0` in place of the model's (a model only: the built-in kinds
-    read no scalar) — one `Batch.solve`; a `Batch` kept open serves many such calls on the same data."""
+    read no scalar) — one `Batch.solve`; a `Batch` kept open serves many such calls on the same data.
+    rows: where a problem's rows live during the solve.  "lds" (the default): in its workgroup's LDS, n ≤ batch_max_n(…).
+    "device": they stay in device memory and every pass streams them from there — n up to batch_max_n(…, rows="device") and
+    what the device's memory holds; every number returned has the bits of the LDS tier, at the price of a round trip to
+    memory per pass.  "auto": LDS where n fits, device rows beyond.  The returned list says which ran (`.rows`)."""
+    pol = _batch_policy(rows)
     model = obj_or_kind if isinstance(obj_or_kind, DeviceObjective) else None
     if model is None and obj_or_kind not in OBJ_KINDS:
         raise ValueError(f"unknown objective kind {obj_or_kind!r}")
@@ -1177,41 +1210,49 @@ def minimizeobjectivebatch(obj_or_kind, X0, config: CGConfig, linesearch_config:
         ctx = ctx or model.ctx
     if scalars is not None:
         scalars = _batch_rows("scalars", scalars, (batch,))
-        with Batch(model, Pc, batch) as B:
+        with Batch(model, Pc, batch, rows=rows) as B:
             return B.solve(X0, config, linesearch_config, scalars=scalars, slice_iters=slice_iters)
     ctx = ctx or default_context()
     o = _BatchOut(batch, n, config)
     cfg, ls = config._c(), linesearch_config._c()
+    polp = C.byref(pol) if pol is not None else None
+    used = C.c_int32(0)
     if model is not None:
-        rows = (dp * max(len(Pc), 1))(*[v.ctypes.data_as(dp) if v is not None else None for v in Pc])
-        check(_lib.lib().cgo_minimize_batch_obj(ctx._h, model._h, batch, X0.ctypes.data_as(dp), rows, len(Pc), C.byref(cfg),
-                                                C.byref(ls), int(slice_iters), C.byref(o.c)))
+        prows = (dp * max(len(Pc), 1))(*[v.ctypes.data_as(dp) if v is not None else None for v in Pc])
+        check(_lib.lib().cgo_minimize_batch_obj_ex(ctx._h, model._h, batch, X0.ctypes.data_as(dp), prows, len(Pc), C.byref(cfg),
+                                                   C.byref(ls), int(slice_iters), polp, C.byref(o.c), C.byref(used)))
     else:
-        check(_lib.lib().cgo_minimize_batch(ctx._h, OBJ_KINDS[obj_or_kind], n, batch, X0.ctypes.data_as(dp),
-                                            Dc.ctypes.data_as(dp) if Dc is not None else None, C.byref(cfg), C.byref(ls),
-                                            int(slice_iters), C.byref(o.c)))
-    return o.results()
+        check(_lib.lib().cgo_minimize_batch_ex(ctx._h, OBJ_KINDS[obj_or_kind], n, batch, X0.ctypes.data_as(dp),
+                                               Dc.ctypes.data_as(dp) if Dc is not None else None, C.byref(cfg), C.byref(ls),
+                                               int(slice_iters), polp, C.byref(o.c), C.byref(used)))
+    return o.results(rows_used=used.value)
 
 
 class Batch:
     """`batch` problems of one run-time compiled objective that STAY ON THE DEVICE between solves (cgo_batch_open): `model` as
     in minimizeobjectivebatch, `params` its n_params arrays [batch, n], uploaded once.  `solve` then runs the batch any number
     of times — each call from its own X0, under its own config and line search, optionally with a scalar per problem and with
-    only some of the problems.  A context manager; `close` frees the device rows."""
+    only some of the problems.  rows: "lds" | "device" | "auto", as in minimizeobjectivebatch; `.rows` says which tier the open
+    batch runs in.  A context manager; `close` frees the device rows."""
 
-    def __init__(self, model: DeviceObjective, params, batch: int):
+    def __init__(self, model: DeviceObjective, params, batch: int, rows: str = "lds"):
         self._h = None
+        pol = _batch_policy(rows)
         if not isinstance(model, DeviceObjective) or model.kind != "user":
             raise ValueError("Batch: the model must be a run-time compiled objective (ElementwiseObjective)")
         self.model, self.batch, self.n = model, int(batch), int(model.n_global)
         if self.batch < 1:
             raise ValueError("Batch: batch must be ≥ 1")
         Pc = [_batch_rows(f"params[{j}]", v, (self.batch, self.n)) for j, v in enumerate(params or [])]
-        rows = (dp * max(len(Pc), 1))(*[v.ctypes.data_as(dp) for v in Pc])
+        prows = (dp * max(len(Pc), 1))(*[v.ctypes.data_as(dp) for v in Pc])
         h = C.c_void_p()
         ctx_h = model.ctx._h if model.ctx is not None else None
-        check(_lib.lib().cgo_batch_open(ctx_h, model._h, self.batch, rows, len(Pc), C.byref(h)))
+        check(_lib.lib().cgo_batch_open_ex(ctx_h, model._h, self.batch, prows, len(Pc), C.byref(pol) if pol is not None else None, C.byref(h)))
         self._h = h
+        used = C.c_int32(0)
+        check(_lib.lib().cgo_batch_rows(h, C.byref(used)))
+        self._rows_used = int(used.value)
+        self.rows = _BATCH_ROWS_NAMES[self._rows_used]
 
     def solve(self, X0, config: CGConfig, linesearch_config: LineSearchConfig, scalars=None, active=None,
               slice_iters: int = 0) -> BatchResults:
@@ -1232,7 +1273,7 @@ class Batch:
         check(_lib.lib().cgo_batch_solve(self._h, X0.ctypes.data_as(dp), sc.ctypes.data_as(dp) if sc is not None else None,
                                          ac.ctypes.data_as(C.POINTER(C.c_uint8)) if ac is not None else None, C.byref(cfg),
                                          C.byref(ls), int(slice_iters), C.byref(o.c)))
-        return o.results(ac)
+        return o.results(ac, rows_used=self._rows_used)
 
     def close(self):
         if self._h is not None:
@@ -1567,7 +1608,7 @@ def _refuse_unbatched(config: CGConfig, linesearch_config: LineSearchConfig):
 
 def primalbarriermethodbatch(constraints: BoxConstraints, f0df0: str, X_initial, centering_config: CGConfig,
                              linesearch_config: LineSearchConfig, barrier_config: PrimalBarrierConfig, *rerun_config_tuples,
-                             params=None, ctx: Optional[Context] = None) -> List[PrimalBarrierResults]:
+                             params=None, ctx: Optional[Context] = None, rows: str = "lds") -> List[PrimalBarrierResults]:
     """primalbarriermethod for `batch` problems at once: X_initial is [batch, D], `params` the base objective's own [batch, D]
     rows (one array per slot), `constraints` one box for all (floats), one set of bounds for all (length-D arrays) or every
     problem's own ([batch, D] arrays: a BatchBoxConstraints).  The loop of primal_barrier.jl:156-255 with every scalar a [batch] array: t (verifyt0
@@ -1575,7 +1616,9 @@ def primalbarriermethodbatch(constraints: BoxConstraints, f0df0: str, X_initial,
     ONE batched solve (`Batch.solve`) with scalars = t and active = the problems still running (for a rerun stage: those whose
     last status is not "success", from the previous stage's minimizers); `X_initial` is never updated, as in the reference.
     Returns what primalbarriermethod returns for each problem.  Configs the batched device loop does not run raise CgoError
-    before any work (no loop of single solves)."""
+    before any work (no loop of single solves).  rows: "lds" | "device" | "auto", passed on to every `Batch` (a box fit with
+    per-variable bounds holds four slots: LDS ends at D = 3 352 there)."""
+    _batch_policy(rows)
     X0 = np.ascontiguousarray(np.asarray(X_initial, dtype=np.float64))
     if X0.ndim != 2:
         raise ValueError("X_initial must be [batch, D]")
@@ -1616,14 +1659,14 @@ def primalbarriermethodbatch(constraints: BoxConstraints, f0df0: str, X_initial,
         if not math.isfinite(bc.t_initial) or bc.t_initial < 0.0:     # verifyt0  (:259-276): f0(x_initial) of every problem, one launch
             base = ElementwiseObjective(D, _base_objective_source(f0df0), param=[None] * len(own) if own else None, ctx=ctx)
             try:
-                with Batch(base, own, batch) as B0:   # max_iters = 0: the initial evaluation (optim.jl:31) and nothing after it
+                with Batch(base, own, batch, rows=rows) as B0:   # max_iters = 0: the initial evaluation (optim.jl:31) and nothing after it
                     c0 = CGConfig(centering_config.ϵ, centering_config.β_config, 0, False, DisableTrace())
                     r0 = B0.solve(np.where(running[:, None], X0, X0[np.flatnonzero(running)[0]]), c0, linesearch_config)
                 f_x0 = np.array([r.objective for r in r0])
             finally:
                 base.close()
             t = (f_x0 - bc.inf_f0_lb) * mu
-        B = Batch(obj, bar_rows, batch)
+        B = Batch(obj, bar_rows, batch, rows=rows)
         for i in range(1, bc.max_iters + 1):                          # :208
             step: List[List[Results]] = [[] for _ in range(batch)]
             act, X = running.copy(), X0

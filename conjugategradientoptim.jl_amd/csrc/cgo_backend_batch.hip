@@ -3,6 +3,9 @@
 // parameter slot ARE the [batch][ld] rows; the loop over launches is the engine's (run_batch, cgo_engine.cpp), the hand-back
 // of a problem the device loop does not finish is the C API's (cgo_minimize_batch[_obj]), through batch_export_row below.
 // A run-time compiled objective (CGO_OBJ_USER) brings its own k_batch, the batch program of its module (cgo_rtc_batch.hip).
+// Two tiers share everything here but the kernel symbol and the dynamic LDS of the launch: rows in LDS (k_batch) and rows
+// streamed from device memory (k_batch_rows, batch_alloc's device_rows) — whose instantiations live in a translation unit of
+// their own (cgo_backend_batch_rows.hip), so that the device code of this one is what it was before that tier existed.
 #include "cgo_backend_internal.hpp"
 #include "cgo_kernels_batch.hip.hpp"
 
@@ -27,6 +30,7 @@ static const void *batch_kernel_for(int obj_kind, int npts) {
     default: return nullptr;
     }
 }
+const void *batch_rows_kernel_for(int obj_kind, int npts);   // the same for the tier whose rows stay in device memory (cgo_backend_batch_rows.hip)
 static const void *batch_grad_kernel_for(int obj_kind) {
     switch (obj_kind) {
 #define ROW(KIND, T) case KIND: return (const void *)k_batch_grad<T>;
@@ -63,14 +67,22 @@ int64_t HipBackend::batch_max_n(HipCtx *ctx, int obj_kind, const RtcModule *rtc)
     return ld_max < 2 ? 0 : ld_max;
 }
 
+// x, u, every slot and the results' gradient, [batch][ld] each; the states, f_x0 and a scalar per problem beside them
+double HipBackend::batch_rows_bytes(int64_t batch, int64_t n, int nparams) {
+    const double ld = (double)n + (double)(n & 1);
+    return (double)batch * (ld * 8.0 * (double)(batch_vecs(nparams) + 1) + (double)sizeof(ResState) + 16.0);
+}
+
 // "allocate + slots": the rows of every parameter slot go up ONCE; the states, f_x0 and (where scalars per problem will come) s0v
 // are allocated.  batch_reset below starts a solve on them, any number of times.
-int HipBackend::batch_alloc(int64_t batch, int64_t n, const double *const *params) {
+int HipBackend::batch_alloc(int64_t batch, int64_t n, const double *const *params, bool device_rows) {
     const int64_t ld = n + (n & 1);
     if (batch < 1 || n < 1 || obj_->n_local != batch * ld || !rmode_ || bat_st_) { set_error("internal: batched solve on a backend of another shape"); return CGO_ESTATE; }
     HIPCHK(hipSetDevice(ctx_->device));
     bat_count_ = batch; bat_n_ = n; bat_ld_ = ld;
-    bat_lds_ = (size_t)ld * 8 * (size_t)batch_vecs(obj_->nparams());
+    bat_rows_ = device_rows;
+    bat_lds_ = device_rows ? 0 : (size_t)ld * 8 * (size_t)batch_vecs(obj_->nparams());
+    if (device_rows && n > batch_rows_max_n()) { set_error("internal: a batch beyond the pass index of the device-rows tier"); return CGO_ESTATE; }
     // rows padded to ld.  No pass reads the padding element (the odd tail is the workgroup's own element n − 1); the ONE
     // gradient launch over the concatenated rows (batch_results) does evaluate it.  Built-in objectives: zero in x, u and the
     // parameter vector, ∇f = D·x = 0 there.  A user's body is never evaluated on data the user did not supply — log(p), 1/p at
@@ -88,10 +100,10 @@ int HipBackend::batch_alloc(int64_t batch, int64_t n, const double *const *param
     HIPCHK(hipMalloc((void **)&bat_st_, sizeof(ResState) * (size_t)batch));
     HIPCHK(hipMalloc((void **)&bat_fx0_, sizeof(double) * (size_t)batch));
     if (obj_->kind == CGO_OBJ_USER) {   // (a module's kernel takes its dynamic LDS as launched, as the resident solver's does)
-        if (!obj_->rtc || !obj_->rtc->batch(3)) { set_error("internal: batched solve before the objective's batch program was compiled"); return CGO_ESTATE; }
+        if (!obj_->rtc || !(device_rows ? obj_->rtc->batch_rows(3) : obj_->rtc->batch(3))) { set_error("internal: batched solve before the objective's batch program was compiled"); return CGO_ESTATE; }
         return CGO_OK;
     }
-    const void *fn = batch_kernel_for(obj_->kind, 3);
+    const void *fn = device_rows ? batch_rows_kernel_for(obj_->kind, 3) : batch_kernel_for(obj_->kind, 3);
     if (!fn) { set_error("batched solves: no k_batch instantiation for this objective"); return CGO_EINVAL; }
     if (bat_lds_ > 48 * 1024) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bat_lds_));
     return CGO_OK;
@@ -170,11 +182,11 @@ int HipBackend::batch_launch(const ResConfig &c, int64_t budget, std::vector<Res
     B.budget = budget;
     void *args[] = {&B};
     if (obj_->kind == CGO_OBJ_USER) {
-        const hipFunction_t mf = obj_->rtc ? obj_->rtc->batch(3) : nullptr;
+        const hipFunction_t mf = !obj_->rtc ? nullptr : bat_rows_ ? obj_->rtc->batch_rows(3) : obj_->rtc->batch(3);
         if (!mf) { set_error("internal: kernel missing from the run-time compiled objective module"); return CGO_EINVAL; }
         HIPCHK(hipModuleLaunchKernel(mf, (unsigned)bat_count_, 1, 1, BLOCK, 1, 1, (unsigned)bat_lds_, ctx_->stream, args, nullptr));
     } else {
-        const void *fn = batch_kernel_for(obj_->kind, 3);
+        const void *fn = bat_rows_ ? batch_rows_kernel_for(obj_->kind, 3) : batch_kernel_for(obj_->kind, 3);   // (bat_lds_ = 0 for the rows in device memory)
         HIPCHK(hipLaunchKernel(fn, dim3((unsigned)bat_count_), dim3(BLOCK), args, bat_lds_, ctx_->stream));
     }
     total_launches_++;
@@ -219,6 +231,10 @@ int HipBackend::batch_grad_rows() {
     G.s0v = bat_s0v_; G.n = bat_n_; G.ld = bat_ld_;
     void *args[] = {&G};
     if (obj_->kind == CGO_OBJ_USER) {
+        if (obj_->rtc && !obj_->rtc->batch_grad()) {   // (a batch opened on rows in device memory never compiled the batch program, where this kernel lives)
+            std::string log;
+            if (int rc = rtc_compile_batch(*obj_->rtc, log)) { set_error("user objective: the batch program did not compile:\n" + log); return rc; }
+        }
         const hipFunction_t mf = obj_->rtc ? obj_->rtc->batch_grad() : nullptr;
         if (!mf) { set_error("internal: kernel missing from the run-time compiled objective module"); return CGO_EINVAL; }
         HIPCHK(hipModuleLaunchKernel(mf, (unsigned)bat_count_, 1, 1, BLOCK, 1, 1, 0, ctx_->stream, args, nullptr));

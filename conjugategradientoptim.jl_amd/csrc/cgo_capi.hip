@@ -987,18 +987,64 @@ static int check_batch_call(cgo_ctx *ctx, const cgo_cg_config *cfg, const cgo_ls
     return CGO_OK;
 }
 
+// ---- where a batch's rows live (cgo_batch_policy): LDS (k_batch) or device memory (k_batch_rows) ---------------------------------
+void cgo_batch_policy_init(cgo_batch_policy *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->size = (int32_t)sizeof(*p);
+    p->rows = CGO_BATCH_ROWS_LDS;
+}
+
+void cgo_batch_rows_shape(int32_t *block, int32_t *pairs_per_trip) {
+    if (block) *block = HipBackend::batch_rows_block();
+    if (pairs_per_trip) *pairs_per_trip = HipBackend::batch_rows_unroll();
+}
+
+// the rows a call asks for: a null policy is the call without one
+static int batch_rows_asked(const cgo_batch_policy *pol, int &rows) {
+    rows = CGO_BATCH_ROWS_LDS;
+    if (!pol) return CGO_OK;
+    REQUIRE(pol->size == (int32_t)sizeof(cgo_batch_policy), "cgo_batch_policy.size does not match this library (call cgo_batch_policy_init first)");
+    REQUIRE(pol->rows == CGO_BATCH_ROWS_LDS || pol->rows == CGO_BATCH_ROWS_DEVICE || pol->rows == CGO_BATCH_ROWS_AUTO,
+            "batched solves: cgo_batch_policy.rows must be CGO_BATCH_ROWS_LDS, CGO_BATCH_ROWS_DEVICE or CGO_BATCH_ROWS_AUTO");
+    rows = pol->rows;
+    return CGO_OK;
+}
+// … and the tier a batch of problems of size n then runs in.  lds_max: what one workgroup's LDS holds of this objective
+// (`lds_name` reports it); beyond the LDS tier the limits are the pass index and the device's free memory.
+static int batch_tier(cgo_ctx *ctx, int rows, int64_t n, int64_t batch, int nparams, int64_t lds_max, const char *lds_name, bool &device_rows) {
+    device_rows = rows == CGO_BATCH_ROWS_DEVICE || (rows == CGO_BATCH_ROWS_AUTO && n > lds_max);
+    if (!device_rows) {
+        if (n > lds_max) { set_error("batched solves: n = " + std::to_string(n) + " exceeds what one workgroup's LDS holds (" + lds_name + " = " + std::to_string(lds_max) + ")"); return CGO_EINVAL; }
+        return CGO_OK;
+    }
+    const int64_t max_n = HipBackend::batch_rows_max_n();
+    if (n > max_n) { set_error("batched solves: n = " + std::to_string(n) + " exceeds the index range of a pass over rows in device memory (cgo_batch_max_n_ex = " + std::to_string(max_n) + ")"); return CGO_EINVAL; }
+    size_t free_b = 0, total_b = 0;
+    HIPCHK2(hipMemGetInfo(&free_b, &total_b));
+    const double need = HipBackend::batch_rows_bytes(batch, n, nparams);
+    if (need > (double)free_b) {
+        char buf[256];
+        std::snprintf(buf, sizeof buf, "batched solves: the rows of %lld problems of n = %lld ask for %.0f bytes of device memory, %zu are free",
+                      (long long)batch, (long long)n, need, free_b);
+        set_error(buf);
+        return CGO_ENOMEM;
+    }
+    return CGO_OK;
+}
+
 // The concatenated problems: ONE objective `cat` (n_local = batch · ld, its parameter slots allocated) and backend whose x, u and
 // parameter slots are the [batch][ld] rows.  batch_backend_on makes the backend and uploads the slot rows; batch_solve_on starts
 // a solve on it — launched until every active problem is finished or handed back, then everything after the launch loop:
 // statuses from stop_status, traces, and the hand-back of the problems the device loop does not finish to ONE ordinary solver on
 // `make_hobj`'s objective of size n (created on the first hand-back), which takes the problem's own scalar where the call has them.
-static int batch_backend_on(cgo_ctx *ctx, HipObjective &cat, int64_t n, int64_t batch, const double *const *params, HipBackend &be) {
+static int batch_backend_on(cgo_ctx *ctx, HipObjective &cat, int64_t n, int64_t batch, const double *const *params, HipBackend &be, bool device_rows) {
     cgo_solver_policy pol;
     { std::string pw; if (int rc = resolve_policy(ctx, nullptr, pol, pw)) { set_error(pw); return rc; } }
     be.set_policy(pol);
     be.set_rmode(true);
     if (int rc = be.alloc()) return rc;
-    return be.batch_alloc(batch, n, params);
+    return be.batch_alloc(batch, n, params, device_rows);
 }
 
 static int batch_solve_on(cgo_ctx *ctx, HipBackend &be, int64_t n, int64_t batch, const double *x0, const double *scalars,
@@ -1087,41 +1133,62 @@ static int batch_solve_on(cgo_ctx *ctx, HipBackend &be, int64_t n, int64_t batch
 
 static int run_batch_on(cgo_ctx *ctx, HipObjective &cat, int64_t n, int64_t batch, const double *x0, const double *const *params,
                         const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out,
-                        const std::function<int(cgo_objective **)> &make_hobj) {
+                        const std::function<int(cgo_objective **)> &make_hobj, bool device_rows) {
     HipBackend be(&ctx->c, &cat);
-    if (int rc = batch_backend_on(ctx, cat, n, batch, params, be)) return rc;
+    if (int rc = batch_backend_on(ctx, cat, n, batch, params, be, device_rows)) return rc;
     return batch_solve_on(ctx, be, n, batch, x0, nullptr, nullptr, cfg, ls, slice_iters, out, make_hobj);
 }
 
 int cgo_minimize_batch(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
                        const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out) {
+    return cgo_minimize_batch_ex(ctx, obj_kind, n, batch, x0, param0, cfg, ls, slice_iters, nullptr, out, nullptr);
+}
+
+int cgo_minimize_batch_ex(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
+                          const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, const cgo_batch_policy *policy,
+                          cgo_batch_results *out, int32_t *rows_used) {
     API_GUARD_BEGIN
     REQUIRE(ctx && x0 && cfg && ls && out, "null argument");
     out->launches = 0; out->handed_back = 0;
+    int rows = 0;
+    if (int rc = batch_rows_asked(policy, rows)) return rc;
     REQUIRE(batch_kind(obj_kind), "batched solves: the objective must be CGO_OBJ_QUAD_DIAG, CGO_OBJ_ROSENBROCK_PAIRED or CGO_OBJ_BOOTH");
     if (int rc = check_batch_call(ctx, cfg, ls, n, batch, slice_iters)) return rc;
     if (obj_kind == CGO_OBJ_ROSENBROCK_PAIRED) REQUIRE(n % 2 == 0, "batched solves: paired Rosenbrock needs an even n");
     if (obj_kind == CGO_OBJ_BOOTH) REQUIRE(n == 2, "batched solves: Booth is 2-dimensional (n = 2)");
     if (obj_kind == CGO_OBJ_QUAD_DIAG) REQUIRE(param0, "batched solves: the quadratic needs param0, the [batch*n] rows of D");
     HIPCHK2(hipSetDevice(ctx->c.device));
-    {
-        const int64_t max_n = cgo_batch_max_n(ctx, obj_kind);
-        if (n > max_n) { set_error("batched solves: n = " + std::to_string(n) + " exceeds what one workgroup's LDS holds (cgo_batch_max_n = " + std::to_string(max_n) + ")"); return CGO_EINVAL; }
-    }
+    bool device_rows = false;
+    if (int rc = batch_tier(ctx, rows, n, batch, obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0, cgo_batch_max_n(ctx, obj_kind), "cgo_batch_max_n", device_rows)) return rc;
+    if (rows_used) *rows_used = device_rows ? CGO_BATCH_ROWS_DEVICE : CGO_BATCH_ROWS_LDS;
     const int64_t ld = n + (n & 1);
     HipObjective cat;
     cat.ctx = &ctx->c; cat.kind = obj_kind; cat.n_global = cat.n_local = batch * ld; cat.offset = 0;
     if (cat.uses_param()) { if (int rc = cat.p[0].alloc((size_t)(batch * ld))) return rc; }
     const double *params[1] = {param0};
     return run_batch_on(ctx, cat, n, batch, x0, params, cfg, ls, slice_iters, out,
-                        [&](cgo_objective **h) { return cgo_objective_create(ctx, obj_kind, n, 0, n, h); });
+                        [&](cgo_objective **h) { return cgo_objective_create(ctx, obj_kind, n, 0, n, h); }, device_rows);
     API_GUARD_END
+}
+
+int64_t cgo_batch_max_n_ex(cgo_ctx *ctx, int32_t obj_kind, const cgo_batch_policy *policy) {
+    int rows = 0;
+    if (batch_rows_asked(policy, rows)) return 0;
+    const int64_t lds = cgo_batch_max_n(ctx, obj_kind);
+    if (rows == CGO_BATCH_ROWS_LDS || lds == 0) return lds;
+    return obj_kind == CGO_OBJ_BOOTH ? lds : HipBackend::batch_rows_max_n();
 }
 
 // The model's batch program (k_batch<UserObjective, …>, cgo_rtc_batch.hip): compiled on the first batched use of its module
 static int batch_program(cgo_objective *model) {
     std::string log;
     if (int rc = rtc_compile_batch(*model->o.rtc, log)) { set_error("user objective: the batch program did not compile:\n" + log); return rc; }
+    return CGO_OK;
+}
+// … and the program of the tier whose rows stay in device memory, on the first use of that tier
+static int batch_rows_program(cgo_objective *model) {
+    std::string log;
+    if (int rc = rtc_compile_batch_rows(*model->o.rtc, log)) { set_error("user objective: the program of the batched solves' device-rows tier did not compile:\n" + log); return rc; }
     return CGO_OK;
 }
 static bool batch_model_whole(const cgo_objective *m) { return m->o.offset == 0 && m->o.n_local == m->o.n_global && m->o.ctx->world() == 1; }
@@ -1131,6 +1198,16 @@ int64_t cgo_batch_max_n_obj(cgo_objective *model) {
         if (!model || model->o.kind != CGO_OBJ_USER || !model->o.rtc || !batch_model_whole(model)) return 0;
         if (batch_program(model)) return 0;
         return HipBackend::batch_max_n(model->o.ctx, CGO_OBJ_USER, model->o.rtc.get());
+    } catch (...) { return 0; }
+}
+
+int64_t cgo_batch_max_n_obj_ex(cgo_objective *model, const cgo_batch_policy *policy) {
+    try {
+        int rows = 0;
+        if (batch_rows_asked(policy, rows)) return 0;
+        if (rows == CGO_BATCH_ROWS_LDS) return cgo_batch_max_n_obj(model);
+        if (!model || model->o.kind != CGO_OBJ_USER || !model->o.rtc || !batch_model_whole(model)) return 0;
+        return HipBackend::batch_rows_max_n();   // (nothing is compiled for the answer)
     } catch (...) { return 0; }
 }
 
@@ -1144,7 +1221,8 @@ static int check_batch_model(cgo_ctx *ctx, cgo_objective *model) {
     REQUIRE(batch_model_whole(model), "batched solves: a sharded or multi-rank model is not supported (n_global = n_local = the size of ONE problem, one rank only)");
     return CGO_OK;
 }
-static int batch_model_cat(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *const *params, int32_t n_params, HipObjective &cat) {
+static int batch_model_cat(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *const *params, int32_t n_params, HipObjective &cat,
+                           int rows, bool &device_rows) {
     const int64_t n = model->o.n_local;
     const int K = model->o.nparams();
     if (n_params != K) { set_error("batched solves: n_params = " + std::to_string(n_params) + ", the model reads " + std::to_string(K) + " parameter slots"); return CGO_EINVAL; }
@@ -1152,11 +1230,14 @@ static int batch_model_cat(cgo_ctx *ctx, cgo_objective *model, int64_t batch, co
     for (int j = 0; j < K; ++j)
         if (!params[j]) { set_error("batched solves: params[" + std::to_string(j) + "] is null (the [batch*n] rows of slot " + std::to_string(j) + ")"); return CGO_EINVAL; }
     HIPCHK2(hipSetDevice(ctx->c.device));
-    if (int rc = batch_program(model)) return rc;
-    {
-        const int64_t max_n = HipBackend::batch_max_n(&ctx->c, CGO_OBJ_USER, model->o.rtc.get());
-        if (n > max_n) { set_error("batched solves: n = " + std::to_string(n) + " exceeds what one workgroup's LDS holds (cgo_batch_max_n_obj = " + std::to_string(max_n) + ")"); return CGO_EINVAL; }
+    // (rows in device memory, asked for outright: the batch program — the LDS tier's kernel — is neither needed nor compiled)
+    int64_t lds_max = 0;
+    if (rows != CGO_BATCH_ROWS_DEVICE) {
+        if (int rc = batch_program(model)) return rc;
+        lds_max = HipBackend::batch_max_n(&ctx->c, CGO_OBJ_USER, model->o.rtc.get());
     }
+    if (int rc = batch_tier(ctx, rows, n, batch, K, lds_max, "cgo_batch_max_n_obj", device_rows)) return rc;
+    if (device_rows) { if (int rc = batch_rows_program(model)) return rc; }
     const int64_t ld = n + (n & 1);
     cat.ctx = &ctx->c; cat.kind = CGO_OBJ_USER; cat.n_global = cat.n_local = batch * ld; cat.offset = 0;
     cat.rtc = model->o.rtc; cat.user_nparams = K; cat.s0 = model->o.s0; cat.user_cheap = model->o.user_cheap;
@@ -1176,15 +1257,25 @@ static std::function<int(cgo_objective **)> batch_model_hobj(cgo_ctx *ctx, cgo_o
 int cgo_minimize_batch_obj(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *x0, const double *const *params,
                            int32_t n_params, const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters,
                            cgo_batch_results *out) {
+    return cgo_minimize_batch_obj_ex(ctx, model, batch, x0, params, n_params, cfg, ls, slice_iters, nullptr, out, nullptr);
+}
+
+int cgo_minimize_batch_obj_ex(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *x0, const double *const *params,
+                              int32_t n_params, const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters,
+                              const cgo_batch_policy *policy, cgo_batch_results *out, int32_t *rows_used) {
     API_GUARD_BEGIN
     REQUIRE(ctx && model && x0 && cfg && ls && out, "null argument");
     out->launches = 0; out->handed_back = 0;
+    int rows = 0;
+    if (int rc = batch_rows_asked(policy, rows)) return rc;
     if (int rc = check_batch_model(ctx, model)) return rc;
     const int64_t n = model->o.n_local;
     if (int rc = check_batch_call(ctx, cfg, ls, n, batch, slice_iters)) return rc;
     HipObjective cat;
-    if (int rc = batch_model_cat(ctx, model, batch, params, n_params, cat)) return rc;
-    return run_batch_on(ctx, cat, n, batch, x0, params, cfg, ls, slice_iters, out, batch_model_hobj(ctx, model));
+    bool device_rows = false;
+    if (int rc = batch_model_cat(ctx, model, batch, params, n_params, cat, rows, device_rows)) return rc;
+    if (rows_used) *rows_used = device_rows ? CGO_BATCH_ROWS_DEVICE : CGO_BATCH_ROWS_LDS;
+    return run_batch_on(ctx, cat, n, batch, x0, params, cfg, ls, slice_iters, out, batch_model_hobj(ctx, model), device_rows);
     API_GUARD_END
 }
 
@@ -1201,9 +1292,24 @@ struct cgo_batch {
 };
 
 int cgo_batch_open(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *const *params, int32_t n_params, cgo_batch **handle) {
+    return cgo_batch_open_ex(ctx, model, batch, params, n_params, nullptr, handle);
+}
+
+int cgo_batch_rows(const cgo_batch *h, int32_t *rows_used) {
+    API_GUARD_BEGIN
+    REQUIRE(h && h->be && rows_used, "null argument");
+    *rows_used = h->be->batch_device_rows() ? CGO_BATCH_ROWS_DEVICE : CGO_BATCH_ROWS_LDS;
+    return CGO_OK;
+    API_GUARD_END
+}
+
+int cgo_batch_open_ex(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *const *params, int32_t n_params,
+                      const cgo_batch_policy *policy, cgo_batch **handle) {
     API_GUARD_BEGIN
     REQUIRE(ctx && model && handle, "null argument");
     *handle = nullptr;
+    int rows = 0;
+    if (int rc = batch_rows_asked(policy, rows)) return rc;
     if (int rc = check_batch_model(ctx, model)) return rc;
     const int64_t n = model->o.n_local;
     REQUIRE(ctx->c.world() == 1, "batched solves: a multi-rank context is not supported (one rank only)");
@@ -1212,9 +1318,10 @@ int cgo_batch_open(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const doub
     REQUIRE(n >= 1, "batched solves: n must be ≥ 1");
     std::unique_ptr<cgo_batch> h(new cgo_batch);
     h->ctx = ctx; h->n = n; h->batch = batch;
-    if (int rc = batch_model_cat(ctx, model, batch, params, n_params, h->cat)) return rc;
+    bool device_rows = false;
+    if (int rc = batch_model_cat(ctx, model, batch, params, n_params, h->cat, rows, device_rows)) return rc;
     h->be = new HipBackend(&ctx->c, &h->cat);
-    if (int rc = batch_backend_on(ctx, h->cat, n, batch, params, *h->be)) return rc;
+    if (int rc = batch_backend_on(ctx, h->cat, n, batch, params, *h->be, device_rows)) return rc;
     h->model = model; model->refs++;
     *handle = h.release();
     return CGO_OK;

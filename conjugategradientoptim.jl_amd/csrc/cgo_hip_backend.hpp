@@ -166,7 +166,14 @@ class HipBackend : public VecBackend {
     // … in its two halves, for a batch that stays on the device between solves (cgo_batch_open / cgo_batch_solve): the slot rows
     // once; then per solve x0, the states, and optionally a scalar per problem (scalars, [batch]) and which problems run
     // (active, [batch] bytes; null: all — an inactive problem's workgroup returns at once)
-    int batch_alloc(int64_t batch, int64_t n, const double *const *params);
+    // device_rows: the second tier (k_batch_rows, cgo_kernels_batch_rows.hip.hpp) — the rows are streamed from where they are in every
+    // pass: no dynamic LDS, n up to batch_rows_max_n() and what the device's memory holds (batch_rows_bytes)
+    int batch_alloc(int64_t batch, int64_t n, const double *const *params, bool device_rows = false);
+    static int64_t batch_rows_max_n();         // the limit of the tier's pass index on n
+    static int batch_rows_unroll();            // pairs per lane and trip of its streaming loop
+    static int batch_rows_block();             // lanes of its workgroup
+    static double batch_rows_bytes(int64_t batch, int64_t n, int nparams);   // device bytes a batch of that shape asks for
+    bool batch_device_rows() const { return bat_rows_; }
     int batch_reset(const double *x0, const double *scalars, const unsigned char *active, int64_t max_iters, bool trace);
     int batch_launch(const ResConfig &c, int64_t budget, std::vector<ResState> &st, std::vector<double> &f_x0) override;
     int batch_records(int64_t b, int64_t count, std::vector<ResRecord> &out);     // the trace records of problem b's first `count` iterations (b < 0: every row)
@@ -415,6 +422,7 @@ class HipBackend : public VecBackend {
     int64_t bat_count_ = 0, bat_n_ = 0, bat_ld_ = 0, bat_rec_stride_ = 0;
     bool bat_trace_ = false;
     size_t bat_lds_ = 0;
+    bool bat_rows_ = false;                  // the tier: rows in LDS (k_batch) or streamed from device memory (k_batch_rows)
     ResState *bat_st_ = nullptr;             // device [batch]
     ResRecord *bat_recs_ = nullptr;          // device [batch][bat_rec_stride_]
     double *bat_fx0_ = nullptr;              // device [batch]

@@ -10,7 +10,9 @@
 //   * then res_iterate (cgo_resident.hpp) — the loop k_resident runs — over ResDev in its SOLO form: the passes, trial and
 //     accept_dir_trial are ResDev's own (cgo_kernels_resident.hip.hpp), the workgroup's row is the total, its lane 0 the leader;
 //   * when the slice ends: x, u back in place if an iteration completed, the state to st[b], the records of the completed
-//     iterations (written by the leader as they completed) in recs[b].
+//     iterations (written by the leader as they completed) in recs[b].  (So a problem handed back before it completes an
+//     iteration leaves its rows untouched.  The tier without LDS, k_batch_rows in cgo_kernels_batch_rows.hip.hpp, differs here:
+//     its R_INIT pass has stored u = −g to the u row by then — a row the host solver does not read when st.it == 0.)
 // The objective's scalar is the launch's (s0) or the problem's own (s0v[b]): a barrier weight, a regularisation strength, a
 // temperature per problem.  With scalars per problem the results' gradient is k_batch_grad's (below), a workgroup per row too.
 //

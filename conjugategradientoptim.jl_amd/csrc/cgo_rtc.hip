@@ -27,6 +27,7 @@ RtcModule::~RtcModule() {
     if (mod) (void)hipModuleUnload(mod);
     if (probe_mod) (void)hipModuleUnload(probe_mod);
     if (batch_mod) (void)hipModuleUnload(batch_mod);
+    if (rows_mod) (void)hipModuleUnload(rows_mod);
 }
 
 static std::string key_cg(int mode, int npts, bool big) {

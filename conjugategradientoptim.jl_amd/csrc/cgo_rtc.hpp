@@ -28,6 +28,10 @@ struct RtcModule {
     hipFunction_t batch(int npts) const;
     hipFunction_t batch_grad() const;         // k_batch_grad<UserObjective>, in the same program
     hipModule_t batch_mod = nullptr;
+    // the batched solves' second tier (problem rows streamed from device memory, cgo_kernels_batch_rows.hip.hpp): a THIRD program,
+    // compiled on the first solve of that tier (rtc_compile_batch_rows) — a user who never asks for the tier does not pay for it
+    hipFunction_t batch_rows(int npts) const;
+    hipModule_t rows_mod = nullptr;
     std::string user_source;
     int n_params = 0;   // parameter slots the objective was created with (0 … CGO_MAX_PARAM_SLOTS)
     int device = 0;
@@ -45,6 +49,8 @@ int rtc_compile_objective(int device, const std::string &source, int n_params,
 int rtc_compile_resident_probe(RtcModule &m, std::string &log);
 // k_batch for the module's objective, one kernel per row of CGO_BATCH_ROWS, compiled and loaded on first use (cgo_rtc_batch.hip)
 int rtc_compile_batch(RtcModule &m, std::string &log);
+// the kernel of the batched solves' second tier for the module's objective, one per row of CGO_BATCH_DEVROWS_ROWS, likewise
+int rtc_compile_batch_rows(RtcModule &m, std::string &log);
 
 // What a further program of a module is built from (cgo_rtc.hip): the embedded kernel templates + the user's objective as one
 // translation unit, and one program → one loaded module: compiles `src` for the name expressions of `wants`, loads the code

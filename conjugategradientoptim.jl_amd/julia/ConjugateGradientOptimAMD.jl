@@ -614,12 +614,23 @@ mutable struct CBatchResults
     launches::Int64
     handed_back::Int64
 end
-function batch_open(model::DeviceObjective, params::Vector{Matrix{Float64}}, batch::Integer)
+struct CBatchPolicy   # cgo_batch_policy
+    size::Int32
+    rows::Int32
+    reserved::NTuple{6,Int32}
+end
+const BATCH_ROWS = Dict(:lds => Int32(0), :device => Int32(1), :auto => Int32(2))   # CGO_BATCH_ROWS_*
+# rows: where a problem's rows live during a solve — :lds (the default: in its workgroup's LDS, n ≤ cgo_batch_max_n_obj),
+# :device (in device memory, streamed by every pass: the size limit lifted) or :auto (LDS where n fits)
+function batch_open(model::DeviceObjective, params::Vector{Matrix{Float64}}, batch::Integer; rows::Symbol = :lds)
+    haskey(BATCH_ROWS, rows) || throw(ArgumentError("rows must be :lds, :device or :auto"))
     r = Ref{Ptr{Cvoid}}(C_NULL)
-    rows = Ptr{Float64}[pointer(p) for p in params]
+    prows = Ptr{Float64}[pointer(p) for p in params]
+    pol = Ref(CBatchPolicy(Int32(sizeof(CBatchPolicy)), BATCH_ROWS[rows], ntuple(_ -> Int32(0), 6)))
     GC.@preserve params begin
-        check(ccall((:cgo_batch_open, libcgo), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}, Int32, Ref{Ptr{Cvoid}}),
-                    model.ctx.h, model.h, batch, rows, length(params), r))
+        check(ccall((:cgo_batch_open_ex, libcgo), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}, Int32, Ref{CBatchPolicy}, Ref{Ptr{Cvoid}}),
+                    model.ctx.h, model.h, batch, prows, length(params), pol, r))
     end
     return r[]
 end

@@ -555,6 +555,42 @@ int cgo_batch_solve(cgo_batch *handle, const double *x0 /* [batch*n] */, const d
                     const unsigned char *active /* [batch] or NULL */, const cgo_cg_config *cfg, const cgo_ls_config *ls,
                     int64_t slice_iters /* 0 = library policy */, cgo_batch_results *out);
 int cgo_batch_close(cgo_batch *handle);
+/* WHERE A PROBLEM'S ROWS LIVE during a batched solve — the size limit of the calls above lifted, as an explicitly chosen way to
+ * run a batch.  Above, every workgroup keeps its problem's rows of x, u and the parameter slots in LDS, so n ends at
+ * cgo_batch_max_n[_obj] (10 056 … 3 352 for 0 … 4 slots).  With rows = CGO_BATCH_ROWS_DEVICE the rows stay where they are —
+ * the [batch][n] rows in device memory — and every pass of the device loop streams them from there (k_batch_rows): still one
+ * workgroup per problem, the same loop, hand-back and results, and every number returned has the BITS of the LDS tier (same
+ * bodies, same order of every sum).  Its limits: the index type of a pass, n ≤ cgo_batch_max_n_ex(…DEVICE…) ≈ 4.29e9, and
+ * the device's free memory — a batch asks for (3 + n_params) · batch · (n + n%2) · 8 bytes (x, u, the slots, the results'
+ * gradient) and is refused with CGO_ENOMEM, the bytes in the message and nothing left allocated, when that exceeds what is free.
+ * A pass costs a round trip to device memory where the LDS tier pays none: where n fits, LDS is the faster tier, and
+ * CGO_BATCH_ROWS_AUTO takes it there and the device rows beyond.  For a run-time compiled objective the tier's kernel is a
+ * third program of the module, compiled on the first call that runs this tier (cgo_batch_max_n_obj_ex compiles nothing for it).
+ * A NULL policy, or rows = CGO_BATCH_ROWS_LDS, makes every _ex call the call it extends — refusals included (n >
+ * cgo_batch_max_n[_obj] with that name in the message).  Any other value of rows: CGO_EINVAL. */
+enum { CGO_BATCH_ROWS_LDS = 0, CGO_BATCH_ROWS_DEVICE = 1, CGO_BATCH_ROWS_AUTO = 2 };
+typedef struct cgo_batch_policy {
+    int32_t size;                 /* sizeof(cgo_batch_policy), written by cgo_batch_policy_init (versioning) */
+    int32_t rows;                 /* CGO_BATCH_ROWS_*; default CGO_BATCH_ROWS_LDS */
+    int32_t reserved[6];          /* zero */
+} cgo_batch_policy;
+void cgo_batch_policy_init(cgo_batch_policy *p);                                  /* every field = its default */
+/* rows_used (may be NULL): the tier that ran, CGO_BATCH_ROWS_LDS or CGO_BATCH_ROWS_DEVICE */
+int cgo_minimize_batch_ex(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
+                          const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters,
+                          const cgo_batch_policy *policy, cgo_batch_results *out, int32_t *rows_used);
+int cgo_minimize_batch_obj_ex(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *x0,
+                              const double *const *params, int32_t n_params,
+                              const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters,
+                              const cgo_batch_policy *policy, cgo_batch_results *out, int32_t *rows_used);
+int cgo_batch_open_ex(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *const *params, int32_t n_params,
+                      const cgo_batch_policy *policy, cgo_batch **handle);
+int cgo_batch_rows(const cgo_batch *handle, int32_t *rows_used);                  /* the tier an open batch runs in */
+/* largest n under `policy` (NULL: cgo_batch_max_n[_obj]); DEVICE and AUTO: the limit of the pass index.  0: none */
+int64_t cgo_batch_max_n_ex(cgo_ctx *ctx, int32_t obj_kind, const cgo_batch_policy *policy);
+int64_t cgo_batch_max_n_obj_ex(cgo_objective *model, const cgo_batch_policy *policy);
+/* The streaming loop of the device-rows tier: lanes per workgroup and pairs of elements per lane and trip (needs no device). */
+void cgo_batch_rows_shape(int32_t *block, int32_t *pairs_per_trip);
 /* The stop test at the top of iteration it + 1 (optim.jl:53-80,162-169) as a function of the loop state — the one rule the
  * engine and the problems a batch finishes on the device share: the terminal status (CGO_INCOMPLETE: the iteration runs) and
  * Results.iters_ran. */
