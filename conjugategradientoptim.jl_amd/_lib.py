@@ -216,6 +216,11 @@ SIGNATURES = {
     "cgo_batch_max_n_ex": (C.c_int64, [_vp, C.c_int32, C.POINTER(BatchPolicyC)]),
     "cgo_batch_max_n_obj_ex": (C.c_int64, [_vp, C.POINTER(BatchPolicyC)]),
     "cgo_batch_rows_shape": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "cgo_minimize_batch_lbfgs": (C.c_int, [_vp, C.c_int32, C.c_int64, C.c_int64, dp, dp, C.POINTER(CGConfigC), C.POINTER(LSConfigC),
+                                           C.c_int64, C.POINTER(BatchResultsC)]),
+    "cgo_batch_lbfgs_max_m": (C.c_int32, []),
+    "cgo_batch_lbfgs_max_n": (C.c_int64, [_vp, C.c_int32]),
+    "cgo_batch_lbfgs_shape": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cgo_stop_status": (C.c_int32, [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, i64p]),
     "cgo_kernel_dir": (C.c_int, [_vp, dp, dp, C.c_double, C.c_int64, dp]),
     "cgo_kernel_beta_partials": (C.c_int, [_vp, dp, dp, dp, C.c_int64, dp]),

@@ -1228,6 +1228,57 @@ def minimizeobjectivebatch(obj_or_kind, X0, config: CGConfig, linesearch_config:
     return o.results(rows_used=used.value)
 
 
+def batch_lbfgs_shape():
+    """(lanes per workgroup, pairs of elements per lane and trip) of the two ring passes of minimizeobjectivebatch_lbfgs."""
+    blk, u = C.c_int32(0), C.c_int32(0)
+    _lib.lib().cgo_batch_lbfgs_shape(C.byref(blk), C.byref(u))
+    return int(blk.value), int(u.value)
+
+
+def batch_lbfgs_max_m() -> int:
+    """Largest history length m of a batched L-BFGS solve."""
+    return int(_lib.lib().cgo_batch_lbfgs_max_m())
+
+
+def batch_lbfgs_max_n(kind: str, ctx: Optional[Context] = None) -> int:
+    """Largest n of one problem of minimizeobjectivebatch_lbfgs: the index range of a pass (memory is the other limit,
+    checked by the call)."""
+    if kind not in OBJ_KINDS:
+        raise ValueError(f"unknown objective kind {kind!r}")
+    ctx = ctx or default_context()
+    return int(_lib.lib().cgo_batch_lbfgs_max_n(ctx._h, OBJ_KINDS[kind]))
+
+
+def minimizeobjectivebatch_lbfgs(kind: str, X0, config: CGConfig, linesearch_config: LineSearchConfig, D=None,
+                                 ctx: Optional[Context] = None, slice_iters: int = 0) -> BatchResults:
+    """minimizeobjectivebatch with a quasi-Newton direction: `config.β_config` is LBFGS(m), 1 ≤ m ≤ batch_lbfgs_max_m() = 10
+    (minimizeobjectivebatch is the CG flavours' and refuses it).  kind: "quad_diag" (D: [batch, n]), "rosenbrock_paired" (n even)
+    or "booth" (n = 2); StrongWolfeBisection or WolfeBisection.  One workgroup per problem; the rows of x, u, D and a ring of
+    2(m+1) rows per problem stay in device memory — (3 + K + 2(m+1)) · batch · (n + n%2) · 8 bytes, checked against the device's
+    free memory before anything is allocated.  Returns what minimizeobjectivebatch returns (`.rows` is "device").  A problem
+    the device loop does not finish is solved AGAIN from its own x0 by the ordinary engine — a whole solve — and counted in
+    `handed_back`.  Anything not covered raises CgoError: run-time compiled objectives, a scalar per problem, Backtracking,
+    m > 10, a multi-rank context."""
+    if not isinstance(kind, str) or kind not in OBJ_KINDS:
+        raise ValueError(f"unknown objective kind {kind!r} (a run-time compiled objective has no batched L-BFGS form)")
+    X0 = np.ascontiguousarray(np.asarray(X0, dtype=np.float64))
+    if X0.ndim != 2:
+        raise ValueError("X0 must be [batch, n]")
+    batch, n = X0.shape
+    Dc = None
+    if D is not None:
+        Dc = np.ascontiguousarray(np.asarray(D, dtype=np.float64))
+        if Dc.shape != X0.shape:
+            raise ValueError("D must have the shape of X0")
+    ctx = ctx or default_context()
+    o = _BatchOut(batch, n, config)
+    cfg, ls = config._c(), linesearch_config._c()
+    check(_lib.lib().cgo_minimize_batch_lbfgs(ctx._h, OBJ_KINDS[kind], n, batch, X0.ctypes.data_as(dp),
+                                              Dc.ctypes.data_as(dp) if Dc is not None else None, C.byref(cfg), C.byref(ls),
+                                              int(slice_iters), C.byref(o.c)))
+    return o.results(rows_used=BATCH_ROWS["device"])
+
+
 class Batch:
     """`batch` problems of one run-time compiled objective that STAY ON THE DEVICE between solves (cgo_batch_open): `model` as
     in minimizeobjectivebatch, `params` its n_params arrays [batch, n], uploaded once.  `solve` then runs the batch any number

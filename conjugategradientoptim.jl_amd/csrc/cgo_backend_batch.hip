@@ -168,6 +168,7 @@ int HipBackend::batch_begin(int64_t batch, int64_t n, const double *x0, const do
 
 int HipBackend::batch_launch(const ResConfig &c, int64_t budget, std::vector<ResState> &st, std::vector<double> &f_x0) {
     if (!bat_st_) { set_error("internal: batch_launch before batch_begin"); return CGO_ESTATE; }
+    if (bat_m_ > 0) return batch_lbfgs_launch(c, budget, st, f_x0);   // a batched L-BFGS solve: k_batch_lbfgs (cgo_backend_batch_lbfgs.hip)
     HIPCHK(hipSetDevice(ctx_->device));
     if (budget < 1) budget = 1;
     if (!bat_trace_) {   // nobody reads the records: the leader still writes one per completed iteration of the slice

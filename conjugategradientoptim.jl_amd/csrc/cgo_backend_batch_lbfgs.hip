@@ -1,0 +1,96 @@
+// cgo_backend_batch_lbfgs.hip — the ahead-of-time instantiations of k_batch_lbfgs (cgo_kernels_batch_lbfgs.hip.hpp), batched
+// solves with β = LBFGS(m), and the host side of what they add to a batch of the device-rows tier: the ring of 2(m+1) rows
+// and the QnState per problem, their reset, and the launch.  Allocation of the rows, reset of the states, records, results and
+// the hand-back are cgo_backend_batch.hip's; this file exists so that the translation units of k_batch and k_batch_rows compile
+// to what they compiled to before.
+#include "cgo_backend_internal.hpp"
+#include "cgo_kernels_batch_lbfgs.hip.hpp"
+
+namespace cgo {
+
+using namespace dev;
+
+// The rows of cgo_instances.def: the last row with NPTS ≤ npts, the first row below that.
+template <class Obj>
+static const void *batch_lbfgs_kernel(int npts) {
+    const void *fn = nullptr;
+#define ROW(NPTS) if (!fn || npts >= NPTS) fn = (const void *)k_batch_lbfgs<Obj, NPTS>;
+    CGO_BATCH_LBFGS_ROWS(ROW)
+#undef ROW
+    return fn;
+}
+static const void *batch_lbfgs_kernel_for(int obj_kind, int npts) {
+    switch (obj_kind) {
+#define ROW(KIND, T) case KIND: return batch_lbfgs_kernel<T>(npts);
+    CGO_OBJ_ROWS(ROW)
+#undef ROW
+    default: return nullptr;
+    }
+}
+
+int64_t HipBackend::batch_lbfgs_max_n() { return (int64_t)BATCH_LBFGS_MAX_N; }
+int HipBackend::batch_lbfgs_unroll() { return BATCH_LBFGS_U; }
+int HipBackend::batch_lbfgs_block() { return BLOCK; }
+
+// x, u, every slot, the results' gradient and the ring, [batch][ld] each; the states beside them
+double HipBackend::batch_lbfgs_bytes(int64_t batch, int64_t n, int nparams, int m) {
+    const double ld = (double)n + (double)(n & 1);
+    return (double)batch * (ld * 8.0 * (double)(3 + nparams + 2 * (m + 1)) + (double)sizeof(ResState) + (double)sizeof(QnState) + 16.0);
+}
+
+int HipBackend::batch_lbfgs_alloc(int m) {
+    if (!bat_st_ || !bat_rows_ || bat_qn_ || m < 1 || m > QN_MAX_M || obj_->kind == CGO_OBJ_USER) { set_error("internal: batched L-BFGS on a batch of another shape"); return CGO_ESTATE; }
+    if (!batch_lbfgs_kernel_for(obj_->kind, 3)) { set_error("batched L-BFGS solves: no k_batch_lbfgs instantiation for this objective"); return CGO_EINVAL; }
+    if (bat_n_ > batch_lbfgs_max_n()) { set_error("internal: a batch beyond the pass index of the batched L-BFGS solves"); return CGO_ESTATE; }
+    HIPCHK(hipSetDevice(ctx_->device));
+    const size_t ring = (size_t)bat_count_ * (size_t)(m + 1) * (size_t)bat_ld_ * sizeof(double);
+    HIPCHK(hipMalloc((void **)&bat_S_, ring));
+    HIPCHK(hipMalloc((void **)&bat_Y_, ring));
+    HIPCHK(hipMalloc((void **)&bat_qn_, sizeof(QnState) * (size_t)bat_count_));
+    bat_m_ = m;
+    return CGO_OK;
+}
+
+// every problem's ring empty.  (The ring rows need no clearing: a pass reads the slots of stored pairs only, and the padding
+// element of an odd n is never read.)
+int HipBackend::batch_lbfgs_reset() {
+    if (!bat_qn_) { set_error("internal: batch_lbfgs_reset before batch_lbfgs_alloc"); return CGO_ESTATE; }
+    HIPCHK(hipSetDevice(ctx_->device));
+    QnState q;
+    std::memset(&q, 0, sizeof q);
+    qn_init(q, bat_m_);
+    std::vector<QnState> qs((size_t)bat_count_, q);
+    HIPCHK(hipMemcpy(bat_qn_, qs.data(), sizeof(QnState) * (size_t)bat_count_, hipMemcpyHostToDevice));
+    return CGO_OK;
+}
+
+int HipBackend::batch_lbfgs_launch(const ResConfig &c, int64_t budget, std::vector<ResState> &st, std::vector<double> &f_x0) {
+    if (!bat_qn_ || bat_s0v_on_) { set_error("internal: batched L-BFGS launch on a batch of another shape"); return CGO_ESTATE; }
+    HIPCHK(hipSetDevice(ctx_->device));
+    if (budget < 1) budget = 1;
+    if (!bat_trace_) {   // nobody reads the records: the leader still writes one per completed iteration of the slice
+        if (int rc = batch_recs_reserve(budget)) return rc;
+    }
+    BatchLbfgsParams L{};
+    BatchParams &B = L.B;
+    B.x = xc_; B.u = uc_; B.p0 = obj_->p[0].p; B.p1 = obj_->p[1].p; B.p2 = obj_->p[2].p; B.p3 = obj_->p[3].p;
+    B.st = bat_st_; B.recs = bat_recs_; B.f_x0 = bat_fx0_;
+    B.n = bat_n_; B.ld = bat_ld_; B.rec_stride = bat_rec_stride_; B.rec_abs = bat_trace_ ? 1 : 0;
+    B.s0 = obj_->s0; B.s0v = nullptr;
+    B.cfg = c; B.cfg.npts = 3; B.cfg.log_on = 0;
+    B.budget = budget;
+    L.S = bat_S_; L.Y = bat_Y_; L.qn = bat_qn_;
+    L.ring_stride = (long long)(bat_m_ + 1) * bat_ld_;
+    void *args[] = {&L};
+    const void *fn = batch_lbfgs_kernel_for(obj_->kind, 3);
+    if (!fn) { set_error("batched L-BFGS solves: no k_batch_lbfgs instantiation for this objective"); return CGO_EINVAL; }
+    HIPCHK(hipLaunchKernel(fn, dim3((unsigned)bat_count_), dim3(BLOCK), args, 0, ctx_->stream));
+    total_launches_++;
+    st.resize((size_t)bat_count_); f_x0.resize((size_t)bat_count_);
+    HIPCHK(hipMemcpyAsync(st.data(), bat_st_, sizeof(ResState) * (size_t)bat_count_, hipMemcpyDeviceToHost, ctx_->stream));
+    HIPCHK(hipMemcpyAsync(f_x0.data(), bat_fx0_, sizeof(double) * (size_t)bat_count_, hipMemcpyDeviceToHost, ctx_->stream));
+    HIPCHK(hipStreamSynchronize(ctx_->stream));
+    return CGO_OK;
+}
+
+}  // namespace cgo

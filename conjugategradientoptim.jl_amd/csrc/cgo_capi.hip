@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "cgo_hip_backend.hpp"
+#include "cgo_qn.hpp"
 #include "cgo_build_id.inc"
 
 using namespace cgo;
@@ -1049,9 +1050,14 @@ static int batch_backend_on(cgo_ctx *ctx, HipObjective &cat, int64_t n, int64_t 
 
 static int batch_solve_on(cgo_ctx *ctx, HipBackend &be, int64_t n, int64_t batch, const double *x0, const double *scalars,
                           const unsigned char *active, const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters,
-                          cgo_batch_results *out, const std::function<int(cgo_objective **)> &make_hobj) {
+                          cgo_batch_results *out, const std::function<int(cgo_objective **)> &make_hobj, bool qn = false,
+                          const double *qn_param0 = nullptr) {
+    // qn: a batched L-BFGS solve (cgo_minimize_batch_lbfgs) — every ring empty at the start, and a handed-back problem is solved
+    // again by the host engine from its own x0 (the ring and Gram state of the device are not exported), with its row of the
+    // caller's x0 and qn_param0 (a quasi-Newton solver keeps a stored gradient: not a backend batch_export_row serves)
     auto on = [&](int64_t b) { return !active || active[b] != 0; };
     if (int rc = be.batch_reset(x0, scalars, active, cfg->max_iters, cfg->trace_enabled != 0)) return rc;
+    if (qn) { if (int rc = be.batch_lbfgs_reset()) return rc; }
     BatchRun run;
     if (int rc = run_batch(&be, *cfg, *ls, batch, slice_iters, run)) { if (rc == CGO_ESTATE) set_error("internal: a batched launch left a problem in a state the driver does not know"); return rc; }
     out->launches = run.launches;
@@ -1098,7 +1104,11 @@ static int batch_solve_on(cgo_ctx *ctx, HipBackend &be, int64_t n, int64_t batch
             if ((rc = make_solver(ctx, hobj, cfg, ls, nullptr, &hp, &hs))) break;
         }
         if (scalars) { if ((rc = cgo_objective_set_scalar(hobj, 0, scalars[b]))) break; }   // (the call's own objective, never the model)
-        if (s.it == 0) {   // nothing completed: the problem's own start, as a single solve has it
+        if (qn) {          // the whole solve, from the problem's own x0 (the device's row of x has moved on)
+            if (qn_param0) { if ((rc = cgo_objective_set_param_host(hobj, 0, qn_param0 + b * n))) break; }
+            if ((rc = hs->be->set_x0_host(x0 + b * n))) break;
+            if ((rc = hs->sv->start())) break;
+        } else if (s.it == 0) {   // nothing completed: the problem's own start, as a single solve has it
             if ((rc = be.batch_export_row(b, *hs->be, false))) break;
             if ((rc = hs->sv->start())) break;
         } else {
@@ -1168,6 +1178,71 @@ int cgo_minimize_batch_ex(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t bat
     const double *params[1] = {param0};
     return run_batch_on(ctx, cat, n, batch, x0, params, cfg, ls, slice_iters, out,
                         [&](cgo_objective **h) { return cgo_objective_create(ctx, obj_kind, n, 0, n, h); }, device_rows);
+    API_GUARD_END
+}
+
+// ---- batched solves with β = LBFGS(m): k_batch_lbfgs, the ring of every problem in device memory -------------------------------------
+int32_t cgo_batch_lbfgs_max_m(void) { return QN_MAX_M; }
+
+void cgo_batch_lbfgs_shape(int32_t *block, int32_t *pairs_per_trip) {
+    if (block) *block = HipBackend::batch_lbfgs_block();
+    if (pairs_per_trip) *pairs_per_trip = HipBackend::batch_lbfgs_unroll();
+}
+
+int64_t cgo_batch_lbfgs_max_n(cgo_ctx *ctx, int32_t obj_kind) {
+    const int64_t lds = cgo_batch_max_n(ctx, obj_kind);   // (0: no context, no such kind, no device)
+    if (lds == 0) return 0;
+    return obj_kind == CGO_OBJ_BOOTH ? lds : HipBackend::batch_lbfgs_max_n();
+}
+
+int cgo_minimize_batch_lbfgs(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
+                             const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out) {
+    API_GUARD_BEGIN
+    REQUIRE(ctx && x0 && cfg && ls && out, "null argument");
+    out->launches = 0; out->handed_back = 0;
+    REQUIRE(batch_kind(obj_kind), "batched L-BFGS solves: the objective must be CGO_OBJ_QUAD_DIAG, CGO_OBJ_ROSENBROCK_PAIRED or CGO_OBJ_BOOTH");
+    {
+        std::string why;
+        if (int rc = check_cg_config(cfg, why)) { set_error(why); return rc; }
+        if (int rc = check_ls_config(ls, why)) { set_error(why); return rc; }
+    }
+    REQUIRE(cfg->beta.kind == CGO_BETA_LBFGS, "batched L-BFGS solves: β must be LBFGS(m) (CG flavours: cgo_minimize_batch; the Broyden family has no batched form)");
+    if (cfg->beta.lbfgs_m > QN_MAX_M) { set_error("batched L-BFGS solves: m = " + std::to_string(cfg->beta.lbfgs_m) + " exceeds cgo_batch_lbfgs_max_m = " + std::to_string(QN_MAX_M)); return CGO_EINVAL; }
+    REQUIRE(ls->kind != CGO_LS_BACKTRACKING, "batched L-BFGS solves: the Backtracking line search is not supported (StrongWolfeBisection or WolfeBisection)");
+    REQUIRE(ctx->c.world() == 1, "batched L-BFGS solves: a multi-rank context is not supported (one rank only)");
+    REQUIRE(batch >= 1, "batched L-BFGS solves: batch must be ≥ 1");
+    REQUIRE(batch <= 0x7FFFFFFF, "batched L-BFGS solves: batch exceeds the largest grid");
+    REQUIRE(slice_iters >= 0, "batched L-BFGS solves: slice_iters must be ≥ 0 (0 = the library's policy)");
+    REQUIRE(n >= 1, "batched L-BFGS solves: n must be ≥ 1");
+    if (obj_kind == CGO_OBJ_ROSENBROCK_PAIRED) REQUIRE(n % 2 == 0, "batched L-BFGS solves: paired Rosenbrock needs an even n");
+    if (obj_kind == CGO_OBJ_BOOTH) REQUIRE(n == 2, "batched L-BFGS solves: Booth is 2-dimensional (n = 2)");
+    if (obj_kind == CGO_OBJ_QUAD_DIAG) REQUIRE(param0, "batched L-BFGS solves: the quadratic needs param0, the [batch*n] rows of D");
+    HIPCHK2(hipSetDevice(ctx->c.device));
+    const int64_t max_n = cgo_batch_lbfgs_max_n(ctx, obj_kind);
+    if (n > max_n) { set_error("batched L-BFGS solves: n = " + std::to_string(n) + " exceeds the index range of a pass (cgo_batch_lbfgs_max_n = " + std::to_string(max_n) + ")"); return CGO_EINVAL; }
+    const int m = cfg->beta.lbfgs_m, nparams = obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0;
+    {   // (3 + K + 2(m+1)) · batch · ld · 8 bytes against what is free, before anything is allocated
+        size_t free_b = 0, total_b = 0;
+        HIPCHK2(hipMemGetInfo(&free_b, &total_b));
+        const double need = HipBackend::batch_lbfgs_bytes(batch, n, nparams, m);
+        if (need > (double)free_b) {
+            char buf[288];
+            std::snprintf(buf, sizeof buf, "batched L-BFGS solves: the rows and rings (m = %d) of %lld problems of n = %lld ask for %.0f bytes of device memory, %zu are free",
+                          m, (long long)batch, (long long)n, need, free_b);
+            set_error(buf);
+            return CGO_ENOMEM;
+        }
+    }
+    const int64_t ld = n + (n & 1);
+    HipObjective cat;
+    cat.ctx = &ctx->c; cat.kind = obj_kind; cat.n_global = cat.n_local = batch * ld; cat.offset = 0;
+    if (cat.uses_param()) { if (int rc = cat.p[0].alloc((size_t)(batch * ld))) return rc; }
+    const double *params[1] = {param0};
+    HipBackend be(&ctx->c, &cat);
+    if (int rc = batch_backend_on(ctx, cat, n, batch, params, be, true)) return rc;
+    if (int rc = be.batch_lbfgs_alloc(m)) return rc;
+    return batch_solve_on(ctx, be, n, batch, x0, nullptr, nullptr, cfg, ls, slice_iters, out,
+                          [&](cgo_objective **h) { return cgo_objective_create(ctx, obj_kind, n, 0, n, h); }, true, param0);
     API_GUARD_END
 }
 

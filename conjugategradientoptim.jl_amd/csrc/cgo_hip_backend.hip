@@ -596,6 +596,9 @@ HipBackend::~HipBackend() {
     if (bat_st_) (void)hipFree(bat_st_);
     if (bat_recs_) (void)hipFree(bat_recs_);
     if (bat_fx0_) (void)hipFree(bat_fx0_);
+    if (bat_S_) (void)hipFree(bat_S_);
+    if (bat_Y_) (void)hipFree(bat_Y_);
+    if (bat_qn_) (void)hipFree(bat_qn_);
     if (bat_s0v_) (void)hipFree(bat_s0v_);
     for (auto &r : ring_) { if (r.e0) (void)hipEventDestroy(r.e0); if (r.e1) (void)hipEventDestroy(r.e1); }
 }

@@ -106,6 +106,7 @@ struct HipObjective {
 
 struct RPlan { bool big; int grid, npts; double bytes; };   // a k_cg / k_chain launch: streaming path, grid, points as launched, algorithmic bytes
 
+struct QnState;   // cgo_qn.hpp
 class HipBackend : public VecBackend {
   public:
     HipBackend(HipCtx *ctx, HipObjective *obj);
@@ -182,6 +183,15 @@ class HipBackend : public VecBackend {
     // dense rows; each may be nullptr; rows of inactive problems are not written.  With a scalar per problem the gradient is
     // k_batch_grad's (a workgroup per row), otherwise the ordinary gradient launch over the concatenated rows
     int batch_results(double *x /*[batch·n]*/, double *g /*[batch·n]*/, const unsigned char *active = nullptr);
+    // Batched solves with β = LBFGS(m) (cgo_backend_batch_lbfgs.hip; k_batch_lbfgs, cgo_kernels_batch_lbfgs.hip.hpp): a batch
+    // allocated with device_rows gets a ring of 2(m+1) rows and a QnState per problem beside its rows; batch_launch then runs
+    // k_batch_lbfgs.  batch_lbfgs_reset after every batch_reset: every problem's ring empty.
+    int batch_lbfgs_alloc(int m);
+    int batch_lbfgs_reset();
+    static int64_t batch_lbfgs_max_n();        // the limit of the pass index on n
+    static int batch_lbfgs_unroll();           // pairs per lane and trip of the two ring passes
+    static int batch_lbfgs_block();            // lanes of the workgroup
+    static double batch_lbfgs_bytes(int64_t batch, int64_t n, int nparams, int m);   // device bytes a batch of that shape asks for
     int64_t push_count(int kind) const { return push_counts_[kind]; }   // 0 speculated, 1 fused (g⁺ formed in the push), 2 plain
     bool sys_supported() const override { return rmode_; }
     int sys_begin() override;
@@ -432,6 +442,10 @@ class HipBackend : public VecBackend {
     void batch_fill_rows(std::vector<double> &rows, const double *src) const;
     int batch_recs_reserve(int64_t stride);
     int batch_grad_rows();
+    int bat_m_ = 0;                          // > 0: a batched L-BFGS solve of that ring depth (batch_lbfgs_alloc)
+    double *bat_S_ = nullptr, *bat_Y_ = nullptr;   // device [batch][m+1][ld]
+    QnState *bat_qn_ = nullptr;             // device [batch]
+    int batch_lbfgs_launch(const ResConfig &c, int64_t budget, std::vector<ResState> &st, std::vector<double> &f_x0);
     bool prof_on_ = false;
     struct ProfSlot { hipEvent_t e0 = nullptr, e1 = nullptr; int kk = -1; double bytes = 0; };
     std::vector<ProfSlot> ring_;

@@ -647,6 +647,23 @@ function batch_solve!(out::CBatchResults, handle::Ptr{Cvoid}, x0::Matrix{Float64
 end
 batch_close(handle::Ptr{Cvoid}) = check(ccall((:cgo_batch_close, libcgo), Cint, (Ptr{Cvoid},), handle))
 
+# ---- batched solves with β = LBFGS(m), m ≤ 10 (cgo_minimize_batch_lbfgs, include/cgo.h) ------------------------------
+# kind: CGO_OBJ_QUAD_DIAG (0, D = the n × batch matrix of diagonals), CGO_OBJ_ROSENBROCK_PAIRED (1), CGO_OBJ_BOOTH (2).  The ring of
+# 2(m+1) rows per problem lives in device memory; a problem the device loop does not finish is solved again from its own x0.
+function minimizeobjectivebatch_lbfgs(out::CBatchResults, kind::Integer, x0::Matrix{Float64}, config::CGConfig, linesearch_config::LineSearchConfig;
+                                       D::Union{Nothing,Matrix{Float64}} = nothing, ctx::Context = defaultcontext(), slice_iters::Integer = 0)
+    n, batch = size(x0)
+    d = D === nothing ? Ptr{Float64}(C_NULL) : pointer(D)
+    GC.@preserve x0 D begin
+        check(ccall((:cgo_minimize_batch_lbfgs, libcgo), Cint,
+                    (Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ref{CCGConfig}, Ref{CLSConfig}, Int64, Ref{CBatchResults}),
+                    ctx.h, kind, n, batch, x0, d, ccfg(config), cls(linesearch_config), slice_iters, out))
+    end
+    return out
+end
+batch_lbfgs_max_n(kind::Integer; ctx::Context = defaultcontext()) =
+    ccall((:cgo_batch_lbfgs_max_n, libcgo), Int64, (Ptr{Cvoid}, Int32), ctx.h, kind)
+
 # ---- kernel-level generics (src/cg_flavours.jl:2-15, 46-170; src/cg_utils.jl:4-23) ---------------------
 function updatedir!(u::Vector{Float64}, df_x::Vector{Float64}, β::Float64; ctx::Context = defaultcontext())
     @assert length(u) == length(df_x)

@@ -591,6 +591,30 @@ int64_t cgo_batch_max_n_ex(cgo_ctx *ctx, int32_t obj_kind, const cgo_batch_polic
 int64_t cgo_batch_max_n_obj_ex(cgo_objective *model, const cgo_batch_policy *policy);
 /* The streaming loop of the device-rows tier: lanes per workgroup and pairs of elements per lane and trip (needs no device). */
 void cgo_batch_rows_shape(int32_t *block, int32_t *pairs_per_trip);
+/* CGO_HOST_ONLY_BEGIN: declarations the run-time compiled modules do not need — csrc/gen_rtc_sources.py leaves the lines from
+ * here to CGO_HOST_ONLY_END out of their text, which so stays what it was */
+/* BATCHED SOLVES WITH A QUASI-NEWTON DIRECTION: β = LBFGS(m), 1 ≤ m ≤ cgo_batch_lbfgs_max_m() = 10.  Every call above is a CG
+ * flavour and refuses LBFGS; this one is the batch for it — a call of its own because it allocates a ring of 2(m+1) rows per
+ * problem and runs another kernel (k_batch_lbfgs): one workgroup per problem, the rows of x, u and the parameter vector and the
+ * ring S, Y [batch][m+1][n + n%2] in device memory, the Gram form of the two-loop recursion on the device between a push pass
+ * and a combine pass.  Arguments and results as cgo_minimize_batch; `launches` and `handed_back` keep their meaning.
+ *   Objectives: CGO_OBJ_QUAD_DIAG, CGO_OBJ_ROSENBROCK_PAIRED, CGO_OBJ_BOOTH.  Line searches: StrongWolfeBisection, WolfeBisection.
+ *   Device memory: (3 + K + 2(m+1)) · batch · (n + n%2) · 8 bytes (K = 1 for the quadratic, else 0), compared with what is
+ *   free BEFORE anything is allocated: a batch that does not fit is CGO_ENOMEM with the bytes in the message.
+ *   Hand-back: a problem whose next iteration the device loop does not run (a line-search outcome other than :success, a
+ *   non-finite value, the rare-path norms, WolfeBisection's bracket collapse) is SOLVED AGAIN FROM ITS OWN x0 by one ordinary
+ *   solver under the same config — it costs a whole solve, and its results and trace replace the device's.
+ * CGO_EINVAL, with the reason in the message: a CG flavour or the Broyden family (those: cgo_minimize_batch), m > 10,
+ * Backtracking, any other objective kind (run-time compiled objectives included: there is no batched L-BFGS form of
+ * cgo_minimize_batch_obj, of a scalar per problem or of the cgo_batch handle), a multi-rank context, batch < 1,
+ * n > cgo_batch_lbfgs_max_n, and what cgo_minimize_batch refuses of shapes (odd n for paired Rosenbrock, n ≠ 2 for Booth, a
+ * missing param0). */
+int cgo_minimize_batch_lbfgs(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
+                             const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out);
+int32_t cgo_batch_lbfgs_max_m(void);                                              /* 10 */
+int64_t cgo_batch_lbfgs_max_n(cgo_ctx *ctx, int32_t obj_kind);                    /* the limit of the pass index, as cgo_batch_max_n_ex(…DEVICE…); 0: none */
+void cgo_batch_lbfgs_shape(int32_t *block, int32_t *pairs_per_trip);              /* of the two ring passes; needs no device */
+/* CGO_HOST_ONLY_END */
 /* The stop test at the top of iteration it + 1 (optim.jl:53-80,162-169) as a function of the loop state — the one rule the
  * engine and the problems a batch finishes on the device share: the terminal status (CGO_INCOMPLETE: the iteration runs) and
  * Results.iters_ran. */
