@@ -117,6 +117,26 @@ class ArmedProbeC(C.Structure):  # cgo_armed_probe
                 ("args_out", CtlArgsC), ("out_dev", C.c_double * 56), ("rec", CtlRecordC * 32), ("symbol", C.c_char * 4096)]
 
 
+class BatchPassC(C.Structure):  # cgo_batch_pass (include/cgo.h)
+    _fields_ = [("kind", C.c_int32), ("k", C.c_int32), ("a", C.c_double * 7), ("a_acc", C.c_double), ("beta", C.c_double),
+                ("co_set", C.c_int32), ("co_count", C.c_int32), ("co_gamma", C.c_double), ("co_cy", C.c_double * 10),
+                ("co_cs", C.c_double * 10)]
+
+
+class BatchPassOutC(C.Structure):  # cgo_batch_pass_out
+    _fields_ = [("ts", (C.c_double * 7) * 7), ("gu", C.c_double), ("uu", C.c_double), ("width", C.c_int64), ("stored", C.c_int64)]
+
+
+class BatchProbeC(C.Structure):  # cgo_batch_probe_args
+    _fields_ = [("tier", C.c_int32), ("obj_kind", C.c_int32), ("m", C.c_int32), ("n_params", C.c_int32), ("model", C.c_void_p),
+                ("n", C.c_int64), ("batch", C.c_int64), ("x", dp), ("u", dp), ("params", dp * 4), ("scalars", dp),
+                ("skip", C.POINTER(C.c_uint8)), ("S", dp), ("Y", dp), ("qn", C.c_void_p), ("npass", C.c_int32),
+                ("reserved", C.c_int32), ("pass_", BatchPassC * 32), ("rows", dp), ("out", C.POINTER(BatchPassOutC)),
+                ("x_out", dp), ("u_out", dp), ("g_out", dp), ("S_out", dp), ("Y_out", dp), ("qn_out", C.c_void_p),
+                ("reason", C.POINTER(C.c_int32)), ("done", i64p), ("passes", i64p), ("points", C.c_int32),
+                ("reserved2", C.c_int32), ("ld", C.c_int64), ("symbol", C.c_char * 128)]
+
+
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, dp, dp, C.c_int32)
 FDF_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, dp, dp, C.c_int64)   # cgo_fdf_fn: f = fdf!(g, x)
 
@@ -221,6 +241,8 @@ SIGNATURES = {
     "cgo_batch_lbfgs_max_m": (C.c_int32, []),
     "cgo_batch_lbfgs_max_n": (C.c_int64, [_vp, C.c_int32]),
     "cgo_batch_lbfgs_shape": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "cgo_batch_probe": (C.c_int, [_vp, C.POINTER(BatchProbeC)]),
+    "cgo_batch_probe_qn_bytes": (C.c_int64, []),
     "cgo_stop_status": (C.c_int32, [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, i64p]),
     "cgo_kernel_dir": (C.c_int, [_vp, dp, dp, C.c_double, C.c_int64, dp]),
     "cgo_kernel_beta_partials": (C.c_int, [_vp, dp, dp, dp, C.c_int64, dp]),

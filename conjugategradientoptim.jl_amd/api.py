@@ -1228,6 +1228,123 @@ def minimizeobjectivebatch(obj_or_kind, X0, config: CGConfig, linesearch_config:
     return o.results(rows_used=used.value)
 
 
+BATCH_PROBE_TIERS = {"lds": 0, "device": 1, "lbfgs": 2}
+BATCH_PROBE_ROW = 64
+NAN_PATTERN = 0x7FF87FF87FF87FF8   # what every probe buffer starts as
+
+
+def batch_probe_qn_words() -> int:
+    """8-byte words of one problem's quasi-Newton state (QnState, csrc/cgo_qn.hpp) as `batch_probe` takes and returns it."""
+    return int(_lib.lib().cgo_batch_probe_qn_bytes()) // 8
+
+
+def batch_probe(tier: str, obj_or_kind, X, U, script, params=None, scalars=None, skip=None, m: int = 0, S=None, Y=None, qn=None,
+                gradient: bool = False, ctx: Optional[Context] = None) -> dict:
+    """A scripted sequence of passes of a batched solve in ONE launch, a workgroup per problem (cgo_batch_probe).  tier: "lds"
+    (k_batch), "device" (k_batch_rows) or "lbfgs" (k_batch_lbfgs).  `obj_or_kind` as in minimizeobjectivebatch; X, U [batch, n];
+    params: the arrays [batch, n] of the slots the objective reads (the quadratic: [D]); scalars, skip: [batch] or None.
+    "lbfgs": m, S and Y [batch, m + 1, n] (absent slots NaN) and qn, a uint64 array [batch, batch_probe_qn_words()].
+    `script`: up to 32 tuples ("trial", a) | ("accept_dir_trial", a_acc, beta, a) | ("init",) | ("push", a_acc) |
+    ("combine", a[, (count, gamma, cy, cs)]), a = the trial steps (k = len(a)).
+    Returns dict(rows= uint64 [npass, batch, 64] (the bits of the row every workgroup holds after that pass; NAN_PATTERN where
+    nothing was stored), width=, stored= [npass, batch], ts= [npass, batch, 7, 7], gu=, uu= [npass, batch], x=, u= [batch, ld],
+    S=, Y= [batch, m + 1, ld], qn=, g= [batch, ld] (gradient=True), reason=, done=, passes= [batch], points=, ld=, symbol=)."""
+    if tier not in BATCH_PROBE_TIERS:
+        raise ValueError(f"tier must be one of {sorted(BATCH_PROBE_TIERS)}, not {tier!r}")
+    model = obj_or_kind if isinstance(obj_or_kind, DeviceObjective) else None
+    if model is None and obj_or_kind not in OBJ_KINDS:
+        raise ValueError(f"unknown objective kind {obj_or_kind!r}")
+    X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
+    if X.ndim != 2:
+        raise ValueError("X must be [batch, n]")
+    batch, n = X.shape
+    U = _batch_rows("U", U, X.shape)
+    ld = n + (n & 1)
+    keep = [X, U]
+    p = _lib.BatchProbeC()
+    p.tier, p.m, p.n, p.batch = BATCH_PROBE_TIERS[tier], int(m), n, batch
+    p.obj_kind = 4 if model is not None else OBJ_KINDS[obj_or_kind]   # (4: CGO_OBJ_USER)
+    p.model = model._h if model is not None else None
+    p.x, p.u = X.ctypes.data_as(dp), U.ctypes.data_as(dp)
+    Pc = [_batch_rows(f"params[{j}]", v, X.shape) for j, v in enumerate(params or [])]
+    if len(Pc) > 4:
+        raise ValueError("at most 4 parameter slots")
+    keep += Pc
+    p.n_params = len(Pc)
+    for j, v in enumerate(Pc):
+        p.params[j] = v.ctypes.data_as(dp)
+    if scalars is not None:
+        scalars = _batch_rows("scalars", scalars, (batch,))
+        p.scalars = scalars.ctypes.data_as(dp)
+    if skip is not None:
+        skip = np.ascontiguousarray(np.asarray(skip, dtype=np.uint8))
+        if skip.shape != (batch,):
+            raise ValueError("skip must be [batch]")
+        p.skip = skip.ctypes.data_as(C.POINTER(C.c_uint8))
+    qw = batch_probe_qn_words()
+    ring = tier == "lbfgs"
+    if ring:
+        S = _batch_rows("S", S, (batch, m + 1, n))
+        Y = _batch_rows("Y", Y, (batch, m + 1, n))
+        qn = np.ascontiguousarray(np.asarray(qn, dtype=np.uint64))
+        if qn.shape != (batch, qw):
+            raise ValueError(f"qn must be [batch, {qw}] 8-byte words")
+        p.S, p.Y, p.qn = S.ctypes.data_as(dp), Y.ctypes.data_as(dp), qn.ctypes.data_as(C.c_void_p)
+    if len(script) > 32:
+        raise ValueError("batch_probe: at most 32 passes")
+    p.npass = len(script)
+    for q, item in enumerate(script):
+        c = p.pass_[q]
+        a = []
+        if item[0] == "trial":
+            c.kind, a = 0, item[1]
+        elif item[0] == "accept_dir_trial":
+            c.kind, c.a_acc, c.beta, a = 1, float(item[1]), float(item[2]), item[3]
+        elif item[0] == "init":
+            c.kind = 2
+        elif item[0] == "push":
+            c.kind, c.a_acc = 3, float(item[1])
+        elif item[0] == "combine":
+            c.kind, a = 4, item[1]
+            if len(item) > 2 and item[2] is not None:
+                cnt, gamma, cy, cs = item[2]
+                if len(cy) > 10 or len(cs) > 10:
+                    raise ValueError("batch_probe: at most 10 coefficients")
+                c.co_set, c.co_count, c.co_gamma = 1, int(cnt), float(gamma)
+                c.co_cy[:len(cy)] = [float(v) for v in cy]
+                c.co_cs[:len(cs)] = [float(v) for v in cs]
+        else:
+            raise ValueError(f"batch_probe: no pass kind {item[0]!r}")
+        if len(a) > 7:
+            raise ValueError("batch_probe: at most 7 trial steps")
+        c.k = len(a)
+        c.a[:len(a)] = [float(v) for v in a]
+    npass = max(p.npass, 1)
+    rows = np.full((npass, batch, BATCH_PROBE_ROW), NAN_PATTERN, dtype=np.uint64)
+    out = (_lib.BatchPassOutC * (npass * batch))()
+    xo, uo = np.empty((batch, ld)), np.empty((batch, ld))
+    reason, done, passes = np.zeros(batch, dtype=np.int32), np.zeros(batch, dtype=np.int64), np.zeros(batch, dtype=np.int64)
+    p.rows, p.out = rows.ctypes.data_as(dp), out
+    p.x_out, p.u_out = xo.ctypes.data_as(dp), uo.ctypes.data_as(dp)
+    p.reason, p.done, p.passes = reason.ctypes.data_as(C.POINTER(C.c_int32)), done.ctypes.data_as(i64p), passes.ctypes.data_as(i64p)
+    go = So = Yo = qo = None
+    if gradient:
+        go = np.empty((batch, ld))
+        p.g_out = go.ctypes.data_as(dp)
+    if ring:
+        So, Yo = np.empty((batch, m + 1, ld)), np.empty((batch, m + 1, ld))
+        qo = np.zeros((batch, qw), dtype=np.uint64)
+        p.S_out, p.Y_out, p.qn_out = So.ctypes.data_as(dp), Yo.ctypes.data_as(dp), qo.ctypes.data_as(C.c_void_p)
+    ctx = ctx or (model.ctx if model is not None else default_context())   # (argument errors above need no device)
+    check(_lib.lib().cgo_batch_probe(ctx._h, C.byref(p)))
+    del keep
+    o = np.frombuffer(out, dtype=np.float64).reshape(npass, batch, 53)
+    return dict(rows=rows, width=o[:, :, 51].view(np.int64).copy(), stored=o[:, :, 52].view(np.int64).copy(),
+                ts=o[:, :, :49].reshape(npass, batch, 7, 7).copy(), gu=o[:, :, 49].copy(), uu=o[:, :, 50].copy(),
+                x=xo, u=uo, S=So, Y=Yo, qn=qo, g=go, reason=reason, done=done, passes=passes, points=int(p.points),
+                ld=int(p.ld), symbol=p.symbol.decode())
+
+
 def batch_lbfgs_shape():
     """(lanes per workgroup, pairs of elements per lane and trip) of the two ring passes of minimizeobjectivebatch_lbfgs."""
     blk, u = C.c_int32(0), C.c_int32(0)

@@ -166,6 +166,15 @@ int HipBackend::batch_begin(int64_t batch, int64_t n, const double *x0, const do
     return batch_reset(x0, nullptr, nullptr, max_iters, trace);
 }
 
+void HipBackend::batch_fill_params(BatchParams &B, const ResConfig &c, int64_t budget) const {
+    B.x = xc_; B.u = uc_; B.p0 = obj_->p[0].p; B.p1 = obj_->p[1].p; B.p2 = obj_->p[2].p; B.p3 = obj_->p[3].p;
+    B.st = bat_st_; B.recs = bat_recs_; B.f_x0 = bat_fx0_;
+    B.n = bat_n_; B.ld = bat_ld_; B.rec_stride = bat_rec_stride_; B.rec_abs = bat_trace_ ? 1 : 0;
+    B.s0 = obj_->s0; B.s0v = bat_s0v_on_ ? bat_s0v_ : nullptr;
+    B.cfg = c; B.cfg.npts = 3; B.cfg.log_on = 0;
+    B.budget = budget;
+}
+
 int HipBackend::batch_launch(const ResConfig &c, int64_t budget, std::vector<ResState> &st, std::vector<double> &f_x0) {
     if (!bat_st_) { set_error("internal: batch_launch before batch_begin"); return CGO_ESTATE; }
     if (bat_m_ > 0) return batch_lbfgs_launch(c, budget, st, f_x0);   // a batched L-BFGS solve: k_batch_lbfgs (cgo_backend_batch_lbfgs.hip)
@@ -175,12 +184,7 @@ int HipBackend::batch_launch(const ResConfig &c, int64_t budget, std::vector<Res
         if (int rc = batch_recs_reserve(budget)) return rc;
     }
     BatchParams B{};
-    B.x = xc_; B.u = uc_; B.p0 = obj_->p[0].p; B.p1 = obj_->p[1].p; B.p2 = obj_->p[2].p; B.p3 = obj_->p[3].p;
-    B.st = bat_st_; B.recs = bat_recs_; B.f_x0 = bat_fx0_;
-    B.n = bat_n_; B.ld = bat_ld_; B.rec_stride = bat_rec_stride_; B.rec_abs = bat_trace_ ? 1 : 0;
-    B.s0 = obj_->s0; B.s0v = bat_s0v_on_ ? bat_s0v_ : nullptr;
-    B.cfg = c; B.cfg.npts = 3; B.cfg.log_on = 0;
-    B.budget = budget;
+    batch_fill_params(B, c, budget);
     void *args[] = {&B};
     if (obj_->kind == CGO_OBJ_USER) {
         const hipFunction_t mf = !obj_->rtc ? nullptr : bat_rows_ ? obj_->rtc->batch_rows(3) : obj_->rtc->batch(3);

@@ -64,6 +64,13 @@ int HipBackend::batch_lbfgs_reset() {
     return CGO_OK;
 }
 
+void HipBackend::batch_lbfgs_fill_params(BatchLbfgsParams &L, const ResConfig &c, int64_t budget) const {
+    batch_fill_params(L.B, c, budget);
+    L.B.s0v = nullptr;   // (no scalar per problem in this family)
+    L.S = bat_S_; L.Y = bat_Y_; L.qn = bat_qn_;
+    L.ring_stride = (long long)(bat_m_ + 1) * bat_ld_;
+}
+
 int HipBackend::batch_lbfgs_launch(const ResConfig &c, int64_t budget, std::vector<ResState> &st, std::vector<double> &f_x0) {
     if (!bat_qn_ || bat_s0v_on_) { set_error("internal: batched L-BFGS launch on a batch of another shape"); return CGO_ESTATE; }
     HIPCHK(hipSetDevice(ctx_->device));
@@ -72,15 +79,7 @@ int HipBackend::batch_lbfgs_launch(const ResConfig &c, int64_t budget, std::vect
         if (int rc = batch_recs_reserve(budget)) return rc;
     }
     BatchLbfgsParams L{};
-    BatchParams &B = L.B;
-    B.x = xc_; B.u = uc_; B.p0 = obj_->p[0].p; B.p1 = obj_->p[1].p; B.p2 = obj_->p[2].p; B.p3 = obj_->p[3].p;
-    B.st = bat_st_; B.recs = bat_recs_; B.f_x0 = bat_fx0_;
-    B.n = bat_n_; B.ld = bat_ld_; B.rec_stride = bat_rec_stride_; B.rec_abs = bat_trace_ ? 1 : 0;
-    B.s0 = obj_->s0; B.s0v = nullptr;
-    B.cfg = c; B.cfg.npts = 3; B.cfg.log_on = 0;
-    B.budget = budget;
-    L.S = bat_S_; L.Y = bat_Y_; L.qn = bat_qn_;
-    L.ring_stride = (long long)(bat_m_ + 1) * bat_ld_;
+    batch_lbfgs_fill_params(L, c, budget);
     void *args[] = {&L};
     const void *fn = batch_lbfgs_kernel_for(obj_->kind, 3);
     if (!fn) { set_error("batched L-BFGS solves: no k_batch_lbfgs instantiation for this objective"); return CGO_EINVAL; }

@@ -1195,6 +1195,26 @@ int64_t cgo_batch_lbfgs_max_n(cgo_ctx *ctx, int32_t obj_kind) {
     return obj_kind == CGO_OBJ_BOOTH ? lds : HipBackend::batch_lbfgs_max_n();
 }
 
+// What a batched L-BFGS solve and its probe refuse of sizes alike: n beyond the pass index, and rows and rings the device's free
+// memory does not hold — (3 + K + 2(m+1)) · batch · ld · 8 bytes against what is free, before anything is allocated.
+static int batch_lbfgs_sizes(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, int m) {
+    HIPCHK2(hipSetDevice(ctx->c.device));
+    const int64_t max_n = cgo_batch_lbfgs_max_n(ctx, obj_kind);
+    if (n > max_n) { set_error("batched L-BFGS solves: n = " + std::to_string(n) + " exceeds the index range of a pass (cgo_batch_lbfgs_max_n = " + std::to_string(max_n) + ")"); return CGO_EINVAL; }
+    const int nparams = obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK2(hipMemGetInfo(&free_b, &total_b));
+    const double need = HipBackend::batch_lbfgs_bytes(batch, n, nparams, m);
+    if (need > (double)free_b) {
+        char buf[288];
+        std::snprintf(buf, sizeof buf, "batched L-BFGS solves: the rows and rings (m = %d) of %lld problems of n = %lld ask for %.0f bytes of device memory, %zu are free",
+                      m, (long long)batch, (long long)n, need, free_b);
+        set_error(buf);
+        return CGO_ENOMEM;
+    }
+    return CGO_OK;
+}
+
 int cgo_minimize_batch_lbfgs(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
                              const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out) {
     API_GUARD_BEGIN
@@ -1217,22 +1237,8 @@ int cgo_minimize_batch_lbfgs(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t 
     if (obj_kind == CGO_OBJ_ROSENBROCK_PAIRED) REQUIRE(n % 2 == 0, "batched L-BFGS solves: paired Rosenbrock needs an even n");
     if (obj_kind == CGO_OBJ_BOOTH) REQUIRE(n == 2, "batched L-BFGS solves: Booth is 2-dimensional (n = 2)");
     if (obj_kind == CGO_OBJ_QUAD_DIAG) REQUIRE(param0, "batched L-BFGS solves: the quadratic needs param0, the [batch*n] rows of D");
-    HIPCHK2(hipSetDevice(ctx->c.device));
-    const int64_t max_n = cgo_batch_lbfgs_max_n(ctx, obj_kind);
-    if (n > max_n) { set_error("batched L-BFGS solves: n = " + std::to_string(n) + " exceeds the index range of a pass (cgo_batch_lbfgs_max_n = " + std::to_string(max_n) + ")"); return CGO_EINVAL; }
-    const int m = cfg->beta.lbfgs_m, nparams = obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0;
-    {   // (3 + K + 2(m+1)) · batch · ld · 8 bytes against what is free, before anything is allocated
-        size_t free_b = 0, total_b = 0;
-        HIPCHK2(hipMemGetInfo(&free_b, &total_b));
-        const double need = HipBackend::batch_lbfgs_bytes(batch, n, nparams, m);
-        if (need > (double)free_b) {
-            char buf[288];
-            std::snprintf(buf, sizeof buf, "batched L-BFGS solves: the rows and rings (m = %d) of %lld problems of n = %lld ask for %.0f bytes of device memory, %zu are free",
-                          m, (long long)batch, (long long)n, need, free_b);
-            set_error(buf);
-            return CGO_ENOMEM;
-        }
-    }
+    const int m = cfg->beta.lbfgs_m;
+    if (int rc = batch_lbfgs_sizes(ctx, obj_kind, n, batch, m)) return rc;
     const int64_t ld = n + (n & 1);
     HipObjective cat;
     cat.ctx = &ctx->c; cat.kind = obj_kind; cat.n_global = cat.n_local = batch * ld; cat.offset = 0;
@@ -1432,6 +1438,63 @@ int cgo_batch_close(cgo_batch *h) {
     delete h;            // (the backend before the model: its objective shares the model's module)
     obj_unref(m);
     return CGO_OK;
+    API_GUARD_END
+}
+
+// ---- cgo_batch_probe: a script of passes of a batched solve in one launch (cgo_backend_batch_probe.hip) ------------------------------
+// The batch is made as the solve of that tier makes it — the same refusals of objectives, shapes and sizes, the same concatenated
+// objective, batch_backend_on, batch_lbfgs_alloc — and lives for this one call.
+int64_t cgo_batch_probe_qn_bytes(void) { return (int64_t)sizeof(QnState); }
+
+int cgo_batch_probe(cgo_ctx *ctx, cgo_batch_probe_args *p) {
+    API_GUARD_BEGIN
+    REQUIRE(ctx && p, "null argument");
+    p->points = 0; p->ld = 0; p->symbol[0] = 0;
+    REQUIRE(p->tier >= 0 && p->tier <= 2, "batch probe: tier must be 0 (LDS), 1 (device rows) or 2 (L-BFGS)");
+    REQUIRE(p->npass >= 1 && p->npass <= CGO_BATCH_PROBE_MAX_PASSES, "batch probe: 1 … 32 passes");
+    REQUIRE(ctx->c.world() == 1, "batch probe: a multi-rank context is not supported (one rank only)");
+    REQUIRE(p->batch >= 1 && p->batch <= 0x7FFFFFFF, "batch probe: 1 ≤ batch ≤ the largest grid");
+    REQUIRE(p->x && p->u, "batch probe: x and u are required");
+    const int64_t batch = p->batch;
+    const int rows = p->tier == 0 ? CGO_BATCH_ROWS_LDS : CGO_BATCH_ROWS_DEVICE;
+    bool device_rows = false;
+    HipObjective cat;
+    int64_t n = p->n;
+    if (p->model) {
+        REQUIRE(p->tier != 2, "batch probe: a run-time compiled objective has no batched L-BFGS form (tiers 0 and 1)");
+        if (int rc = check_batch_model(ctx, p->model)) return rc;
+        n = p->model->o.n_local;
+        REQUIRE(p->n == n, "batch probe: n is not the size of the model objective");
+        REQUIRE(n >= 1, "batch probe: n must be ≥ 1");
+        if (p->scalars)
+            for (int64_t b = 0; b < batch; ++b)
+                if (!std::isfinite(p->scalars[b])) { set_error("batch probe: scalars[" + std::to_string(b) + "] is not finite"); return CGO_EINVAL; }
+        if (int rc = batch_model_cat(ctx, p->model, batch, p->params, p->n_params, cat, rows, device_rows)) return rc;
+    } else {
+        const int32_t obj_kind = p->obj_kind;
+        REQUIRE(batch_kind(obj_kind), "batch probe: the objective must be CGO_OBJ_QUAD_DIAG, CGO_OBJ_ROSENBROCK_PAIRED, CGO_OBJ_BOOTH or a model");
+        REQUIRE(n >= 1, "batch probe: n must be ≥ 1");
+        REQUIRE(!p->scalars, "batch probe: scalars belong to a run-time compiled objective");
+        if (obj_kind == CGO_OBJ_ROSENBROCK_PAIRED) REQUIRE(n % 2 == 0, "batch probe: paired Rosenbrock needs an even n");
+        if (obj_kind == CGO_OBJ_BOOTH) REQUIRE(n == 2, "batch probe: Booth is 2-dimensional (n = 2)");
+        if (obj_kind == CGO_OBJ_QUAD_DIAG) REQUIRE(p->params[0], "batch probe: the quadratic needs params[0], the [batch*n] rows of D");
+        HIPCHK2(hipSetDevice(ctx->c.device));
+        if (p->tier == 2) {
+            REQUIRE(p->m >= 1, "batch probe: m must be ≥ 1");
+            if (p->m > QN_MAX_M) { set_error("batch probe: m = " + std::to_string(p->m) + " exceeds cgo_batch_lbfgs_max_m = " + std::to_string(QN_MAX_M)); return CGO_EINVAL; }
+            if (int rc = batch_lbfgs_sizes(ctx, obj_kind, n, batch, p->m)) return rc;
+            device_rows = true;
+        } else {
+            if (int rc = batch_tier(ctx, rows, n, batch, obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0, cgo_batch_max_n(ctx, obj_kind), "cgo_batch_max_n", device_rows)) return rc;
+        }
+        const int64_t ld = n + (n & 1);
+        cat.ctx = &ctx->c; cat.kind = obj_kind; cat.n_global = cat.n_local = batch * ld; cat.offset = 0;
+        if (cat.uses_param()) { if (int rc = cat.p[0].alloc((size_t)(batch * ld))) return rc; }
+    }
+    HipBackend be(&ctx->c, &cat);
+    if (int rc = batch_backend_on(ctx, cat, n, batch, p->params, be, device_rows)) return rc;
+    if (p->tier == 2) { if (int rc = be.batch_lbfgs_alloc(p->m)) return rc; }
+    return be.batch_probe(*p);
     API_GUARD_END
 }
 

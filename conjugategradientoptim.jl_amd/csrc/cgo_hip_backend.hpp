@@ -14,7 +14,7 @@
 
 namespace cgo {
 
-namespace dev { struct CtlArgs; struct Tail; struct LoopParams; struct ResParams; }
+namespace dev { struct CtlArgs; struct Tail; struct LoopParams; struct ResParams; struct BatchParams; struct BatchLbfgsParams; }
 
 void set_error(const std::string &msg);
 const char *get_error();
@@ -192,6 +192,10 @@ class HipBackend : public VecBackend {
     static int batch_lbfgs_unroll();           // pairs per lane and trip of the two ring passes
     static int batch_lbfgs_block();            // lanes of the workgroup
     static double batch_lbfgs_bytes(int64_t batch, int64_t n, int nparams, int m);   // device bytes a batch of that shape asks for
+    // Test entry point (cgo_batch_probe, cgo_backend_batch_probe.hip): a script of passes in ONE launch of the PROBE twin of this
+    // batch's kernel, on host vectors; the batch is one batch_alloc (and batch_lbfgs_alloc) made, the launch arguments are
+    // batch_fill_params' / batch_lbfgs_fill_params'.  Every buffer of the batch gets NaN slack: a probed batch is for probing only.
+    int batch_probe(cgo_batch_probe_args &p);
     int64_t push_count(int kind) const { return push_counts_[kind]; }   // 0 speculated, 1 fused (g⁺ formed in the push), 2 plain
     bool sys_supported() const override { return rmode_; }
     int sys_begin() override;
@@ -442,6 +446,9 @@ class HipBackend : public VecBackend {
     void batch_fill_rows(std::vector<double> &rows, const double *src) const;
     int batch_recs_reserve(int64_t stride);
     int batch_grad_rows();
+    // what a launch reads of the batch — ld, the slot pointers, s0 / s0v, the record stride: batch_launch's and the probe's alike
+    void batch_fill_params(dev::BatchParams &B, const ResConfig &c, int64_t budget) const;
+    void batch_lbfgs_fill_params(dev::BatchLbfgsParams &L, const ResConfig &c, int64_t budget) const;   // … and the ring, its stride, the states
     int bat_m_ = 0;                          // > 0: a batched L-BFGS solve of that ring depth (batch_lbfgs_alloc)
     double *bat_S_ = nullptr, *bat_Y_ = nullptr;   // device [batch][m+1][ld]
     QnState *bat_qn_ = nullptr;             // device [batch]

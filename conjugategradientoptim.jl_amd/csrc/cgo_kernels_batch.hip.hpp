@@ -18,6 +18,11 @@
 //
 // Workgroups never wait for one another: no atomics, no polling, no read of another problem's rows.  More workgroups than CUs
 // simply queue.  A launch is bounded by `budget` outer iterations per problem, each by the line search's own limits.
+//
+// PROBE (template flag, default false; cgo_batch_probe): the same kernel with a script of passes in place of res_iterate, every
+// workgroup storing the row it holds after each pass — what tests/test_batch_kernel_sums.py compares.  Everything else — the
+// early return, the LDS load, the vector-operations object, the write-back rule, the state store — is the code below.  The
+// PROBE twins are instantiated in a translation unit of their own (cgo_backend_batch_probe.hip).
 #pragma once
 
 #include "cgo_kernels_resident.hip.hpp"
@@ -39,8 +44,72 @@ struct BatchParams {
     const double *s0v;                        // [batch]: every problem's own objective scalar; null: s0 is every problem's
 };
 
-template <class Obj, int NPTS>
-__global__ __launch_bounds__(BLOCK, 1) void k_batch(const BatchParams B) {
+// ---- cgo_batch_probe: the script of the PROBE twins of k_batch, k_batch_rows and k_batch_lbfgs ----------------------------------
+constexpr int BATCH_PROBE_MAX_PASSES = 32;
+constexpr int BATCH_PROBE_ROW = 64;       // stride of a stored row: the push row of k_batch_lbfgs (QN_SUMS), the widest there is
+constexpr int BATCH_PROBE_MAX_M = 10;     // = QN_MAX_M (cgo_kernels_batch_lbfgs.hip.hpp asserts it)
+static_assert(RES_WMAX <= BATCH_PROBE_ROW, "a stored row holds the widest row of totals");
+// One pass: kind 0 trial(a, k) | 1 accept_dir_trial(a_acc, beta, a, k) | 2 pass<R_INIT, 1> | 3 push_update(a_acc) |
+// 4 combine_trial(a, k) — with the coefficients the last push left, or (co_count ≥ 0) those given here.  a[] is padded by the
+// host as the loops pad it (entries ≥ k repeat a[k − 1]).
+struct BatchProbePass {
+    int kind, k;
+    double a[RES_MAXP];
+    double a_acc, beta;
+    int co_count, pad_;
+    double co_gamma, co_cy[BATCH_PROBE_MAX_M], co_cs[BATCH_PROBE_MAX_M];
+};
+struct BatchProbeOut { TrialSums ts[RES_MAXP]; double gu, uu; long long width, stored; };
+struct BatchProbe {
+    const BatchProbePass *script; int npass;  // DEVICE [npass]
+    double *rows;                             // DEVICE [npass][batch][BATCH_PROBE_ROW]: the row EVERY workgroup holds after each pass
+    BatchProbeOut *out;                       // DEVICE [npass][batch]: what the member function returned in every problem
+};
+// (the PROBE twin's argument IS a BatchParams with the script behind it: the kernel text below reads B.… in both forms)
+struct BatchProbeParams : BatchParams { BatchProbe pr; };
+template <bool PROBE> struct BatchArg { using type = BatchParams; };
+template <> struct BatchArg<true> { using type = BatchProbeParams; };
+
+// after a member call: the workgroup's row (W slots of `row`, LDS) and, by lane 0, what the call returned
+__device__ __forceinline__ void batch_probe_store(const BatchProbe &pr, int q, const double *row, int W, const TrialSums *out, double gu, double uu, int stored) {
+    const size_t at = (size_t)q * gridDim.x + blockIdx.x;
+    if ((int)threadIdx.x < W) pr.rows[at * BATCH_PROBE_ROW + threadIdx.x] = row[threadIdx.x];
+    if (threadIdx.x == 0) {
+        BatchProbeOut &o = pr.out[at];
+        for (int j = 0; j < RES_MAXP; ++j) o.ts[j] = out[j];
+        o.gu = gu; o.uu = uu; o.width = W; o.stored = stored;
+    }
+}
+
+// The passes the CG loop (res_iterate) issues, through the member functions it calls.  An accepting pass counts as a completed
+// iteration (s.done), so that k_batch's write-back runs as after a slice that completed one.  false: not one of them.
+template <class V>
+__device__ __forceinline__ bool batch_probe_cg_pass(const BatchProbe &pr, int q, const BatchProbePass &c, ResState &s, V &v, const double *tot) {
+    constexpr int NPTS = V::kNpts, NT = NPTS < 3 ? NPTS : 3;
+    TrialSums out[RES_MAXP] = {};
+    double gu = 0.0, uu = 0.0;
+    int rc = 0, W = 0;
+    if (c.kind == 0) { rc = v.trial(c.a, c.k, out); W = RW<NT>::W; }
+    else if (c.kind == 1) { rc = v.accept_dir_trial(c.a_acc, c.beta, c.a, c.k, out, gu, uu); W = c.k == 0 ? RW<1>::W : RW<NPTS>::W; if (!rc) s.done++; }
+    else if (c.kind == 2) { double sums[RW<1>::W]; rc = v.template pass<R_INIT, 1>(0.0, 0.0, nullptr, 0, sums); W = RW<1>::W; }
+    else return false;
+    if (rc) { s.reason = RES_ERROR; return true; }
+    s.passes++;
+    batch_probe_store(pr, q, tot, W, out, gu, uu, 0);
+    return true;
+}
+template <class V>
+__device__ __forceinline__ void batch_probe_script(const BatchProbe &pr, ResState &s, V &v, const double *tot) {
+    s.done = 0; s.log_len = 0; s.evals = 0; s.passes = 0; s.reason = RES_BUDGET;
+    s.t_machine = 0; s.t_eval = 0; s.t_post = 0;
+    for (int q = 0; q < pr.npass && s.reason == RES_BUDGET; ++q) {
+        const BatchProbePass c = pr.script[q];
+        if (!batch_probe_cg_pass(pr, q, c, s, v, tot)) s.reason = RES_ERROR;   // (the host refuses such a script)
+    }
+}
+
+template <class Obj, int NPTS, bool PROBE = false>
+__global__ __launch_bounds__(BLOCK, 1) void k_batch(const typename BatchArg<PROBE>::type B) {
     extern __shared__ __attribute__((aligned(16))) double res_lds[];
     __shared__ double tot[RES_WMAX];
     __shared__ double fs[BLOCK];
@@ -105,7 +174,8 @@ __global__ __launch_bounds__(BLOCK, 1) void k_batch(const BatchParams B) {
     }
     if (go) {
         ResRecord *recs = B.recs + b * B.rec_stride + (B.rec_abs ? s.it : 0);
-        res_iterate(cfg, s, v, (int64_t)B.budget, recs, nullptr, 0);
+        if constexpr (PROBE) batch_probe_script(B.pr, s, v, tot);
+        else res_iterate(cfg, s, v, (int64_t)B.budget, recs, nullptr, 0);
     }
     s.t_total = 0; s.t_compute = 0; s.t_reduce = 0; s.t_exchange = 0; s.t_cycles = 0;
     __syncthreads();

@@ -257,8 +257,43 @@ struct LbfgsDev : RowsDev<Obj, NPTS> {
     }
 };
 
-template <class Obj, int NPTS>
-__global__ __launch_bounds__(BLOCK, 1) void k_batch_lbfgs(const BatchLbfgsParams L) {
+// ---- cgo_batch_probe: the passes the quasi-Newton loop (res_iterate_qn) issues, in its place -------------------------------------
+static_assert(BATCH_PROBE_MAX_M == QN_MAX_M && BATCH_PROBE_ROW == QN_SUMS, "the probe's pass and row hold the largest ring's");
+struct BatchLbfgsProbeParams : BatchLbfgsParams { BatchProbe pr; };   // (as BatchProbeParams: the kernel text reads L.… in both forms)
+template <bool PROBE> struct BatchLbfgsArg { using type = BatchLbfgsParams; };
+template <> struct BatchLbfgsArg<true> { using type = BatchLbfgsProbeParams; };
+
+// trial and R_INIT are RowsDev's (batch_probe_cg_pass); a push counts as a completed iteration, as in res_iterate_qn.  A combine
+// runs on the coefficients the last push left in LDS, or on those of its pass, written there by lane 0 as push_update writes them.
+template <class V>
+__device__ __forceinline__ void batch_lbfgs_probe_script(const BatchProbe &pr, ResState &s, V &v) {
+    s.done = 0; s.log_len = 0; s.evals = 0; s.passes = 0; s.reason = RES_BUDGET;
+    s.t_machine = 0; s.t_eval = 0; s.t_post = 0;
+    for (int q = 0; q < pr.npass && s.reason == RES_BUDGET; ++q) {
+        const BatchProbePass c = pr.script[q];
+        TrialSums out[RES_MAXP] = {};
+        if (c.kind == 3) {
+            const int stored = v.push_update(c.a_acc);
+            s.passes++; s.done++;
+            batch_probe_store(pr, q, v.qsum, QN_SUMS, out, 0.0, 0.0, stored);
+        } else if (c.kind == 4) {
+            if (c.co_count >= 0) {
+                if (threadIdx.x == 0) {
+                    v.co->count = c.co_count; v.co->pad_ = 0; v.co->gamma = c.co_gamma;
+                    for (int j = 0; j < QN_MAX_M; ++j) { v.co->cy[j] = c.co_cy[j]; v.co->cs[j] = c.co_cs[j]; }
+                }
+                __syncthreads();
+            }
+            double gu = 0.0, uu = 0.0;
+            if (v.combine_trial(c.a, c.k, out, gu, uu)) { s.reason = RES_ERROR; break; }
+            s.passes++;
+            batch_probe_store(pr, q, v.tot, RW<V::kNpts>::W, out, gu, uu, v.co->count);
+        } else if (c.kind == 1 || !batch_probe_cg_pass(pr, q, c, s, v, v.tot)) s.reason = RES_ERROR;   // (the host refuses such a script)
+    }
+}
+
+template <class Obj, int NPTS, bool PROBE = false>
+__global__ __launch_bounds__(BLOCK, 1) void k_batch_lbfgs(const typename BatchLbfgsArg<PROBE>::type L) {
     __shared__ double tot[RES_WMAX];
     __shared__ double qsum[QN_SUMS];
     __shared__ ResState s_out;
@@ -307,7 +342,8 @@ __global__ __launch_bounds__(BLOCK, 1) void k_batch_lbfgs(const BatchLbfgsParams
     }
     if (go) {
         ResRecord *recs = B.recs + b * B.rec_stride + (B.rec_abs ? s.it : 0);
-        res_iterate_qn(cfg, s, v, (int64_t)B.budget, recs);
+        if constexpr (PROBE) batch_lbfgs_probe_script(L.pr, s, v);
+        else res_iterate_qn(cfg, s, v, (int64_t)B.budget, recs);
     }
     s.t_total = 0; s.t_compute = 0; s.t_reduce = 0; s.t_exchange = 0; s.t_cycles = 0;
     constexpr int WS = sizeof(ResState) / 8;

@@ -184,8 +184,9 @@ struct RowsDev {
     }
 };
 
-template <class Obj, int NPTS>
-__global__ __launch_bounds__(BLOCK, 1) void k_batch_rows(const BatchParams B) {
+// PROBE: k_batch's note (cgo_batch_probe; the script in place of res_iterate, nothing else differs).
+template <class Obj, int NPTS, bool PROBE = false>
+__global__ __launch_bounds__(BLOCK, 1) void k_batch_rows(const typename BatchArg<PROBE>::type B) {
     __shared__ double tot[RES_WMAX];
     __shared__ ResState s_out;
     const int tid = threadIdx.x;
@@ -225,7 +226,8 @@ __global__ __launch_bounds__(BLOCK, 1) void k_batch_rows(const BatchParams B) {
     }
     if (go) {
         ResRecord *recs = B.recs + b * B.rec_stride + (B.rec_abs ? s.it : 0);
-        res_iterate(cfg, s, v, (int64_t)B.budget, recs, nullptr, 0);
+        if constexpr (PROBE) batch_probe_script(B.pr, s, v, tot);
+        else res_iterate(cfg, s, v, (int64_t)B.budget, recs, nullptr, 0);
     }
     s.t_total = 0; s.t_compute = 0; s.t_reduce = 0; s.t_exchange = 0; s.t_cycles = 0;
     constexpr int WS = sizeof(ResState) / 8;

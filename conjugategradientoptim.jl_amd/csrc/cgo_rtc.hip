@@ -28,6 +28,7 @@ RtcModule::~RtcModule() {
     if (probe_mod) (void)hipModuleUnload(probe_mod);
     if (batch_mod) (void)hipModuleUnload(batch_mod);
     if (rows_mod) (void)hipModuleUnload(rows_mod);
+    if (batch_probe_mod) (void)hipModuleUnload(batch_probe_mod);
 }
 
 static std::string key_cg(int mode, int npts, bool big) {

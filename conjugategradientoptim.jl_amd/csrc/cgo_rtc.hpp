@@ -32,6 +32,10 @@ struct RtcModule {
     // compiled on the first solve of that tier (rtc_compile_batch_rows) — a user who never asks for the tier does not pay for it
     hipFunction_t batch_rows(int npts) const;
     hipModule_t rows_mod = nullptr;
+    // the PROBE twins of k_batch and k_batch_rows (cgo_batch_probe): one more program, compiled from the kept source on the
+    // first probe (rtc_compile_batch_probe) — creating an objective and its first batched solve cost what they did
+    hipFunction_t batch_probe(bool device_rows, int npts) const;
+    hipModule_t batch_probe_mod = nullptr;
     std::string user_source;
     int n_params = 0;   // parameter slots the objective was created with (0 … CGO_MAX_PARAM_SLOTS)
     int device = 0;
@@ -51,6 +55,8 @@ int rtc_compile_resident_probe(RtcModule &m, std::string &log);
 int rtc_compile_batch(RtcModule &m, std::string &log);
 // the kernel of the batched solves' second tier for the module's objective, one per row of CGO_BATCH_DEVROWS_ROWS, likewise
 int rtc_compile_batch_rows(RtcModule &m, std::string &log);
+// the PROBE twins of both, one per row of CGO_BATCH_ROWS and of CGO_BATCH_DEVROWS_ROWS, in one program, likewise
+int rtc_compile_batch_probe(RtcModule &m, std::string &log);
 
 // What a further program of a module is built from (cgo_rtc.hip): the embedded kernel templates + the user's objective as one
 // translation unit, and one program → one loaded module: compiles `src` for the name expressions of `wants`, loads the code

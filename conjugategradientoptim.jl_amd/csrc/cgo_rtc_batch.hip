@@ -1,7 +1,8 @@
 // cgo_rtc_batch.hip — batched solves on a run-time compiled objective: k_batch<UserObjective, NPTS> (cgo_kernels_batch.hip.hpp,
 // embedded with the other kernel templates) for the rows of CGO_BATCH_ROWS, and k_batch_grad<UserObjective> beside them, as a
 // SECOND program of the objective's module — and k_batch_rows<UserObjective, NPTS> (cgo_kernels_batch_rows.hip.hpp, the tier
-// whose problem rows stay in device memory) as a THIRD, compiled on the first solve of that tier only.
+// whose problem rows stay in device memory) as a THIRD, compiled on the first solve of that tier only.  The PROBE twins of both
+// (cgo_batch_probe) are a FOURTH, compiled on the first probe only.
 //
 // k_batch is a 512-VGPR kernel that takes hiprtc about as long as k_resident: it is not part of the program every user
 // objective compiles at creation (cgo_rtc.hip), but compiled from the kept source on the first batched solve and kept on
@@ -63,6 +64,31 @@ int rtc_compile_batch_rows(RtcModule &m, std::string &log) {
     CGO_BATCH_DEVROWS_ROWS(ROW)
 #undef ROW
     return rtc_build(rtc_program_source(m.user_source, m.n_params), "cgo_user_objective_batch_rows.hip", wants, m.rows_mod, m.fn, log);
+}
+
+// ---- the PROBE twins of both tiers (cgo_batch_probe): a FOURTH program, compiled on the first probe only ----------------------
+hipFunction_t RtcModule::batch_probe(bool device_rows, int npts) const {
+    hipFunction_t f = nullptr;
+#define ROW(NPTS) \
+    if (!f || npts >= NPTS) { auto it = fn.find(std::string(device_rows ? "batch_rows_probe:" : "batch_probe:") + #NPTS); if (it != fn.end()) f = it->second; }
+    if (device_rows) { CGO_BATCH_DEVROWS_ROWS(ROW) } else { CGO_BATCH_ROWS(ROW) }
+#undef ROW
+    return f;
+}
+
+int rtc_compile_batch_probe(RtcModule &m, std::string &log) {
+    static std::mutex mu;   // (as rtc_compile_batch)
+    std::lock_guard<std::mutex> lock(mu);
+    if (m.batch_probe_mod) return CGO_OK;
+    if (hipSetDevice(m.device) != hipSuccess) { log = "hipSetDevice failed"; return CGO_EHIP; }
+    std::vector<Want> wants;
+#define ROW(NPTS) wants.push_back({"batch_probe:" #NPTS, "cgo::dev::k_batch<cgo::dev::UserObjective, " #NPTS ", true>"});
+    CGO_BATCH_ROWS(ROW)
+#undef ROW
+#define ROW(NPTS) wants.push_back({"batch_rows_probe:" #NPTS, "cgo::dev::k_batch_rows<cgo::dev::UserObjective, " #NPTS ", true>"});
+    CGO_BATCH_DEVROWS_ROWS(ROW)
+#undef ROW
+    return rtc_build(rtc_program_source(m.user_source, m.n_params), "cgo_user_objective_batch_probe.hip", wants, m.batch_probe_mod, m.fn, log);
 }
 
 }  // namespace cgo

@@ -614,6 +614,78 @@ int cgo_minimize_batch_lbfgs(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t 
 int32_t cgo_batch_lbfgs_max_m(void);                                              /* 10 */
 int64_t cgo_batch_lbfgs_max_n(cgo_ctx *ctx, int32_t obj_kind);                    /* the limit of the pass index, as cgo_batch_max_n_ex(…DEVICE…); 0: none */
 void cgo_batch_lbfgs_shape(int32_t *block, int32_t *pairs_per_trip);              /* of the two ring passes; needs no device */
+/* A scripted sequence of passes of a BATCHED solve in ONE launch, a workgroup per problem, on host vectors — for tests that check
+ * every slot of every pass in EVERY workgroup (tests/test_batch_kernel_sums.py).  The batch is allocated as a solve allocates it
+ * and the launch arguments are filled by the code that fills them for a solve (ld, the slot pointers, s0 / s0v, the ring stride,
+ * the record stride); the kernel is the product kernel instantiated with its PROBE flag: in place of the scalar loop
+ * (res_iterate / res_iterate_qn) it runs pass[0..npass) through the member functions that loop calls —
+ *   tier 0  k_batch        rows in LDS                 tier 1  k_batch_rows   rows streamed from device memory
+ *   tier 2  k_batch_lbfgs  tier 1 with the ring S, Y [batch][m+1][ld] and a quasi-Newton state per problem
+ *   kind 0  trial(a, k, out)                              1 ≤ k ≤ 3                     tiers 0, 1, 2
+ *   kind 1  accept_dir_trial(a_acc, beta, a, k, …)        0 ≤ k ≤ 3                     tiers 0, 1
+ *   kind 2  pass<R_INIT, 1>                               u = −g, f, g·g                tiers 0, 1, 2
+ *   kind 3  push_update(a_acc)                            x ← x + a_acc·u, the pair into the free slot, the scalar recursion   tier 2
+ *   kind 4  combine_trial(a, k, …)                        0 ≤ k ≤ 3                     tier 2
+ * — a[k..) repeating a[k − 1] as the loops pad them (done here).  A combine runs on the coefficients the last push of the script
+ * left, or (co_set) on count = co_count, γ = co_gamma, co_cy, co_cs, written into the workgroup's coefficient block; a combine
+ * with neither is refused.  An accepting pass or a push counts as a completed iteration, so tier 0 writes its rows back as after
+ * a slice that completed one; a script without one leaves them alone.
+ * In: obj_kind (a built-in kind; tiers 0, 1, 2) or model (a run-time compiled objective, obj_kind = CGO_OBJ_USER; tiers 0, 1 —
+ * its PROBE kernels are one more program of its module, compiled on the first probe); x, u [batch][n]; params[j] [batch][n] for
+ * every slot the objective reads; scalars [batch] or NULL (tiers 0, 1; a model only); skip [batch] or NULL — a flagged problem
+ * is preset finished (RES_STOP) and its workgroup returns at once; tier 2: m, S and Y [batch][m+1][n] (an absent slot: NaN rows)
+ * and qn, every problem's QnState (csrc/cgo_qn.hpp) as cgo_batch_probe_qn_bytes() bytes each — list, count and free_slot are
+ * checked against m here, before any of them indexes the ring.
+ * Out (each pointer may be NULL): rows [npass][batch][64] — the row every workgroup holds after that pass, out[…].width slots of
+ * it (64 after a push), the rest still the NaN pattern 0x7FF87FF87FF87FF8 the buffer starts with; out [npass][batch] what the
+ * member function returned there (stored: push_update's pair count; for a combine the count it ran on); x_out, u_out, g_out
+ * [batch][ld] and S_out, Y_out [batch][m+1][ld] with ld = n + n%2, i.e. WITH the padding element of an odd n, which is uploaded as
+ * the NaN pattern in every row; g_out = the results' gradient formed after the script by the backend's own path (k_batch_grad with
+ * scalars — which leaves the padding element alone — else the gradient launch over the concatenated rows, which evaluates it);
+ * qn_out; reason, done, passes [batch] of every ResState; points, ld; symbol, e.g. "k_batch_rows<ObjQuadDiag, 3, true>".
+ * Every device buffer of the batch carries NaN slack behind its used part (rows, parameter slots, ring, states, quasi-Newton
+ * states, scalars, the probe's own rows), checked after the launch: CGO_ESTATE if a word of it changed, or if a problem that
+ * was not skipped ran another number of passes.  CGO_EINVAL: a kind the tier's loop never issues, k beyond the instantiation's
+ * points, more than 32 passes, a multi-rank context, and what the solve of that tier refuses of objectives and sizes
+ * (n > cgo_batch_max_n* of the tier); CGO_ENOMEM as the solve. */
+#define CGO_BATCH_PROBE_MAX_PASSES 32
+typedef struct cgo_batch_pass {
+    int32_t kind, k;
+    double a[7];
+    double a_acc, beta;
+    int32_t co_set, co_count;
+    double co_gamma, co_cy[10], co_cs[10];
+} cgo_batch_pass;
+typedef struct cgo_batch_pass_out {
+    double ts[7][7];          /* per point: f, gtu, gtgt, gtg, yy, uy, ygt */
+    double gu, uu;
+    int64_t width, stored;
+} cgo_batch_pass_out;
+typedef struct cgo_batch_probe_args {
+    int32_t tier, obj_kind, m, n_params;
+    cgo_objective *model;
+    int64_t n, batch;
+    const double *x, *u;
+    const double *params[4];
+    const double *scalars;
+    const unsigned char *skip;
+    const double *S, *Y;
+    const void *qn;
+    int32_t npass, reserved;
+    cgo_batch_pass pass[CGO_BATCH_PROBE_MAX_PASSES];
+    /* out */
+    double *rows;
+    cgo_batch_pass_out *out;
+    double *x_out, *u_out, *g_out, *S_out, *Y_out;
+    void *qn_out;
+    int32_t *reason;
+    int64_t *done, *passes;
+    int32_t points, reserved2;
+    int64_t ld;
+    char symbol[128];
+} cgo_batch_probe_args;
+int cgo_batch_probe(cgo_ctx *ctx, cgo_batch_probe_args *p);
+int64_t cgo_batch_probe_qn_bytes(void);                                           /* sizeof(QnState): what a mirror of it must measure */
 /* CGO_HOST_ONLY_END */
 /* The stop test at the top of iteration it + 1 (optim.jl:53-80,162-169) as a function of the loop state — the one rule the
  * engine and the problems a batch finishes on the device share: the terminal status (CGO_INCOMPLETE: the iteration runs) and

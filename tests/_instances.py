@@ -34,4 +34,4 @@ def stray_uses():
     `#define ROW(` expander of the table.  Strings (reported symbols, hiprtc names) and comments do not count."""
     text = "\n".join(open(p).read() for p in sorted(glob.glob(os.path.join(CSRC, "*.hip")))).replace("\\\n", " ")
     code = [re.sub(r'"(?:\\.|[^"\\])*"', '""', line).split("//")[0] for line in text.split("\n")]
-    return [c.strip() for c in code if re.search(r"\bk_(cg|cg_armed|chain|fused|resident|resident_chain)<", c) and not c.startswith("#define ROW(")]
+    return [c.strip() for c in code if re.search(r"\bk_(cg|cg_armed|chain|fused|resident|resident_chain|batch|batch_rows|batch_lbfgs|batch_grad)<", c) and not c.startswith("#define ROW(")]

@@ -181,5 +181,22 @@ int simq_ring(int m, int64_t n, int npush, const double *s_all, const double *y_
 }
 
 int simq_state_bytes(void) { return (int)sizeof(QnState); }
+int simq_coef_bytes(void) { return (int)sizeof(QnCoef); }
+
+// What lane 0 of k_batch_lbfgs does after a push pass, on the host: qn_update (which commits a kept pair) and qn_coefficients of
+// cgo_qn.hpp on a state given as its 8-byte words and the 64 sums of the push row.  Out: the state and the coefficient block
+// as words, whether the pair was kept.  (tests/test_batch_kernel_sums.py: the device's state, word for word.)
+int simq_update(const unsigned long long *state_in, const double *sums, unsigned long long *state_out, unsigned long long *coef_out, int32_t *kept) {
+    QnState q; QnCoef co;
+    std::memcpy(&q, state_in, sizeof q);
+    std::memset(&co, 0, sizeof co);
+    if (q.m < 1 || q.m > QN_MAX_M || q.count < 0 || q.count > q.m || q.free_slot < 0 || q.free_slot > q.m) return CGO_EINVAL;
+    for (int j = 0; j <= QN_SLOTS; ++j) if (q.list[j] < 0 || q.list[j] > q.m) return CGO_EINVAL;
+    *kept = qn_update(q, sums) ? 1 : 0;
+    qn_coefficients(q, co);
+    std::memcpy(state_out, &q, sizeof q);
+    std::memcpy(coef_out, &co, sizeof co);
+    return CGO_OK;
+}
 
 }  // extern "C"

@@ -122,7 +122,9 @@ def test_embedded_kernel_sources_carry_the_rows_kernel_last(tmp_path):
     out = tmp_path / "cgo_rtc_sources.inc"
     subprocess.run([sys.executable, os.path.join(I.CSRC, "gen_rtc_sources.py"), str(out)], check=True)
     text = out.read_text(encoding="utf-8")
-    assert "void k_batch_rows(const BatchParams B)" in text
+    # (the argument is BatchParams itself unless the PROBE flag of cgo_batch_probe is set: BatchArg<false>::type)
+    assert "void k_batch_rows(const typename BatchArg<PROBE>::type B)" in text
+    assert "template <bool PROBE> struct BatchArg { using type = BatchParams; };" in text
     assert text.index("// ---- cgo_kernels_batch.hip.hpp") < text.index("// ---- cgo_kernels_batch_rows.hip.hpp")
     assert '#include "' not in text.split("// ---- cgo_kernels_batch_rows.hip.hpp")[1]
     # the kernel takes BatchParams as it is, no dynamic LDS, and none of what the pool forbids for data exchange

@@ -86,7 +86,8 @@ def test_the_gradient_kernel_is_built_ahead_of_time_and_in_the_batch_program(tmp
     out = tmp_path / "cgo_rtc_sources.inc"
     subprocess.run([sys.executable, os.path.join(I.CSRC, "gen_rtc_sources.py"), str(out)], check=True)
     text = out.read_text(encoding="utf-8")
-    assert "void k_batch_grad(const BatchGradParams G)" in text and "void k_batch(const BatchParams B)" in text
+    assert "void k_batch_grad(const BatchGradParams G)" in text and "void k_batch(const typename BatchArg<PROBE>::type B)" in text
+    assert "template <bool PROBE> struct BatchArg { using type = BatchParams; };" in text   # (BatchParams itself unless PROBE)
 
 
 def _stand_in(cgo, n=8):

@@ -94,7 +94,9 @@ def test_embedded_kernel_sources_contain_k_batch(tmp_path):
     out = tmp_path / "cgo_rtc_sources.inc"
     subprocess.run([sys.executable, os.path.join(I.CSRC, "gen_rtc_sources.py"), str(out)], check=True)
     text = out.read_text(encoding="utf-8")
-    assert "void k_batch(const BatchParams B)" in text
+    # (the argument is BatchParams itself unless the PROBE flag of cgo_batch_probe is set: BatchArg<false>::type)
+    assert "void k_batch(const typename BatchArg<PROBE>::type B)" in text
+    assert "template <bool PROBE> struct BatchArg { using type = BatchParams; };" in text
     assert text.index("// ---- cgo_kernels_resident.hip.hpp") < text.index("// ---- cgo_kernels_batch.hip.hpp")
     assert '#include "' not in text.split("// ---- cgo_kernels_batch.hip.hpp")[1]
 
