@@ -1374,10 +1374,10 @@ def minimizeobjectivebatch_lbfgs(kind: str, X0, config: CGConfig, linesearch_con
     2(m+1) rows per problem stay in device memory — (3 + K + 2(m+1)) · batch · (n + n%2) · 8 bytes, checked against the device's
     free memory before anything is allocated.  Returns what minimizeobjectivebatch returns (`.rows` is "device").  A problem
     the device loop does not finish is solved AGAIN from its own x0 by the ordinary engine — a whole solve — and counted in
-    `handed_back`.  Anything not covered raises CgoError: run-time compiled objectives, a scalar per problem, Backtracking,
-    m > 10, a multi-rank context."""
+    `handed_back`.  Anything not covered raises CgoError: Backtracking, m > 10, a multi-rank context.  Run-time compiled
+    objectives, with parameter slots and a scalar per problem: minimizeobjectivebatch_lbfgs_obj."""
     if not isinstance(kind, str) or kind not in OBJ_KINDS:
-        raise ValueError(f"unknown objective kind {kind!r} (a run-time compiled objective has no batched L-BFGS form)")
+        raise ValueError(f"unknown objective kind {kind!r} (a run-time compiled objective: minimizeobjectivebatch_lbfgs_obj)")
     X0 = np.ascontiguousarray(np.asarray(X0, dtype=np.float64))
     if X0.ndim != 2:
         raise ValueError("X0 must be [batch, n]")
@@ -1393,6 +1393,66 @@ def minimizeobjectivebatch_lbfgs(kind: str, X0, config: CGConfig, linesearch_con
     check(_lib.lib().cgo_minimize_batch_lbfgs(ctx._h, OBJ_KINDS[kind], n, batch, X0.ctypes.data_as(dp),
                                               Dc.ctypes.data_as(dp) if Dc is not None else None, C.byref(cfg), C.byref(ls),
                                               int(slice_iters), C.byref(o.c)))
+    return o.results(rows_used=BATCH_ROWS["device"])
+
+
+def batch_lbfgs_shape_obj(n_params: int):
+    """(lanes per workgroup, pairs of elements per lane and trip) of the two ring passes of minimizeobjectivebatch_lbfgs_obj on a
+    model of `n_params` parameter slots: fewer pairs per trip for two or more slots (no bit of a result depends on it)."""
+    blk, u = C.c_int32(0), C.c_int32(0)
+    _lib.lib().cgo_batch_lbfgs_shape_obj(int(n_params), C.byref(blk), C.byref(u))
+    return int(blk.value), int(u.value)
+
+
+def batch_lbfgs_max_n_obj(model: "DeviceObjective") -> int:
+    """Largest n of one problem of minimizeobjectivebatch_lbfgs_obj on `model`: the index range of a pass (0: not a run-time
+    compiled, whole, single-rank objective).  Compiles nothing."""
+    if not isinstance(model, DeviceObjective):
+        raise ValueError("model must be a run-time compiled DeviceObjective (ElementwiseObjective)")
+    return int(_lib.lib().cgo_batch_lbfgs_max_n_obj(model._h))
+
+
+def minimizeobjectivebatch_lbfgs_obj(model: "DeviceObjective", X0, config: CGConfig, linesearch_config: LineSearchConfig,
+                                     params=None, scalars=None, ctx: Optional[Context] = None, slice_iters: int = 0) -> BatchResults:
+    """minimizeobjectivebatch_lbfgs on a run-time compiled objective: `model` (ElementwiseObjective) as in minimizeobjectivebatch
+    — its source, size, scalar and cost class are every problem's — with `params`, its n_params arrays [batch, n], the rows of
+    slot 0, 1, …, and optionally `scalars`, a [batch] array of every problem's own `s0` (None: the model's for all).
+    `config.β_config` is LBFGS(m), 1 ≤ m ≤ 10; StrongWolfeBisection or WolfeBisection.  The first call on a compiled source
+    compiles its batched L-BFGS program (seconds); later ones find it.  Device memory: (3 + n_params + 2(m+1)) · batch ·
+    (n + n%2) · 8 bytes, checked before anything is allocated.  Returns what minimizeobjectivebatch_lbfgs returns (`.rows` is
+    "device"); a problem the device loop does not finish is solved again from its own x0, with its own slot rows and scalar, by
+    the ordinary engine and counted in `handed_back`.  Not covered (CgoError or ValueError): CG flavours and Broyden
+    (minimizeobjectivebatch), Backtracking, m > 10, a multi-rank context; there is no `Batch` handle, `active` mask, barrier
+    method or LDS tier on L-BFGS."""
+    if not isinstance(model, DeviceObjective):
+        raise ValueError("model must be a run-time compiled DeviceObjective (ElementwiseObjective); built-in kinds: minimizeobjectivebatch_lbfgs")
+    X0 = np.ascontiguousarray(np.asarray(X0, dtype=np.float64))
+    if X0.ndim != 2:
+        raise ValueError("X0 must be [batch, n]")
+    batch, n = X0.shape
+    if n != model.n_global:
+        raise ValueError(f"X0 must be [batch, {model.n_global}], the size of the model objective")
+    Pc = []
+    for j, v in enumerate(params if params is not None else []):
+        if v is None:
+            raise ValueError(f"params[{j}] is None: every slot needs its [batch, n] rows")
+        Pc.append(np.ascontiguousarray(np.asarray(v, dtype=np.float64)))
+        if Pc[-1].shape != X0.shape:
+            raise ValueError(f"params[{j}] must have the shape of X0")
+    sc = None
+    if scalars is not None:
+        sc = _batch_rows("scalars", scalars, (batch,))
+        if not np.all(np.isfinite(sc)):
+            raise ValueError("scalars must be finite")
+    if not isinstance(slice_iters, (int, np.integer)) or slice_iters < 0:
+        raise ValueError("slice_iters must be an integer ≥ 0")
+    ctx = ctx or model.ctx
+    o = _BatchOut(batch, n, config)
+    cfg, ls = config._c(), linesearch_config._c()
+    prows = (dp * max(len(Pc), 1))(*[v.ctypes.data_as(dp) for v in Pc])
+    check(_lib.lib().cgo_minimize_batch_lbfgs_obj(ctx._h, model._h, batch, X0.ctypes.data_as(dp), prows, len(Pc),
+                                                  sc.ctypes.data_as(dp) if sc is not None else None, C.byref(cfg), C.byref(ls),
+                                                  int(slice_iters), C.byref(o.c)))
     return o.results(rows_used=BATCH_ROWS["device"])
 
 

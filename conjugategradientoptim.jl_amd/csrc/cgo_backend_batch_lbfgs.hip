@@ -2,7 +2,8 @@
 // solves with β = LBFGS(m), and the host side of what they add to a batch of the device-rows tier: the ring of 2(m+1) rows
 // and the QnState per problem, their reset, and the launch.  Allocation of the rows, reset of the states, records, results and
 // the hand-back are cgo_backend_batch.hip's; this file exists so that the translation units of k_batch and k_batch_rows compile
-// to what they compiled to before.
+// to what they compiled to before.  A run-time compiled objective brings its own kernel: the batched L-BFGS program of its
+// module (cgo_rtc_batch_lbfgs.hip), compiled by the caller before batch_lbfgs_alloc.
 #include "cgo_backend_internal.hpp"
 #include "cgo_kernels_batch_lbfgs.hip.hpp"
 
@@ -30,6 +31,7 @@ static const void *batch_lbfgs_kernel_for(int obj_kind, int npts) {
 
 int64_t HipBackend::batch_lbfgs_max_n() { return (int64_t)BATCH_LBFGS_MAX_N; }
 int HipBackend::batch_lbfgs_unroll() { return BATCH_LBFGS_U; }
+int HipBackend::batch_lbfgs_unroll_for(int nparams) { return batch_lbfgs_u_of(nparams); }
 int HipBackend::batch_lbfgs_block() { return BLOCK; }
 
 // x, u, every slot, the results' gradient and the ring, [batch][ld] each; the states beside them
@@ -39,8 +41,10 @@ double HipBackend::batch_lbfgs_bytes(int64_t batch, int64_t n, int nparams, int 
 }
 
 int HipBackend::batch_lbfgs_alloc(int m) {
-    if (!bat_st_ || !bat_rows_ || bat_qn_ || m < 1 || m > QN_MAX_M || obj_->kind == CGO_OBJ_USER) { set_error("internal: batched L-BFGS on a batch of another shape"); return CGO_ESTATE; }
-    if (!batch_lbfgs_kernel_for(obj_->kind, 3)) { set_error("batched L-BFGS solves: no k_batch_lbfgs instantiation for this objective"); return CGO_EINVAL; }
+    if (!bat_st_ || !bat_rows_ || bat_qn_ || m < 1 || m > QN_MAX_M) { set_error("internal: batched L-BFGS on a batch of another shape"); return CGO_ESTATE; }
+    if (obj_->kind == CGO_OBJ_USER) {
+        if (!obj_->rtc || !obj_->rtc->batch_lbfgs(3)) { set_error("internal: batched L-BFGS solve before the objective's batched L-BFGS program was compiled"); return CGO_ESTATE; }
+    } else if (!batch_lbfgs_kernel_for(obj_->kind, 3)) { set_error("batched L-BFGS solves: no k_batch_lbfgs instantiation for this objective"); return CGO_EINVAL; }
     if (bat_n_ > batch_lbfgs_max_n()) { set_error("internal: a batch beyond the pass index of the batched L-BFGS solves"); return CGO_ESTATE; }
     HIPCHK(hipSetDevice(ctx_->device));
     const size_t ring = (size_t)bat_count_ * (size_t)(m + 1) * (size_t)bat_ld_ * sizeof(double);
@@ -66,13 +70,12 @@ int HipBackend::batch_lbfgs_reset() {
 
 void HipBackend::batch_lbfgs_fill_params(BatchLbfgsParams &L, const ResConfig &c, int64_t budget) const {
     batch_fill_params(L.B, c, budget);
-    L.B.s0v = nullptr;   // (no scalar per problem in this family)
     L.S = bat_S_; L.Y = bat_Y_; L.qn = bat_qn_;
     L.ring_stride = (long long)(bat_m_ + 1) * bat_ld_;
 }
 
 int HipBackend::batch_lbfgs_launch(const ResConfig &c, int64_t budget, std::vector<ResState> &st, std::vector<double> &f_x0) {
-    if (!bat_qn_ || bat_s0v_on_) { set_error("internal: batched L-BFGS launch on a batch of another shape"); return CGO_ESTATE; }
+    if (!bat_qn_) { set_error("internal: batched L-BFGS launch on a batch of another shape"); return CGO_ESTATE; }
     HIPCHK(hipSetDevice(ctx_->device));
     if (budget < 1) budget = 1;
     if (!bat_trace_) {   // nobody reads the records: the leader still writes one per completed iteration of the slice
@@ -81,9 +84,15 @@ int HipBackend::batch_lbfgs_launch(const ResConfig &c, int64_t budget, std::vect
     BatchLbfgsParams L{};
     batch_lbfgs_fill_params(L, c, budget);
     void *args[] = {&L};
-    const void *fn = batch_lbfgs_kernel_for(obj_->kind, 3);
-    if (!fn) { set_error("batched L-BFGS solves: no k_batch_lbfgs instantiation for this objective"); return CGO_EINVAL; }
-    HIPCHK(hipLaunchKernel(fn, dim3((unsigned)bat_count_), dim3(BLOCK), args, 0, ctx_->stream));
+    if (obj_->kind == CGO_OBJ_USER) {
+        const hipFunction_t mf = obj_->rtc ? obj_->rtc->batch_lbfgs(3) : nullptr;
+        if (!mf) { set_error("internal: kernel missing from the run-time compiled objective module"); return CGO_EINVAL; }
+        HIPCHK(hipModuleLaunchKernel(mf, (unsigned)bat_count_, 1, 1, BLOCK, 1, 1, 0, ctx_->stream, args, nullptr));
+    } else {
+        const void *fn = batch_lbfgs_kernel_for(obj_->kind, 3);
+        if (!fn) { set_error("batched L-BFGS solves: no k_batch_lbfgs instantiation for this objective"); return CGO_EINVAL; }
+        HIPCHK(hipLaunchKernel(fn, dim3((unsigned)bat_count_), dim3(BLOCK), args, 0, ctx_->stream));
+    }
     total_launches_++;
     st.resize((size_t)bat_count_); f_x0.resize((size_t)bat_count_);
     HIPCHK(hipMemcpyAsync(st.data(), bat_st_, sizeof(ResState) * (size_t)bat_count_, hipMemcpyDeviceToHost, ctx_->stream));

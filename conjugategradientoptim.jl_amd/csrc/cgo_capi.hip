@@ -1051,10 +1051,10 @@ static int batch_backend_on(cgo_ctx *ctx, HipObjective &cat, int64_t n, int64_t 
 static int batch_solve_on(cgo_ctx *ctx, HipBackend &be, int64_t n, int64_t batch, const double *x0, const double *scalars,
                           const unsigned char *active, const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters,
                           cgo_batch_results *out, const std::function<int(cgo_objective **)> &make_hobj, bool qn = false,
-                          const double *qn_param0 = nullptr) {
-    // qn: a batched L-BFGS solve (cgo_minimize_batch_lbfgs) — every ring empty at the start, and a handed-back problem is solved
-    // again by the host engine from its own x0 (the ring and Gram state of the device are not exported), with its row of the
-    // caller's x0 and qn_param0 (a quasi-Newton solver keeps a stored gradient: not a backend batch_export_row serves)
+                          const double *const *qn_params = nullptr, int qn_nparams = 0) {
+    // qn: a batched L-BFGS solve (cgo_minimize_batch_lbfgs[_obj]) — every ring empty at the start, and a handed-back problem is
+    // solved again by the host engine from its own x0 (the ring and Gram state of the device are not exported), with its row of the
+    // caller's x0 and of every slot of qn_params (a quasi-Newton solver keeps a stored gradient: not a backend batch_export_row serves)
     auto on = [&](int64_t b) { return !active || active[b] != 0; };
     if (int rc = be.batch_reset(x0, scalars, active, cfg->max_iters, cfg->trace_enabled != 0)) return rc;
     if (qn) { if (int rc = be.batch_lbfgs_reset()) return rc; }
@@ -1105,7 +1105,9 @@ static int batch_solve_on(cgo_ctx *ctx, HipBackend &be, int64_t n, int64_t batch
         }
         if (scalars) { if ((rc = cgo_objective_set_scalar(hobj, 0, scalars[b]))) break; }   // (the call's own objective, never the model)
         if (qn) {          // the whole solve, from the problem's own x0 (the device's row of x has moved on)
-            if (qn_param0) { if ((rc = cgo_objective_set_param_host(hobj, 0, qn_param0 + b * n))) break; }
+            for (int j = 0; j < qn_nparams && !rc; ++j)
+                if (qn_params[j]) rc = cgo_objective_set_param_host(hobj, j, qn_params[j] + b * n);
+            if (rc) break;
             if ((rc = hs->be->set_x0_host(x0 + b * n))) break;
             if ((rc = hs->sv->start())) break;
         } else if (s.it == 0) {   // nothing completed: the problem's own start, as a single solve has it
@@ -1197,11 +1199,9 @@ int64_t cgo_batch_lbfgs_max_n(cgo_ctx *ctx, int32_t obj_kind) {
 
 // What a batched L-BFGS solve and its probe refuse of sizes alike: n beyond the pass index, and rows and rings the device's free
 // memory does not hold — (3 + K + 2(m+1)) · batch · ld · 8 bytes against what is free, before anything is allocated.
-static int batch_lbfgs_sizes(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, int m) {
+static int batch_lbfgs_sizes_of(cgo_ctx *ctx, int64_t max_n, const char *max_name, int nparams, int64_t n, int64_t batch, int m) {
     HIPCHK2(hipSetDevice(ctx->c.device));
-    const int64_t max_n = cgo_batch_lbfgs_max_n(ctx, obj_kind);
-    if (n > max_n) { set_error("batched L-BFGS solves: n = " + std::to_string(n) + " exceeds the index range of a pass (cgo_batch_lbfgs_max_n = " + std::to_string(max_n) + ")"); return CGO_EINVAL; }
-    const int nparams = obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0;
+    if (n > max_n) { set_error("batched L-BFGS solves: n = " + std::to_string(n) + " exceeds the index range of a pass (" + max_name + " = " + std::to_string(max_n) + ")"); return CGO_EINVAL; }
     size_t free_b = 0, total_b = 0;
     HIPCHK2(hipMemGetInfo(&free_b, &total_b));
     const double need = HipBackend::batch_lbfgs_bytes(batch, n, nparams, m);
@@ -1214,19 +1214,19 @@ static int batch_lbfgs_sizes(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t 
     }
     return CGO_OK;
 }
+static int batch_lbfgs_sizes(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, int m) {
+    return batch_lbfgs_sizes_of(ctx, cgo_batch_lbfgs_max_n(ctx, obj_kind), "cgo_batch_lbfgs_max_n", obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0, n, batch, m);
+}
 
-int cgo_minimize_batch_lbfgs(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
-                             const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out) {
-    API_GUARD_BEGIN
-    REQUIRE(ctx && x0 && cfg && ls && out, "null argument");
-    out->launches = 0; out->handed_back = 0;
-    REQUIRE(batch_kind(obj_kind), "batched L-BFGS solves: the objective must be CGO_OBJ_QUAD_DIAG, CGO_OBJ_ROSENBROCK_PAIRED or CGO_OBJ_BOOTH");
+// What both entry points refuse of a config and a call alike; `cg_entry`: where a CG flavour belongs instead
+static int check_batch_lbfgs_call(cgo_ctx *ctx, const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t n, int64_t batch, int64_t slice_iters,
+                                  const char *cg_entry) {
     {
         std::string why;
         if (int rc = check_cg_config(cfg, why)) { set_error(why); return rc; }
         if (int rc = check_ls_config(ls, why)) { set_error(why); return rc; }
     }
-    REQUIRE(cfg->beta.kind == CGO_BETA_LBFGS, "batched L-BFGS solves: β must be LBFGS(m) (CG flavours: cgo_minimize_batch; the Broyden family has no batched form)");
+    if (cfg->beta.kind != CGO_BETA_LBFGS) { set_error(std::string("batched L-BFGS solves: β must be LBFGS(m) (CG flavours: ") + cg_entry + "; the Broyden family has no batched form)"); return CGO_EINVAL; }
     if (cfg->beta.lbfgs_m > QN_MAX_M) { set_error("batched L-BFGS solves: m = " + std::to_string(cfg->beta.lbfgs_m) + " exceeds cgo_batch_lbfgs_max_m = " + std::to_string(QN_MAX_M)); return CGO_EINVAL; }
     REQUIRE(ls->kind != CGO_LS_BACKTRACKING, "batched L-BFGS solves: the Backtracking line search is not supported (StrongWolfeBisection or WolfeBisection)");
     REQUIRE(ctx->c.world() == 1, "batched L-BFGS solves: a multi-rank context is not supported (one rank only)");
@@ -1234,6 +1234,16 @@ int cgo_minimize_batch_lbfgs(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t 
     REQUIRE(batch <= 0x7FFFFFFF, "batched L-BFGS solves: batch exceeds the largest grid");
     REQUIRE(slice_iters >= 0, "batched L-BFGS solves: slice_iters must be ≥ 0 (0 = the library's policy)");
     REQUIRE(n >= 1, "batched L-BFGS solves: n must be ≥ 1");
+    return CGO_OK;
+}
+
+int cgo_minimize_batch_lbfgs(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
+                             const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out) {
+    API_GUARD_BEGIN
+    REQUIRE(ctx && x0 && cfg && ls && out, "null argument");
+    out->launches = 0; out->handed_back = 0;
+    REQUIRE(batch_kind(obj_kind), "batched L-BFGS solves: the objective must be CGO_OBJ_QUAD_DIAG, CGO_OBJ_ROSENBROCK_PAIRED or CGO_OBJ_BOOTH");
+    if (int rc = check_batch_lbfgs_call(ctx, cfg, ls, n, batch, slice_iters, "cgo_minimize_batch")) return rc;
     if (obj_kind == CGO_OBJ_ROSENBROCK_PAIRED) REQUIRE(n % 2 == 0, "batched L-BFGS solves: paired Rosenbrock needs an even n");
     if (obj_kind == CGO_OBJ_BOOTH) REQUIRE(n == 2, "batched L-BFGS solves: Booth is 2-dimensional (n = 2)");
     if (obj_kind == CGO_OBJ_QUAD_DIAG) REQUIRE(param0, "batched L-BFGS solves: the quadratic needs param0, the [batch*n] rows of D");
@@ -1248,7 +1258,7 @@ int cgo_minimize_batch_lbfgs(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t 
     if (int rc = batch_backend_on(ctx, cat, n, batch, params, be, true)) return rc;
     if (int rc = be.batch_lbfgs_alloc(m)) return rc;
     return batch_solve_on(ctx, be, n, batch, x0, nullptr, nullptr, cfg, ls, slice_iters, out,
-                          [&](cgo_objective **h) { return cgo_objective_create(ctx, obj_kind, n, 0, n, h); }, true, param0);
+                          [&](cgo_objective **h) { return cgo_objective_create(ctx, obj_kind, n, 0, n, h); }, true, params, 1);
     API_GUARD_END
 }
 
@@ -1302,14 +1312,28 @@ static int check_batch_model(cgo_ctx *ctx, cgo_objective *model) {
     REQUIRE(batch_model_whole(model), "batched solves: a sharded or multi-rank model is not supported (n_global = n_local = the size of ONE problem, one rank only)");
     return CGO_OK;
 }
-static int batch_model_cat(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *const *params, int32_t n_params, HipObjective &cat,
-                           int rows, bool &device_rows) {
-    const int64_t n = model->o.n_local;
+static int check_batch_model_params(cgo_objective *model, const double *const *params, int32_t n_params) {
     const int K = model->o.nparams();
     if (n_params != K) { set_error("batched solves: n_params = " + std::to_string(n_params) + ", the model reads " + std::to_string(K) + " parameter slots"); return CGO_EINVAL; }
     REQUIRE(K == 0 || params, "batched solves: params is null, the model reads parameter slots");
     for (int j = 0; j < K; ++j)
         if (!params[j]) { set_error("batched solves: params[" + std::to_string(j) + "] is null (the [batch*n] rows of slot " + std::to_string(j) + ")"); return CGO_EINVAL; }
+    return CGO_OK;
+}
+// the concatenated objective itself: the model's module, scalar and cost class, its own [batch][ld] slot rows
+static int batch_model_cat_rows(cgo_ctx *ctx, cgo_objective *model, int64_t batch, HipObjective &cat) {
+    const int64_t n = model->o.n_local, ld = n + (n & 1);
+    const int K = model->o.nparams();
+    cat.ctx = &ctx->c; cat.kind = CGO_OBJ_USER; cat.n_global = cat.n_local = batch * ld; cat.offset = 0;
+    cat.rtc = model->o.rtc; cat.user_nparams = K; cat.s0 = model->o.s0; cat.user_cheap = model->o.user_cheap;
+    for (int j = 0; j < K; ++j) { if (int rc = cat.p[j].alloc((size_t)(batch * ld))) return rc; }
+    return CGO_OK;
+}
+static int batch_model_cat(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *const *params, int32_t n_params, HipObjective &cat,
+                           int rows, bool &device_rows) {
+    const int64_t n = model->o.n_local;
+    const int K = model->o.nparams();
+    if (int rc = check_batch_model_params(model, params, n_params)) return rc;
     HIPCHK2(hipSetDevice(ctx->c.device));
     // (rows in device memory, asked for outright: the batch program — the LDS tier's kernel — is neither needed nor compiled)
     int64_t lds_max = 0;
@@ -1319,11 +1343,7 @@ static int batch_model_cat(cgo_ctx *ctx, cgo_objective *model, int64_t batch, co
     }
     if (int rc = batch_tier(ctx, rows, n, batch, K, lds_max, "cgo_batch_max_n_obj", device_rows)) return rc;
     if (device_rows) { if (int rc = batch_rows_program(model)) return rc; }
-    const int64_t ld = n + (n & 1);
-    cat.ctx = &ctx->c; cat.kind = CGO_OBJ_USER; cat.n_global = cat.n_local = batch * ld; cat.offset = 0;
-    cat.rtc = model->o.rtc; cat.user_nparams = K; cat.s0 = model->o.s0; cat.user_cheap = model->o.user_cheap;
-    for (int j = 0; j < K; ++j) { if (int rc = cat.p[j].alloc((size_t)(batch * ld))) return rc; }
-    return CGO_OK;
+    return batch_model_cat_rows(ctx, model, batch, cat);
 }
 static std::function<int(cgo_objective **)> batch_model_hobj(cgo_ctx *ctx, cgo_objective *model) {
     return [ctx, model](cgo_objective **h) {
@@ -1357,6 +1377,49 @@ int cgo_minimize_batch_obj_ex(cgo_ctx *ctx, cgo_objective *model, int64_t batch,
     if (int rc = batch_model_cat(ctx, model, batch, params, n_params, cat, rows, device_rows)) return rc;
     if (rows_used) *rows_used = device_rows ? CGO_BATCH_ROWS_DEVICE : CGO_BATCH_ROWS_LDS;
     return run_batch_on(ctx, cat, n, batch, x0, params, cfg, ls, slice_iters, out, batch_model_hobj(ctx, model), device_rows);
+    API_GUARD_END
+}
+
+// ---- batched L-BFGS solves on a run-time compiled objective: k_batch_lbfgs<UserObjective, 3>, the fifth program of its module ------
+// (cgo_rtc_batch_lbfgs.hip).  The model and params are checked as cgo_minimize_batch_obj checks them, the config as
+// cgo_minimize_batch_lbfgs checks it; the batch is the device-rows tier's with the ring beside it.
+void cgo_batch_lbfgs_shape_obj(int32_t n_params, int32_t *block, int32_t *pairs_per_trip) {
+    if (block) *block = HipBackend::batch_lbfgs_block();
+    if (pairs_per_trip) *pairs_per_trip = HipBackend::batch_lbfgs_unroll_for(n_params);
+}
+
+int64_t cgo_batch_lbfgs_max_n_obj(cgo_objective *model) {
+    try {
+        if (!model || model->o.kind != CGO_OBJ_USER || !model->o.rtc || !batch_model_whole(model)) return 0;
+        return HipBackend::batch_lbfgs_max_n();   // (nothing is compiled for the answer)
+    } catch (...) { return 0; }
+}
+
+int cgo_minimize_batch_lbfgs_obj(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *x0, const double *const *params,
+                                 int32_t n_params, const double *scalars, const cgo_cg_config *cfg, const cgo_ls_config *ls,
+                                 int64_t slice_iters, cgo_batch_results *out) {
+    API_GUARD_BEGIN
+    REQUIRE(ctx && model && x0 && cfg && ls && out, "null argument");
+    out->launches = 0; out->handed_back = 0;
+    if (int rc = check_batch_model(ctx, model)) return rc;
+    const int64_t n = model->o.n_local;
+    if (int rc = check_batch_lbfgs_call(ctx, cfg, ls, n, batch, slice_iters, "cgo_minimize_batch_obj")) return rc;
+    if (int rc = check_batch_model_params(model, params, n_params)) return rc;
+    if (scalars)
+        for (int64_t b = 0; b < batch; ++b)
+            if (!std::isfinite(scalars[b])) { set_error("batched L-BFGS solves: scalars[" + std::to_string(b) + "] is not finite"); return CGO_EINVAL; }
+    const int m = cfg->beta.lbfgs_m, K = model->o.nparams();
+    if (int rc = batch_lbfgs_sizes_of(ctx, cgo_batch_lbfgs_max_n_obj(model), "cgo_batch_lbfgs_max_n_obj", K, n, batch, m)) return rc;
+    {   // the model's batched L-BFGS program: compiled on the first such solve on its module
+        std::string log;
+        if (int rc = rtc_compile_batch_lbfgs(*model->o.rtc, log)) { set_error("user objective: the batched L-BFGS program did not compile:\n" + log); return rc; }
+    }
+    HipObjective cat;
+    if (int rc = batch_model_cat_rows(ctx, model, batch, cat)) return rc;
+    HipBackend be(&ctx->c, &cat);
+    if (int rc = batch_backend_on(ctx, cat, n, batch, params, be, true)) return rc;
+    if (int rc = be.batch_lbfgs_alloc(m)) return rc;
+    return batch_solve_on(ctx, be, n, batch, x0, scalars, nullptr, cfg, ls, slice_iters, out, batch_model_hobj(ctx, model), true, params, K);
     API_GUARD_END
 }
 
@@ -1461,7 +1524,7 @@ int cgo_batch_probe(cgo_ctx *ctx, cgo_batch_probe_args *p) {
     HipObjective cat;
     int64_t n = p->n;
     if (p->model) {
-        REQUIRE(p->tier != 2, "batch probe: a run-time compiled objective has no batched L-BFGS form (tiers 0 and 1)");
+        REQUIRE(p->tier != 2, "batch probe: the batched L-BFGS kernel of a run-time compiled objective has no PROBE twin (tiers 0 and 1)");
         if (int rc = check_batch_model(ctx, p->model)) return rc;
         n = p->model->o.n_local;
         REQUIRE(p->n == n, "batch probe: n is not the size of the model objective");

@@ -185,11 +185,13 @@ class HipBackend : public VecBackend {
     int batch_results(double *x /*[batch·n]*/, double *g /*[batch·n]*/, const unsigned char *active = nullptr);
     // Batched solves with β = LBFGS(m) (cgo_backend_batch_lbfgs.hip; k_batch_lbfgs, cgo_kernels_batch_lbfgs.hip.hpp): a batch
     // allocated with device_rows gets a ring of 2(m+1) rows and a QnState per problem beside its rows; batch_launch then runs
-    // k_batch_lbfgs.  batch_lbfgs_reset after every batch_reset: every problem's ring empty.
+    // k_batch_lbfgs.  batch_lbfgs_reset after every batch_reset: every problem's ring empty.  A run-time compiled objective runs
+    // the kernel of its module's batched L-BFGS program (cgo_rtc_batch_lbfgs.hip), which the caller compiles first.
     int batch_lbfgs_alloc(int m);
     int batch_lbfgs_reset();
     static int64_t batch_lbfgs_max_n();        // the limit of the pass index on n
     static int batch_lbfgs_unroll();           // pairs per lane and trip of the two ring passes
+    static int batch_lbfgs_unroll_for(int nparams);   // … for an objective of that many parameter slots (run-time compiled ones)
     static int batch_lbfgs_block();            // lanes of the workgroup
     static double batch_lbfgs_bytes(int64_t batch, int64_t n, int nparams, int m);   // device bytes a batch of that shape asks for
     // Test entry point (cgo_batch_probe, cgo_backend_batch_probe.hip): a script of passes in ONE launch of the PROBE twin of this

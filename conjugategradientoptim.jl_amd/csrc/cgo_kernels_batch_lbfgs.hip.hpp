@@ -20,7 +20,13 @@
 // re-reads what it wrote itself, with plain global loads and stores — no fence and no barrier for data.  No atomics, no polling,
 // no read of another problem's rows; every loop is bounded by n, m or the line search's own limits.
 // The streaming loops follow RowsDev::trip: all 16-byte loads of a trip first, whole trips without a guard, the partial trip
-// loading from a clamped in-row index, uniform trip counts.  BATCH_LBFGS_U pairs per lane and trip: DESIGN.md §2.14.
+// loading from a clamped in-row index, uniform trip counts.
+// Pairs per lane and trip of the two ring passes: batch_lbfgs_u<Obj>(), a compile-time function of the objective's slot count K —
+// BATCH_LBFGS_U for K ≤ 1 (the built-ins and one-slot bodies), BATCH_LBFGS_U_SLOTS for K ≥ 2, where a trip also holds K slot
+// values per pair and two pairs per trip put the kernel into scratch memory.  The choice cannot change a bit of
+// any result: a lane owns pairs tid, tid + BLOCK, … whatever U is, and within a trip it adds t = 0 … U−1 in ascending order into
+// the same accumulators, so every per-lane sum is formed over the same pairs in the same order for every U; the reduction over
+// lanes does not know U.
 #pragma once
 
 #include "cgo_kernels_batch_rows.hip.hpp"
@@ -29,12 +35,19 @@
 #ifndef CGO_BATCH_LBFGS_U
 #define CGO_BATCH_LBFGS_U 2   // A/B builds: make EXTRA=-DCGO_BATCH_LBFGS_U=…
 #endif
+#ifndef CGO_BATCH_LBFGS_U_SLOTS
+#define CGO_BATCH_LBFGS_U_SLOTS 1   // objectives of two or more slots.  A/B builds: make EXTRA=-DCGO_BATCH_LBFGS_U_SLOTS=2
+#endif
 
 namespace cgo {
 namespace dev {
 
 constexpr int BATCH_LBFGS_U = CGO_BATCH_LBFGS_U;   // independent pairs per lane and trip of the two ring passes
 static_assert(BATCH_LBFGS_U >= 1 && BATCH_LBFGS_U <= BATCH_ROWS_U, "pairs per lane and trip (the trial passes' index limit covers the ring passes')");
+constexpr int BATCH_LBFGS_U_SLOTS = CGO_BATCH_LBFGS_U_SLOTS;   // … of an objective that reads two or more parameter slots
+static_assert(BATCH_LBFGS_U_SLOTS >= 1 && BATCH_LBFGS_U_SLOTS <= BATCH_LBFGS_U, "an objective with slots takes no more pairs per trip than one without");
+constexpr int batch_lbfgs_u_of(int nparams) { return nparams >= 2 ? BATCH_LBFGS_U_SLOTS : BATCH_LBFGS_U; }
+template <class Obj> constexpr int batch_lbfgs_u() { return batch_lbfgs_u_of(obj_nparams<Obj>()); }
 constexpr long long BATCH_LBFGS_MAX_N = BATCH_ROWS_MAX_N;   // the pass index limit: RowsDev's passes run here too
 
 struct BatchLbfgsParams {
@@ -59,7 +72,7 @@ struct LbfgsDev : RowsDev<Obj, NPTS> {
     // ---- push -----------------------------------------------------------------------------------------------------------
     template <bool TAIL>
     __device__ __forceinline__ void push_trip(double a, int c, int i0, double (&acc)[QN_SUMS]) {
-        constexpr int U = BATCH_LBFGS_U;
+        constexpr int U = batch_lbfgs_u<Obj>();
         d2 xv[U], uv[U], sv[QN_MAX_M][U], yv[QN_MAX_M][U];
         PV<Obj> pv[U];
         int idx[U], il[U];
@@ -116,7 +129,7 @@ struct LbfgsDev : RowsDev<Obj, NPTS> {
 
     // the push pass, then the scalar recursion: returns the number of stored pairs (the whole workgroup's alike)
     __device__ __forceinline__ int push_update(double a) {
-        constexpr int U = BATCH_LBFGS_U;
+        constexpr int U = batch_lbfgs_u<Obj>();
         const int tid = threadIdx.x;
         const int c = q->count, npairs = this->npairs;
         double acc[QN_SUMS];
@@ -165,7 +178,7 @@ struct LbfgsDev : RowsDev<Obj, NPTS> {
     template <int NP, bool TAIL>
     __device__ __forceinline__ void combine_trip(const RParams &rp, int c, double ng, const double (&cy)[QN_MAX_M], const double (&cs)[QN_MAX_M],
                                                  int i0, double (&acc)[RW<NP>::W]) {
-        constexpr int U = BATCH_LBFGS_U;
+        constexpr int U = batch_lbfgs_u<Obj>();
         d2 xv[U], sv[QN_MAX_M][U], yv[QN_MAX_M][U];
         PV<Obj> pv[U];
         int idx[U], il[U];
@@ -212,7 +225,7 @@ struct LbfgsDev : RowsDev<Obj, NPTS> {
     __device__ __forceinline__ int combine_trial(const double *a, int k, TrialSums *out, double &gu, double &uu) {
         constexpr int NP = NPTS;
         constexpr int W = RW<NP>::W;
-        constexpr int U = BATCH_LBFGS_U;
+        constexpr int U = batch_lbfgs_u<Obj>();
         const int tid = threadIdx.x;
         const int c = co->count, npairs = this->npairs;
         const double ng = -co->gamma;

@@ -29,6 +29,7 @@ RtcModule::~RtcModule() {
     if (batch_mod) (void)hipModuleUnload(batch_mod);
     if (rows_mod) (void)hipModuleUnload(rows_mod);
     if (batch_probe_mod) (void)hipModuleUnload(batch_probe_mod);
+    if (batch_lbfgs_mod) (void)hipModuleUnload(batch_lbfgs_mod);
 }
 
 static std::string key_cg(int mode, int npts, bool big) {
@@ -63,11 +64,15 @@ hipFunction_t RtcModule::fused(int mode, bool big) const {
 }
 
 // the embedded kernel templates + the user's objective as one translation unit
-std::string rtc_program_source(const std::string &source, int n_params) {
+std::string rtc_program_source(const std::string &source, int n_params) { return rtc_program_source_with(source, n_params, std::string()); }
+
+// … with `more`, further headers a program of its own needs, between the embedded templates and the user's objective
+std::string rtc_program_source_with(const std::string &source, int n_params, const std::string &more) {
     const bool has_param = n_params > 0;
     const std::string K = std::to_string(n_params);
     std::string src;
     for (const char *c : kRtcKernelSourceChunks) src += c;
+    src += more;
     src += "\nnamespace cgo { namespace dev {\n";
     if (source.find("struct UserObjective") != std::string::npos) {
         src += source;

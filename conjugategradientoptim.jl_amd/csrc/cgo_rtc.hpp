@@ -36,6 +36,11 @@ struct RtcModule {
     // first probe (rtc_compile_batch_probe) — creating an objective and its first batched solve cost what they did
     hipFunction_t batch_probe(bool device_rows, int npts) const;
     hipModule_t batch_probe_mod = nullptr;
+    // the batched L-BFGS solves' kernel (cgo_rtc_batch_lbfgs.hip): a FIFTH program, compiled on the first batched L-BFGS solve on
+    // the objective (rtc_compile_batch_lbfgs).  It carries a k_batch_grad of its own, so that the results' gradient of such a
+    // solve with a scalar per problem does not compile the LDS tier's batch program: batch_grad() finds either.
+    hipFunction_t batch_lbfgs(int npts) const;
+    hipModule_t batch_lbfgs_mod = nullptr;
     std::string user_source;
     int n_params = 0;   // parameter slots the objective was created with (0 … CGO_MAX_PARAM_SLOTS)
     int device = 0;
@@ -57,12 +62,16 @@ int rtc_compile_batch(RtcModule &m, std::string &log);
 int rtc_compile_batch_rows(RtcModule &m, std::string &log);
 // the PROBE twins of both, one per row of CGO_BATCH_ROWS and of CGO_BATCH_DEVROWS_ROWS, in one program, likewise
 int rtc_compile_batch_probe(RtcModule &m, std::string &log);
+// the batched L-BFGS kernel for the module's objective, one per row of CGO_BATCH_LBFGS_ROWS, and k_batch_grad, likewise
+int rtc_compile_batch_lbfgs(RtcModule &m, std::string &log);
 
 // What a further program of a module is built from (cgo_rtc.hip): the embedded kernel templates + the user's objective as one
 // translation unit, and one program → one loaded module: compiles `src` for the name expressions of `wants`, loads the code
 // object as `mod` and files every kernel in `fn` under its key.  On failure `mod` is unloaded again and `fn` is as it was.
 struct Want { std::string key, expr; };
 std::string rtc_program_source(const std::string &source, int n_params);
+// … with further headers (`more`) between the embedded templates and the user's objective
+std::string rtc_program_source_with(const std::string &source, int n_params, const std::string &more);
 int rtc_build(const std::string &src, const char *name, const std::vector<Want> &wants, hipModule_t &mod,
               std::map<std::string, hipFunction_t> &fn, std::string &log);
 

@@ -29,6 +29,7 @@ hipFunction_t RtcModule::batch(int npts) const {
 
 hipFunction_t RtcModule::batch_grad() const {
     auto it = fn.find("batch:grad");
+    if (it == fn.end()) it = fn.find("batch_qn:grad");   // (the same kernel in the batched quasi-Newton program, where only that one was compiled)
     return it != fn.end() ? it->second : nullptr;
 }
 

@@ -663,6 +663,31 @@ function minimizeobjectivebatch_lbfgs(out::CBatchResults, kind::Integer, x0::Mat
 end
 batch_lbfgs_max_n(kind::Integer; ctx::Context = defaultcontext()) =
     ccall((:cgo_batch_lbfgs_max_n, libcgo), Int64, (Ptr{Cvoid}, Int32), ctx.h, kind)
+# … on a run-time compiled objective (cgo_minimize_batch_lbfgs_obj): `model` and `params` as batch_open takes them (n × batch
+# matrices, one per parameter slot), `scalars` every problem's own s0 (nothing: the model's).  The first call on a compiled
+# source compiles its batched L-BFGS program.  No handle, `active` mask, barrier method or LDS tier on L-BFGS.
+function minimizeobjectivebatch_lbfgs_obj(out::CBatchResults, model::DeviceObjective, x0::Matrix{Float64}, config::CGConfig,
+                                           linesearch_config::LineSearchConfig; params::Vector{Matrix{Float64}} = Matrix{Float64}[],
+                                           scalars::Union{Nothing,Vector{Float64}} = nothing, slice_iters::Integer = 0)
+    n, batch = size(x0)
+    all(size(p) == (n, batch) for p in params) || throw(ArgumentError("every params[j] must have the size of x0"))
+    scalars === nothing || length(scalars) == batch || throw(ArgumentError("scalars must have one entry per problem"))
+    prows = Ptr{Float64}[pointer(p) for p in params]
+    s = scalars === nothing ? Ptr{Float64}(C_NULL) : pointer(scalars)
+    GC.@preserve x0 params scalars begin
+        check(ccall((:cgo_minimize_batch_lbfgs_obj, libcgo), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Ptr{Float64}}, Int32, Ptr{Float64}, Ref{CCGConfig}, Ref{CLSConfig}, Int64,
+                     Ref{CBatchResults}),
+                    model.ctx.h, model.h, batch, x0, prows, length(params), s, ccfg(config), cls(linesearch_config), slice_iters, out))
+    end
+    return out
+end
+batch_lbfgs_max_n_obj(model::DeviceObjective) = ccall((:cgo_batch_lbfgs_max_n_obj, libcgo), Int64, (Ptr{Cvoid},), model.h)
+function batch_lbfgs_shape_obj(n_params::Integer)
+    blk, u = Ref{Int32}(0), Ref{Int32}(0)
+    ccall((:cgo_batch_lbfgs_shape_obj, libcgo), Cvoid, (Int32, Ref{Int32}, Ref{Int32}), n_params, blk, u)
+    return Int(blk[]), Int(u[])
+end
 
 # ---- kernel-level generics (src/cg_flavours.jl:2-15, 46-170; src/cg_utils.jl:4-23) ---------------------
 function updatedir!(u::Vector{Float64}, df_x::Vector{Float64}, β::Float64; ctx::Context = defaultcontext())

@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""Many small fits at once, on YOUR objective, with a quasi-Newton direction: 256 robust location fits of n = 1000 residuals,
+
+    f_b(x) = Σ_i w_bi (sqrt(1 + (x_i − y_bi)²) − 1)        (pseudo-Huber; slot 0 = the weights w_b, slot 1 = the data y_b)
+
+— the body of examples/batch_fit.py — under LBFGS(5) and StrongWolfeBisection(1e-5, 0.5) to ϵ = 1e-5, through
+
+    model = ElementwiseObjective(n, BODY, param=[None, None])
+    rets = minimizeobjectivebatch_lbfgs_obj(model, X0, config, linesearch_config, params=[W, Y])      # W, Y: [batch, n]
+
+One workgroup per problem runs the outer loop, the line search and the two-loop recursion on the device
+(k_batch_lbfgs<UserObjective, 3>: a program of its own of the model's compiled module, built by the first such call); the ring
+of 2(m+1) rows per problem lives in device memory.  A problem the device loop does not finish is solved again from its own
+start, with its own slot rows, by the ordinary engine (`rets.handed_back`).
+
+Part 1 prints the one-off compile time, then the wall time of the batched call and of the loop it replaces — set the two
+parameter vectors, call minimizeobjective, 256 times on the same objective — in one process: medians of REPS repetitions after
+one untimed, with min … max.
+Part 2 sweeps a regularisation strength PER PROBLEM through `scalars`: the same 32 data sets under 8 strengths λ_b in one call,
+
+    f_b(x) = Σ_i w_bi (sqrt(1 + (x_i − y_bi)²) − 1) + ½ λ_b x_i²             (λ_b = s0 of problem b)
+
+    python examples/batch_lbfgs_fit.py [max_iters] [once]   # needs an MI355X; `once`: the batched call alone, one run (for a kernel trace)
+"""
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import numpy as np
+
+import cgo_amd as cgo
+
+N, BATCH, REPS, M = 1000, 256, 7, 5
+BODY = "const double d = x - p1; const double r = __builtin_sqrt(1.0 + d*d); gi = p*(d/r); fi = p*(r - 1.0);"
+RIDGE = "const double d = x - p1; const double r = __builtin_sqrt(1.0 + d*d); gi = p*(d/r) + s0*x; fi = p*(r - 1.0) + 0.5*((s0*x)*x);"
+max_iters = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
+config = cgo.setupCGConfig(1e-5, cgo.LBFGS(M), cgo.EnableTrace(), max_iters=max_iters)
+ls = cgo.setupStrongWolfeBisection(1e-5, 0.5)
+
+rng = np.random.default_rng(24)
+W = 0.5 + 3.5 * rng.random((BATCH, N))
+Y = 4.0 * rng.random((BATCH, N)) - 2.0
+X0 = 4.0 * rng.random((BATCH, N)) - 2.0
+
+
+def timed(f, reps=REPS):
+    f()   # (once untimed: allocations, first launch of the kernel)
+    ts = []
+    for _ in range(reps):
+        t = time.perf_counter()
+        r = f()
+        ts.append(time.perf_counter() - t)
+    return float(np.median(ts)), min(ts), max(ts), r
+
+
+def report(name, t, rets):
+    med, lo, hi, _ = t
+    its = np.array([r.iters_ran for r in rets])
+    print(f"{name}: {med * 1e3:9.3f} ms ({lo * 1e3:.3f} … {hi * 1e3:.3f}); iterations per problem {its.min()} … {its.max()}, median {int(np.median(its))}, "
+          f"sum {its.sum()}; statuses {sorted(set(r.status for r in rets))}")
+
+
+t = time.perf_counter()
+model = cgo.ElementwiseObjective(N, BODY, param=[None, None])
+t_create = time.perf_counter() - t
+t = time.perf_counter()
+rets = cgo.minimizeobjectivebatch_lbfgs_obj(model, X0, config, ls, params=[W, Y])   # the first such call on the source: compiles its program
+t_first = time.perf_counter() - t
+print(f"creating the objective (every kernel of a single solve): {t_create:.2f} s; the first batched L-BFGS call, which compiles the program once "
+      f"per source: {t_first:.2f} s; pairs per lane and trip with two slots: {cgo.batch_lbfgs_shape_obj(2)[1]}")
+if len(sys.argv) > 2 and sys.argv[2] == "once":
+    rets = cgo.minimizeobjectivebatch_lbfgs_obj(model, X0, config, ls, params=[W, Y])
+    print(f"one batched call: {rets.launches} launch(es), {rets.handed_back} handed back, {sum(r.iters_ran for r in rets)} iterations")
+    model.close()
+    sys.exit(0)
+
+# ---- part 1: the batch against the loop of single solves ---------------------------------------------------------------------
+tb = timed(lambda: cgo.minimizeobjectivebatch_lbfgs_obj(model, X0, config, ls, params=[W, Y]))
+rets = tb[3]
+report(f"batched LBFGS({M}), {BATCH} fits", tb, rets)
+print(f"    {rets.launches} launch(es), {rets.handed_back} handed back to the host engine")
+
+
+def loop():
+    out = []
+    for b in range(BATCH):
+        model.set_param(W[b], slot=0)
+        model.set_param(Y[b], slot=1)
+        out.append(cgo.minimizeobjective(model, X0[b], config, ls))
+    return out
+
+
+tl = timed(loop, reps=3)
+report(f"loop of {BATCH} minimizeobjective calls, LBFGS({M})", tl, tl[3])
+K = 5
+same = sum(np.array_equal(a.trace.step_size[:K], b.trace.step_size[:K]) for a, b in zip(rets, tl[3]))
+worst = max(float(np.max(np.abs(a.minimizer - b.minimizer))) for a, b in zip(rets, tl[3]))
+print(f"    batch against that loop: {tl[0] / tb[0]:.1f} x; the first {K} accepted steps are identical in {same} of {BATCH} fits; "
+      f"largest |x_batch − x_loop|: {worst:.2e}")
+model.close()
+
+# ---- part 2: a regularisation strength per problem ---------------------------------------------------------------------------
+SETS, LAMBDAS = 32, np.array([0.0, 1e-3, 1e-2, 0.1, 0.3, 1.0, 3.0, 10.0])
+idx = np.repeat(np.arange(SETS), len(LAMBDAS))            # problem b fits data set idx[b] under strength lam[b]
+lam = np.tile(LAMBDAS, SETS)
+ridge = cgo.ElementwiseObjective(N, RIDGE, param=[None, None])
+t = time.perf_counter()
+sweep = cgo.minimizeobjectivebatch_lbfgs_obj(ridge, X0[idx], config, ls, params=[W[idx], Y[idx]], scalars=lam)
+t_first = time.perf_counter() - t
+ts = timed(lambda: cgo.minimizeobjectivebatch_lbfgs_obj(ridge, X0[idx], config, ls, params=[W[idx], Y[idx]], scalars=lam))
+report(f"{SETS} data sets × {len(LAMBDAS)} strengths in one call (first call {t_first:.2f} s)", ts, ts[3])
+print(f"    {ts[3].launches} launch(es), {ts[3].handed_back} handed back")
+for j, l in enumerate(LAMBDAS):
+    rs = [ts[3][b] for b in range(len(lam)) if lam[b] == l]
+    print(f"    λ = {l:6.3f}: mean |x̂| {np.mean([np.mean(np.abs(r.minimizer)) for r in rs]):.4f}, mean iterations {np.mean([r.iters_ran for r in rs]):.1f}, "
+          f"largest |∇f| {max(float(np.linalg.norm(r.gradient)) for r in rs):.2e}")
+ridge.close()

@@ -605,8 +605,8 @@ void cgo_batch_rows_shape(int32_t *block, int32_t *pairs_per_trip);
  *   non-finite value, the rare-path norms, WolfeBisection's bracket collapse) is SOLVED AGAIN FROM ITS OWN x0 by one ordinary
  *   solver under the same config — it costs a whole solve, and its results and trace replace the device's.
  * CGO_EINVAL, with the reason in the message: a CG flavour or the Broyden family (those: cgo_minimize_batch), m > 10,
- * Backtracking, any other objective kind (run-time compiled objectives included: there is no batched L-BFGS form of
- * cgo_minimize_batch_obj, of a scalar per problem or of the cgo_batch handle), a multi-rank context, batch < 1,
+ * Backtracking, any other objective kind (CGO_OBJ_USER included: run-time compiled objectives, with parameter slots and a
+ * scalar per problem, are cgo_minimize_batch_lbfgs_obj's, below), a multi-rank context, batch < 1,
  * n > cgo_batch_lbfgs_max_n, and what cgo_minimize_batch refuses of shapes (odd n for paired Rosenbrock, n ≠ 2 for Booth, a
  * missing param0). */
 int cgo_minimize_batch_lbfgs(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
@@ -614,6 +614,28 @@ int cgo_minimize_batch_lbfgs(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t 
 int32_t cgo_batch_lbfgs_max_m(void);                                              /* 10 */
 int64_t cgo_batch_lbfgs_max_n(cgo_ctx *ctx, int32_t obj_kind);                    /* the limit of the pass index, as cgo_batch_max_n_ex(…DEVICE…); 0: none */
 void cgo_batch_lbfgs_shape(int32_t *block, int32_t *pairs_per_trip);              /* of the two ring passes; needs no device */
+/* … on a RUN-TIME COMPILED objective with parameter slots: cgo_minimize_batch_obj with a quasi-Newton direction.  `model`,
+ * `params` and `n_params` as there — every problem has the model's source, size, scalar and cost class and its own row of every
+ * slot; `scalars`: every problem's own s0 for this solve, or NULL for the model's.  The kernel is k_batch_lbfgs<UserObjective, 3>
+ * in a program of its own of the model's module, compiled on the FIRST batched L-BFGS solve on that module (seconds) and kept
+ * while an objective of the same text lives.  Its two ring passes take cgo_batch_lbfgs_shape_obj(n_params) pairs per lane and
+ * trip — fewer for two or more slots, which changes no bit of any result.
+ *   Device memory: (3 + K + 2(m+1)) · batch · (n + n%2) · 8 bytes with K = n_params, checked against what is free before
+ *   anything is allocated (CGO_ENOMEM, the bytes in the message).
+ *   Hand-back: as above — the problem is solved again from its own x0 by one ordinary solver on an objective of the model's
+ *   source with the problem's row of every slot and its own scalar.
+ * CGO_EINVAL: what cgo_minimize_batch_obj refuses of a model and of params (a model that is not run-time compiled, of another
+ * context, sharded or multi-rank; n_params other than the model's; a null params[j]), what cgo_minimize_batch_lbfgs refuses of a
+ * config (a CG flavour or the Broyden family — those: cgo_minimize_batch_obj —, m > 10, Backtracking, a multi-rank context,
+ * batch < 1), a scalars[b] that is not finite, n > cgo_batch_lbfgs_max_n_obj.
+ * Not built: the cgo_batch handle and its `active` mask, the batched barrier method and an LDS tier on L-BFGS, and PROBE twins
+ * of this kernel (cgo_batch_probe's tier 2 stays the built-in objectives'). */
+int cgo_minimize_batch_lbfgs_obj(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *x0 /* [batch*n] */,
+                                 const double *const *params /* n_params × [batch*n] */, int32_t n_params,
+                                 const double *scalars /* [batch] or NULL: the model's s0 for all */,
+                                 const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out);
+int64_t cgo_batch_lbfgs_max_n_obj(cgo_objective *model);        /* the pass-index limit; 0: none; compiles nothing */
+void cgo_batch_lbfgs_shape_obj(int32_t n_params, int32_t *block, int32_t *pairs_per_trip);   /* needs no device */
 /* A scripted sequence of passes of a BATCHED solve in ONE launch, a workgroup per problem, on host vectors — for tests that check
  * every slot of every pass in EVERY workgroup (tests/test_batch_kernel_sums.py).  The batch is allocated as a solve allocates it
  * and the launch arguments are filled by the code that fills them for a solve (ld, the slot pointers, s0 / s0v, the ring stride,
