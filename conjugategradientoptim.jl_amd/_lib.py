@@ -245,6 +245,15 @@ SIGNATURES = {
                                                C.c_int64, C.POINTER(BatchResultsC)]),
     "cgo_batch_lbfgs_max_n_obj": (C.c_int64, [_vp]),
     "cgo_batch_lbfgs_shape_obj": (None, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "cgo_minimize_batch_lbfgs_ex": (C.c_int, [_vp, C.c_int32, C.c_int64, C.c_int64, dp, dp, C.POINTER(CGConfigC), C.POINTER(LSConfigC),
+                                              C.c_int64, C.POINTER(BatchPolicyC), C.POINTER(BatchResultsC), C.POINTER(C.c_int32)]),
+    "cgo_minimize_batch_lbfgs_obj_ex": (C.c_int, [_vp, _vp, C.c_int64, dp, C.POINTER(dp), C.c_int32, dp, C.POINTER(CGConfigC),
+                                                  C.POINTER(LSConfigC), C.c_int64, C.POINTER(BatchPolicyC), C.POINTER(BatchResultsC),
+                                                  C.POINTER(C.c_int32)]),
+    "cgo_batch_lbfgs_max_n_ex": (C.c_int64, [_vp, C.c_int32, C.c_int32, C.POINTER(BatchPolicyC)]),
+    "cgo_batch_lbfgs_max_n_obj_ex": (C.c_int64, [_vp, C.c_int32, C.POINTER(BatchPolicyC)]),
+    "cgo_batch_lbfgs_lds_rows": (C.c_int32, [C.c_int32, C.c_int32]),
+    "cgo_batch_lbfgs_lds_shape": (None, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cgo_batch_probe": (C.c_int, [_vp, C.POINTER(BatchProbeC)]),
     "cgo_batch_probe_qn_bytes": (C.c_int64, []),
     "cgo_stop_status": (C.c_int32, [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, i64p]),

@@ -1228,7 +1228,7 @@ def minimizeobjectivebatch(obj_or_kind, X0, config: CGConfig, linesearch_config:
     return o.results(rows_used=used.value)
 
 
-BATCH_PROBE_TIERS = {"lds": 0, "device": 1, "lbfgs": 2}
+BATCH_PROBE_TIERS = {"lds": 0, "device": 1, "lbfgs": 2, "lbfgs_lds": 3}
 BATCH_PROBE_ROW = 64
 NAN_PATTERN = 0x7FF87FF87FF87FF8   # what every probe buffer starts as
 
@@ -1241,7 +1241,8 @@ def batch_probe_qn_words() -> int:
 def batch_probe(tier: str, obj_or_kind, X, U, script, params=None, scalars=None, skip=None, m: int = 0, S=None, Y=None, qn=None,
                 gradient: bool = False, ctx: Optional[Context] = None) -> dict:
     """A scripted sequence of passes of a batched solve in ONE launch, a workgroup per problem (cgo_batch_probe).  tier: "lds"
-    (k_batch), "device" (k_batch_rows) or "lbfgs" (k_batch_lbfgs).  `obj_or_kind` as in minimizeobjectivebatch; X, U [batch, n];
+    (k_batch), "device" (k_batch_rows), "lbfgs" (k_batch_lbfgs) or "lbfgs_lds" (k_batch_lbfgs_lds, tier 3: the inputs and outputs of
+    "lbfgs", built-in kinds only).  `obj_or_kind` as in minimizeobjectivebatch; X, U [batch, n];
     params: the arrays [batch, n] of the slots the objective reads (the quadratic: [D]); scalars, skip: [batch] or None.
     "lbfgs": m, S and Y [batch, m + 1, n] (absent slots NaN) and qn, a uint64 array [batch, batch_probe_qn_words()].
     `script`: up to 32 tuples ("trial", a) | ("accept_dir_trial", a_acc, beta, a) | ("init",) | ("push", a_acc) |
@@ -1282,7 +1283,7 @@ def batch_probe(tier: str, obj_or_kind, X, U, script, params=None, scalars=None,
             raise ValueError("skip must be [batch]")
         p.skip = skip.ctypes.data_as(C.POINTER(C.c_uint8))
     qw = batch_probe_qn_words()
-    ring = tier == "lbfgs"
+    ring = tier in ("lbfgs", "lbfgs_lds")
     if ring:
         S = _batch_rows("S", S, (batch, m + 1, n))
         Y = _batch_rows("Y", Y, (batch, m + 1, n))
@@ -1357,27 +1358,71 @@ def batch_lbfgs_max_m() -> int:
     return int(_lib.lib().cgo_batch_lbfgs_max_m())
 
 
-def batch_lbfgs_max_n(kind: str, ctx: Optional[Context] = None) -> int:
-    """Largest n of one problem of minimizeobjectivebatch_lbfgs: the index range of a pass (memory is the other limit,
-    checked by the call)."""
+def _batch_lbfgs_policy(rows) -> Optional["_lib.BatchPolicyC"]:
+    """`rows` of a batched L-BFGS call as a cgo_batch_policy — None for "device", the calls without a policy.  Checked and
+    built without any library call."""
+    if not isinstance(rows, str) or rows not in BATCH_ROWS:
+        raise ValueError(f"rows must be one of 'device', 'lds', 'auto', not {rows!r}")
+    if rows == "device":
+        return None
+    pol = _lib.BatchPolicyC()
+    pol.size, pol.rows = C.sizeof(_lib.BatchPolicyC), BATCH_ROWS[rows]
+    return pol
+
+
+def _batch_lbfgs_m(m, rows: str) -> int:
+    if rows == "lds" and m is None:
+        raise ValueError("rows='lds' needs m: what one workgroup's LDS holds depends on the ring depth")
+    if m is not None and (not isinstance(m, (int, np.integer)) or isinstance(m, bool)):
+        raise ValueError("m must be an integer")
+    return 1 if m is None else int(m)
+
+
+def batch_lbfgs_max_n(kind: str, ctx: Optional[Context] = None, m: Optional[int] = None, rows: str = "device") -> int:
+    """Largest n of one problem of minimizeobjectivebatch_lbfgs.  rows="device" (the default) / "auto": the index range of a
+    pass (memory is the other limit, checked by the call).  rows="lds": what one workgroup's LDS holds of the problem's
+    batch_lbfgs_lds_rows(K, m) rows — `m` is required; 0 for m outside 1 … batch_lbfgs_max_m()."""
     if kind not in OBJ_KINDS:
         raise ValueError(f"unknown objective kind {kind!r}")
+    pol = _batch_lbfgs_policy(rows)
+    mm = _batch_lbfgs_m(m, rows)
     ctx = ctx or default_context()
-    return int(_lib.lib().cgo_batch_lbfgs_max_n(ctx._h, OBJ_KINDS[kind]))
+    if pol is None and m is None:
+        return int(_lib.lib().cgo_batch_lbfgs_max_n(ctx._h, OBJ_KINDS[kind]))
+    return int(_lib.lib().cgo_batch_lbfgs_max_n_ex(ctx._h, OBJ_KINDS[kind], mm, C.byref(pol) if pol is not None else None))
+
+
+def batch_lbfgs_lds_rows(n_params: int, m: int) -> int:
+    """Rows of n + n%2 doubles a problem of rows="lds" keeps in its workgroup's LDS: x, u, the n_params slots and the ring —
+    2 + n_params + 2(m+1); 0 for n_params outside 0 … 4 or m outside 1 … 10.  Needs no device."""
+    return int(_lib.lib().cgo_batch_lbfgs_lds_rows(int(n_params), int(m)))
+
+
+def batch_lbfgs_lds_shape(n_params: int = 0):
+    """(lanes per workgroup, pairs of elements per lane and trip) of the two ring passes of rows="lds" on an objective of
+    `n_params` parameter slots (no bit of a result depends on it).  Needs no device."""
+    blk, u = C.c_int32(0), C.c_int32(0)
+    _lib.lib().cgo_batch_lbfgs_lds_shape(int(n_params), C.byref(blk), C.byref(u))
+    return int(blk.value), int(u.value)
 
 
 def minimizeobjectivebatch_lbfgs(kind: str, X0, config: CGConfig, linesearch_config: LineSearchConfig, D=None,
-                                 ctx: Optional[Context] = None, slice_iters: int = 0) -> BatchResults:
+                                 ctx: Optional[Context] = None, slice_iters: int = 0, rows: str = "device") -> BatchResults:
     """minimizeobjectivebatch with a quasi-Newton direction: `config.β_config` is LBFGS(m), 1 ≤ m ≤ batch_lbfgs_max_m() = 10
     (minimizeobjectivebatch is the CG flavours' and refuses it).  kind: "quad_diag" (D: [batch, n]), "rosenbrock_paired" (n even)
     or "booth" (n = 2); StrongWolfeBisection or WolfeBisection.  One workgroup per problem; the rows of x, u, D and a ring of
     2(m+1) rows per problem stay in device memory — (3 + K + 2(m+1)) · batch · (n + n%2) · 8 bytes, checked against the device's
-    free memory before anything is allocated.  Returns what minimizeobjectivebatch returns (`.rows` is "device").  A problem
+    free memory before anything is allocated.  Returns what minimizeobjectivebatch returns (`.rows`: the tier that ran).
+    rows: "device" (the default): every pass streams the problem's rows and ring from device memory.  "lds": a workgroup keeps
+    them in its LDS during a launch and writes back what it changed — n ≤ batch_lbfgs_max_n(kind, m=m, rows="lds"), refused
+    beyond; every number returned has the bits of "device".  "auto": "device" at every n — the LDS tier did not beat the device tier by more than its spread at every
+    measured shape, so it is reached by asking for it.  A problem
     the device loop does not finish is solved AGAIN from its own x0 by the ordinary engine — a whole solve — and counted in
     `handed_back`.  Anything not covered raises CgoError: Backtracking, m > 10, a multi-rank context.  Run-time compiled
     objectives, with parameter slots and a scalar per problem: minimizeobjectivebatch_lbfgs_obj."""
     if not isinstance(kind, str) or kind not in OBJ_KINDS:
         raise ValueError(f"unknown objective kind {kind!r} (a run-time compiled objective: minimizeobjectivebatch_lbfgs_obj)")
+    pol = _batch_lbfgs_policy(rows)
     X0 = np.ascontiguousarray(np.asarray(X0, dtype=np.float64))
     if X0.ndim != 2:
         raise ValueError("X0 must be [batch, n]")
@@ -1390,10 +1435,16 @@ def minimizeobjectivebatch_lbfgs(kind: str, X0, config: CGConfig, linesearch_con
     ctx = ctx or default_context()
     o = _BatchOut(batch, n, config)
     cfg, ls = config._c(), linesearch_config._c()
-    check(_lib.lib().cgo_minimize_batch_lbfgs(ctx._h, OBJ_KINDS[kind], n, batch, X0.ctypes.data_as(dp),
-                                              Dc.ctypes.data_as(dp) if Dc is not None else None, C.byref(cfg), C.byref(ls),
-                                              int(slice_iters), C.byref(o.c)))
-    return o.results(rows_used=BATCH_ROWS["device"])
+    if pol is None:   # the default: exactly the call without a policy
+        check(_lib.lib().cgo_minimize_batch_lbfgs(ctx._h, OBJ_KINDS[kind], n, batch, X0.ctypes.data_as(dp),
+                                                  Dc.ctypes.data_as(dp) if Dc is not None else None, C.byref(cfg), C.byref(ls),
+                                                  int(slice_iters), C.byref(o.c)))
+        return o.results(rows_used=BATCH_ROWS["device"])
+    used = C.c_int32(BATCH_ROWS["device"])
+    check(_lib.lib().cgo_minimize_batch_lbfgs_ex(ctx._h, OBJ_KINDS[kind], n, batch, X0.ctypes.data_as(dp),
+                                                 Dc.ctypes.data_as(dp) if Dc is not None else None, C.byref(cfg), C.byref(ls),
+                                                 int(slice_iters), C.byref(pol), C.byref(o.c), C.byref(used)))
+    return o.results(rows_used=used.value)
 
 
 def batch_lbfgs_shape_obj(n_params: int):
@@ -1404,28 +1455,37 @@ def batch_lbfgs_shape_obj(n_params: int):
     return int(blk.value), int(u.value)
 
 
-def batch_lbfgs_max_n_obj(model: "DeviceObjective") -> int:
-    """Largest n of one problem of minimizeobjectivebatch_lbfgs_obj on `model`: the index range of a pass (0: not a run-time
-    compiled, whole, single-rank objective).  Compiles nothing."""
+def batch_lbfgs_max_n_obj(model: "DeviceObjective", m: Optional[int] = None, rows: str = "device") -> int:
+    """Largest n of one problem of minimizeobjectivebatch_lbfgs_obj on `model` (0: not a run-time compiled, whole, single-rank
+    objective).  rows="device" (the default) / "auto": the index range of a pass; compiles nothing.  rows="lds": what one
+    workgroup's LDS holds of the problem's rows and ring for ring depth `m` (required) — the first such call on a compiled source
+    compiles its program of that tier, as batch_max_n compiles the batch program."""
     if not isinstance(model, DeviceObjective):
         raise ValueError("model must be a run-time compiled DeviceObjective (ElementwiseObjective)")
-    return int(_lib.lib().cgo_batch_lbfgs_max_n_obj(model._h))
+    pol = _batch_lbfgs_policy(rows)
+    mm = _batch_lbfgs_m(m, rows)
+    if pol is None and m is None:
+        return int(_lib.lib().cgo_batch_lbfgs_max_n_obj(model._h))
+    return int(_lib.lib().cgo_batch_lbfgs_max_n_obj_ex(model._h, mm, C.byref(pol) if pol is not None else None))
 
 
 def minimizeobjectivebatch_lbfgs_obj(model: "DeviceObjective", X0, config: CGConfig, linesearch_config: LineSearchConfig,
-                                     params=None, scalars=None, ctx: Optional[Context] = None, slice_iters: int = 0) -> BatchResults:
+                                     params=None, scalars=None, ctx: Optional[Context] = None, slice_iters: int = 0,
+                                     rows: str = "device") -> BatchResults:
     """minimizeobjectivebatch_lbfgs on a run-time compiled objective: `model` (ElementwiseObjective) as in minimizeobjectivebatch
     — its source, size, scalar and cost class are every problem's — with `params`, its n_params arrays [batch, n], the rows of
     slot 0, 1, …, and optionally `scalars`, a [batch] array of every problem's own `s0` (None: the model's for all).
     `config.β_config` is LBFGS(m), 1 ≤ m ≤ 10; StrongWolfeBisection or WolfeBisection.  The first call on a compiled source
     compiles its batched L-BFGS program (seconds); later ones find it.  Device memory: (3 + n_params + 2(m+1)) · batch ·
-    (n + n%2) · 8 bytes, checked before anything is allocated.  Returns what minimizeobjectivebatch_lbfgs returns (`.rows` is
-    "device"); a problem the device loop does not finish is solved again from its own x0, with its own slot rows and scalar, by
+    (n + n%2) · 8 bytes, checked before anything is allocated.  rows: "device" | "lds" | "auto" as in minimizeobjectivebatch_lbfgs
+    (the limit of "lds": batch_lbfgs_max_n_obj(model, m=m, rows="lds"); its kernel is one more program of the source, compiled by
+    the first call that runs the tier).  Returns what minimizeobjectivebatch_lbfgs returns (`.rows`: the tier that ran); a problem the device loop does not finish is solved again from its own x0, with its own slot rows and scalar, by
     the ordinary engine and counted in `handed_back`.  Not covered (CgoError or ValueError): CG flavours and Broyden
-    (minimizeobjectivebatch), Backtracking, m > 10, a multi-rank context; there is no `Batch` handle, `active` mask, barrier
-    method or LDS tier on L-BFGS."""
+    (minimizeobjectivebatch), Backtracking, m > 10, a multi-rank context; there is no `Batch` handle, `active` mask or barrier
+    method on L-BFGS."""
     if not isinstance(model, DeviceObjective):
         raise ValueError("model must be a run-time compiled DeviceObjective (ElementwiseObjective); built-in kinds: minimizeobjectivebatch_lbfgs")
+    pol = _batch_lbfgs_policy(rows)
     X0 = np.ascontiguousarray(np.asarray(X0, dtype=np.float64))
     if X0.ndim != 2:
         raise ValueError("X0 must be [batch, n]")
@@ -1450,10 +1510,16 @@ def minimizeobjectivebatch_lbfgs_obj(model: "DeviceObjective", X0, config: CGCon
     o = _BatchOut(batch, n, config)
     cfg, ls = config._c(), linesearch_config._c()
     prows = (dp * max(len(Pc), 1))(*[v.ctypes.data_as(dp) for v in Pc])
-    check(_lib.lib().cgo_minimize_batch_lbfgs_obj(ctx._h, model._h, batch, X0.ctypes.data_as(dp), prows, len(Pc),
-                                                  sc.ctypes.data_as(dp) if sc is not None else None, C.byref(cfg), C.byref(ls),
-                                                  int(slice_iters), C.byref(o.c)))
-    return o.results(rows_used=BATCH_ROWS["device"])
+    if pol is None:   # the default: exactly the call without a policy
+        check(_lib.lib().cgo_minimize_batch_lbfgs_obj(ctx._h, model._h, batch, X0.ctypes.data_as(dp), prows, len(Pc),
+                                                      sc.ctypes.data_as(dp) if sc is not None else None, C.byref(cfg), C.byref(ls),
+                                                      int(slice_iters), C.byref(o.c)))
+        return o.results(rows_used=BATCH_ROWS["device"])
+    used = C.c_int32(BATCH_ROWS["device"])
+    check(_lib.lib().cgo_minimize_batch_lbfgs_obj_ex(ctx._h, model._h, batch, X0.ctypes.data_as(dp), prows, len(Pc),
+                                                     sc.ctypes.data_as(dp) if sc is not None else None, C.byref(cfg), C.byref(ls),
+                                                     int(slice_iters), C.byref(pol), C.byref(o.c), C.byref(used)))
+    return o.results(rows_used=used.value)
 
 
 class Batch:

@@ -101,7 +101,7 @@ int HipBackend::batch_alloc(int64_t batch, int64_t n, const double *const *param
     HIPCHK(hipMalloc((void **)&bat_fx0_, sizeof(double) * (size_t)batch));
     if (obj_->kind == CGO_OBJ_USER) {   // (a module's kernel takes its dynamic LDS as launched, as the resident solver's does)
         // (rows in device memory: the device-rows program, or the batched L-BFGS program of a batch batch_lbfgs_alloc follows on)
-        if (!obj_->rtc || !(device_rows ? (obj_->rtc->batch_rows(3) || obj_->rtc->batch_lbfgs(3)) : obj_->rtc->batch(3) != nullptr)) { set_error("internal: batched solve before the objective's batch program was compiled"); return CGO_ESTATE; }
+        if (!obj_->rtc || !(device_rows ? (obj_->rtc->batch_rows(3) || obj_->rtc->batch_lbfgs(3) || obj_->rtc->batch_lbfgs_lds(3)) : obj_->rtc->batch(3) != nullptr)) { set_error("internal: batched solve before the objective's batch program was compiled"); return CGO_ESTATE; }
         return CGO_OK;
     }
     const void *fn = device_rows ? batch_rows_kernel_for(obj_->kind, 3) : batch_kernel_for(obj_->kind, 3);

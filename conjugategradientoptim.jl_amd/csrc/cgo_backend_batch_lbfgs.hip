@@ -40,10 +40,10 @@ double HipBackend::batch_lbfgs_bytes(int64_t batch, int64_t n, int nparams, int 
     return (double)batch * (ld * 8.0 * (double)(3 + nparams + 2 * (m + 1)) + (double)sizeof(ResState) + (double)sizeof(QnState) + 16.0);
 }
 
-int HipBackend::batch_lbfgs_alloc(int m) {
+int HipBackend::batch_lbfgs_alloc(int m, bool lds) {
     if (!bat_st_ || !bat_rows_ || bat_qn_ || m < 1 || m > QN_MAX_M) { set_error("internal: batched L-BFGS on a batch of another shape"); return CGO_ESTATE; }
-    if (obj_->kind == CGO_OBJ_USER) {
-        if (!obj_->rtc || !obj_->rtc->batch_lbfgs(3)) { set_error("internal: batched L-BFGS solve before the objective's batched L-BFGS program was compiled"); return CGO_ESTATE; }
+    if (obj_->kind == CGO_OBJ_USER) {   // (lds: the kernel is the LDS tier's program's, checked by batch_lbfgs_lds_on)
+        if (!obj_->rtc || !(lds ? obj_->rtc->batch_lbfgs_lds(3) : obj_->rtc->batch_lbfgs(3))) { set_error("internal: batched L-BFGS solve before the objective's batched L-BFGS program was compiled"); return CGO_ESTATE; }
     } else if (!batch_lbfgs_kernel_for(obj_->kind, 3)) { set_error("batched L-BFGS solves: no k_batch_lbfgs instantiation for this objective"); return CGO_EINVAL; }
     if (bat_n_ > batch_lbfgs_max_n()) { set_error("internal: a batch beyond the pass index of the batched L-BFGS solves"); return CGO_ESTATE; }
     HIPCHK(hipSetDevice(ctx_->device));
@@ -52,7 +52,7 @@ int HipBackend::batch_lbfgs_alloc(int m) {
     HIPCHK(hipMalloc((void **)&bat_Y_, ring));
     HIPCHK(hipMalloc((void **)&bat_qn_, sizeof(QnState) * (size_t)bat_count_));
     bat_m_ = m;
-    return CGO_OK;
+    return lds ? batch_lbfgs_lds_on() : (int)CGO_OK;   // (cgo_backend_batch_lbfgs_lds.hip)
 }
 
 // every problem's ring empty.  (The ring rows need no clearing: a pass reads the slots of stored pairs only, and the padding
@@ -84,7 +84,9 @@ int HipBackend::batch_lbfgs_launch(const ResConfig &c, int64_t budget, std::vect
     BatchLbfgsParams L{};
     batch_lbfgs_fill_params(L, c, budget);
     void *args[] = {&L};
-    if (obj_->kind == CGO_OBJ_USER) {
+    if (bat_qn_lds_) {   // rows and ring in LDS during the launch: k_batch_lbfgs_lds (cgo_backend_batch_lbfgs_lds.hip)
+        if (int rc = batch_lbfgs_lds_launch(L)) return rc;
+    } else if (obj_->kind == CGO_OBJ_USER) {
         const hipFunction_t mf = obj_->rtc ? obj_->rtc->batch_lbfgs(3) : nullptr;
         if (!mf) { set_error("internal: kernel missing from the run-time compiled objective module"); return CGO_EINVAL; }
         HIPCHK(hipModuleLaunchKernel(mf, (unsigned)bat_count_, 1, 1, BLOCK, 1, 1, 0, ctx_->stream, args, nullptr));

@@ -1,4 +1,4 @@
-// cgo_backend_batch_probe.hip — cgo_batch_probe: the PROBE twins of k_batch, k_batch_rows and k_batch_lbfgs (the rows of
+// cgo_backend_batch_probe.hip — cgo_batch_probe: the PROBE twins of k_batch, k_batch_rows, k_batch_lbfgs and k_batch_lbfgs_lds (the rows of
 // cgo_instances.def × the objectives, each with the template's PROBE flag set) and the host side of a probe.  A translation unit
 // of its own, for the reason cgo_backend_batch_rows.hip and cgo_backend_batch_lbfgs.hip exist: the device code of the product
 // units is what it was before the probe.
@@ -8,7 +8,7 @@
 // is DATA: every buffer is re-allocated with NaN slack behind its used part, the padding element of an odd n is the NaN
 // pattern in every row, and the states are the caller's.  Every index a kernel will use is checked here first.
 #include "cgo_backend_internal.hpp"
-#include "cgo_kernels_batch_lbfgs.hip.hpp"
+#include "cgo_kernels_batch_lbfgs_lds.hip.hpp"
 
 namespace cgo {
 
@@ -29,9 +29,13 @@ static const void *batch_probe_kernel(int tier, int npts, int &picked) {
 #define ROW(NPTS) if (!fn || npts >= NPTS) { fn = (const void *)k_batch_rows<Obj, NPTS, true>; picked = NPTS; }
         CGO_BATCH_DEVROWS_ROWS(ROW)
 #undef ROW
-    } else {
+    } else if (tier == 2) {
 #define ROW(NPTS) if (!fn || npts >= NPTS) { fn = (const void *)k_batch_lbfgs<Obj, NPTS, true>; picked = NPTS; }
         CGO_BATCH_LBFGS_ROWS(ROW)
+#undef ROW
+    } else {
+#define ROW(NPTS) if (!fn || npts >= NPTS) { fn = (const void *)k_batch_lbfgs_lds<Obj, NPTS, true>; picked = NPTS; }
+        CGO_BATCH_LBFGS_LDS_ROWS(ROW)
 #undef ROW
     }
     return fn;
@@ -84,7 +88,8 @@ int HipBackend::batch_probe(cgo_batch_probe_args &p) {
     const bool user = obj_->kind == CGO_OBJ_USER;
     const int64_t batch = bat_count_, n = bat_n_, ld = bat_ld_;
     const int m = bat_m_, K = obj_->nparams();
-    if ((tier == 0) != !bat_rows_ || (tier == 2) != (m > 0)) { set_error("internal: batch_probe on a batch of another tier"); return CGO_ESTATE; }
+    const bool qnt = tier >= 2;   // the two tiers of batched L-BFGS: the ring in device memory (2) or, with the rows, in LDS (3)
+    if ((tier == 0) != !bat_rows_ || qnt != (m > 0) || (tier == 3) != bat_qn_lds_) { set_error("internal: batch_probe on a batch of another tier"); return CGO_ESTATE; }
     // ---- the script: what this tier's loop issues, for the points of its instantiation
     const int npts = batch_probe_points(tier, user), nt = npts < 3 ? npts : 3;
     if (p.npass < 1 || p.npass > CGO_BATCH_PROBE_MAX_PASSES) { set_error("batch probe: 1 … 32 passes"); return CGO_EINVAL; }
@@ -95,10 +100,10 @@ int HipBackend::batch_probe(cgo_batch_probe_args &p) {
         bool known = false, k_ok = true;
         switch (c.kind) {
         case 0: known = true; k_ok = c.k >= 1 && c.k <= nt; break;
-        case 1: known = tier != 2; k_ok = c.k >= 0 && c.k <= npts; break;
+        case 1: known = !qnt; k_ok = c.k >= 0 && c.k <= npts; break;
         case 2: known = true; break;
-        case 3: known = tier == 2; pushed = pushed || known; break;
-        case 4: known = tier == 2; k_ok = c.k >= 0 && c.k <= npts; break;
+        case 3: known = qnt; pushed = pushed || known; break;
+        case 4: known = qnt; k_ok = c.k >= 0 && c.k <= npts; break;
         default: break;
         }
         if (!known) { set_error("batch probe: pass " + std::to_string(q) + " (kind " + std::to_string(c.kind) + ") is not one the loop of tier " + std::to_string(tier) + " issues"); return CGO_EINVAL; }
@@ -121,8 +126,8 @@ int HipBackend::batch_probe(cgo_batch_probe_args &p) {
     for (int j = 0; j < K; ++j)
         if (!p.params[j]) { set_error("batch probe: params[" + std::to_string(j) + "] is null, the objective reads " + std::to_string(K) + " parameter slots"); return CGO_EINVAL; }
     std::vector<QnState> qn;
-    if (tier == 2) {
-        if (!p.S || !p.Y || !p.qn) { set_error("batch probe: tier 2 needs S, Y and the quasi-Newton states"); return CGO_EINVAL; }
+    if (qnt) {
+        if (!p.S || !p.Y || !p.qn) { set_error("batch probe: tiers 2 and 3 need S, Y and the quasi-Newton states"); return CGO_EINVAL; }
         qn.resize((size_t)batch);
         std::memcpy(qn.data(), p.qn, sizeof(QnState) * (size_t)batch);
         for (int64_t b = 0; b < batch; ++b) {   // every index the kernel takes from the state
@@ -132,7 +137,7 @@ int HipBackend::batch_probe(cgo_batch_probe_args &p) {
             if (!ok) { set_error("batch probe: the quasi-Newton state of problem " + std::to_string(b) + " names a slot outside the ring (m, count, free_slot, list against m = " + std::to_string(m) + ")"); return CGO_EINVAL; }
         }
     } else if (p.scalars && !user) { set_error("batch probe: scalars belong to a run-time compiled objective"); return CGO_EINVAL; }
-    if (tier == 2 && p.scalars) { set_error("batch probe: the batched L-BFGS solves take no scalar per problem"); return CGO_EINVAL; }
+    if (qnt && p.scalars) { set_error("batch probe: the batched L-BFGS solves take no scalar per problem"); return CGO_EINVAL; }
 
     // ---- the kernel
     int picked = 0;
@@ -169,7 +174,7 @@ int HipBackend::batch_probe(cgo_batch_probe_args &p) {
     if (int rc = slack_alloc(own, &d_st, sizeof(ResState) * (size_t)batch, "the states", st)) return rc;
     if (int rc = slack_alloc(own, &d_fx0, sizeof(double) * (size_t)batch, "f_x0", st)) return rc;
     if (p.scalars) { if (int rc = slack_alloc(own, &d_s0v, sizeof(double) * (size_t)batch, "the scalars", st)) return rc; }
-    if (tier == 2) {
+    if (qnt) {
         const size_t ring = row_b * (size_t)(m + 1);
         if (int rc = slack_alloc(own, &d_S, ring, "the ring S", st)) return rc;
         if (int rc = slack_alloc(own, &d_Y, ring, "the ring Y", st)) return rc;
@@ -181,7 +186,7 @@ int HipBackend::batch_probe(cgo_batch_probe_args &p) {
     (void)hipFree(bat_fx0_); bat_fx0_ = (double *)d_fx0; freer.keep[1] = d_fx0;
     if (d_s0v) { if (bat_s0v_) (void)hipFree(bat_s0v_); bat_s0v_ = (double *)d_s0v; freer.keep[2] = d_s0v; }
     bat_s0v_on_ = d_s0v != nullptr;
-    if (tier == 2) {
+    if (qnt) {
         (void)hipFree(bat_S_); bat_S_ = (double *)d_S; freer.keep[3] = d_S;
         (void)hipFree(bat_Y_); bat_Y_ = (double *)d_Y; freer.keep[4] = d_Y;
         (void)hipFree(bat_qn_); bat_qn_ = (QnState *)d_qn; freer.keep[5] = d_qn;
@@ -198,7 +203,7 @@ int HipBackend::batch_probe(cgo_batch_probe_args &p) {
             v = padded_rows(p.params[j], batch, n, ld);
             HIPCHK(hipMemcpy(obj_->p[j].p, v.data(), row_b, hipMemcpyHostToDevice));
         }
-        if (tier == 2) {
+        if (qnt) {
             v = padded_rows(p.S, batch * (m + 1), n, ld);
             HIPCHK(hipMemcpy(bat_S_, v.data(), row_b * (size_t)(m + 1), hipMemcpyHostToDevice));
             v = padded_rows(p.Y, batch * (m + 1), n, ld);
@@ -226,8 +231,8 @@ int HipBackend::batch_probe(cgo_batch_probe_args &p) {
     BatchProbeParams A{};
     BatchLbfgsProbeParams AL{};
     void *args[1];
-    const char *family = tier == 0 ? "k_batch" : tier == 1 ? "k_batch_rows" : "k_batch_lbfgs";
-    if (tier == 2) { batch_lbfgs_fill_params(AL, cfg, 1); AL.pr = pr; args[0] = &AL; }
+    const char *family = tier == 0 ? "k_batch" : tier == 1 ? "k_batch_rows" : tier == 2 ? "k_batch_lbfgs" : "k_batch_lbfgs_lds";
+    if (qnt) { batch_lbfgs_fill_params(AL, cfg, 1); AL.pr = pr; args[0] = &AL; }
     else { batch_fill_params(A, cfg, 1); A.pr = pr; args[0] = &A; }
     p.points = picked; p.ld = ld;
     snprintf(p.symbol, sizeof p.symbol, "%s<%s, %d, true>", family, obj_tname(), picked);
@@ -248,7 +253,7 @@ int HipBackend::batch_probe(cgo_batch_probe_args &p) {
     if (p.out) HIPCHK(hipMemcpy(p.out, d_out, sizeof(BatchProbeOut) * (size_t)p.npass * (size_t)batch, hipMemcpyDeviceToHost));
     if (p.x_out) HIPCHK(hipMemcpy(p.x_out, xc_, row_b, hipMemcpyDeviceToHost));
     if (p.u_out) HIPCHK(hipMemcpy(p.u_out, uc_, row_b, hipMemcpyDeviceToHost));
-    if (tier == 2) {
+    if (qnt) {
         if (p.S_out) HIPCHK(hipMemcpy(p.S_out, bat_S_, row_b * (size_t)(m + 1), hipMemcpyDeviceToHost));
         if (p.Y_out) HIPCHK(hipMemcpy(p.Y_out, bat_Y_, row_b * (size_t)(m + 1), hipMemcpyDeviceToHost));
         if (p.qn_out) HIPCHK(hipMemcpy(p.qn_out, bat_qn_, sizeof(QnState) * (size_t)batch, hipMemcpyDeviceToHost));

@@ -1183,7 +1183,7 @@ int cgo_minimize_batch_ex(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t bat
     API_GUARD_END
 }
 
-// ---- batched solves with β = LBFGS(m): k_batch_lbfgs, the ring of every problem in device memory -------------------------------------
+// ---- batched solves with β = LBFGS(m): k_batch_lbfgs, the ring of every problem in device memory (k_batch_lbfgs_lds: in LDS) -------------------------------------
 int32_t cgo_batch_lbfgs_max_m(void) { return QN_MAX_M; }
 
 void cgo_batch_lbfgs_shape(int32_t *block, int32_t *pairs_per_trip) {
@@ -1237,18 +1237,80 @@ static int check_batch_lbfgs_call(cgo_ctx *ctx, const cgo_cg_config *cfg, const 
     return CGO_OK;
 }
 
+// ---- … and their LDS tier (k_batch_lbfgs_lds): the calls above with a policy.  A null policy is the call without one — device rows.
+static int batch_lbfgs_rows_asked(const cgo_batch_policy *pol, int &rows) {
+    rows = CGO_BATCH_ROWS_DEVICE;
+    if (!pol) return CGO_OK;
+    REQUIRE(pol->size == (int32_t)sizeof(cgo_batch_policy), "cgo_batch_policy.size does not match this library (call cgo_batch_policy_init first)");
+    REQUIRE(pol->rows == CGO_BATCH_ROWS_LDS || pol->rows == CGO_BATCH_ROWS_DEVICE || pol->rows == CGO_BATCH_ROWS_AUTO,
+            "batched L-BFGS solves: cgo_batch_policy.rows must be CGO_BATCH_ROWS_LDS, CGO_BATCH_ROWS_DEVICE or CGO_BATCH_ROWS_AUTO");
+    rows = pol->rows;
+    return CGO_OK;
+}
+// THE rule of CGO_BATCH_ROWS_AUTO for batched L-BFGS (stated in include/cgo.h): device rows.  "LDS where n fits" needed the LDS
+// tier's kernel time below the device tier's by more than that tier's own spread at EVERY measured shape, and at n = 1000, m = 5
+// it is not.  true: LDS where n fits for this m and slot count.
+static constexpr bool kBatchLbfgsAutoTakesLds = false;
+// the tier a batch of problems of size n runs in: lds_max = what one workgroup's LDS holds for this m and slot count
+static int batch_lbfgs_tier(int rows, int64_t n, int64_t lds_max, bool &lds) {
+    lds = rows == CGO_BATCH_ROWS_LDS || (rows == CGO_BATCH_ROWS_AUTO && kBatchLbfgsAutoTakesLds && n <= lds_max);
+    if (lds && n > lds_max) {
+        set_error("batched L-BFGS solves: n = " + std::to_string(n) + " exceeds what one workgroup's LDS holds of a problem's rows and ring (cgo_batch_lbfgs_max_n_ex = " + std::to_string(lds_max) + ")");
+        return CGO_EINVAL;
+    }
+    return CGO_OK;
+}
+
 int cgo_minimize_batch_lbfgs(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
                              const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out) {
+    return cgo_minimize_batch_lbfgs_ex(ctx, obj_kind, n, batch, x0, param0, cfg, ls, slice_iters, nullptr, out, nullptr);
+}
+
+int32_t cgo_batch_lbfgs_lds_rows(int32_t n_params, int32_t m) { return HipBackend::batch_lbfgs_lds_rows(n_params, m); }
+
+void cgo_batch_lbfgs_lds_shape(int32_t n_params, int32_t *block, int32_t *pairs_per_trip) {
+    if (block) *block = HipBackend::batch_lbfgs_block();
+    if (pairs_per_trip) *pairs_per_trip = HipBackend::batch_lbfgs_lds_unroll_for(n_params);
+}
+
+// what one workgroup's LDS holds of a built-in problem's rows and ring (0: no context, kind or device, a bad m)
+static int64_t batch_lbfgs_lds_max_n(cgo_ctx *ctx, int32_t obj_kind, int32_t m) {
+    if (!ctx || !batch_kind(obj_kind)) return 0;
+    const int64_t ld = HipBackend::batch_lbfgs_lds_max_ld(&ctx->c, obj_kind, m);
+    return obj_kind == CGO_OBJ_BOOTH ? std::min<int64_t>(ld, 2) : ld;
+}
+
+int64_t cgo_batch_lbfgs_max_n_ex(cgo_ctx *ctx, int32_t obj_kind, int32_t m, const cgo_batch_policy *policy) {
+    try {
+        int rows = 0;
+        if (batch_lbfgs_rows_asked(policy, rows)) return 0;
+        if (m < 1 || m > QN_MAX_M) return 0;
+        if (rows == CGO_BATCH_ROWS_LDS) return batch_lbfgs_lds_max_n(ctx, obj_kind, m);
+        return cgo_batch_lbfgs_max_n(ctx, obj_kind);
+    } catch (...) { return 0; }
+}
+
+int cgo_minimize_batch_lbfgs_ex(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
+                                const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, const cgo_batch_policy *policy,
+                                cgo_batch_results *out, int32_t *rows_used) {
     API_GUARD_BEGIN
     REQUIRE(ctx && x0 && cfg && ls && out, "null argument");
     out->launches = 0; out->handed_back = 0;
+    int rows = 0;
+    if (int rc = batch_lbfgs_rows_asked(policy, rows)) return rc;
     REQUIRE(batch_kind(obj_kind), "batched L-BFGS solves: the objective must be CGO_OBJ_QUAD_DIAG, CGO_OBJ_ROSENBROCK_PAIRED or CGO_OBJ_BOOTH");
     if (int rc = check_batch_lbfgs_call(ctx, cfg, ls, n, batch, slice_iters, "cgo_minimize_batch")) return rc;
     if (obj_kind == CGO_OBJ_ROSENBROCK_PAIRED) REQUIRE(n % 2 == 0, "batched L-BFGS solves: paired Rosenbrock needs an even n");
     if (obj_kind == CGO_OBJ_BOOTH) REQUIRE(n == 2, "batched L-BFGS solves: Booth is 2-dimensional (n = 2)");
     if (obj_kind == CGO_OBJ_QUAD_DIAG) REQUIRE(param0, "batched L-BFGS solves: the quadratic needs param0, the [batch*n] rows of D");
     const int m = cfg->beta.lbfgs_m;
+    bool lds = false;
+    if (rows != CGO_BATCH_ROWS_DEVICE) {
+        HIPCHK2(hipSetDevice(ctx->c.device));
+        if (int rc = batch_lbfgs_tier(rows, n, batch_lbfgs_lds_max_n(ctx, obj_kind, m), lds)) return rc;
+    }
     if (int rc = batch_lbfgs_sizes(ctx, obj_kind, n, batch, m)) return rc;
+    if (rows_used) *rows_used = lds ? CGO_BATCH_ROWS_LDS : CGO_BATCH_ROWS_DEVICE;
     const int64_t ld = n + (n & 1);
     HipObjective cat;
     cat.ctx = &ctx->c; cat.kind = obj_kind; cat.n_global = cat.n_local = batch * ld; cat.offset = 0;
@@ -1256,7 +1318,7 @@ int cgo_minimize_batch_lbfgs(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t 
     const double *params[1] = {param0};
     HipBackend be(&ctx->c, &cat);
     if (int rc = batch_backend_on(ctx, cat, n, batch, params, be, true)) return rc;
-    if (int rc = be.batch_lbfgs_alloc(m)) return rc;
+    if (int rc = be.batch_lbfgs_alloc(m, lds)) return rc;
     return batch_solve_on(ctx, be, n, batch, x0, nullptr, nullptr, cfg, ls, slice_iters, out,
                           [&](cgo_objective **h) { return cgo_objective_create(ctx, obj_kind, n, 0, n, h); }, true, params, 1);
     API_GUARD_END
@@ -1398,9 +1460,36 @@ int64_t cgo_batch_lbfgs_max_n_obj(cgo_objective *model) {
 int cgo_minimize_batch_lbfgs_obj(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *x0, const double *const *params,
                                  int32_t n_params, const double *scalars, const cgo_cg_config *cfg, const cgo_ls_config *ls,
                                  int64_t slice_iters, cgo_batch_results *out) {
+    return cgo_minimize_batch_lbfgs_obj_ex(ctx, model, batch, x0, params, n_params, scalars, cfg, ls, slice_iters, nullptr, out, nullptr);
+}
+
+// the model's program of the LDS tier (k_batch_lbfgs_lds<UserObjective, …>, cgo_rtc_batch_lbfgs_lds.hip): compiled on the first use of the tier
+static int batch_lbfgs_lds_program(cgo_objective *model) {
+    std::string log;
+    if (int rc = rtc_compile_batch_lbfgs_lds(*model->o.rtc, log)) { set_error("user objective: the program of the batched L-BFGS solves' LDS tier did not compile:\n" + log); return rc; }
+    return CGO_OK;
+}
+
+int64_t cgo_batch_lbfgs_max_n_obj_ex(cgo_objective *model, int32_t m, const cgo_batch_policy *policy) {
+    try {
+        int rows = 0;
+        if (batch_lbfgs_rows_asked(policy, rows)) return 0;
+        if (m < 1 || m > QN_MAX_M) return 0;
+        if (rows != CGO_BATCH_ROWS_LDS) return cgo_batch_lbfgs_max_n_obj(model);   // (nothing is compiled for the answer)
+        if (!model || model->o.kind != CGO_OBJ_USER || !model->o.rtc || !batch_model_whole(model)) return 0;
+        if (batch_lbfgs_lds_program(model)) return 0;   // (as cgo_batch_max_n_obj compiles the batch program: the limit follows from the kernel's static LDS)
+        return HipBackend::batch_lbfgs_lds_max_ld(model->o.ctx, CGO_OBJ_USER, m, model->o.rtc.get());
+    } catch (...) { return 0; }
+}
+
+int cgo_minimize_batch_lbfgs_obj_ex(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *x0, const double *const *params,
+                                    int32_t n_params, const double *scalars, const cgo_cg_config *cfg, const cgo_ls_config *ls,
+                                    int64_t slice_iters, const cgo_batch_policy *policy, cgo_batch_results *out, int32_t *rows_used) {
     API_GUARD_BEGIN
     REQUIRE(ctx && model && x0 && cfg && ls && out, "null argument");
     out->launches = 0; out->handed_back = 0;
+    int rows = 0;
+    if (int rc = batch_lbfgs_rows_asked(policy, rows)) return rc;
     if (int rc = check_batch_model(ctx, model)) return rc;
     const int64_t n = model->o.n_local;
     if (int rc = check_batch_lbfgs_call(ctx, cfg, ls, n, batch, slice_iters, "cgo_minimize_batch_obj")) return rc;
@@ -1409,16 +1498,23 @@ int cgo_minimize_batch_lbfgs_obj(cgo_ctx *ctx, cgo_objective *model, int64_t bat
         for (int64_t b = 0; b < batch; ++b)
             if (!std::isfinite(scalars[b])) { set_error("batched L-BFGS solves: scalars[" + std::to_string(b) + "] is not finite"); return CGO_EINVAL; }
     const int m = cfg->beta.lbfgs_m, K = model->o.nparams();
+    bool lds = false;
+    if (rows != CGO_BATCH_ROWS_DEVICE && (rows == CGO_BATCH_ROWS_LDS || kBatchLbfgsAutoTakesLds)) {   // the tier's program: its static LDS decides the limit
+        HIPCHK2(hipSetDevice(ctx->c.device));
+        if (int rc = batch_lbfgs_lds_program(model)) return rc;
+        if (int rc = batch_lbfgs_tier(rows, n, HipBackend::batch_lbfgs_lds_max_ld(&ctx->c, CGO_OBJ_USER, m, model->o.rtc.get()), lds)) return rc;
+    }
     if (int rc = batch_lbfgs_sizes_of(ctx, cgo_batch_lbfgs_max_n_obj(model), "cgo_batch_lbfgs_max_n_obj", K, n, batch, m)) return rc;
-    {   // the model's batched L-BFGS program: compiled on the first such solve on its module
+    if (!lds) {   // the model's batched L-BFGS program: compiled on the first such solve on its module
         std::string log;
         if (int rc = rtc_compile_batch_lbfgs(*model->o.rtc, log)) { set_error("user objective: the batched L-BFGS program did not compile:\n" + log); return rc; }
     }
+    if (rows_used) *rows_used = lds ? CGO_BATCH_ROWS_LDS : CGO_BATCH_ROWS_DEVICE;
     HipObjective cat;
     if (int rc = batch_model_cat_rows(ctx, model, batch, cat)) return rc;
     HipBackend be(&ctx->c, &cat);
     if (int rc = batch_backend_on(ctx, cat, n, batch, params, be, true)) return rc;
-    if (int rc = be.batch_lbfgs_alloc(m)) return rc;
+    if (int rc = be.batch_lbfgs_alloc(m, lds)) return rc;
     return batch_solve_on(ctx, be, n, batch, x0, scalars, nullptr, cfg, ls, slice_iters, out, batch_model_hobj(ctx, model), true, params, K);
     API_GUARD_END
 }
@@ -1513,7 +1609,7 @@ int cgo_batch_probe(cgo_ctx *ctx, cgo_batch_probe_args *p) {
     API_GUARD_BEGIN
     REQUIRE(ctx && p, "null argument");
     p->points = 0; p->ld = 0; p->symbol[0] = 0;
-    REQUIRE(p->tier >= 0 && p->tier <= 2, "batch probe: tier must be 0 (LDS), 1 (device rows) or 2 (L-BFGS)");
+    REQUIRE(p->tier >= 0 && p->tier <= 3, "batch probe: tier must be 0 (LDS), 1 (device rows), 2 (L-BFGS) or 3 (L-BFGS in LDS)");
     REQUIRE(p->npass >= 1 && p->npass <= CGO_BATCH_PROBE_MAX_PASSES, "batch probe: 1 … 32 passes");
     REQUIRE(ctx->c.world() == 1, "batch probe: a multi-rank context is not supported (one rank only)");
     REQUIRE(p->batch >= 1 && p->batch <= 0x7FFFFFFF, "batch probe: 1 ≤ batch ≤ the largest grid");
@@ -1524,7 +1620,7 @@ int cgo_batch_probe(cgo_ctx *ctx, cgo_batch_probe_args *p) {
     HipObjective cat;
     int64_t n = p->n;
     if (p->model) {
-        REQUIRE(p->tier != 2, "batch probe: the batched L-BFGS kernel of a run-time compiled objective has no PROBE twin (tiers 0 and 1)");
+        REQUIRE(p->tier < 2, "batch probe: the batched L-BFGS kernels of a run-time compiled objective have no PROBE twin (tiers 0 and 1)");
         if (int rc = check_batch_model(ctx, p->model)) return rc;
         n = p->model->o.n_local;
         REQUIRE(p->n == n, "batch probe: n is not the size of the model objective");
@@ -1542,9 +1638,10 @@ int cgo_batch_probe(cgo_ctx *ctx, cgo_batch_probe_args *p) {
         if (obj_kind == CGO_OBJ_BOOTH) REQUIRE(n == 2, "batch probe: Booth is 2-dimensional (n = 2)");
         if (obj_kind == CGO_OBJ_QUAD_DIAG) REQUIRE(p->params[0], "batch probe: the quadratic needs params[0], the [batch*n] rows of D");
         HIPCHK2(hipSetDevice(ctx->c.device));
-        if (p->tier == 2) {
+        if (p->tier >= 2) {
             REQUIRE(p->m >= 1, "batch probe: m must be ≥ 1");
             if (p->m > QN_MAX_M) { set_error("batch probe: m = " + std::to_string(p->m) + " exceeds cgo_batch_lbfgs_max_m = " + std::to_string(QN_MAX_M)); return CGO_EINVAL; }
+            if (p->tier == 3) { bool lds = false; if (int rc = batch_lbfgs_tier(CGO_BATCH_ROWS_LDS, n, batch_lbfgs_lds_max_n(ctx, obj_kind, p->m), lds)) return rc; }
             if (int rc = batch_lbfgs_sizes(ctx, obj_kind, n, batch, p->m)) return rc;
             device_rows = true;
         } else {
@@ -1556,7 +1653,7 @@ int cgo_batch_probe(cgo_ctx *ctx, cgo_batch_probe_args *p) {
     }
     HipBackend be(&ctx->c, &cat);
     if (int rc = batch_backend_on(ctx, cat, n, batch, p->params, be, device_rows)) return rc;
-    if (p->tier == 2) { if (int rc = be.batch_lbfgs_alloc(p->m)) return rc; }
+    if (p->tier >= 2) { if (int rc = be.batch_lbfgs_alloc(p->m, p->tier == 3)) return rc; }
     return be.batch_probe(*p);
     API_GUARD_END
 }

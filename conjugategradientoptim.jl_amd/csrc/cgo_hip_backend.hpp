@@ -187,13 +187,23 @@ class HipBackend : public VecBackend {
     // allocated with device_rows gets a ring of 2(m+1) rows and a QnState per problem beside its rows; batch_launch then runs
     // k_batch_lbfgs.  batch_lbfgs_reset after every batch_reset: every problem's ring empty.  A run-time compiled objective runs
     // the kernel of its module's batched L-BFGS program (cgo_rtc_batch_lbfgs.hip), which the caller compiles first.
-    int batch_lbfgs_alloc(int m);
+    int batch_lbfgs_alloc(int m, bool lds = false);
     int batch_lbfgs_reset();
     static int64_t batch_lbfgs_max_n();        // the limit of the pass index on n
     static int batch_lbfgs_unroll();           // pairs per lane and trip of the two ring passes
     static int batch_lbfgs_unroll_for(int nparams);   // … for an objective of that many parameter slots (run-time compiled ones)
     static int batch_lbfgs_block();            // lanes of the workgroup
     static double batch_lbfgs_bytes(int64_t batch, int64_t n, int nparams, int m);   // device bytes a batch of that shape asks for
+    // … with the problem's rows and ring in LDS during a launch (cgo_backend_batch_lbfgs_lds.hip; k_batch_lbfgs_lds,
+    // cgo_kernels_batch_lbfgs_lds.hip.hpp): batch_lbfgs_alloc(m, true) — the same allocation, the launches take
+    // 8 · ld · batch_lbfgs_lds_rows(K, m) bytes of dynamic LDS.  A run-time compiled objective runs the kernel of its module's
+    // program of this tier (cgo_rtc_batch_lbfgs_lds.hip), which the caller compiles first.
+    static int batch_lbfgs_lds_rows(int nparams, int m);        // 2 + K + 2(m+1); 0: K or m out of range
+    static int batch_lbfgs_lds_unroll_for(int nparams);         // pairs per lane and trip of the two ring passes over LDS
+    static int64_t batch_lbfgs_lds_ld_of(int64_t max_lds, int64_t static_lds, int rows);   // the size arithmetic alone
+    // largest ld (even) one workgroup's LDS holds of a problem's rows and ring; 0: none.  CGO_OBJ_USER: `rtc` with that program
+    static int64_t batch_lbfgs_lds_max_ld(HipCtx *ctx, int obj_kind, int m, const RtcModule *rtc = nullptr);
+    bool batch_lbfgs_in_lds() const { return bat_qn_lds_; }
     // Test entry point (cgo_batch_probe, cgo_backend_batch_probe.hip): a script of passes in ONE launch of the PROBE twin of this
     // batch's kernel, on host vectors; the batch is one batch_alloc (and batch_lbfgs_alloc) made, the launch arguments are
     // batch_fill_params' / batch_lbfgs_fill_params'.  Every buffer of the batch gets NaN slack: a probed batch is for probing only.
@@ -455,6 +465,9 @@ class HipBackend : public VecBackend {
     double *bat_S_ = nullptr, *bat_Y_ = nullptr;   // device [batch][m+1][ld]
     QnState *bat_qn_ = nullptr;             // device [batch]
     int batch_lbfgs_launch(const ResConfig &c, int64_t budget, std::vector<ResState> &st, std::vector<double> &f_x0);
+    bool bat_qn_lds_ = false;                // … whose launches keep the rows and the ring in LDS (batch_lbfgs_lds_on)
+    int batch_lbfgs_lds_on();
+    int batch_lbfgs_lds_launch(const dev::BatchLbfgsParams &L);
     bool prof_on_ = false;
     struct ProfSlot { hipEvent_t e0 = nullptr, e1 = nullptr; int kk = -1; double bytes = 0; };
     std::vector<ProfSlot> ring_;

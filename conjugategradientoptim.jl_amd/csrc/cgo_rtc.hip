@@ -30,6 +30,7 @@ RtcModule::~RtcModule() {
     if (rows_mod) (void)hipModuleUnload(rows_mod);
     if (batch_probe_mod) (void)hipModuleUnload(batch_probe_mod);
     if (batch_lbfgs_mod) (void)hipModuleUnload(batch_lbfgs_mod);
+    if (batch_lbfgs_lds_mod) (void)hipModuleUnload(batch_lbfgs_lds_mod);
 }
 
 static std::string key_cg(int mode, int npts, bool big) {

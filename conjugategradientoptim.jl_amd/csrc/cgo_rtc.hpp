@@ -41,6 +41,10 @@ struct RtcModule {
     // solve with a scalar per problem does not compile the LDS tier's batch program: batch_grad() finds either.
     hipFunction_t batch_lbfgs(int npts) const;
     hipModule_t batch_lbfgs_mod = nullptr;
+    // … and of their LDS tier (cgo_rtc_batch_lbfgs_lds.hip): one more program, holding k_batch_lbfgs_lds alone, compiled on the
+    // first solve of that tier on the objective (rtc_compile_batch_lbfgs_lds)
+    hipFunction_t batch_lbfgs_lds(int npts) const;
+    hipModule_t batch_lbfgs_lds_mod = nullptr;
     std::string user_source;
     int n_params = 0;   // parameter slots the objective was created with (0 … CGO_MAX_PARAM_SLOTS)
     int device = 0;
@@ -64,6 +68,8 @@ int rtc_compile_batch_rows(RtcModule &m, std::string &log);
 int rtc_compile_batch_probe(RtcModule &m, std::string &log);
 // the batched L-BFGS kernel for the module's objective, one per row of CGO_BATCH_LBFGS_ROWS, and k_batch_grad, likewise
 int rtc_compile_batch_lbfgs(RtcModule &m, std::string &log);
+// the kernel of the batched L-BFGS solves' LDS tier for the module's objective, one per row of CGO_BATCH_LBFGS_LDS_ROWS, likewise
+int rtc_compile_batch_lbfgs_lds(RtcModule &m, std::string &log);
 
 // What a further program of a module is built from (cgo_rtc.hip): the embedded kernel templates + the user's objective as one
 // translation unit, and one program → one loaded module: compiles `src` for the name expressions of `wants`, loads the code

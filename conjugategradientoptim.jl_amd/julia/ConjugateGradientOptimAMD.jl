@@ -650,10 +650,25 @@ batch_close(handle::Ptr{Cvoid}) = check(ccall((:cgo_batch_close, libcgo), Cint, 
 # ---- batched solves with β = LBFGS(m), m ≤ 10 (cgo_minimize_batch_lbfgs, include/cgo.h) ------------------------------
 # kind: CGO_OBJ_QUAD_DIAG (0, D = the n × batch matrix of diagonals), CGO_OBJ_ROSENBROCK_PAIRED (1), CGO_OBJ_BOOTH (2).  The ring of
 # 2(m+1) rows per problem lives in device memory; a problem the device loop does not finish is solved again from its own x0.
+# rows: :device (the default — exactly the call without a policy), :lds (a workgroup keeps its problem's rows and ring in LDS during
+# a launch: n ≤ batch_lbfgs_max_n(kind, m, :lds), same bits) or :auto (device rows at every n: include/cgo.h has the rule).  `out` as above.
+batch_lbfgs_policy(rows::Symbol) = (haskey(BATCH_ROWS, rows) || throw(ArgumentError("rows must be :device, :lds or :auto"));
+                                    Ref(CBatchPolicy(Int32(sizeof(CBatchPolicy)), BATCH_ROWS[rows], ntuple(_ -> Int32(0), 6))))
 function minimizeobjectivebatch_lbfgs(out::CBatchResults, kind::Integer, x0::Matrix{Float64}, config::CGConfig, linesearch_config::LineSearchConfig;
-                                       D::Union{Nothing,Matrix{Float64}} = nothing, ctx::Context = defaultcontext(), slice_iters::Integer = 0)
+                                       D::Union{Nothing,Matrix{Float64}} = nothing, ctx::Context = defaultcontext(), slice_iters::Integer = 0,
+                                       rows::Symbol = :device)
     n, batch = size(x0)
     d = D === nothing ? Ptr{Float64}(C_NULL) : pointer(D)
+    if rows != :device
+        pol, used = batch_lbfgs_policy(rows), Ref{Int32}(BATCH_ROWS[:device])
+        GC.@preserve x0 D begin
+            check(ccall((:cgo_minimize_batch_lbfgs_ex, libcgo), Cint,
+                        (Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ref{CCGConfig}, Ref{CLSConfig}, Int64, Ref{CBatchPolicy},
+                         Ref{CBatchResults}, Ref{Int32}),
+                        ctx.h, kind, n, batch, x0, d, ccfg(config), cls(linesearch_config), slice_iters, pol, out, used))
+        end
+        return out
+    end
     GC.@preserve x0 D begin
         check(ccall((:cgo_minimize_batch_lbfgs, libcgo), Cint,
                     (Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ref{CCGConfig}, Ref{CLSConfig}, Int64, Ref{CBatchResults}),
@@ -663,17 +678,38 @@ function minimizeobjectivebatch_lbfgs(out::CBatchResults, kind::Integer, x0::Mat
 end
 batch_lbfgs_max_n(kind::Integer; ctx::Context = defaultcontext()) =
     ccall((:cgo_batch_lbfgs_max_n, libcgo), Int64, (Ptr{Cvoid}, Int32), ctx.h, kind)
+# … under rows (:lds: what one workgroup's LDS holds for ring depth m; :device, :auto: the pass-index limit)
+batch_lbfgs_max_n(kind::Integer, m::Integer, rows::Symbol; ctx::Context = defaultcontext()) =
+    ccall((:cgo_batch_lbfgs_max_n_ex, libcgo), Int64, (Ptr{Cvoid}, Int32, Int32, Ref{CBatchPolicy}), ctx.h, kind, m, batch_lbfgs_policy(rows))
+batch_lbfgs_lds_rows(n_params::Integer, m::Integer) = Int(ccall((:cgo_batch_lbfgs_lds_rows, libcgo), Int32, (Int32, Int32), n_params, m))
+function batch_lbfgs_lds_shape(n_params::Integer)
+    blk, u = Ref{Int32}(0), Ref{Int32}(0)
+    ccall((:cgo_batch_lbfgs_lds_shape, libcgo), Cvoid, (Int32, Ref{Int32}, Ref{Int32}), n_params, blk, u)
+    return Int(blk[]), Int(u[])
+end
 # … on a run-time compiled objective (cgo_minimize_batch_lbfgs_obj): `model` and `params` as batch_open takes them (n × batch
 # matrices, one per parameter slot), `scalars` every problem's own s0 (nothing: the model's).  The first call on a compiled
-# source compiles its batched L-BFGS program.  No handle, `active` mask, barrier method or LDS tier on L-BFGS.
+# source compiles its batched L-BFGS program.  rows as above (:lds compiles one more program of the source, on its first use).
+# No handle, `active` mask or barrier method on L-BFGS.
 function minimizeobjectivebatch_lbfgs_obj(out::CBatchResults, model::DeviceObjective, x0::Matrix{Float64}, config::CGConfig,
                                            linesearch_config::LineSearchConfig; params::Vector{Matrix{Float64}} = Matrix{Float64}[],
-                                           scalars::Union{Nothing,Vector{Float64}} = nothing, slice_iters::Integer = 0)
+                                           scalars::Union{Nothing,Vector{Float64}} = nothing, slice_iters::Integer = 0,
+                                           rows::Symbol = :device)
     n, batch = size(x0)
     all(size(p) == (n, batch) for p in params) || throw(ArgumentError("every params[j] must have the size of x0"))
     scalars === nothing || length(scalars) == batch || throw(ArgumentError("scalars must have one entry per problem"))
     prows = Ptr{Float64}[pointer(p) for p in params]
     s = scalars === nothing ? Ptr{Float64}(C_NULL) : pointer(scalars)
+    if rows != :device
+        pol, used = batch_lbfgs_policy(rows), Ref{Int32}(BATCH_ROWS[:device])
+        GC.@preserve x0 params scalars begin
+            check(ccall((:cgo_minimize_batch_lbfgs_obj_ex, libcgo), Cint,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Ptr{Float64}}, Int32, Ptr{Float64}, Ref{CCGConfig}, Ref{CLSConfig}, Int64,
+                         Ref{CBatchPolicy}, Ref{CBatchResults}, Ref{Int32}),
+                        model.ctx.h, model.h, batch, x0, prows, length(params), s, ccfg(config), cls(linesearch_config), slice_iters, pol, out, used))
+        end
+        return out
+    end
     GC.@preserve x0 params scalars begin
         check(ccall((:cgo_minimize_batch_lbfgs_obj, libcgo), Cint,
                     (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Ptr{Float64}}, Int32, Ptr{Float64}, Ref{CCGConfig}, Ref{CLSConfig}, Int64,
@@ -683,6 +719,8 @@ function minimizeobjectivebatch_lbfgs_obj(out::CBatchResults, model::DeviceObjec
     return out
 end
 batch_lbfgs_max_n_obj(model::DeviceObjective) = ccall((:cgo_batch_lbfgs_max_n_obj, libcgo), Int64, (Ptr{Cvoid},), model.h)
+batch_lbfgs_max_n_obj(model::DeviceObjective, m::Integer, rows::Symbol) =
+    ccall((:cgo_batch_lbfgs_max_n_obj_ex, libcgo), Int64, (Ptr{Cvoid}, Int32, Ref{CBatchPolicy}), model.h, m, batch_lbfgs_policy(rows))
 function batch_lbfgs_shape_obj(n_params::Integer)
     blk, u = Ref{Int32}(0), Ref{Int32}(0)
     ccall((:cgo_batch_lbfgs_shape_obj, libcgo), Cvoid, (Int32, Ref{Int32}, Ref{Int32}), n_params, blk, u)

@@ -13,7 +13,9 @@ Times three things in one process — medians of REPS repetitions after one unti
     the loop it replaces: minimizeobjective called 256 times with the same config;
     the existing batched Polak–Ribière solve of the same problems to the same ϵ (minimizeobjectivebatch).
 
-    python examples/batch_lbfgs.py [max_iters] [once]      # needs an MI355X; `once`: the batched call alone, one run (for a kernel trace)
+    python examples/batch_lbfgs.py [max_iters] [once] [--rows device|lds|auto] [--batch-only] [--m M] [--n N]
+    # needs an MI355X; `once`: the batched call alone, one run (for a kernel trace); --rows lds: the problem's rows and ring in LDS
+    # during a launch (k_batch_lbfgs_lds; n ≤ batch_lbfgs_max_n(kind, m=M, rows="lds"), e.g. --m 3 --n 1800), same bits
 """
 import os
 import sys
@@ -25,6 +27,22 @@ import numpy as np
 import cgo_amd as cgo
 
 N, BATCH, REPS, M = 1000, 256, 7, 5
+
+
+def option(name, default):
+    """--name value, taken out of sys.argv"""
+    if name in sys.argv:
+        i = sys.argv.index(name)
+        v = sys.argv[i + 1]
+        del sys.argv[i:i + 2]
+        return v
+    return default
+
+
+ROWS, M, N = option("--rows", "device"), int(option("--m", M)), int(option("--n", N))
+BATCH_ONLY = "--batch-only" in sys.argv      # (the batched call's timing alone, without the loop it replaces)
+if BATCH_ONLY:
+    sys.argv.remove("--batch-only")
 max_iters = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
 config = cgo.setupCGConfig(1e-5, cgo.LBFGS(M), cgo.EnableTrace(), max_iters=max_iters)
 config_pr = cgo.setupCGConfig(1e-5, cgo.PolakRibiere(), cgo.EnableTrace(), max_iters=max_iters)
@@ -51,14 +69,17 @@ def report(name, t, rets):
 
 
 if len(sys.argv) > 2 and sys.argv[2] == "once":
-    rets = cgo.minimizeobjectivebatch_lbfgs("rosenbrock_paired", X0, config, ls)
-    print(f"one batched call: {rets.launches} launch(es), {rets.handed_back} handed back, {sum(r.iters_ran for r in rets)} iterations")
+    rets = cgo.minimizeobjectivebatch_lbfgs("rosenbrock_paired", X0, config, ls, rows=ROWS)
+    print(f"one batched call (rows in {rets.rows}): {rets.launches} launch(es), {rets.handed_back} handed back, {sum(r.iters_ran for r in rets)} iterations")
     sys.exit(0)
 
-tb = timed(lambda: cgo.minimizeobjectivebatch_lbfgs("rosenbrock_paired", X0, config, ls))
+tb = timed(lambda: cgo.minimizeobjectivebatch_lbfgs("rosenbrock_paired", X0, config, ls, rows=ROWS))
 rets = tb[3]
-report(f"batched LBFGS({M}), {BATCH} problems", tb, rets)
-print(f"    {rets.launches} launch(es), {rets.handed_back} handed back to the host engine")
+report(f"batched LBFGS({M}), {BATCH} problems of n = {N}, rows in {rets.rows}", tb, rets)
+print(f"    {rets.launches} launch(es), {rets.handed_back} handed back to the host engine; largest n with the rows and the ring in LDS for m = {M}: "
+      f"{cgo.batch_lbfgs_max_n('rosenbrock_paired', m=M, rows='lds')}")
+if BATCH_ONLY:
+    sys.exit(0)
 
 obj = cgo.RosenbrockPaired(N)
 tl = timed(lambda: [cgo.minimizeobjective(obj, x0, config, ls) for x0 in X0], reps=3)

@@ -20,7 +20,9 @@ Part 2 sweeps a regularisation strength PER PROBLEM through `scalars`: the same 
 
     f_b(x) = Σ_i w_bi (sqrt(1 + (x_i − y_bi)²) − 1) + ½ λ_b x_i²             (λ_b = s0 of problem b)
 
-    python examples/batch_lbfgs_fit.py [max_iters] [once]   # needs an MI355X; `once`: the batched call alone, one run (for a kernel trace)
+    python examples/batch_lbfgs_fit.py [max_iters] [once] [--rows device|lds|auto] [--batch-only]
+    # needs an MI355X; `once`: the batched call alone, one run (for a kernel trace); --rows lds: the problem's rows and ring in LDS
+    # during a launch (k_batch_lbfgs_lds<UserObjective, 3>, one more program of the source), same bits
 """
 import os
 import sys
@@ -34,6 +36,14 @@ import cgo_amd as cgo
 N, BATCH, REPS, M = 1000, 256, 7, 5
 BODY = "const double d = x - p1; const double r = __builtin_sqrt(1.0 + d*d); gi = p*(d/r); fi = p*(r - 1.0);"
 RIDGE = "const double d = x - p1; const double r = __builtin_sqrt(1.0 + d*d); gi = p*(d/r) + s0*x; fi = p*(r - 1.0) + 0.5*((s0*x)*x);"
+ROWS = "device"
+if "--rows" in sys.argv:
+    i = sys.argv.index("--rows")
+    ROWS = sys.argv[i + 1]
+    del sys.argv[i:i + 2]
+BATCH_ONLY = "--batch-only" in sys.argv      # (the batched call's timing alone, without the loop it replaces)
+if BATCH_ONLY:
+    sys.argv.remove("--batch-only")
 max_iters = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
 config = cgo.setupCGConfig(1e-5, cgo.LBFGS(M), cgo.EnableTrace(), max_iters=max_iters)
 ls = cgo.setupStrongWolfeBisection(1e-5, 0.5)
@@ -65,21 +75,24 @@ t = time.perf_counter()
 model = cgo.ElementwiseObjective(N, BODY, param=[None, None])
 t_create = time.perf_counter() - t
 t = time.perf_counter()
-rets = cgo.minimizeobjectivebatch_lbfgs_obj(model, X0, config, ls, params=[W, Y])   # the first such call on the source: compiles its program
+rets = cgo.minimizeobjectivebatch_lbfgs_obj(model, X0, config, ls, params=[W, Y], rows=ROWS)   # the first such call on the source: compiles its program
 t_first = time.perf_counter() - t
 print(f"creating the objective (every kernel of a single solve): {t_create:.2f} s; the first batched L-BFGS call, which compiles the program once "
       f"per source: {t_first:.2f} s; pairs per lane and trip with two slots: {cgo.batch_lbfgs_shape_obj(2)[1]}")
 if len(sys.argv) > 2 and sys.argv[2] == "once":
-    rets = cgo.minimizeobjectivebatch_lbfgs_obj(model, X0, config, ls, params=[W, Y])
-    print(f"one batched call: {rets.launches} launch(es), {rets.handed_back} handed back, {sum(r.iters_ran for r in rets)} iterations")
+    rets = cgo.minimizeobjectivebatch_lbfgs_obj(model, X0, config, ls, params=[W, Y], rows=ROWS)
+    print(f"one batched call (rows in {rets.rows}): {rets.launches} launch(es), {rets.handed_back} handed back, {sum(r.iters_ran for r in rets)} iterations")
     model.close()
     sys.exit(0)
 
 # ---- part 1: the batch against the loop of single solves ---------------------------------------------------------------------
-tb = timed(lambda: cgo.minimizeobjectivebatch_lbfgs_obj(model, X0, config, ls, params=[W, Y]))
+tb = timed(lambda: cgo.minimizeobjectivebatch_lbfgs_obj(model, X0, config, ls, params=[W, Y], rows=ROWS))
 rets = tb[3]
-report(f"batched LBFGS({M}), {BATCH} fits", tb, rets)
+report(f"batched LBFGS({M}), {BATCH} fits, rows in {rets.rows}", tb, rets)
 print(f"    {rets.launches} launch(es), {rets.handed_back} handed back to the host engine")
+if BATCH_ONLY:
+    model.close()
+    sys.exit(0)
 
 
 def loop():
@@ -106,9 +119,9 @@ idx = np.repeat(np.arange(SETS), len(LAMBDAS))            # problem b fits data 
 lam = np.tile(LAMBDAS, SETS)
 ridge = cgo.ElementwiseObjective(N, RIDGE, param=[None, None])
 t = time.perf_counter()
-sweep = cgo.minimizeobjectivebatch_lbfgs_obj(ridge, X0[idx], config, ls, params=[W[idx], Y[idx]], scalars=lam)
+sweep = cgo.minimizeobjectivebatch_lbfgs_obj(ridge, X0[idx], config, ls, params=[W[idx], Y[idx]], scalars=lam, rows=ROWS)
 t_first = time.perf_counter() - t
-ts = timed(lambda: cgo.minimizeobjectivebatch_lbfgs_obj(ridge, X0[idx], config, ls, params=[W[idx], Y[idx]], scalars=lam))
+ts = timed(lambda: cgo.minimizeobjectivebatch_lbfgs_obj(ridge, X0[idx], config, ls, params=[W[idx], Y[idx]], scalars=lam, rows=ROWS))
 report(f"{SETS} data sets × {len(LAMBDAS)} strengths in one call (first call {t_first:.2f} s)", ts, ts[3])
 print(f"    {ts[3].launches} launch(es), {ts[3].handed_back} handed back")
 for j, l in enumerate(LAMBDAS):

@@ -628,14 +628,49 @@ void cgo_batch_lbfgs_shape(int32_t *block, int32_t *pairs_per_trip);            
  * context, sharded or multi-rank; n_params other than the model's; a null params[j]), what cgo_minimize_batch_lbfgs refuses of a
  * config (a CG flavour or the Broyden family — those: cgo_minimize_batch_obj —, m > 10, Backtracking, a multi-rank context,
  * batch < 1), a scalars[b] that is not finite, n > cgo_batch_lbfgs_max_n_obj.
- * Not built: the cgo_batch handle and its `active` mask, the batched barrier method and an LDS tier on L-BFGS, and PROBE twins
- * of this kernel (cgo_batch_probe's tier 2 stays the built-in objectives'). */
+ * Not built: the cgo_batch handle and its `active` mask and the batched barrier method on L-BFGS, and PROBE twins
+ * of this kernel (cgo_batch_probe's tiers 2 and 3 stay the built-in objectives'). */
 int cgo_minimize_batch_lbfgs_obj(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *x0 /* [batch*n] */,
                                  const double *const *params /* n_params × [batch*n] */, int32_t n_params,
                                  const double *scalars /* [batch] or NULL: the model's s0 for all */,
                                  const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out);
 int64_t cgo_batch_lbfgs_max_n_obj(cgo_objective *model);        /* the pass-index limit; 0: none; compiles nothing */
 void cgo_batch_lbfgs_shape_obj(int32_t n_params, int32_t *block, int32_t *pairs_per_trip);   /* needs no device */
+/* AN LDS TIER FOR BATCHED L-BFGS: the two calls above with a cgo_batch_policy and rows_used.  Under CGO_BATCH_ROWS_LDS a
+ * workgroup keeps its problem's x, u, parameter slots AND ring in LDS during a launch (k_batch_lbfgs_lds) —
+ * cgo_batch_lbfgs_lds_rows(K, m) = 2 + K + 2(m+1) rows of n + n%2 doubles, loaded at entry (the ring: the stored pairs only) and
+ * written back at exit if an iteration completed (the ring: the slots a push of that launch wrote).  Device memory is allocated
+ * exactly as above, the ring included: launches resume from it.  Every number returned has the BITS of the device tier: the same
+ * per-pair expressions, every lane's pairs in the same order into the same sums, the same reduction.
+ * THE POLICY RULE DIFFERS FROM THE CG _ex CALLS ON PURPOSE, because the call these extend runs on device rows:
+ *   NULL, CGO_BATCH_ROWS_DEVICE  the call it extends (k_batch_lbfgs), refusals included;
+ *   CGO_BATCH_ROWS_LDS           the LDS tier; n above what one workgroup's LDS holds for this m and slot count is CGO_EINVAL,
+ *                                with cgo_batch_lbfgs_max_n_ex and its value in the message;
+ *   CGO_BATCH_ROWS_AUTO          DEVICE ROWS, at every n.  The rule: AUTO takes "LDS where n fits for this m and slot count" only
+ *                                if the LDS tier's summed kernel time is below the device tier's by more than the device tier's
+ *                                own run-to-run spread at EVERY measured shape.  It is at n = 1800, m = 3 (4.54 against 5.06 ms)
+ *                                and on a two-slot objective at n = 1000, m = 5 (0.47 against 0.53 ms per launch), but not on
+ *                                paired Rosenbrock at n = 1000, m = 5 (4.10 … 4.13 against 4.13 … 4.18 ms: inside the spread),
+ *                                so the tier is reached by asking for it;
+ *   any other value              CGO_EINVAL.
+ * rows_used (may be NULL): CGO_BATCH_ROWS_LDS or CGO_BATCH_ROWS_DEVICE, the tier that ran.  For a run-time compiled objective
+ * the LDS tier's kernel is one more program of the module (k_batch_lbfgs_lds<UserObjective, 3> alone), compiled on the first
+ * solve of this tier on that module. */
+int cgo_minimize_batch_lbfgs_ex(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
+                                const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters,
+                                const cgo_batch_policy *policy, cgo_batch_results *out, int32_t *rows_used);
+int cgo_minimize_batch_lbfgs_obj_ex(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *x0,
+                                    const double *const *params, int32_t n_params, const double *scalars,
+                                    const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters,
+                                    const cgo_batch_policy *policy, cgo_batch_results *out, int32_t *rows_used);
+/* largest n under `policy` for ring depth m: LDS — what one workgroup's LDS holds (the device's bytes per block minus the kernel's
+ * static LDS and 512 bytes of slack, over 8 · cgo_batch_lbfgs_lds_rows, down to even); DEVICE, AUTO, NULL — the pass-index limit.
+ * 0: no context, kind or model, or m outside 1 … 10.  The _obj form under LDS compiles the module's program of the tier if it
+ * is not there, as cgo_batch_max_n_obj compiles the batch program; under the other policies it compiles nothing. */
+int64_t cgo_batch_lbfgs_max_n_ex(cgo_ctx *ctx, int32_t obj_kind, int32_t m, const cgo_batch_policy *policy);
+int64_t cgo_batch_lbfgs_max_n_obj_ex(cgo_objective *model, int32_t m, const cgo_batch_policy *policy);
+int32_t cgo_batch_lbfgs_lds_rows(int32_t n_params, int32_t m);   /* 2 + K + 2(m+1); 0 for K outside 0 … 4 or m outside 1 … 10; needs no device */
+void cgo_batch_lbfgs_lds_shape(int32_t n_params, int32_t *block, int32_t *pairs_per_trip);   /* of the two ring passes over LDS; needs no device */
 /* A scripted sequence of passes of a BATCHED solve in ONE launch, a workgroup per problem, on host vectors — for tests that check
  * every slot of every pass in EVERY workgroup (tests/test_batch_kernel_sums.py).  The batch is allocated as a solve allocates it
  * and the launch arguments are filled by the code that fills them for a solve (ld, the slot pointers, s0 / s0v, the ring stride,
@@ -643,19 +678,20 @@ void cgo_batch_lbfgs_shape_obj(int32_t n_params, int32_t *block, int32_t *pairs_
  * (res_iterate / res_iterate_qn) it runs pass[0..npass) through the member functions that loop calls —
  *   tier 0  k_batch        rows in LDS                 tier 1  k_batch_rows   rows streamed from device memory
  *   tier 2  k_batch_lbfgs  tier 1 with the ring S, Y [batch][m+1][ld] and a quasi-Newton state per problem
- *   kind 0  trial(a, k, out)                              1 ≤ k ≤ 3                     tiers 0, 1, 2
+ *   tier 3  k_batch_lbfgs_lds  tier 2 with the rows and the ring in LDS during the launch: same inputs, outputs and kinds
+ *   kind 0  trial(a, k, out)                              1 ≤ k ≤ 3                     tiers 0, 1, 2, 3
  *   kind 1  accept_dir_trial(a_acc, beta, a, k, …)        0 ≤ k ≤ 3                     tiers 0, 1
- *   kind 2  pass<R_INIT, 1>                               u = −g, f, g·g                tiers 0, 1, 2
- *   kind 3  push_update(a_acc)                            x ← x + a_acc·u, the pair into the free slot, the scalar recursion   tier 2
- *   kind 4  combine_trial(a, k, …)                        0 ≤ k ≤ 3                     tier 2
+ *   kind 2  pass<R_INIT, 1>                               u = −g, f, g·g                tiers 0, 1, 2, 3
+ *   kind 3  push_update(a_acc)                            x ← x + a_acc·u, the pair into the free slot, the scalar recursion   tiers 2, 3
+ *   kind 4  combine_trial(a, k, …)                        0 ≤ k ≤ 3                     tiers 2, 3
  * — a[k..) repeating a[k − 1] as the loops pad them (done here).  A combine runs on the coefficients the last push of the script
  * left, or (co_set) on count = co_count, γ = co_gamma, co_cy, co_cs, written into the workgroup's coefficient block; a combine
  * with neither is refused.  An accepting pass or a push counts as a completed iteration, so tier 0 writes its rows back as after
  * a slice that completed one; a script without one leaves them alone.
- * In: obj_kind (a built-in kind; tiers 0, 1, 2) or model (a run-time compiled objective, obj_kind = CGO_OBJ_USER; tiers 0, 1 —
+ * In: obj_kind (a built-in kind; tiers 0, 1, 2, 3) or model (a run-time compiled objective, obj_kind = CGO_OBJ_USER; tiers 0, 1 —
  * its PROBE kernels are one more program of its module, compiled on the first probe); x, u [batch][n]; params[j] [batch][n] for
  * every slot the objective reads; scalars [batch] or NULL (tiers 0, 1; a model only); skip [batch] or NULL — a flagged problem
- * is preset finished (RES_STOP) and its workgroup returns at once; tier 2: m, S and Y [batch][m+1][n] (an absent slot: NaN rows)
+ * is preset finished (RES_STOP) and its workgroup returns at once; tiers 2, 3: m, S and Y [batch][m+1][n] (an absent slot: NaN rows)
  * and qn, every problem's QnState (csrc/cgo_qn.hpp) as cgo_batch_probe_qn_bytes() bytes each — list, count and free_slot are
  * checked against m here, before any of them indexes the ring.
  * Out (each pointer may be NULL): rows [npass][batch][64] — the row every workgroup holds after that pass, out[…].width slots of
