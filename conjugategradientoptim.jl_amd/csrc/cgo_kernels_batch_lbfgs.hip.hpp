@@ -8,6 +8,8 @@
 // scratch memory.  There is no gradient row: g = ∇f(x) is recomputed from the stored x by the same expression, as in the CG family.
 //
 //   * R_INIT and the trial passes are RowsDev's own, unchanged (LbfgsDev derives from it);
+//   * the two ring passes below are written ONCE, as LbfgsRing, for this tier and for the LDS tier
+//     (cgo_kernels_batch_lbfgs_lds.hip.hpp): the tiers differ in where the rows lie, not in a pass's text;
 //   * the PUSH pass, after the line search accepted a step a: per pair g, xp = x + a·u, g⁺ = ∇f(xp), s = a·u, y = g⁺ − g; x ← xp,
 //     s and y into the free slot; 4 + 5c sums (those of k_lbfgs_push_gram) in a 64-slot row.  The loop over the c stored pairs is
 //     unrolled to the compile-time maximum under wave-uniform `j < c` guards, so accumulator indices are compile-time constants
@@ -17,8 +19,8 @@
 //   * the COMBINE pass: u = −γ·g + Σ cy_j·Y_j + Σ cs_j·S_j with g recomputed from the new x; u stored; g·u, u·u and the first
 //     trial points of the next line search (cg_pair's R_TRIAL block: the sums a trial pass would form).
 // Lane tid owns pairs tid, tid + BLOCK, … in every pass and every row, ring rows included, lane 0 the odd tail: a lane only
-// re-reads what it wrote itself, with plain global loads and stores — no fence and no barrier for data.  No atomics, no polling,
-// no read of another problem's rows; every loop is bounded by n, m or the line search's own limits.
+// re-reads what it wrote itself, with plain loads and stores (global here, LDS in the LDS tier) — no fence and no barrier for
+// data.  No atomics, no polling, no read of another problem's rows; every loop is bounded by n, m or the line search's own limits.
 // The streaming loops follow RowsDev::trip: all 16-byte loads of a trip first, whole trips without a guard, the partial trip
 // loading from a clamped in-row index, uniform trip counts.
 // Pairs per lane and trip of the two ring passes: batch_lbfgs_u<Obj>(), a compile-time function of the objective's slot count K —
@@ -57,53 +59,76 @@ struct BatchLbfgsParams {
     long long ring_stride;     // (m+1)·ld: doubles between two problems' rings
 };
 
+// What the ring passes read of a tier's vector-operations object, under one set of names: x_row(), u_row(), slot_ptrs(),
+// scalar().  This is RowsDev's form; the LDS tier's is in its own header.
 template <class Obj, int NPTS>
-struct LbfgsDev : RowsDev<Obj, NPTS> {
+struct LbfgsRows : RowsDev<Obj, NPTS> {
     using R = RowsDev<Obj, NPTS>;
-    double *Sr, *Yr;           // this problem's ring (device memory), slot p at p·ld
-    long long ld;
+    using Objective = Obj;
+    __device__ __forceinline__ LbfgsRows(const R &r) : R(r) {}
+    __device__ __forceinline__ double *x_row() const { return this->xr; }
+    __device__ __forceinline__ double *u_row() const { return this->ur; }
+    __device__ __forceinline__ ParamPtrs slot_ptrs() const { return this->pl; }
+    __device__ __forceinline__ double scalar() const { return this->s0; }
+};
+struct RingPushNone { __device__ __forceinline__ void operator()(int) {} };   // device rows: a push stores straight to the ring
+
+// The two ring passes of BOTH tiers: push_update and combine_trial, once.
+//   Base    the tier's vector-operations object behind the four names above (R_INIT, the trial passes and the zero checks are its own);
+//   Off     the type of a ring offset and of the odd tail's index: long long over device rows, int over LDS — the address
+//           arithmetic is part of the device code, so each tier keeps its own;
+//   U       pairs per lane and trip, from the objective's slot count (each tier passes its own function's value, once);
+//   Pushed  called by a push with the free slot it is about to write.
+// The per-pair expressions, the order of loads, stores and dsum calls, the `j < c` guards and the clamped tail index are the
+// same text for both tiers, so every number of one tier has the bits of the other.
+template <class Base, class Off, int U, class Pushed>
+struct LbfgsRing : Base {
+    using Obj = typename Base::Objective;
+    static constexpr int NPTS = Base::kNpts;
+    double *Sr, *Yr;           // this problem's ring, slot p at p·ld
+    Off ld;
     QnState *q;                // LDS
     QnCoef *co;                // LDS
     double *qsum;              // LDS [QN_SUMS]
+    Pushed pushed;
 
-    __device__ __forceinline__ LbfgsDev(const R &r, double *S, double *Y, long long ld_, QnState *q_, QnCoef *co_, double *qs)
-        : R(r), Sr(S), Yr(Y), ld(ld_), q(q_), co(co_), qsum(qs) {}
+    __device__ __forceinline__ LbfgsRing(const typename Base::R &r, double *S, double *Y, Off ld_, QnState *q_, QnCoef *co_, double *qs)
+        : Base(r), Sr(S), Yr(Y), ld(ld_), q(q_), co(co_), qsum(qs) {}
 
     // ---- push -----------------------------------------------------------------------------------------------------------
     template <bool TAIL>
     __device__ __forceinline__ void push_trip(double a, int c, int i0, double (&acc)[QN_SUMS]) {
-        constexpr int U = batch_lbfgs_u<Obj>();
         d2 xv[U], uv[U], sv[QN_MAX_M][U], yv[QN_MAX_M][U];
         PV<Obj> pv[U];
         int idx[U], il[U];
 #pragma unroll
         for (int t = 0; t < U; ++t) {
             idx[t] = i0 + t * BLOCK + (int)threadIdx.x;
-            il[t] = (TAIL && idx[t] >= this->npairs) ? this->npairs - 1 : idx[t];
-            xv[t] = ldg2<false>(this->xr, il[t]);
-            uv[t] = ldg2<false>(this->ur, il[t]);
-            pv[t] = pv_load<Obj, false>(this->pl, il[t]);
+            il[t] = (TAIL && idx[t] >= this->npairs) ? this->npairs - 1 : idx[t];   // (a lane past the end reads the row's last pair and drops it)
+            xv[t] = ldg2<false>(this->x_row(), il[t]);
+            uv[t] = ldg2<false>(this->u_row(), il[t]);
+            pv[t] = pv_load<Obj, false>(this->slot_ptrs(), il[t]);
         }
 #pragma unroll
         for (int j = 0; j < QN_MAX_M; ++j) {
             if (j < c) {   // (wave-uniform: c is the workgroup's)
-                const long long off = (long long)q->list[j] * ld;
+                const Off off = (Off)q->list[j] * ld;
 #pragma unroll
                 for (int t = 0; t < U; ++t) { sv[j][t] = ldg2<false>(Sr + off, il[t]); yv[j][t] = ldg2<false>(Yr + off, il[t]); }
             }
         }
-        const long long offn = (long long)q->free_slot * ld;
+        const Off offn = (Off)q->free_slot * ld;
 #pragma unroll
         for (int t = 0; t < U; ++t) {
             if (!TAIL || idx[t] < this->npairs) {
                 d2 g, gp, xp, s, y;
                 double f0 = 0.0, f1 = 0.0;
-                obj_eval2<Obj>(xv[t], pv[t], this->s0, f0, g);
+                obj_eval2<Obj>(xv[t], pv[t], this->scalar(), f0, g);
                 s.x = a * uv[t].x; s.y = a * uv[t].y;
                 xp.x = xv[t].x + s.x; xp.y = xv[t].y + s.y;
-                obj_eval2<Obj>(xp, pv[t], this->s0, f1, gp);
+                obj_eval2<Obj>(xp, pv[t], this->scalar(), f1, gp);
                 y.x = gp.x - g.x; y.y = gp.y - g.y;
-                stg2<false>(this->xr, idx[t], xp);
+                stg2<false>(this->x_row(), idx[t], xp);
                 stg2<false>(Sr + offn, idx[t], s);
                 stg2<false>(Yr + offn, idx[t], y);
                 acc[QS_SY] = dsum(acc[QS_SY], s.x, y.x); acc[QS_SY] = dsum(acc[QS_SY], s.y, y.y);
@@ -129,39 +154,39 @@ struct LbfgsDev : RowsDev<Obj, NPTS> {
 
     // the push pass, then the scalar recursion: returns the number of stored pairs (the whole workgroup's alike)
     __device__ __forceinline__ int push_update(double a) {
-        constexpr int U = batch_lbfgs_u<Obj>();
         const int tid = threadIdx.x;
         const int c = q->count, npairs = this->npairs;
+        pushed(q->free_slot);
         double acc[QN_SUMS];
 #pragma unroll
         for (int s = 0; s < QN_SUMS; ++s) acc[s] = 0.0;
         int i0 = 0;
-        for (; i0 + U * BLOCK <= npairs; i0 += U * BLOCK) push_trip<false>(a, c, i0, acc);
+        for (; i0 + U * BLOCK <= npairs; i0 += U * BLOCK) push_trip<false>(a, c, i0, acc);   // (uniform: npairs is the workgroup's)
         if (i0 < npairs) push_trip<true>(a, c, i0, acc);
         if (this->odd && tid == 0) {   // the odd tail element (objectives that are not pair-only)
-            const long long i = 2LL * npairs;
-            const PS<Obj> p = ps_load<Obj>(this->pl, i);
+            const Off i = (Off)2 * npairs;
+            const PS<Obj> p = ps_load<Obj>(this->slot_ptrs(), i);
             double f0 = 0.0, f1 = 0.0, g = 0.0, gp = 0.0;
-            const double x = this->xr[i];
-            obj_eval1<Obj>(x, p, this->s0, f0, g);
-            const double s = a * this->ur[i], xp = x + s;
-            obj_eval1<Obj>(xp, p, this->s0, f1, gp);
+            const double x = this->x_row()[i];
+            obj_eval1<Obj>(x, p, this->scalar(), f0, g);
+            const double s = a * this->u_row()[i], xp = x + s;
+            obj_eval1<Obj>(xp, p, this->scalar(), f1, gp);
             const double y = gp - g;
-            const long long offn = (long long)q->free_slot * ld;
+            const Off offn = (Off)q->free_slot * ld;
             acc[QS_SY] = dsum(acc[QS_SY], s, y); acc[QS_YY] = dsum(acc[QS_YY], y, y);
             acc[QS_SGN] = dsum(acc[QS_SGN], s, gp); acc[QS_YGN] = dsum(acc[QS_YGN], y, gp);
 #pragma unroll
             for (int j = 0; j < QN_MAX_M; ++j) {
                 if (j < c) {
                     const int b = QS_PAIR0 + QP_PER_PAIR * j;
-                    const long long off = (long long)q->list[j] * ld;
+                    const Off off = (Off)q->list[j] * ld;
                     const double sj = Sr[off + i], yj = Yr[off + i];
                     acc[b + QP_SJG] = dsum(acc[b + QP_SJG], sj, gp); acc[b + QP_YJG] = dsum(acc[b + QP_YJG], yj, gp);
                     acc[b + QP_SJYN] = dsum(acc[b + QP_SJYN], sj, y); acc[b + QP_YJSN] = dsum(acc[b + QP_YJSN], yj, s);
                     acc[b + QP_YJYN] = dsum(acc[b + QP_YJYN], yj, y);
                 }
             }
-            this->xr[i] = xp; Sr[offn + i] = s; Yr[offn + i] = y;
+            this->x_row()[i] = xp; Sr[offn + i] = s; Yr[offn + i] = y;
         }
         const double own = wg_reduce_n<QN_SUMS>(acc);
         if (tid < QN_SUMS) qsum[tid] = own;   // the workgroup's row is the total
@@ -178,7 +203,6 @@ struct LbfgsDev : RowsDev<Obj, NPTS> {
     template <int NP, bool TAIL>
     __device__ __forceinline__ void combine_trip(const RParams &rp, int c, double ng, const double (&cy)[QN_MAX_M], const double (&cs)[QN_MAX_M],
                                                  int i0, double (&acc)[RW<NP>::W]) {
-        constexpr int U = batch_lbfgs_u<Obj>();
         d2 xv[U], sv[QN_MAX_M][U], yv[QN_MAX_M][U];
         PV<Obj> pv[U];
         int idx[U], il[U];
@@ -186,13 +210,13 @@ struct LbfgsDev : RowsDev<Obj, NPTS> {
         for (int t = 0; t < U; ++t) {
             idx[t] = i0 + t * BLOCK + (int)threadIdx.x;
             il[t] = (TAIL && idx[t] >= this->npairs) ? this->npairs - 1 : idx[t];
-            xv[t] = ldg2<false>(this->xr, il[t]);
-            pv[t] = pv_load<Obj, false>(this->pl, il[t]);
+            xv[t] = ldg2<false>(this->x_row(), il[t]);
+            pv[t] = pv_load<Obj, false>(this->slot_ptrs(), il[t]);
         }
 #pragma unroll
         for (int j = 0; j < QN_MAX_M; ++j) {
             if (j < c) {
-                const long long off = (long long)q->list[j] * ld;
+                const Off off = (Off)q->list[j] * ld;
 #pragma unroll
                 for (int t = 0; t < U; ++t) { sv[j][t] = ldg2<false>(Sr + off, il[t]); yv[j][t] = ldg2<false>(Yr + off, il[t]); }
             }
@@ -202,7 +226,7 @@ struct LbfgsDev : RowsDev<Obj, NPTS> {
             if (!TAIL || idx[t] < this->npairs) {
                 d2 g, u;
                 double f0 = 0.0;
-                obj_eval2<Obj>(xv[t], pv[t], this->s0, f0, g);
+                obj_eval2<Obj>(xv[t], pv[t], this->scalar(), f0, g);
                 u.x = ng * g.x; u.y = ng * g.y;
 #pragma unroll
                 for (int j = 0; j < QN_MAX_M; ++j) {
@@ -212,7 +236,7 @@ struct LbfgsDev : RowsDev<Obj, NPTS> {
                 for (int j = 0; j < QN_MAX_M; ++j) {
                     if (j < c) { u.x = u.x + cs[j] * sv[j][t].x; u.y = u.y + cs[j] * sv[j][t].y; }
                 }
-                stg2<false>(this->ur, idx[t], u);
+                stg2<false>(this->u_row(), idx[t], u);
                 acc[RW<NP>::GU] = dsum(acc[RW<NP>::GU], g.x, u.x); acc[RW<NP>::GU] = dsum(acc[RW<NP>::GU], g.y, u.y);
                 acc[RW<NP>::UU] = dsum(acc[RW<NP>::UU], u.x, u.x); acc[RW<NP>::UU] = dsum(acc[RW<NP>::UU], u.y, u.y);
                 bool wx = false, wu = false;
@@ -225,7 +249,6 @@ struct LbfgsDev : RowsDev<Obj, NPTS> {
     __device__ __forceinline__ int combine_trial(const double *a, int k, TrialSums *out, double &gu, double &uu) {
         constexpr int NP = NPTS;
         constexpr int W = RW<NP>::W;
-        constexpr int U = batch_lbfgs_u<Obj>();
         const int tid = threadIdx.x;
         const int c = co->count, npairs = this->npairs;
         const double ng = -co->gamma;
@@ -233,7 +256,7 @@ struct LbfgsDev : RowsDev<Obj, NPTS> {
 #pragma unroll
         for (int j = 0; j < QN_MAX_M; ++j) { cy[j] = co->cy[j]; cs[j] = co->cs[j]; }   // (compile-time indices: registers)
         RParams rp;
-        rp.a_acc = 0.0; rp.beta = 0.0; rp.s0 = this->s0; rp.n = 0;
+        rp.a_acc = 0.0; rp.beta = 0.0; rp.s0 = this->scalar(); rp.n = 0;
 #pragma unroll
         for (int j = 0; j < MAXP; ++j) rp.a[j] = (j < NP && k > 0) ? a[j] : 0.0;   // the caller pads a[] to NP entries
         double acc[W];
@@ -243,32 +266,35 @@ struct LbfgsDev : RowsDev<Obj, NPTS> {
         for (; i0 + U * BLOCK <= npairs; i0 += U * BLOCK) combine_trip<NP, false>(rp, c, ng, cy, cs, i0, acc);
         if (i0 < npairs) combine_trip<NP, true>(rp, c, ng, cy, cs, i0, acc);
         if (this->odd && tid == 0) {
-            const long long i = 2LL * npairs;
-            const PS<Obj> p = ps_load<Obj>(this->pl, i);
+            const Off i = (Off)2 * npairs;
+            const PS<Obj> p = ps_load<Obj>(this->slot_ptrs(), i);
             double f0 = 0.0, g = 0.0;
-            obj_eval1<Obj>(this->xr[i], p, this->s0, f0, g);
+            obj_eval1<Obj>(this->x_row()[i], p, this->scalar(), f0, g);
             double u = ng * g;
 #pragma unroll
-            for (int j = 0; j < QN_MAX_M; ++j) { if (j < c) u = u + cy[j] * Yr[(long long)q->list[j] * ld + i]; }
+            for (int j = 0; j < QN_MAX_M; ++j) { if (j < c) u = u + cy[j] * Yr[(Off)q->list[j] * ld + i]; }
 #pragma unroll
-            for (int j = 0; j < QN_MAX_M; ++j) { if (j < c) u = u + cs[j] * Sr[(long long)q->list[j] * ld + i]; }
-            this->ur[i] = u;
+            for (int j = 0; j < QN_MAX_M; ++j) { if (j < c) u = u + cs[j] * Sr[(Off)q->list[j] * ld + i]; }
+            this->u_row()[i] = u;
             acc[RW<NP>::GU] = dsum(acc[RW<NP>::GU], g, u);
             acc[RW<NP>::UU] = dsum(acc[RW<NP>::UU], u, u);
-            rp.x = this->xr; rp.u = this->ur; rp.p0 = this->pl.p0; rp.p1 = this->pl.p1; rp.p2 = this->pl.p2; rp.p3 = this->pl.p3;
-            rp.xo = this->xr; rp.uo = this->ur; rp.gout = nullptr; rp.x2 = nullptr;
+            rp.x = this->x_row(); rp.u = this->u_row(); rp.p0 = this->slot_ptrs().p0; rp.p1 = this->slot_ptrs().p1; rp.p2 = this->slot_ptrs().p2; rp.p3 = this->slot_ptrs().p3;
+            rp.xo = this->x_row(); rp.uo = this->u_row(); rp.gout = nullptr; rp.x2 = nullptr;
             cg_single<Obj, R_TRIAL, NP>(rp, i, acc);   // (reads back the u this lane stored just above)
         }
         const double own = wg_reduce_n<W>(acc);
         if (tid < W) this->tot[tid] = own;
         __syncthreads();
 #pragma unroll
-        for (int j = 0; j < NP; ++j) out[j] = R::ts(this->tot + RS_PER_POINT * j);
+        for (int j = 0; j < NP; ++j) out[j] = Base::ts(this->tot + RS_PER_POINT * j);
         gu = this->tot[RW<NP>::GU]; uu = this->tot[RW<NP>::UU];
         __syncthreads();   // tot is written again by the next pass
         return 0;
     }
 };
+
+template <class Obj, int NPTS>
+using LbfgsDev = LbfgsRing<LbfgsRows<Obj, NPTS>, long long, batch_lbfgs_u<Obj>(), RingPushNone>;
 
 // ---- cgo_batch_probe: the passes the quasi-Newton loop (res_iterate_qn) issues, in its place -------------------------------------
 static_assert(BATCH_PROBE_MAX_M == QN_MAX_M && BATCH_PROBE_ROW == QN_SUMS, "the probe's pass and row hold the largest ring's");
@@ -305,6 +331,21 @@ __device__ __forceinline__ void batch_lbfgs_probe_script(const BatchProbe &pr, R
     }
 }
 
+// ---- what the kernels of both tiers share around the loop ------------------------------------------------------------------------
+// (Only the pinning, and as a macro: the QnState copies, the fresh start and the state's write-out stay in the kernels — as
+// __forceinline__ functions they change the kernels' instructions; DESIGN.md §2.14 has what was tried and measured.)
+// As k_resident: the loop state is FP64 arithmetic throughout — into VGPRs once, opaquely; see the note there.
+#define CGO_RES_V(x) asm volatile("" : "+v"(x))
+#define CGO_BATCH_LBFGS_PIN(s, cfg) do { \
+    CGO_RES_V(s.f_x); CGO_RES_V(s.gg); CGO_RES_V(s.norm); CGO_RES_V(s.dphi0); CGO_RES_V(s.uu); CGO_RES_V(s.a_initial); CGO_RES_V(s.last_a); CGO_RES_V(s.last_beta); \
+    _Pragma("unroll") \
+    for (int j = 0; j < RES_MAXP; ++j) { \
+        CGO_RES_V(s.ca[j]); CGO_RES_V(s.cs[j].f); CGO_RES_V(s.cs[j].gtu); CGO_RES_V(s.cs[j].gtgt); CGO_RES_V(s.cs[j].gtg); CGO_RES_V(s.cs[j].yy); CGO_RES_V(s.cs[j].uy); CGO_RES_V(s.cs[j].ygt); \
+    } \
+    CGO_RES_V(cfg.ls.c1); CGO_RES_V(cfg.ls.c2); CGO_RES_V(cfg.ls.a_max_growth_factor); CGO_RES_V(cfg.ls.delta1); CGO_RES_V(cfg.ls.max_step_size); \
+    CGO_RES_V(cfg.ls.discount_factor); CGO_RES_V(cfg.eps); CGO_RES_V(cfg.mu); \
+} while (0)
+
 template <class Obj, int NPTS, bool PROBE = false>
 __global__ __launch_bounds__(BLOCK, 1) void k_batch_lbfgs(const typename BatchLbfgsArg<PROBE>::type L) {
     __shared__ double tot[RES_WMAX];
@@ -327,16 +368,7 @@ __global__ __launch_bounds__(BLOCK, 1) void k_batch_lbfgs(const typename BatchLb
                             (int)(B.n >> 1), (B.n & 1) != 0, B.s0v ? B.s0v[b] : B.s0, tot};
     LbfgsDev<Obj, NPTS> v(rows, L.S + b * L.ring_stride, L.Y + b * L.ring_stride, B.ld, &s_q, &s_co, qsum);
     ResConfig cfg = B.cfg;
-    // (as k_resident: the loop state is FP64 arithmetic throughout — into VGPRs once, opaquely; see the note there)
-#define RES_V(x) asm volatile("" : "+v"(x))
-    RES_V(s.f_x); RES_V(s.gg); RES_V(s.norm); RES_V(s.dphi0); RES_V(s.uu); RES_V(s.a_initial); RES_V(s.last_a); RES_V(s.last_beta);
-#pragma unroll
-    for (int j = 0; j < RES_MAXP; ++j) {
-        RES_V(s.ca[j]); RES_V(s.cs[j].f); RES_V(s.cs[j].gtu); RES_V(s.cs[j].gtgt); RES_V(s.cs[j].gtg); RES_V(s.cs[j].yy); RES_V(s.cs[j].uy); RES_V(s.cs[j].ygt);
-    }
-    RES_V(cfg.ls.c1); RES_V(cfg.ls.c2); RES_V(cfg.ls.a_max_growth_factor); RES_V(cfg.ls.delta1); RES_V(cfg.ls.max_step_size);
-    RES_V(cfg.ls.discount_factor); RES_V(cfg.eps); RES_V(cfg.mu);
-#undef RES_V
+    CGO_BATCH_LBFGS_PIN(s, cfg);
     bool go = true;
     if (s.reason == RES_FRESH) {   // optim.jl:25-47: f_x = fdf!(df_x, x); u = −df_x (stored to the u row)
         double sums[RW<1>::W];

@@ -63,6 +63,13 @@ hipFunction_t RtcModule::fused(int mode, bool big) const {
     auto it = fn.find(key_fused(mode, big));
     return it == fn.end() ? nullptr : it->second;
 }
+hipFunction_t RtcModule::row_kernel(const std::string &prefix, std::initializer_list<int> rows, int npts) const {
+    hipFunction_t f = nullptr;
+    for (int r : rows) {
+        if (!f || npts >= r) { auto it = fn.find(prefix + std::to_string(r)); if (it != fn.end()) f = it->second; }
+    }
+    return f;
+}
 
 // the embedded kernel templates + the user's objective as one translation unit
 std::string rtc_program_source(const std::string &source, int n_params) { return rtc_program_source_with(source, n_params, std::string()); }

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <string>
@@ -50,6 +51,10 @@ struct RtcModule {
     int device = 0;
     hipFunction_t spec(bool big, bool push) const;   // k_lbfgs_combine_spec<UserObjective, big, push>
     hipFunction_t lite(bool big) const;              // k_lbfgs_push_lite<UserObjective, big>
+private:
+    // the kernel filed under `prefix` + NPTS for the last of `rows` with NPTS ≤ npts, the first row below that (the rule of the
+    // ahead-of-time dispatch); `rows` are the values of a row macro of cgo_instances.def, in its order
+    hipFunction_t row_kernel(const std::string &prefix, std::initializer_list<int> rows, int npts) const;
 };
 
 // `source`: either a complete `struct UserObjective { … };` (functor interface of
@@ -70,6 +75,8 @@ int rtc_compile_batch_probe(RtcModule &m, std::string &log);
 int rtc_compile_batch_lbfgs(RtcModule &m, std::string &log);
 // the kernel of the batched L-BFGS solves' LDS tier for the module's objective, one per row of CGO_BATCH_LBFGS_LDS_ROWS, likewise
 int rtc_compile_batch_lbfgs_lds(RtcModule &m, std::string &log);
+// the head of both programs' further text: this build's pairs per lane and trip of the device tier's ring passes, as #defines
+std::string rtc_batch_lbfgs_defines();
 
 // What a further program of a module is built from (cgo_rtc.hip): the embedded kernel templates + the user's objective as one
 // translation unit, and one program → one loaded module: compiles `src` for the name expressions of `wants`, loads the code

@@ -17,15 +17,9 @@
 
 namespace cgo {
 
-hipFunction_t RtcModule::batch(int npts) const {
-    // the last row with NPTS ≤ npts, the first row below that (the rule of the ahead-of-time dispatch, cgo_backend_batch.hip)
-    hipFunction_t f = nullptr;
-#define ROW(NPTS) \
-    if (!f || npts >= NPTS) { auto it = fn.find("batch:" #NPTS); if (it != fn.end()) f = it->second; }
-    CGO_BATCH_ROWS(ROW)
-#undef ROW
-    return f;
-}
+#define ROW_NPTS(NPTS) NPTS,   // (for the lookups: the values of a row macro)
+
+hipFunction_t RtcModule::batch(int npts) const { return row_kernel("batch:", {CGO_BATCH_ROWS(ROW_NPTS)}, npts); }
 
 hipFunction_t RtcModule::batch_grad() const {
     auto it = fn.find("batch:grad");
@@ -46,14 +40,7 @@ int rtc_compile_batch(RtcModule &m, std::string &log) {
     return rtc_build(rtc_program_source(m.user_source, m.n_params), "cgo_user_objective_batch.hip", wants, m.batch_mod, m.fn, log);
 }
 
-hipFunction_t RtcModule::batch_rows(int npts) const {
-    hipFunction_t f = nullptr;
-#define ROW(NPTS) \
-    if (!f || npts >= NPTS) { auto it = fn.find("batch_rows:" #NPTS); if (it != fn.end()) f = it->second; }
-    CGO_BATCH_DEVROWS_ROWS(ROW)
-#undef ROW
-    return f;
-}
+hipFunction_t RtcModule::batch_rows(int npts) const { return row_kernel("batch_rows:", {CGO_BATCH_DEVROWS_ROWS(ROW_NPTS)}, npts); }
 
 int rtc_compile_batch_rows(RtcModule &m, std::string &log) {
     static std::mutex mu;   // (as rtc_compile_batch)
@@ -69,12 +56,7 @@ int rtc_compile_batch_rows(RtcModule &m, std::string &log) {
 
 // ---- the PROBE twins of both tiers (cgo_batch_probe): a FOURTH program, compiled on the first probe only ----------------------
 hipFunction_t RtcModule::batch_probe(bool device_rows, int npts) const {
-    hipFunction_t f = nullptr;
-#define ROW(NPTS) \
-    if (!f || npts >= NPTS) { auto it = fn.find(std::string(device_rows ? "batch_rows_probe:" : "batch_probe:") + #NPTS); if (it != fn.end()) f = it->second; }
-    if (device_rows) { CGO_BATCH_DEVROWS_ROWS(ROW) } else { CGO_BATCH_ROWS(ROW) }
-#undef ROW
-    return f;
+    return device_rows ? row_kernel("batch_rows_probe:", {CGO_BATCH_DEVROWS_ROWS(ROW_NPTS)}, npts) : row_kernel("batch_probe:", {CGO_BATCH_ROWS(ROW_NPTS)}, npts);
 }
 
 int rtc_compile_batch_probe(RtcModule &m, std::string &log) {

@@ -18,26 +18,23 @@
 
 namespace cgo {
 
-hipFunction_t RtcModule::batch_lbfgs(int npts) const {
-    // the last row with NPTS ≤ npts, the first row below that (the rule of the ahead-of-time dispatch)
-    hipFunction_t f = nullptr;
-#define ROW(NPTS) \
-    if (!f || npts >= NPTS) { auto it = fn.find("batch_qn:" #NPTS); if (it != fn.end()) f = it->second; }
-    CGO_BATCH_LBFGS_ROWS(ROW)
-#undef ROW
-    return f;
-}
+#define ROW_NPTS(NPTS) NPTS,
+hipFunction_t RtcModule::batch_lbfgs(int npts) const { return row_kernel("batch_qn:", {CGO_BATCH_LBFGS_ROWS(ROW_NPTS)}, npts); }
 
 #define CGO_STR2(x) #x
 #define CGO_STR(x) CGO_STR2(x)
+
+// (an A/B build's EXTRA reaches the program's text too)
+std::string rtc_batch_lbfgs_defines() {
+    return "\n#define CGO_BATCH_LBFGS_U " CGO_STR(CGO_BATCH_LBFGS_U) "\n#define CGO_BATCH_LBFGS_U_SLOTS " CGO_STR(CGO_BATCH_LBFGS_U_SLOTS) "\n";
+}
 
 int rtc_compile_batch_lbfgs(RtcModule &m, std::string &log) {
     static std::mutex mu;   // (as rtc_compile_batch)
     std::lock_guard<std::mutex> lock(mu);
     if (m.batch_lbfgs_mod) return CGO_OK;
     if (hipSetDevice(m.device) != hipSuccess) { log = "hipSetDevice failed"; return CGO_EHIP; }
-    // the pairs per lane and trip this library was built with (an A/B build's EXTRA reaches the program's text too)
-    std::string more = "\n#define CGO_BATCH_LBFGS_U " CGO_STR(CGO_BATCH_LBFGS_U) "\n#define CGO_BATCH_LBFGS_U_SLOTS " CGO_STR(CGO_BATCH_LBFGS_U_SLOTS) "\n";
+    std::string more = rtc_batch_lbfgs_defines();   // the pairs per lane and trip this library was built with
     for (const char *c : kRtcLbfgsSourceChunks) more += c;
     std::vector<Want> wants;
 #define ROW(NPTS) wants.push_back({"batch_qn:" #NPTS, "cgo::dev::k_batch_lbfgs<cgo::dev::UserObjective, " #NPTS ">"});

@@ -19,15 +19,8 @@
 
 namespace cgo {
 
-hipFunction_t RtcModule::batch_lbfgs_lds(int npts) const {
-    // the last row with NPTS ≤ npts, the first row below that (the rule of the ahead-of-time dispatch)
-    hipFunction_t f = nullptr;
-#define ROW(NPTS) \
-    if (!f || npts >= NPTS) { auto it = fn.find("batch_qn_lds:" #NPTS); if (it != fn.end()) f = it->second; }
-    CGO_BATCH_LBFGS_LDS_ROWS(ROW)
-#undef ROW
-    return f;
-}
+#define ROW_NPTS(NPTS) NPTS,
+hipFunction_t RtcModule::batch_lbfgs_lds(int npts) const { return row_kernel("batch_qn_lds:", {CGO_BATCH_LBFGS_LDS_ROWS(ROW_NPTS)}, npts); }
 
 #define CGO_STR2(x) #x
 #define CGO_STR(x) CGO_STR2(x)
@@ -38,8 +31,8 @@ int rtc_compile_batch_lbfgs_lds(RtcModule &m, std::string &log) {
     if (m.batch_lbfgs_lds_mod) return CGO_OK;
     if (hipSetDevice(m.device) != hipSuccess) { log = "hipSetDevice failed"; return CGO_EHIP; }
     // the pairs per lane and trip this library was built with (an A/B build's EXTRA reaches the program's text too)
-    std::string more = "\n#define CGO_BATCH_LBFGS_U " CGO_STR(CGO_BATCH_LBFGS_U) "\n#define CGO_BATCH_LBFGS_U_SLOTS " CGO_STR(CGO_BATCH_LBFGS_U_SLOTS)
-                       "\n#define CGO_BATCH_LBFGS_LDS_U " CGO_STR(CGO_BATCH_LBFGS_LDS_U) "\n#define CGO_BATCH_LBFGS_LDS_U_SLOTS " CGO_STR(CGO_BATCH_LBFGS_LDS_U_SLOTS) "\n";
+    std::string more = rtc_batch_lbfgs_defines();
+    more += "#define CGO_BATCH_LBFGS_LDS_U " CGO_STR(CGO_BATCH_LBFGS_LDS_U) "\n#define CGO_BATCH_LBFGS_LDS_U_SLOTS " CGO_STR(CGO_BATCH_LBFGS_LDS_U_SLOTS) "\n";
     for (const char *c : kRtcLbfgsSourceChunks) more += c;
     more += "\n";
     for (const char *c : kRtcLbfgsLdsSourceChunks) more += c;

@@ -16,6 +16,21 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"cgo_minimize_batch_lbfgs_ex": 12, "cgo_minimize_batch_lbfgs_obj_ex": 13, "cgo_batch_lbfgs_max_n_ex": 4,
        "cgo_batch_lbfgs_max_n_obj_ex": 3, "cgo_batch_lbfgs_lds_rows": 2, "cgo_batch_lbfgs_lds_shape": 3}
 BLOCK = 256
+RING_PASSES = ("push_trip", "push_update", "combine_trip", "combine_trial")
+
+
+def _code(name):
+    return re.sub(r"//.*", "", open(os.path.join(I.CSRC, name)).read())
+
+
+def ring_template_body():
+    """the code of LbfgsRing, the one template of the ring passes of both tiers"""
+    return re.search(r"^struct LbfgsRing\b.*?^};", _code("cgo_kernels_batch_lbfgs.hip.hpp"), re.M | re.S).group(0)
+
+
+def ring_pass_definitions(code):
+    """how often `code` DEFINES each of the four ring-pass functions (a call has no return type before the name)"""
+    return {f: len(re.findall(r"\b(?:void|int) " + f + r"\(", code)) for f in RING_PASSES}
 
 
 # ---- 1. the interface -----------------------------------------------------------------------------------------------------------
@@ -69,9 +84,14 @@ def test_rows_and_shape_need_no_device(cgo):
     for K in range(5):
         block, u = cgo.batch_lbfgs_lds_shape(K)
         assert block == BLOCK and u == (u_max if K <= 1 else u_slots) and 1 <= u <= 8
-    # the kernel takes its pairs per trip from the objective in all four places, and says why no bit depends on it
+    # every ring pass takes its pairs per trip from the objective: the tier hands batch_lbfgs_lds_u<Obj>() to the one template
+    # of the ring passes, once, and that template's body knows no other source of it; the header says why no bit depends on it
     code = re.sub(r"//.*", "", src)
-    assert code.count("constexpr int U = batch_lbfgs_lds_u<Obj>();") == 4
+    assert code.count("batch_lbfgs_lds_u<Obj>()") == 1
+    assert re.search(r"using LbfgsLdsDev = LbfgsRing<[^;]*\bbatch_lbfgs_lds_u<Obj>\(\)[^;]*>;", code)
+    ring = ring_template_body()
+    for name in ("BATCH_LBFGS_U", "BATCH_LBFGS_LDS_U", "batch_lbfgs_u", "batch_lbfgs_lds_u"):
+        assert name not in ring, name
     assert "in the same order for every U" in src
     assert "extern __shared__" in code and "__launch_bounds__(BLOCK, 1)" in code
     assert "atomic" not in code and "__threadfence" not in code
@@ -100,9 +120,14 @@ def test_the_table_row_and_the_translation_units():
     probe = open(os.path.join(I.CSRC, "cgo_backend_batch_probe.hip")).read()
     assert "k_batch_lbfgs_lds<Obj, NPTS, true>" in probe and "CGO_BATCH_LBFGS_LDS_ROWS(ROW)" in probe
     assert ", true>" not in tu
-    # the device tier's kernel text is what it was
+    # the device tier has no dynamic LDS
     dev = re.sub(r"//.*", "", open(os.path.join(I.CSRC, "cgo_kernels_batch_lbfgs.hip.hpp")).read())
-    assert "extern __shared__" not in dev and dev.count("constexpr int U = batch_lbfgs_u<Obj>();") == 4
+    assert "extern __shared__" not in dev
+    # … and it hands its own pairs per trip to the template of the ring passes, once; the four passes exist once in the two headers
+    assert dev.count("batch_lbfgs_u<Obj>()") == 1
+    assert re.search(r"using LbfgsDev = LbfgsRing<[^;]*\bbatch_lbfgs_u<Obj>\(\)[^;]*>;", dev)
+    assert ring_pass_definitions(ring_template_body()) == dict.fromkeys(RING_PASSES, 1)
+    assert ring_pass_definitions(dev + _code("cgo_kernels_batch_lbfgs_lds.hip.hpp")) == dict.fromkeys(RING_PASSES, 1)
     rtc = open(os.path.join(I.CSRC, "cgo_rtc_batch_lbfgs_lds.hip")).read()
     assert "k_batch_lbfgs_lds<cgo::dev::UserObjective, " in rtc and "std::mutex" in rtc and "batch_lbfgs_lds_mod" in rtc
     assert "k_batch_grad" not in re.sub(r"//.*", "", rtc) and "k_batch_lbfgs<" not in rtc      # that one kernel and nothing else
@@ -122,6 +147,11 @@ def test_existing_generated_texts_are_unchanged_and_the_new_one_carries_the_kern
     now = {g: _generate(I.CSRC, g, tmp_path / (g + ".now.inc")) for g in ("gen_rtc_sources.py", "gen_rtc_lbfgs_sources.py")}
     for g, text in now.items():
         assert "k_batch_lbfgs_lds" not in text and "LbfgsLdsDev" not in text, g
+    # the ring passes of both tiers are the device tier's text: defined there once, and nowhere in what the LDS tier adds
+    code = {g: re.sub(r"//.*", "", text) for g, text in dict(now, lds=new).items()}
+    assert ring_pass_definitions(code["gen_rtc_lbfgs_sources.py"]) == dict.fromkeys(RING_PASSES, 1)
+    assert ring_pass_definitions(code["lds"]) == dict.fromkeys(RING_PASSES, 0)
+    assert ring_pass_definitions(code["gen_rtc_sources.py"]) == dict.fromkeys(RING_PASSES, 0)
     if shutil.which("git") is None:
         pytest.skip("git is absent: the parent commit's generators cannot be read")
     top = subprocess.run(["git", "-C", ROOT, "rev-parse", "--show-toplevel"], capture_output=True, text=True)
@@ -143,9 +173,8 @@ def test_existing_generated_texts_are_unchanged_and_the_new_one_carries_the_kern
         if blob.returncode == 0:
             with open(tmp_path / "parent" / path, "wb") as f:
                 f.write(blob.stdout)
-    for g, text in now.items():
-        was = _generate(str(old), g, tmp_path / (g + ".was.inc"))
-        assert was == text, f"{g}: the generated text changed"
+    was = _generate(str(old), "gen_rtc_sources.py", tmp_path / "gen_rtc_sources.py.was.inc")
+    assert was == now["gen_rtc_sources.py"], "gen_rtc_sources.py: the generated text changed"
 
 
 # ---- 4. Python argument checks ------------------------------------------------------------------------------------------------------

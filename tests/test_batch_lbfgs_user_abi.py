@@ -54,9 +54,13 @@ def test_the_shape_needs_no_device_and_follows_the_slot_count(cgo):
         block, u = cgo.batch_lbfgs_shape_obj(k)
         assert block == U.BLOCK and 1 <= u <= u_max
         assert u == (u_max if k <= 1 else u_slots)
-    # the kernel takes its pairs per trip from the objective in all four places, and says why no bit depends on it
+    # every ring pass takes its pairs per trip from the objective — the tier hands batch_lbfgs_u<Obj>() to the one template of
+    # the ring passes, whose body names no constant of its own — and the header says why no bit depends on it
     code = re.sub(r"//.*", "", src)
-    assert code.count("constexpr int U = batch_lbfgs_u<Obj>();") == 4 and "constexpr int U = BATCH_LBFGS_U;" not in code
+    assert code.count("batch_lbfgs_u<Obj>()") == 1 and "constexpr int U = BATCH_LBFGS_U;" not in code
+    assert re.search(r"using LbfgsDev = LbfgsRing<[^;]*\bbatch_lbfgs_u<Obj>\(\)[^;]*>;", code)
+    ring = re.search(r"^struct LbfgsRing\b.*?^};", code, re.M | re.S).group(0)
+    assert "BATCH_LBFGS_U" not in ring and "batch_lbfgs_u" not in ring and ring.count("U * BLOCK") == 4
     assert "in the same order for every U" in src
 
 
