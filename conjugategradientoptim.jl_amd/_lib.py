@@ -254,6 +254,10 @@ SIGNATURES = {
     "cgo_batch_lbfgs_max_n_obj_ex": (C.c_int64, [_vp, C.c_int32, C.POINTER(BatchPolicyC)]),
     "cgo_batch_lbfgs_lds_rows": (C.c_int32, [C.c_int32, C.c_int32]),
     "cgo_batch_lbfgs_lds_shape": (None, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "cgo_batch_lbfgs_open": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(dp), C.c_int32, C.c_int32, C.POINTER(BatchPolicyC), C.POINTER(_vp)]),
+    "cgo_batch_lbfgs_solve": (C.c_int, [_vp, dp, dp, C.POINTER(C.c_uint8), C.POINTER(CGConfigC), C.POINTER(LSConfigC), C.c_int64,
+                                        C.POINTER(BatchResultsC)]),
+    "cgo_batch_lbfgs_m": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
     "cgo_batch_probe": (C.c_int, [_vp, C.POINTER(BatchProbeC)]),
     "cgo_batch_probe_qn_bytes": (C.c_int64, []),
     "cgo_stop_status": (C.c_int32, [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, i64p]),

@@ -1481,8 +1481,8 @@ def minimizeobjectivebatch_lbfgs_obj(model: "DeviceObjective", X0, config: CGCon
     (the limit of "lds": batch_lbfgs_max_n_obj(model, m=m, rows="lds"); its kernel is one more program of the source, compiled by
     the first call that runs the tier).  Returns what minimizeobjectivebatch_lbfgs returns (`.rows`: the tier that ran); a problem the device loop does not finish is solved again from its own x0, with its own slot rows and scalar, by
     the ordinary engine and counted in `handed_back`.  Not covered (CgoError or ValueError): CG flavours and Broyden
-    (minimizeobjectivebatch), Backtracking, m > 10, a multi-rank context; there is no `Batch` handle, `active` mask or barrier
-    method on L-BFGS."""
+    (minimizeobjectivebatch), Backtracking, m > 10, a multi-rank context.  A batch that stays on the device between such
+    solves, with an `active` mask: `BatchLBFGS`; box-constrained fits on it: primalbarriermethodbatch_lbfgs."""
     if not isinstance(model, DeviceObjective):
         raise ValueError("model must be a run-time compiled DeviceObjective (ElementwiseObjective); built-in kinds: minimizeobjectivebatch_lbfgs")
     pol = _batch_lbfgs_policy(rows)
@@ -1586,6 +1586,62 @@ class Batch:
             self.close()
         except Exception:
             pass
+
+
+class BatchLBFGS(Batch):
+    """`Batch` for β = LBFGS(m) (cgo_batch_lbfgs_open): the slot rows of `params` go up once, and the rows of x, u, the gradient
+    and a ring of 2(m+1) rows per problem stay allocated between solves — what minimizeobjectivebatch_lbfgs_obj allocates,
+    uploads and frees on every call.  `m` is the largest history length a `solve` on the handle may ask for (1 …
+    batch_lbfgs_max_m()); the device memory, (3 + n_params + 2(m+1)) · batch · (n + n%2) · 8 bytes, is checked against what is
+    free before anything is allocated.  rows: "device" (the default) | "lds" | "auto", the rule of
+    minimizeobjectivebatch_lbfgs — the limit of "lds" is batch_lbfgs_max_n_obj(model, m=m, rows="lds").  The tier's program of
+    the model's source is compiled here, so a solve never compiles.  `.rows` says which tier the handle runs in, `.m` the m it
+    was opened with.  A context manager; `close` frees the device rows."""
+
+    def __init__(self, model: DeviceObjective, params, batch: int, m: int, rows: str = "device"):
+        self._h = None
+        pol = _batch_lbfgs_policy(rows)
+        if not isinstance(model, DeviceObjective) or model.kind != "user":
+            raise ValueError("BatchLBFGS: the model must be a run-time compiled objective (ElementwiseObjective)")
+        if not isinstance(m, (int, np.integer)) or isinstance(m, bool):
+            raise ValueError("BatchLBFGS: m must be an integer")
+        self.model, self.batch, self.n, self.m = model, int(batch), int(model.n_global), int(m)
+        if self.batch < 1:
+            raise ValueError("BatchLBFGS: batch must be ≥ 1")
+        Pc = [_batch_rows(f"params[{j}]", v, (self.batch, self.n)) for j, v in enumerate(params or [])]
+        prows = (dp * max(len(Pc), 1))(*[v.ctypes.data_as(dp) for v in Pc])
+        h = C.c_void_p()
+        ctx_h = model.ctx._h if model.ctx is not None else None
+        check(_lib.lib().cgo_batch_lbfgs_open(ctx_h, model._h, self.batch, prows, len(Pc), self.m,
+                                              C.byref(pol) if pol is not None else None, C.byref(h)))
+        self._h = h
+        used = C.c_int32(0)
+        check(_lib.lib().cgo_batch_rows(h, C.byref(used)))
+        self._rows_used = int(used.value)
+        self.rows = _BATCH_ROWS_NAMES[self._rows_used]
+
+    def solve(self, X0, config: CGConfig, linesearch_config: LineSearchConfig, scalars=None, active=None,
+              slice_iters: int = 0) -> BatchResults:
+        """One batched L-BFGS solve from X0 ([batch, n]): `config.β_config` is LBFGS(m) with m ≤ `.m`; every ring starts empty
+        with this solve's m, so nothing of an earlier solve is read.  scalars, active and the returned list as `Batch.solve` has
+        them.  Every number has the bits of minimizeobjectivebatch_lbfgs_obj with the same inputs, rows and m.  A problem the
+        device loop does not finish is solved again from its row of X0 by the ordinary engine, with the handle's slot rows
+        and its own scalar, and counted in `handed_back`."""
+        if self._h is None:
+            raise ValueError("BatchLBFGS: closed")
+        X0 = _batch_rows("X0", X0, (self.batch, self.n))
+        sc = None if scalars is None else _batch_rows("scalars", scalars, (self.batch,))
+        ac = None
+        if active is not None:
+            ac = np.ascontiguousarray(np.asarray(active).astype(bool).astype(np.uint8))
+            if ac.shape != (self.batch,):
+                raise ValueError(f"active must be [{self.batch}]")
+        o = _BatchOut(self.batch, self.n, config)
+        cfg, ls = config._c(), linesearch_config._c()
+        check(_lib.lib().cgo_batch_lbfgs_solve(self._h, X0.ctypes.data_as(dp), sc.ctypes.data_as(dp) if sc is not None else None,
+                                               ac.ctypes.data_as(C.POINTER(C.c_uint8)) if ac is not None else None, C.byref(cfg),
+                                               C.byref(ls), int(slice_iters), C.byref(o.c)))
+        return o.results(ac, rows_used=self._rows_used)
 
 
 class UndefVarError(RuntimeError):
@@ -1900,26 +1956,19 @@ def _refuse_unbatched(config: CGConfig, linesearch_config: LineSearchConfig):
         raise _lib.CgoError(1, "batched solves: the Backtracking line search is not supported (StrongWolfeBisection or WolfeBisection)")
 
 
-def primalbarriermethodbatch(constraints: BoxConstraints, f0df0: str, X_initial, centering_config: CGConfig,
-                             linesearch_config: LineSearchConfig, barrier_config: PrimalBarrierConfig, *rerun_config_tuples,
-                             params=None, ctx: Optional[Context] = None, rows: str = "lds") -> List[PrimalBarrierResults]:
-    """primalbarriermethod for `batch` problems at once: X_initial is [batch, D], `params` the base objective's own [batch, D]
-    rows (one array per slot), `constraints` one box for all (floats), one set of bounds for all (length-D arrays) or every
-    problem's own ([batch, D] arrays: a BatchBoxConstraints).  The loop of primal_barrier.jl:156-255 with every scalar a [batch] array: t (verifyt0
-    from ONE batched evaluation of f0), the status of the last stage, the stop tests.  Every stage of every centering step is
-    ONE batched solve (`Batch.solve`) with scalars = t and active = the problems still running (for a rerun stage: those whose
-    last status is not "success", from the previous stage's minimizers); `X_initial` is never updated, as in the reference.
-    Returns what primalbarriermethod returns for each problem.  Configs the batched device loop does not run raise CgoError
-    before any work (no loop of single solves).  rows: "lds" | "device" | "auto", passed on to every `Batch` (a box fit with
-    per-variable bounds holds four slots: LDS ends at D = 3 352 there)."""
-    _batch_policy(rows)
+def _primalbarrierbatch(open_batch, refuse, constraints: BoxConstraints, f0df0: str, X_initial, centering_config: CGConfig,
+                        linesearch_config: LineSearchConfig, barrier_config: PrimalBarrierConfig, rerun_config_tuples,
+                        params, ctx: Optional[Context]) -> List[PrimalBarrierResults]:
+    """The loop of primalbarriermethodbatch and primalbarriermethodbatch_lbfgs.  `refuse(config, linesearch_config)` raises for a
+    stage the handle does not run, before any work; `open_batch(model, rows, batch)` opens the handle — a `Batch` or a
+    `BatchLBFGS` — every stage of every centering step, and the one evaluation of verifyt0, are solved on."""
     X0 = np.ascontiguousarray(np.asarray(X_initial, dtype=np.float64))
     if X0.ndim != 2:
         raise ValueError("X_initial must be [batch, D]")
     batch, D = X0.shape
-    _refuse_unbatched(centering_config, linesearch_config)
+    refuse(centering_config, linesearch_config)
     for tup in rerun_config_tuples:
-        _refuse_unbatched(tup[0], tup[1])
+        refuse(tup[0], tup[1])
     own = [_batch_rows(f"params[{j}]", v, (batch, D)) for j, v in enumerate(params or [])]
     bar_rows = list(own)
     if constraints.per_variable:
@@ -1953,14 +2002,14 @@ def primalbarriermethodbatch(constraints: BoxConstraints, f0df0: str, X_initial,
         if not math.isfinite(bc.t_initial) or bc.t_initial < 0.0:     # verifyt0  (:259-276): f0(x_initial) of every problem, one launch
             base = ElementwiseObjective(D, _base_objective_source(f0df0), param=[None] * len(own) if own else None, ctx=ctx)
             try:
-                with Batch(base, own, batch, rows=rows) as B0:   # max_iters = 0: the initial evaluation (optim.jl:31) and nothing after it
+                with open_batch(base, own, batch) as B0:   # max_iters = 0: the initial evaluation (optim.jl:31) and nothing after it
                     c0 = CGConfig(centering_config.ϵ, centering_config.β_config, 0, False, DisableTrace())
                     r0 = B0.solve(np.where(running[:, None], X0, X0[np.flatnonzero(running)[0]]), c0, linesearch_config)
                 f_x0 = np.array([r.objective for r in r0])
             finally:
                 base.close()
             t = (f_x0 - bc.inf_f0_lb) * mu
-        B = Batch(obj, bar_rows, batch, rows=rows)
+        B = open_batch(obj, bar_rows, batch)
         for i in range(1, bc.max_iters + 1):                          # :208
             step: List[List[Results]] = [[] for _ in range(batch)]
             act, X = running.copy(), X0
@@ -1992,6 +2041,51 @@ def primalbarriermethodbatch(constraints: BoxConstraints, f0df0: str, X_initial,
         if B is not None:
             B.close()
         obj.close()
+
+
+def primalbarriermethodbatch(constraints: BoxConstraints, f0df0: str, X_initial, centering_config: CGConfig,
+                             linesearch_config: LineSearchConfig, barrier_config: PrimalBarrierConfig, *rerun_config_tuples,
+                             params=None, ctx: Optional[Context] = None, rows: str = "lds") -> List[PrimalBarrierResults]:
+    """primalbarriermethod for `batch` problems at once: X_initial is [batch, D], `params` the base objective's own [batch, D]
+    rows (one array per slot), `constraints` one box for all (floats), one set of bounds for all (length-D arrays) or every
+    problem's own ([batch, D] arrays: a BatchBoxConstraints).  The loop of primal_barrier.jl:156-255 with every scalar a [batch] array: t (verifyt0
+    from ONE batched evaluation of f0), the status of the last stage, the stop tests.  Every stage of every centering step is
+    ONE batched solve (`Batch.solve`) with scalars = t and active = the problems still running (for a rerun stage: those whose
+    last status is not "success", from the previous stage's minimizers); `X_initial` is never updated, as in the reference.
+    Returns what primalbarriermethod returns for each problem.  Configs the batched device loop does not run raise CgoError
+    before any work (no loop of single solves).  rows: "lds" | "device" | "auto", passed on to every `Batch` (a box fit with
+    per-variable bounds holds four slots: LDS ends at D = 3 352 there)."""
+    _batch_policy(rows)
+    return _primalbarrierbatch(lambda model, P, batch: Batch(model, P, batch, rows=rows), _refuse_unbatched, constraints, f0df0,
+                               X_initial, centering_config, linesearch_config, barrier_config, rerun_config_tuples, params, ctx)
+
+
+def _refuse_unbatched_lbfgs(config: CGConfig, linesearch_config: LineSearchConfig):
+    """What a `BatchLBFGS` does not run, in the library's words (check_batch_lbfgs_call) — before any work is done."""
+    if not isinstance(config.β_config, LBFGS):
+        raise _lib.CgoError(1, "batched L-BFGS solves: β must be LBFGS(m) (CG flavours: primalbarriermethodbatch; the Broyden family has no batched form)")
+    if isinstance(linesearch_config, Backtracking):
+        raise _lib.CgoError(1, "batched L-BFGS solves: the Backtracking line search is not supported (StrongWolfeBisection or WolfeBisection)")
+
+
+def primalbarriermethodbatch_lbfgs(constraints: BoxConstraints, f0df0: str, X_initial, centering_config: CGConfig,
+                                   linesearch_config: LineSearchConfig, barrier_config: PrimalBarrierConfig, *rerun_config_tuples,
+                                   params=None, ctx: Optional[Context] = None, rows: str = "device") -> List[PrimalBarrierResults]:
+    """primalbarriermethodbatch with a quasi-Newton direction: the same loop, arguments and results, every stage of every
+    centering step ONE `BatchLBFGS.solve` with scalars = t and active = the problems still running.  Every stage's β_config
+    must be LBFGS(m) — each stage its own m; the handle is opened once with the largest — any other raises CgoError before any
+    work and names primalbarriermethodbatch, and Backtracking is refused as there.  verifyt0 stays ONE batched evaluation of
+    the base objective with max_iters = 0; it runs on a `BatchLBFGS` of its own on the base objective (the same rows and m as
+    the fit's handle), under the centering stage's config.  rows: "device" (the default) | "lds" | "auto", the rule of
+    minimizeobjectivebatch_lbfgs, passed on to both handles (with per-variable bounds a fit holds four slots: at m = 5 one
+    workgroup's LDS then holds 18 rows of D + D%2 doubles)."""
+    _batch_lbfgs_policy(rows)
+    stages = [centering_config] + [t[0] for t in rerun_config_tuples]
+
+    def open_batch(model, P, batch):   # (called after every stage has passed the refusal rule)
+        return BatchLBFGS(model, P, batch, max(int(c.β_config.m) for c in stages), rows=rows)
+    return _primalbarrierbatch(open_batch, _refuse_unbatched_lbfgs, constraints, f0df0, X_initial, centering_config,
+                               linesearch_config, barrier_config, rerun_config_tuples, params, ctx)
 
 
 def minimizeobjectivererun(fdf, x_initial, config: CGConfig, linesearch_config: LineSearchConfig,

@@ -220,7 +220,16 @@ int HipBackend::batch_export_row(int64_t b, HipBackend &dst, bool with_u) {
     if (int rc = dst.set_x0_device(xc_ + (size_t)b * (size_t)bat_ld_)) return rc;   // (ends whatever the last problem left pending there)
     const size_t nb = sizeof(double) * (size_t)bat_n_;
     if (with_u) HIPCHK(hipMemcpyAsync(dst.uc_, uc_ + (size_t)b * (size_t)bat_ld_, nb, hipMemcpyDeviceToDevice, ctx_->stream));
-    if (dst.obj_->nparams() != obj_->nparams()) { set_error("internal: batch_export_row to an objective of other parameter slots"); return CGO_ESTATE; }
+    return batch_export_slots(b, dst);
+}
+
+// … the slots alone: what a handed-back problem of a batched L-BFGS solve on a handle takes from the batch (its x0 is the
+// caller's, and a quasi-Newton solver forms its own u and stored gradient at its start)
+int HipBackend::batch_export_slots(int64_t b, HipBackend &dst) {
+    if (b < 0 || b >= bat_count_ || dst.obj_->n_local != bat_n_ || dst.obj_->kind != obj_->kind) { set_error("internal: batch_export_slots to a solver of another shape"); return CGO_ESTATE; }
+    if (dst.obj_->nparams() != obj_->nparams()) { set_error("internal: batch_export_slots to an objective of other parameter slots"); return CGO_ESTATE; }
+    HIPCHK(hipSetDevice(ctx_->device));
+    const size_t nb = sizeof(double) * (size_t)bat_n_;
     for (int j = 0; j < obj_->nparams(); ++j) {
         HIPCHK(hipMemcpyAsync(dst.obj_->p[j].p, obj_->p[j].p + (size_t)b * (size_t)bat_ld_, nb, hipMemcpyDeviceToDevice, ctx_->stream));
         dst.obj_->p_set[j] = true;

@@ -56,13 +56,17 @@ int HipBackend::batch_lbfgs_alloc(int m, bool lds) {
 }
 
 // every problem's ring empty.  (The ring rows need no clearing: a pass reads the slots of stored pairs only, and the padding
-// element of an odd n is never read.)
-int HipBackend::batch_lbfgs_reset() {
+// element of an odd n is never read.)  m: the ring depth of the solve that starts — the kernels lay a problem's ring out from its
+// QnState's own m, inside the (bat_m_ + 1) rows the ring was allocated with, whose stride stays (a batch that outlives a solve:
+// cgo_batch_lbfgs_solve).
+int HipBackend::batch_lbfgs_reset(int m) {
     if (!bat_qn_) { set_error("internal: batch_lbfgs_reset before batch_lbfgs_alloc"); return CGO_ESTATE; }
+    if (m == 0) m = bat_m_;
+    if (m < 1 || m > bat_m_) { set_error("internal: batch_lbfgs_reset with a ring deeper than the one allocated"); return CGO_ESTATE; }
     HIPCHK(hipSetDevice(ctx_->device));
     QnState q;
     std::memset(&q, 0, sizeof q);
-    qn_init(q, bat_m_);
+    qn_init(q, m);
     std::vector<QnState> qs((size_t)bat_count_, q);
     HIPCHK(hipMemcpy(bat_qn_, qs.data(), sizeof(QnState) * (size_t)bat_count_, hipMemcpyHostToDevice));
     return CGO_OK;

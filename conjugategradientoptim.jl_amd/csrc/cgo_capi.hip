@@ -1051,13 +1051,15 @@ static int batch_backend_on(cgo_ctx *ctx, HipObjective &cat, int64_t n, int64_t 
 static int batch_solve_on(cgo_ctx *ctx, HipBackend &be, int64_t n, int64_t batch, const double *x0, const double *scalars,
                           const unsigned char *active, const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters,
                           cgo_batch_results *out, const std::function<int(cgo_objective **)> &make_hobj, bool qn = false,
-                          const double *const *qn_params = nullptr, int qn_nparams = 0) {
+                          const double *const *qn_params = nullptr, int qn_nparams = 0, int qn_m = 0) {
     // qn: a batched L-BFGS solve (cgo_minimize_batch_lbfgs[_obj]) — every ring empty at the start, and a handed-back problem is
     // solved again by the host engine from its own x0 (the ring and Gram state of the device are not exported), with its row of the
-    // caller's x0 and of every slot of qn_params (a quasi-Newton solver keeps a stored gradient: not a backend batch_export_row serves)
+    // caller's x0 and of every slot of qn_params (a quasi-Newton solver keeps a stored gradient: not a backend batch_export_row serves).
+    // On a handle (cgo_batch_lbfgs_solve) qn_params is null — the caller's arrays were valid during open only — and the slot rows
+    // come from the batch's own device rows (batch_export_slots); qn_m: this solve's ring depth on a ring allocated for more.
     auto on = [&](int64_t b) { return !active || active[b] != 0; };
     if (int rc = be.batch_reset(x0, scalars, active, cfg->max_iters, cfg->trace_enabled != 0)) return rc;
-    if (qn) { if (int rc = be.batch_lbfgs_reset()) return rc; }
+    if (qn) { if (int rc = be.batch_lbfgs_reset(qn_m)) return rc; }
     BatchRun run;
     if (int rc = run_batch(&be, *cfg, *ls, batch, slice_iters, run)) { if (rc == CGO_ESTATE) set_error("internal: a batched launch left a problem in a state the driver does not know"); return rc; }
     out->launches = run.launches;
@@ -1105,7 +1107,8 @@ static int batch_solve_on(cgo_ctx *ctx, HipBackend &be, int64_t n, int64_t batch
         }
         if (scalars) { if ((rc = cgo_objective_set_scalar(hobj, 0, scalars[b]))) break; }   // (the call's own objective, never the model)
         if (qn) {          // the whole solve, from the problem's own x0 (the device's row of x has moved on)
-            for (int j = 0; j < qn_nparams && !rc; ++j)
+            if (!qn_params) rc = be.batch_export_slots(b, *hs->be);
+            for (int j = 0; qn_params && j < qn_nparams && !rc; ++j)
                 if (qn_params[j]) rc = cgo_objective_set_param_host(hobj, j, qn_params[j] + b * n);
             if (rc) break;
             if ((rc = hs->be->set_x0_host(x0 + b * n))) break;
@@ -1252,10 +1255,10 @@ static int batch_lbfgs_rows_asked(const cgo_batch_policy *pol, int &rows) {
 // it is not.  true: LDS where n fits for this m and slot count.
 static constexpr bool kBatchLbfgsAutoTakesLds = false;
 // the tier a batch of problems of size n runs in: lds_max = what one workgroup's LDS holds for this m and slot count
-static int batch_lbfgs_tier(int rows, int64_t n, int64_t lds_max, bool &lds) {
+static int batch_lbfgs_tier(int rows, int64_t n, int64_t lds_max, bool &lds, const char *lds_name = "cgo_batch_lbfgs_max_n_ex") {
     lds = rows == CGO_BATCH_ROWS_LDS || (rows == CGO_BATCH_ROWS_AUTO && kBatchLbfgsAutoTakesLds && n <= lds_max);
     if (lds && n > lds_max) {
-        set_error("batched L-BFGS solves: n = " + std::to_string(n) + " exceeds what one workgroup's LDS holds of a problem's rows and ring (cgo_batch_lbfgs_max_n_ex = " + std::to_string(lds_max) + ")");
+        set_error("batched L-BFGS solves: n = " + std::to_string(n) + " exceeds what one workgroup's LDS holds of a problem's rows and ring (" + lds_name + " = " + std::to_string(lds_max) + ")");
         return CGO_EINVAL;
     }
     return CGO_OK;
@@ -1526,6 +1529,7 @@ struct cgo_batch {
     cgo_ctx *ctx = nullptr;
     cgo_objective *model = nullptr;   // a reference is held: its scalar and cost class are read at every solve
     int64_t n = 0, batch = 0;
+    int m_max = 0;                    // > 0: opened for L-BFGS (cgo_batch_lbfgs_open) with a ring of that depth per problem
     HipObjective cat;
     HipBackend *be = nullptr;
     ~cgo_batch() { delete be; }
@@ -1538,7 +1542,8 @@ int cgo_batch_open(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const doub
 int cgo_batch_rows(const cgo_batch *h, int32_t *rows_used) {
     API_GUARD_BEGIN
     REQUIRE(h && h->be && rows_used, "null argument");
-    *rows_used = h->be->batch_device_rows() ? CGO_BATCH_ROWS_DEVICE : CGO_BATCH_ROWS_LDS;
+    if (h->m_max > 0) *rows_used = h->be->batch_lbfgs_in_lds() ? CGO_BATCH_ROWS_LDS : CGO_BATCH_ROWS_DEVICE;   // (its rows are device rows in both tiers)
+    else *rows_used = h->be->batch_device_rows() ? CGO_BATCH_ROWS_DEVICE : CGO_BATCH_ROWS_LDS;
     return CGO_OK;
     API_GUARD_END
 }
@@ -1573,6 +1578,7 @@ int cgo_batch_solve(cgo_batch *h, const double *x0, const double *scalars, const
     API_GUARD_BEGIN
     REQUIRE(h && x0 && cfg && ls && out, "null argument");
     out->launches = 0; out->handed_back = 0;
+    REQUIRE(h->m_max == 0, "batched solves: the handle was opened for L-BFGS: cgo_batch_lbfgs_solve");
     if (int rc = check_batch_call(h->ctx, cfg, ls, h->n, h->batch, slice_iters)) return rc;
     if (scalars)
         for (int64_t b = 0; b < h->batch; ++b)
@@ -1597,6 +1603,82 @@ int cgo_batch_close(cgo_batch *h) {
     delete h;            // (the backend before the model: its objective shares the model's module)
     obj_unref(m);
     return CGO_OK;
+    API_GUARD_END
+}
+
+// ---- … for β = LBFGS(m): the batch of cgo_minimize_batch_lbfgs_obj_ex, kept -----------------------------------------------------
+// The rows, the slot rows and a ring of m_max + 1 slots per problem stay allocated; every cgo_batch_lbfgs_solve resets the rows
+// and states (batch_reset), empties every ring with ITS m ≤ m_max (batch_lbfgs_reset(m): the kernels lay the ring out from the
+// QnState's own m, the stride between two problems' rings stays (m_max + 1) · ld) and is then the one-shot call.  A handed-back
+// problem takes its slot rows from the batch's device rows: the caller's params were valid during open only.
+int cgo_batch_lbfgs_open(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *const *params, int32_t n_params,
+                         int32_t m_max, const cgo_batch_policy *policy, cgo_batch **handle) {
+    API_GUARD_BEGIN
+    REQUIRE(ctx && model && handle, "null argument");
+    *handle = nullptr;
+    int rows = 0;
+    if (int rc = batch_lbfgs_rows_asked(policy, rows)) return rc;
+    if (int rc = check_batch_model(ctx, model)) return rc;
+    const int64_t n = model->o.n_local;
+    if (m_max < 1 || m_max > QN_MAX_M) { set_error("batched L-BFGS solves: m_max = " + std::to_string(m_max) + " lies outside 1 … cgo_batch_lbfgs_max_m = " + std::to_string(QN_MAX_M)); return CGO_EINVAL; }
+    REQUIRE(ctx->c.world() == 1, "batched L-BFGS solves: a multi-rank context is not supported (one rank only)");
+    REQUIRE(batch >= 1, "batched L-BFGS solves: batch must be ≥ 1");
+    REQUIRE(batch <= 0x7FFFFFFF, "batched L-BFGS solves: batch exceeds the largest grid");
+    REQUIRE(n >= 1, "batched L-BFGS solves: n must be ≥ 1");
+    if (int rc = check_batch_model_params(model, params, n_params)) return rc;
+    const int K = model->o.nparams();
+    bool lds = false;
+    if (rows != CGO_BATCH_ROWS_DEVICE && (rows == CGO_BATCH_ROWS_LDS || kBatchLbfgsAutoTakesLds)) {   // the tier's program: its static LDS decides the limit
+        HIPCHK2(hipSetDevice(ctx->c.device));
+        if (int rc = batch_lbfgs_lds_program(model)) return rc;
+        if (int rc = batch_lbfgs_tier(rows, n, HipBackend::batch_lbfgs_lds_max_ld(&ctx->c, CGO_OBJ_USER, m_max, model->o.rtc.get()), lds, "cgo_batch_lbfgs_max_n_obj_ex")) return rc;
+    }
+    if (int rc = batch_lbfgs_sizes_of(ctx, cgo_batch_lbfgs_max_n_obj(model), "cgo_batch_lbfgs_max_n_obj", K, n, batch, m_max)) return rc;
+    if (!lds) {   // compiled here, so that a solve never compiles
+        std::string log;
+        if (int rc = rtc_compile_batch_lbfgs(*model->o.rtc, log)) { set_error("user objective: the batched L-BFGS program did not compile:\n" + log); return rc; }
+    }
+    std::unique_ptr<cgo_batch> h(new cgo_batch);
+    h->ctx = ctx; h->n = n; h->batch = batch; h->m_max = m_max;
+    if (int rc = batch_model_cat_rows(ctx, model, batch, h->cat)) return rc;
+    h->be = new HipBackend(&ctx->c, &h->cat);
+    if (int rc = batch_backend_on(ctx, h->cat, n, batch, params, *h->be, true)) return rc;
+    if (int rc = h->be->batch_lbfgs_alloc(m_max, lds)) return rc;
+    h->model = model; model->refs++;
+    *handle = h.release();
+    return CGO_OK;
+    API_GUARD_END
+}
+
+int cgo_batch_lbfgs_m(const cgo_batch *h, int32_t *m_max) {
+    API_GUARD_BEGIN
+    REQUIRE(h && h->be && m_max, "null argument");
+    *m_max = h->m_max;
+    return CGO_OK;
+    API_GUARD_END
+}
+
+int cgo_batch_lbfgs_solve(cgo_batch *h, const double *x0, const double *scalars, const unsigned char *active, const cgo_cg_config *cfg,
+                          const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out) {
+    API_GUARD_BEGIN
+    REQUIRE(h && x0 && cfg && ls && out, "null argument");
+    out->launches = 0; out->handed_back = 0;
+    REQUIRE(h->m_max > 0, "batched L-BFGS solves: the handle was opened for the CG flavours: cgo_batch_solve");
+    if (int rc = check_batch_lbfgs_call(h->ctx, cfg, ls, h->n, h->batch, slice_iters, "cgo_batch_solve")) return rc;
+    const int m = cfg->beta.lbfgs_m;
+    if (m > h->m_max) { set_error("batched L-BFGS solves: m = " + std::to_string(m) + " exceeds the m_max = " + std::to_string(h->m_max) + " the handle was opened with"); return CGO_EINVAL; }
+    if (scalars)
+        for (int64_t b = 0; b < h->batch; ++b)
+            if (!std::isfinite(scalars[b])) { set_error("batched solves: scalars[" + std::to_string(b) + "] is not finite"); return CGO_EINVAL; }
+    if (active) {
+        bool any = false;
+        for (int64_t b = 0; b < h->batch && !any; ++b) any = active[b] != 0;
+        REQUIRE(any, "batched solves: active selects no problem");
+    }
+    HIPCHK2(hipSetDevice(h->ctx->c.device));
+    h->cat.s0 = h->model->o.s0; h->cat.user_cheap = h->model->o.user_cheap;
+    return batch_solve_on(h->ctx, *h->be, h->n, h->batch, x0, scalars, active, cfg, ls, slice_iters, out, batch_model_hobj(h->ctx, h->model),
+                          true, nullptr, h->model->o.nparams(), m);
     API_GUARD_END
 }
 

@@ -180,6 +180,7 @@ class HipBackend : public VecBackend {
     int batch_records(int64_t b, int64_t count, std::vector<ResRecord> &out);     // the trace records of problem b's first `count` iterations (b < 0: every row)
     int64_t batch_rec_stride() const { return bat_rec_stride_; }
     int batch_export_row(int64_t b, HipBackend &dst, bool with_u);                // row b of x (u), and of every parameter slot → dst
+    int batch_export_slots(int64_t b, HipBackend &dst);                           // row b of every parameter slot alone → dst's objective
     // dense rows; each may be nullptr; rows of inactive problems are not written.  With a scalar per problem the gradient is
     // k_batch_grad's (a workgroup per row), otherwise the ordinary gradient launch over the concatenated rows
     int batch_results(double *x /*[batch·n]*/, double *g /*[batch·n]*/, const unsigned char *active = nullptr);
@@ -188,7 +189,8 @@ class HipBackend : public VecBackend {
     // k_batch_lbfgs.  batch_lbfgs_reset after every batch_reset: every problem's ring empty.  A run-time compiled objective runs
     // the kernel of its module's batched L-BFGS program (cgo_rtc_batch_lbfgs.hip), which the caller compiles first.
     int batch_lbfgs_alloc(int m, bool lds = false);
-    int batch_lbfgs_reset();
+    int batch_lbfgs_reset(int m = 0);          // m: this solve's ring depth, 1 … the allocated one (0: the allocated one) — the ring keeps its stride
+    int batch_lbfgs_m() const { return bat_m_; }   // the ring depth allocated (0: not a batched L-BFGS batch)
     static int64_t batch_lbfgs_max_n();        // the limit of the pass index on n
     static int batch_lbfgs_unroll();           // pairs per lane and trip of the two ring passes
     static int batch_lbfgs_unroll_for(int nparams);   // … for an objective of that many parameter slots (run-time compiled ones)

@@ -647,6 +647,48 @@ function batch_solve!(out::CBatchResults, handle::Ptr{Cvoid}, x0::Matrix{Float64
 end
 batch_close(handle::Ptr{Cvoid}) = check(ccall((:cgo_batch_close, libcgo), Cint, (Ptr{Cvoid},), handle))
 
+# ---- … for β = LBFGS(m) (cgo_batch_lbfgs_open / _solve, include/cgo.h): the slot rows go up once, the rows and a ring of 2(m+1) rows
+# per problem stay allocated between solves.  m: the largest history length a solve! may ask for (1 … 10).  rows: :device (the
+# default), :lds or :auto — the rule of minimizeobjectivebatch_lbfgs below.  Every solve! starts every ring empty with ITS m ≤ B.m and
+# returns the bits of minimizeobjectivebatch_lbfgs_obj with the same inputs, rows and m.  ccall wrappers only, as above.
+mutable struct BatchLBFGS
+    h::Ptr{Cvoid}
+    m::Int32
+    rows::Symbol        # the tier the handle runs in: :device or :lds
+end
+function BatchLBFGS(model::DeviceObjective, params::Vector{Matrix{Float64}}, batch::Integer, m::Integer; rows::Symbol = :device)
+    haskey(BATCH_ROWS, rows) || throw(ArgumentError("rows must be :device, :lds or :auto"))
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    prows = Ptr{Float64}[pointer(p) for p in params]
+    pol = Ref(CBatchPolicy(Int32(sizeof(CBatchPolicy)), BATCH_ROWS[rows], ntuple(_ -> Int32(0), 6)))
+    GC.@preserve params begin
+        check(ccall((:cgo_batch_lbfgs_open, libcgo), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}, Int32, Int32, Ref{CBatchPolicy}, Ref{Ptr{Cvoid}}),
+                    model.ctx.h, model.h, batch, prows, length(params), m, pol, r))
+    end
+    used, mm = Ref{Int32}(0), Ref{Int32}(0)
+    check(ccall((:cgo_batch_rows, libcgo), Cint, (Ptr{Cvoid}, Ref{Int32}), r[], used))
+    check(ccall((:cgo_batch_lbfgs_m, libcgo), Cint, (Ptr{Cvoid}, Ref{Int32}), r[], mm))
+    return BatchLBFGS(r[], mm[], used[] == BATCH_ROWS[:lds] ? :lds : :device)
+end
+function solve!(out::CBatchResults, B::BatchLBFGS, x0::Matrix{Float64}, config::CGConfig, linesearch_config::LineSearchConfig;
+                scalars::Union{Nothing,Vector{Float64}} = nothing, active::Union{Nothing,Vector{UInt8}} = nothing, slice_iters::Integer = 0)
+    B.h == C_NULL && throw(ArgumentError("BatchLBFGS: closed"))
+    s = scalars === nothing ? Ptr{Float64}(C_NULL) : pointer(scalars)
+    a = active === nothing ? Ptr{UInt8}(C_NULL) : pointer(active)
+    GC.@preserve x0 scalars active begin
+        check(ccall((:cgo_batch_lbfgs_solve, libcgo), Cint,
+                    (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ref{CCGConfig}, Ref{CLSConfig}, Int64, Ref{CBatchResults}),
+                    B.h, x0, s, a, ccfg(config), cls(linesearch_config), slice_iters, out))
+    end
+    return out
+end
+function Base.close(B::BatchLBFGS)
+    h, B.h = B.h, C_NULL
+    h == C_NULL || batch_close(h)
+    return nothing
+end
+
 # ---- batched solves with β = LBFGS(m), m ≤ 10 (cgo_minimize_batch_lbfgs, include/cgo.h) ------------------------------
 # kind: CGO_OBJ_QUAD_DIAG (0, D = the n × batch matrix of diagonals), CGO_OBJ_ROSENBROCK_PAIRED (1), CGO_OBJ_BOOTH (2).  The ring of
 # 2(m+1) rows per problem lives in device memory; a problem the device loop does not finish is solved again from its own x0.

@@ -16,11 +16,17 @@ start, with its own slot rows, by the ordinary engine (`rets.handed_back`).
 Part 1 prints the one-off compile time, then the wall time of the batched call and of the loop it replaces — set the two
 parameter vectors, call minimizeobjective, 256 times on the same objective — in one process: medians of REPS repetitions after
 one untimed, with min … max.
+It also prints the same batch on a handle, `BatchLBFGS(model, [W, Y], batch, m)`: the slot rows go up once and the rows and
+the ring stay allocated, so a solve is the reset, the launches and the results — and returns the one-shot call's bits.
 Part 2 sweeps a regularisation strength PER PROBLEM through `scalars`: the same 32 data sets under 8 strengths λ_b in one call,
 
     f_b(x) = Σ_i w_bi (sqrt(1 + (x_i − y_bi)²) − 1) + ½ λ_b x_i²             (λ_b = s0 of problem b)
 
-    python examples/batch_lbfgs_fit.py [max_iters] [once] [--rows device|lds|auto] [--batch-only]
+— and, beside it, the form a sweep takes when the strengths are not known together: ONE BatchLBFGS of the 32 data sets, solved 8
+times, each time with `scalars` = one strength for all; and 8 one-shot calls of 32 problems, which upload the 32 data sets 8 times.
+
+    python examples/batch_lbfgs_fit.py [max_iters] [once] [--rows device|lds|auto] [--batch-only] [--no-loop]
+    # --no-loop: everything but the loop of 256 single solves
     # needs an MI355X; `once`: the batched call alone, one run (for a kernel trace); --rows lds: the problem's rows and ring in LDS
     # during a launch (k_batch_lbfgs_lds<UserObjective, 3>, one more program of the source), same bits
 """
@@ -44,6 +50,9 @@ if "--rows" in sys.argv:
 BATCH_ONLY = "--batch-only" in sys.argv      # (the batched call's timing alone, without the loop it replaces)
 if BATCH_ONLY:
     sys.argv.remove("--batch-only")
+NO_LOOP = "--no-loop" in sys.argv
+if NO_LOOP:
+    sys.argv.remove("--no-loop")
 max_iters = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
 config = cgo.setupCGConfig(1e-5, cgo.LBFGS(M), cgo.EnableTrace(), max_iters=max_iters)
 ls = cgo.setupStrongWolfeBisection(1e-5, 0.5)
@@ -93,6 +102,12 @@ print(f"    {rets.launches} launch(es), {rets.handed_back} handed back to the ho
 if BATCH_ONLY:
     model.close()
     sys.exit(0)
+with cgo.BatchLBFGS(model, [W, Y], BATCH, M, rows=ROWS) as handle:
+    th = timed(lambda: handle.solve(X0, config, ls))
+report(f"the same on a BatchLBFGS handle (rows uploaded once, ring kept), rows in {th[3].rows}", th, th[3])
+bits = all(np.array_equal(a.minimizer, b.minimizer) and np.array_equal(a.gradient, b.gradient) and a.objective == b.objective and
+           np.array_equal(a.trace.grad_norm, b.trace.grad_norm) for a, b in zip(th[3], rets))
+print(f"    handle against the one-shot call: {tb[0] / th[0]:.2f} x; every minimizer, gradient, objective and trace bit for bit the same: {bits}")
 
 
 def loop():
@@ -104,13 +119,14 @@ def loop():
     return out
 
 
-tl = timed(loop, reps=3)
-report(f"loop of {BATCH} minimizeobjective calls, LBFGS({M})", tl, tl[3])
-K = 5
-same = sum(np.array_equal(a.trace.step_size[:K], b.trace.step_size[:K]) for a, b in zip(rets, tl[3]))
-worst = max(float(np.max(np.abs(a.minimizer - b.minimizer))) for a, b in zip(rets, tl[3]))
-print(f"    batch against that loop: {tl[0] / tb[0]:.1f} x; the first {K} accepted steps are identical in {same} of {BATCH} fits; "
-      f"largest |x_batch − x_loop|: {worst:.2e}")
+if not NO_LOOP:
+    tl = timed(loop, reps=3)
+    report(f"loop of {BATCH} minimizeobjective calls, LBFGS({M})", tl, tl[3])
+    K = 5
+    same = sum(np.array_equal(a.trace.step_size[:K], b.trace.step_size[:K]) for a, b in zip(rets, tl[3]))
+    worst = max(float(np.max(np.abs(a.minimizer - b.minimizer))) for a, b in zip(rets, tl[3]))
+    print(f"    batch against that loop: {tl[0] / tb[0]:.1f} x; the first {K} accepted steps are identical in {same} of {BATCH} fits; "
+          f"largest |x_batch − x_loop|: {worst:.2e}")
 model.close()
 
 # ---- part 2: a regularisation strength per problem ---------------------------------------------------------------------------
@@ -128,4 +144,24 @@ for j, l in enumerate(LAMBDAS):
     rs = [ts[3][b] for b in range(len(lam)) if lam[b] == l]
     print(f"    λ = {l:6.3f}: mean |x̂| {np.mean([np.mean(np.abs(r.minimizer)) for r in rs]):.4f}, mean iterations {np.mean([r.iters_ran for r in rs]):.1f}, "
           f"largest |∇f| {max(float(np.linalg.norm(r.gradient)) for r in rs):.2e}")
+
+
+# … the same sweep as 8 solves of the 32 data sets on ONE handle, a strength for all per solve, and as 8 one-shot calls
+def by_strength(solve):
+    out = [None] * len(lam)
+    for j, l in enumerate(LAMBDAS):
+        for b, r in enumerate(solve(np.full(SETS, l))):
+            out[b * len(LAMBDAS) + j] = r
+    return out
+
+
+X0s, Ws, Ys = X0[:SETS], W[:SETS], Y[:SETS]
+with cgo.BatchLBFGS(ridge, [Ws, Ys], SETS, M, rows=ROWS) as handle:
+    tsh = timed(lambda: by_strength(lambda sc: handle.solve(X0s, config, ls, scalars=sc)))
+tso = timed(lambda: by_strength(lambda sc: cgo.minimizeobjectivebatch_lbfgs_obj(ridge, X0s, config, ls, params=[Ws, Ys], scalars=sc, rows=ROWS)))
+report(f"{len(LAMBDAS)} solves of {SETS} problems on one BatchLBFGS", tsh, tsh[3])
+report(f"{len(LAMBDAS)} one-shot calls of {SETS} problems", tso, tso[3])
+bits = all(np.array_equal(a.minimizer, b.minimizer) and np.array_equal(a.trace.grad_norm, b.trace.grad_norm) for a, b in zip(tsh[3], ts[3]))
+print(f"    one handle against the one call of {len(lam)}: {ts[0] / tsh[0]:.2f} x; against the {len(LAMBDAS)} one-shot calls: {tso[0] / tsh[0]:.2f} x; "
+      f"every problem's minimizer and trace as in the one call, bit for bit: {bits}")
 ridge.close()

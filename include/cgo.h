@@ -628,8 +628,8 @@ void cgo_batch_lbfgs_shape(int32_t *block, int32_t *pairs_per_trip);            
  * context, sharded or multi-rank; n_params other than the model's; a null params[j]), what cgo_minimize_batch_lbfgs refuses of a
  * config (a CG flavour or the Broyden family — those: cgo_minimize_batch_obj —, m > 10, Backtracking, a multi-rank context,
  * batch < 1), a scalars[b] that is not finite, n > cgo_batch_lbfgs_max_n_obj.
- * Not built: the cgo_batch handle and its `active` mask and the batched barrier method on L-BFGS, and PROBE twins
- * of this kernel (cgo_batch_probe's tiers 2 and 3 stay the built-in objectives'). */
+ * A batch that stays on the device between such solves, with an `active` mask: cgo_batch_lbfgs_open, below.
+ * Not built: PROBE twins of this kernel (cgo_batch_probe's tiers 2 and 3 stay the built-in objectives'). */
 int cgo_minimize_batch_lbfgs_obj(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *x0 /* [batch*n] */,
                                  const double *const *params /* n_params × [batch*n] */, int32_t n_params,
                                  const double *scalars /* [batch] or NULL: the model's s0 for all */,
@@ -671,6 +671,33 @@ int64_t cgo_batch_lbfgs_max_n_ex(cgo_ctx *ctx, int32_t obj_kind, int32_t m, cons
 int64_t cgo_batch_lbfgs_max_n_obj_ex(cgo_objective *model, int32_t m, const cgo_batch_policy *policy);
 int32_t cgo_batch_lbfgs_lds_rows(int32_t n_params, int32_t m);   /* 2 + K + 2(m+1); 0 for K outside 0 … 4 or m outside 1 … 10; needs no device */
 void cgo_batch_lbfgs_lds_shape(int32_t n_params, int32_t *block, int32_t *pairs_per_trip);   /* of the two ring passes over LDS; needs no device */
+/* A BATCH THAT STAYS ON THE DEVICE between L-BFGS solves: cgo_batch_open / cgo_batch_solve for β = LBFGS(m).  The handle is a
+ * cgo_batch — cgo_batch_close and cgo_batch_rows serve both kinds — but the two kinds do not mix: cgo_batch_solve on a handle
+ * opened here, and cgo_batch_lbfgs_solve on a handle of cgo_batch_open[_ex], are CGO_EINVAL with the other call's name in the message.
+ *   open   allocates what cgo_minimize_batch_lbfgs_obj_ex allocates for ring depth m_max (1 … cgo_batch_lbfgs_max_m(), else
+ *          CGO_EINVAL) — x, u, the gradient row, the K slot rows (uploaded here, once: `params` is not read afterwards) and 2(m_max+1)
+ *          ring rows per problem, checked against the free device memory before anything is allocated (CGO_ENOMEM, the bytes in the
+ *          message, nothing left allocated) — and compiles the tier's program of the model's module, so that a solve never compiles.
+ *          policy: the L-BFGS rule above (NULL / DEVICE: device rows; LDS: the LDS tier, refused with CGO_EINVAL above
+ *          cgo_batch_lbfgs_max_n_obj_ex(model, m_max, policy), that name and its value in the message; AUTO: device rows).  It
+ *          refuses what cgo_minimize_batch_lbfgs_obj_ex refuses of a model, params, batch, n, policy and context; the handle holds
+ *          a reference on the model, whose scalar and cost class are read at every solve.
+ *   solve  cfg->beta must be LBFGS(m) with 1 ≤ m ≤ m_max (a larger m: CGO_EINVAL naming both; a CG flavour or Broyden: CGO_EINVAL
+ *          pointing to cgo_batch_solve; Backtracking refused as in the one-shot call); x0, scalars and active as cgo_batch_solve
+ *          has them, refusals included.  Every solve starts every ring EMPTY with this solve's m: nothing of an earlier solve is
+ *          read, the ring keeps the stride of m_max, and the LDS tier launches with the dynamic LDS of m_max.  Every number
+ *          returned has the BITS of cgo_minimize_batch_lbfgs_obj_ex with the same inputs, tier and m.  After a refusal the
+ *          handle is what it was.
+ *   Hand-back: as in the one-shot call the problem is solved again from its own row of this solve's x0 by one ordinary solver,
+ *          under its own scalar where the solve has them, else the model's; its slot rows are copied device to device from the
+ *          handle's rows.  (The ring is not exported: a handed-back problem does not resume where it stands.)
+ *   cgo_batch_lbfgs_m: the m_max a handle was opened with; 0 for a handle of cgo_batch_open[_ex]. */
+int cgo_batch_lbfgs_open(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *const *params, int32_t n_params,
+                         int32_t m_max, const cgo_batch_policy *policy /* NULL: device rows */, cgo_batch **handle);
+int cgo_batch_lbfgs_solve(cgo_batch *handle, const double *x0 /* [batch*n] */, const double *scalars /* [batch] or NULL */,
+                          const unsigned char *active /* [batch] or NULL */, const cgo_cg_config *cfg, const cgo_ls_config *ls,
+                          int64_t slice_iters /* 0 = library policy */, cgo_batch_results *out);
+int cgo_batch_lbfgs_m(const cgo_batch *handle, int32_t *m_max);
 /* A scripted sequence of passes of a BATCHED solve in ONE launch, a workgroup per problem, on host vectors — for tests that check
  * every slot of every pass in EVERY workgroup (tests/test_batch_kernel_sums.py).  The batch is allocated as a solve allocates it
  * and the launch arguments are filled by the code that fills them for a solve (ld, the slot pointers, s0 / s0v, the ring stride,
