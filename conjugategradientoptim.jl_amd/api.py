@@ -797,8 +797,26 @@ class Solver:
         stays bit for bit.  Takes effect at the next launch."""
         check(_lib.lib().cgo_solver_set_lean_sums(self._h, int(bool(on))))
 
+    def set_path_prediction(self, on: bool):
+        """Predicted path for this solver (cgo_solver_set_path_prediction): where the replay cycle's launches N and S would run
+        their lean rows they evaluate only the steps the line search is predicted to ask for (separable quadratic, Polak–Ribière,
+        a bisection search with the Wolfe conditions; any other solver keeps its rows).  Every number a solve returns stays bit
+        for bit.  Takes effect at the next launch."""
+        check(_lib.lib().cgo_solver_set_path_prediction(self._h, int(bool(on))))
+
+    def path_stats(self):
+        """dict(by_nact={points evaluated: path launches}, predicted=, tree=, misses=) of this solver (cgo_solver_path_stats)."""
+        by = (C.c_int64 * 8)()
+        p, t, m = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(_lib.lib().cgo_solver_path_stats(self._h, by, C.byref(p), C.byref(t), C.byref(m)))
+        return dict(by_nact={j: int(by[j]) for j in (1, 2, 3, 4, 5, 7)}, predicted=p.value, tree=t.value, misses=m.value)
+
+    def debug_set_path_skew(self, factor: float):
+        """Tests only: a factor on the predicted path's curvature model (cgo_solver_debug_set_path_skew)."""
+        check(_lib.lib().cgo_solver_debug_set_path_skew(self._h, float(factor)))
+
     def probe_launch(self, kind_name: str, variant: int, a_acc: float, beta: float, a: Sequence[float], x, u=None, aux=None,
-                     beta_prev: Optional[float] = None, replay: Optional[Sequence] = None):
+                     beta_prev: Optional[float] = None, replay: Optional[Sequence] = None, path_nact: Optional[int] = None):
         """ONE launch of kind `kind_name` with mode bits `variant` on this rank's host vectors (cgo_solver_probe_launch): returns
         dict(sums=the whole reduced row, x=, u=, g= the vectors after the launch, symbol=the instantiation).  A test entry point:
         the solver is for probing only from the first call on.
@@ -818,6 +836,8 @@ class Solver:
             ra = np.ascontiguousarray([p[0] for p in replay], dtype=np.float64)
             rb = np.ascontiguousarray([p[1] for p in replay], dtype=np.float64)
             check(L.cgo_solver_probe_set_replay(self._h, len(replay), ra.ctypes.data_as(dp), rb.ctypes.data_as(dp)))
+        if path_nact is not None:   # a lean row as its path twin k_cg_path<…, path_nact, true> (this launch only)
+            check(L.cgo_solver_probe_set_path(self._h, int(path_nact)))
         n = self.obj.n_local
         vec = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float64)
         x, u, aux = vec(x), vec(u), vec(aux)

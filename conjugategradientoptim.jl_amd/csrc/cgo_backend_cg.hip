@@ -4,6 +4,7 @@
 
 #include "cgo_kernels.hip.hpp"
 #include "cgo_kernels_cg.hip.hpp"
+#include "cgo_kernels_cg_path.hip.hpp"
 #include "cgo_kernels_chain.hip.hpp"
 #include "cgo_kernels_lse.hip.hpp"
 #include "cgo_kernels_resident.hip.hpp"
@@ -56,6 +57,34 @@ static int launch_cg(int mode, int npts, const RParams &P, int grid, hipStream_t
     return -1;
 }
 
+// the path rows of cgo_instances.def (k_cg_path: pure-HBM streaming, the 7-point row, `nact` points evaluated); -1: no such row
+template <class Obj>
+static int launch_cg_path(int mode, int nact, const RParams &P, int grid, hipStream_t st) {
+#define ROW(MODE, NACT) if (mode == (MODE) && nact == (NACT)) { k_cg_path<Obj, (MODE), (NACT), true><<<grid, BLOCK, 0, st>>>(P); return 0; }
+    CGO_CG_PATH_ROWS(ROW)
+#undef ROW
+    return -1;
+}
+static inline bool path_row(int mode, int nact) {
+#define ROW(MODE, NACT) if (mode == (MODE) && nact == (NACT)) return true;
+    CGO_CG_PATH_ROWS(ROW)
+#undef ROW
+    return false;
+}
+static inline bool path_objective(int kind) {   // the objectives that declare a constant Hessian (ObjCurv)
+#define ROW(KIND, T) if (kind == KIND) return true;
+    CGO_OBJ_CURV_ROWS(ROW)
+#undef ROW
+    return false;
+}
+// Predicted path: launches N and S of this solver run as path launches — where the switch is on, the replay
+// cycle runs, and both would otherwise run their lean rows.
+bool HipBackend::path_rows() const {
+    if (!path_on_ || !path_objective(obj_->kind) || replay_depth_ < 2 || !lazy_eligible()) return false;
+    const int mode_n = r_mode_of(KK_ACCEPT_TRIAL_NOSTORE), mode_s = R_REPLAY | R_ADT;
+    return path_row(mode_n | lean_for(mode_n), MAXP) && path_row(mode_s | lean_for(mode_s), MAXP);
+}
+
 // Lean sums: the R_NO… bits to or into `mode` — those of the solver's β flavour where the table has that row.
 static inline bool lean_row(int mode) {
 #define ROW(MODE, MAXPTS) if (mode == (MODE)) return true;
@@ -103,7 +132,7 @@ int HipBackend::launch_r(int kk, int mode, double a_acc, double beta, const doub
     // gets both vectors stored first.
     if (rep_n_ > 0 && !(mode & R_REPLAY)) { if (int rc = materialize_lag()) return rc; }
     RPlan plan;
-    const int npts = npts_for(k);
+    const int npts = path_nact_ ? MAXP : npts_for(k);   // a path launch fills the 7-point row whatever k
     if (int rc = launch_r_kernel(kk, mode, a_acc, beta, a, k, npts, nullptr, &plan)) return rc;
     const int grid = plan.grid;
     total_launches_++;
@@ -159,7 +188,10 @@ bool HipBackend::lazy_eligible() const {
 int HipBackend::materialize_u() {
     if (!u_lag_) return CGO_OK;
     const int64_t asked = total_launches_;
+    const int nact = path_nact_;   // (met on the way to a path launch: this pass is not one)
+    path_nact_ = 0;
     const int rc = launch_rk(KK_MATERIALIZE_U, 0.0, 0.0, nullptr, 0, false, nullptr);
+    path_nact_ = nact;
     total_launches_ = asked;
     if (rc) return rc;
     u_lag_ = false;
@@ -173,7 +205,10 @@ int HipBackend::materialize_lag() {
     if (int rc = materialize_u()) return rc;
     if (rep_n_ == 0) return CGO_OK;
     const int64_t asked = total_launches_;
+    const int nact = path_nact_;
+    path_nact_ = 0;
     const int rc = launch_rk(KK_MATERIALIZE_XU, 0.0, 0.0, nullptr, 0, false, nullptr);
+    path_nact_ = nact;
     total_launches_ = asked;
     if (rc) return rc;
     rep_n_ = 0;
@@ -201,12 +236,14 @@ int HipBackend::accept_dir_trial_r(double a_acc, double beta, const double *a, i
         if (rep_n_ < replay_depth_ - 1 && rep_n_ < RMAX) {   // launch N: the new pair in registers only
             const int mode_n = r_mode_of(KK_ACCEPT_TRIAL_NOSTORE);
             if (int rc = launch_r(KK_ACCEPT_TRIAL_NOSTORE, mode_n | lean_for(mode_n), a_acc, beta, a, k, true, s)) return rc;
+            if (path_nact_) { path_last_n_ = path_nact_; path_count_[path_nact_]++; }
             rep_a_[rep_n_] = a_acc; rep_b_[rep_n_] = beta; rep_n_++;
             return CGO_OK;
         }
         // launch S: replays the outstanding steps, then today's launch
         const int mode_s = R_REPLAY | R_ADT;
         if (int rc = launch_r(KK_ACCEPT_DIR_TRIAL, mode_s | lean_for(mode_s), a_acc, beta, a, k, true, s)) return rc;
+        if (path_nact_) { path_last_s_ = path_nact_; path_count_[path_nact_]++; }
         rep_n_ = 0;
         return CGO_OK;
     }
@@ -261,7 +298,8 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
     const bool has_sums = r_has_sums(mode);
     const RPlan plan = *plan_out = r_plan(mode, npts);
     const bool big = plan.big; const int grid = plan.grid;
-    last_mode_ = mode; last_npts_ = plan.npts; last_big_ = big;
+    last_mode_ = mode; last_npts_ = plan.npts; last_big_ = big; last_nact_ = path_nact_;
+    if (path_nact_ && (chain() || !big || ctl || !path_row(mode, path_nact_) || !path_objective(obj_->kind))) { set_error("internal: not a path row"); return CGO_EINVAL; }
     if (chain()) {
         if (int rc = prof_begin(kk)) return rc;
         if (int rc = launch_chain_kernel(mode, a_acc, beta, a, k, plan.npts, big, grid, make_tail(has_sums && !ctl && tail_fused(grid)))) return rc;
@@ -296,7 +334,14 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
     hipStream_t st = ctx_->stream;
     if (int rc = prof_begin(kk)) return rc;
     int r = -2;
-    switch (obj_->kind) {
+    if (path_nact_) {
+        switch (obj_->kind) {
+#define ROW(KIND, T) case KIND: r = launch_cg_path<T>(mode, path_nact_, P, grid, st); break;
+        CGO_OBJ_CURV_ROWS(ROW)
+#undef ROW
+        default: break;
+        }
+    } else switch (obj_->kind) {
 #define ROW(KIND, T) case KIND: r = big ? launch_cg<T, true>(mode, npts, P, grid, st) : launch_cg<T, false>(mode, npts, P, grid, st); break;
     CGO_OBJ_ROWS(ROW)
 #undef ROW
@@ -349,9 +394,10 @@ int HipBackend::launch_chain_kernel(int mode, double a_acc, double beta, const d
 }
 
 // A k_cg / k_chain instantiation as rocprofv3 prints it minus namespaces.
-std::string HipBackend::r_symbol(int mode, int npts, bool big) const {
+std::string HipBackend::r_symbol(int mode, int npts, bool big, int nact) const {
     char buf[160];
     if (chain()) snprintf(buf, sizeof buf, "k_chain<%d, %d, %s>", mode, npts, big ? "true" : "false");
+    else if (nact) snprintf(buf, sizeof buf, "k_cg_path<%s, %d, %d, true>", obj_tname(), mode, nact);
     else snprintf(buf, sizeof buf, "k_cg<%s, %d, %d, %s>", obj_tname(), mode, npts, big ? "true" : "false");
     return buf;
 }
@@ -376,6 +422,10 @@ std::string HipBackend::kernel_symbol(int kk) const {
     }
     const RPlan plan = r_plan(mode, rk->pts == PTS_ONE ? 1 : npts_for(rk->pts == PTS_MAX ? max_points() : std::min(max_points(), 3)));
     if ((mode & R_REPLAY) && (mode & R_ACCEPT)) mode |= lean_for(mode);   // N and S: the lean row where that is what runs
+    if ((mode & R_REPLAY) && (mode & R_ACCEPT) && path_rows()) {   // … or the path row that last ran for the kind (none yet: the tree's)
+        const int last = kk == KK_ACCEPT_TRIAL_NOSTORE ? path_last_n_ : path_last_s_;
+        return r_symbol(mode, plan.npts, plan.big, last ? last : MAXP);
+    }
     return r_symbol(mode, plan.npts, plan.big);
 }
 
@@ -757,6 +807,8 @@ int HipBackend::probe_launch(int kk, int variant, double a_acc, double beta, con
                              const double *u, const double *aux, double *sums, int sums_cap, int *sums_len, double *x_out,
                              double *u_out, double *g_out, std::string &symbol) {
     *sums_len = 0;
+    const int want_nact = probe_nact_;   // a lean row as its path twin (cgo_solver_probe_set_path): asked once, for this call
+    probe_nact_ = 0;
     const bool lse = obj_->two_phase();
     if (k < 0 || k > MAXP || (k > 0 && !a)) { set_error("probe: 0 ≤ k ≤ 7 trial steps"); return CGO_EINVAL; }
     if (!rmode_ && !lse) return probe_launch_stored(kk, variant, a_acc, beta, a, k, x, u, aux, sums, sums_cap, sums_len, x_out, u_out, g_out, symbol);
@@ -830,10 +882,15 @@ int HipBackend::probe_launch(int kk, int variant, double a_acc, double beta, con
         symbol = buf;
     } else {
         double s[64];
+        if (want_nact) {
+            if (!path_row(mode, want_nact) || !path_objective(obj_->kind) || k > want_nact) { rep_n_ = 0; set_error("probe: not a path row of this solver, or more steps than it evaluates"); return CGO_EINVAL; }
+            path_nact_ = want_nact;
+        }
         rc = launch_r(kk, mode, a_acc, beta, a, k, true, s);
+        path_nact_ = 0;
         rep_n_ = 0;
         if (rc) return rc;
-        symbol = r_symbol(last_mode_, last_npts_, last_big_);
+        symbol = r_symbol(last_mode_, last_npts_, last_big_, last_nact_);
     }
     HIPCHK(hipStreamSynchronize(st));
     if (x_out) HIPCHK(hipMemcpyAsync(x_out, xc_, nb, hipMemcpyDeviceToHost, st));

@@ -379,8 +379,10 @@ int cgo_ctx_set_default_policy(cgo_ctx *ctx, const cgo_solver_policy *policy) {
 }
 
 // explicit argument > context default > CGO_* experiment override > library policy, field by field
-static const int kReplayDepth = 6;   // best median of 1, 2, 3, 4, 6, 8 on one MI355X at n = 1e8: BASELINE.md, profiles/r06_replay_*
+static const int kReplayDepth = 8;   // 6 was the best median of 1, 2, 3, 4, 6, 8 on one MI355X at n = 1e8 (profiles/r06_replay_*) while a replayed
+                                     // step cost seven trial points of arithmetic; with the predicted path 8 is + 3.8 % over 6 (profiles/r09_path_*)
 static const bool kLeanSums = true;   // lean sums where replay's default is on: BASELINE.md, profiles/r07_lean_*
+static const bool kPathPredict = true;   // predicted path where lean sums' default is on: DESIGN.md §4
 static int env_tri(const char *name) { const char *e = getenv(name); return e ? (e[0] != '0' ? 1 : 0) : -1; }
 static int resolve_policy(cgo_ctx *ctx, const cgo_solver_policy *arg, cgo_solver_policy &r, std::string &why) {
     cgo_solver_policy lib; cgo_solver_policy_init(&lib);
@@ -459,6 +461,13 @@ int cgo_solver_get_policy(cgo_solver *s, cgo_solver_policy *out) {
 }
 
 // ---- solver -----------------------------------------------------------------
+// the configurations the curvature model of the predicted path covers (cgo_path.hpp: ls_predicted_path; Solver::path_points)
+static bool path_applies(const cgo_objective *obj, const cgo_cg_config *cfg, const cgo_ls_config *ls) {
+    if (!ls || obj->o.kind != CGO_OBJ_QUAD_DIAG || cfg->beta.kind != CGO_BETA_POLAK_RIBIERE) return false;
+    if (ls->kind == CGO_LS_STRONG_WOLFE_BISECTION) return true;
+    return ls->kind == CGO_LS_WOLFE_BISECTION && ls->cond_kind == CGO_COND_WOLFE;
+}
+
 static int make_solver(cgo_ctx *ctx, cgo_objective *obj, const cgo_cg_config *cfg, const cgo_ls_config *ls,
                        const cgo_lss_config *lss, const cgo_solver_policy *policy, cgo_solver **out) {
     *out = nullptr;
@@ -567,6 +576,17 @@ static int make_solver(cgo_ctx *ctx, cgo_objective *obj, const cgo_cg_config *cf
         if (forced >= 0) lean = forced != 0;
         s->be->set_beta_unread(beta_unread_sums(cfg->beta.kind));
         s->be->set_lean_sums(lean);
+    }
+    // Predicted path: where launches N and S would run their lean rows they evaluate the steps the line search
+    // is predicted to ask for instead of the whole tree, from a curvature model that is exact for a constant Hessian.  Library
+    // policy: on exactly where lean sums are on by the library's own default (not where replay or lean sums are merely forced).
+    // CGO_PATH_PREDICT=0|1 forces the switch; cgo_solver_set_path_prediction has the last word.  It takes effect only for an
+    // objective that declares a constant Hessian, Polak–Ribière and a bisection line search with the plain Wolfe conditions.
+    {
+        bool predict = kPathPredict && kLeanSums && obj->o.kind == CGO_OBJ_QUAD_DIAG && 8.0 * (double)obj->o.n_local * 5.0 > 1.4e9;
+        const int forced = env_tri("CGO_PATH_PREDICT");
+        if (forced >= 0) predict = forced != 0;
+        s->be->set_path_prediction(predict && path_applies(obj, cfg, ls));
     }
     if (int prc = s->be->place()) { delete s; obj_unref(obj); return prc; }
     if (pol.resident >= 0) s->be->set_resident(pol.resident != 0);
@@ -796,6 +816,46 @@ int cgo_solver_set_lean_sums(cgo_solver *s, int32_t on) {
     API_GUARD_BEGIN
     REQUIRE(s, "null argument");
     s->be->set_lean_sums(on != 0);
+    return CGO_OK;
+    API_GUARD_END
+}
+
+int cgo_solver_set_path_prediction(cgo_solver *s, int32_t on) {
+    API_GUARD_BEGIN
+    REQUIRE(s, "null argument");
+    const bool applies = s->sv && !s->sv->is_sys() && path_applies(s->obj, &s->sv->config(), &s->sv->linesearch());
+    s->be->set_path_prediction(on != 0 && applies);   // (any other configuration keeps its rows)
+    return CGO_OK;
+    API_GUARD_END
+}
+
+int cgo_solver_path_stats(cgo_solver *s, int64_t *by_nact, int64_t *predicted, int64_t *tree, int64_t *misses) {
+    API_GUARD_BEGIN
+    REQUIRE(s && s->sv, "null argument");
+    if (by_nact) for (int j = 0; j < 8; ++j) by_nact[j] = s->be->path_launches(j);
+    int64_t p = 0, t = 0, m = 0;
+    s->sv->path_stats(p, t, m);
+    if (predicted) *predicted = p;
+    if (tree) *tree = t;
+    if (misses) *misses = m;
+    return CGO_OK;
+    API_GUARD_END
+}
+
+int cgo_solver_debug_set_path_skew(cgo_solver *s, double factor) {
+    API_GUARD_BEGIN
+    REQUIRE(s && s->sv, "null argument");
+    REQUIRE(factor > 0.0 && std::isfinite(factor), "path skew: a positive factor");
+    s->sv->set_path_skew(factor);
+    return CGO_OK;
+    API_GUARD_END
+}
+
+int cgo_solver_probe_set_path(cgo_solver *s, int32_t nact) {
+    API_GUARD_BEGIN
+    REQUIRE(s, "null argument");
+    REQUIRE(nact >= 0 && nact <= 7, "probe path row: 0 … 7 active points");
+    s->be->set_probe_path(nact);
     return CGO_OK;
     API_GUARD_END
 }

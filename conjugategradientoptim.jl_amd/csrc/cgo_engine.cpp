@@ -186,6 +186,8 @@ int Solver::start() {
     qn_trial_done_ = false;
     res_fail_streak_ = 0; res_backoff_ = 0;
     tr_f_.clear(); tr_g_.clear(); tr_a_.clear(); tr_e_.clear(); log_.clear();
+    path_part_ = false; path_reset_ = false;
+    path_pred_ = 0; path_tree_ = 0; path_miss_ = 0;
     return CGO_OK;
 }
 
@@ -194,6 +196,7 @@ void Solver::finish(int64_t iters, int status) {
     status_ = status;
     finished_ = true;
     ncache_ = 0;
+    path_part_ = false;
     qn_trial_done_ = false;
     be_->discard_pending();   // (every committed update has run by now: the direction pass that carries a deferred one belongs to the same iteration)
     if (cfg_.trace_enabled) {  // resizetrace!(ret.trace, i)  types.jl:129,148
@@ -217,8 +220,23 @@ int Solver::evaln(double a, double &phi, double &dphi, const double *hs, int nh)
     int hit = -1;
     for (int j = 0; j < ncache_; ++j)
         if (std::memcmp(&a, &cache_[j].a, sizeof(double)) == 0) { hit = j; break; }
+    int in_tree = -1;   // a step of the tree that a path launch left out: the prediction missed
+    if (hit < 0 && path_part_)
+        for (int j = 0; j < ntree_; ++j)
+            if (std::memcmp(&a, &tree_[j], sizeof(double)) == 0) { in_tree = j; break; }
     if (hit >= 0) {
         last_ = cache_[hit].s;
+    } else if (in_tree >= 0) {
+        // The whole tree in one trial launch: the row, grid and chains of the launch that left these points out, so every sum
+        // has the bits that launch would have formed, and the search goes on as if it had.  (No curvature: the next launch
+        // evaluates its whole tree.)
+        Scal out[7];
+        if (int rc = be_->trial(tree_, ntree_, out)) return rc;
+        ncache_ = ntree_;
+        for (int j = 0; j < ntree_; ++j) cache_[j] = {tree_[j], out[j]};
+        last_ = out[in_tree];
+        path_part_ = false;
+        path_miss_++;
     } else {
         double pts[7] = {a, 0, 0, 0, 0, 0, 0};
         int k = 1;
@@ -291,6 +309,7 @@ int Solver::ls_wolfe_bisection(double a_initial, LSOut &o) {
             // The line search itself keeps its by-value copy of dϕ₀ (not recomputed, wolfe.jl:125-129).
             s->dphi0_ = sc.gu;
             s->dir_is_neg_grad_ = true;
+            s->path_part_ = false; s->path_reset_ = true;   // the tree belonged to the old direction; the curvature model to its dϕ₀
             return 0;
         }
     } bk{this};
@@ -467,12 +486,14 @@ int Solver::iterate(int64_t iters, bool &finished) {
             --res_backoff_;
         }
         host_next = false;
+        path_reset_ = false;
         LSOut o{};
         int rc = (ls_.kind == CGO_LS_STRONG_WOLFE_BISECTION) ? ls_strong_wolfe(a_initial_, o)
                  : (ls_.kind == CGO_LS_WOLFE_BISECTION)      ? ls_wolfe_bisection(a_initial_, o)
                                                              : ls_backtracking(a_initial_, o);
         if (rc) return rc;
         ncache_ = 0;  // x, u are about to change (or the solve ends): cached trials are void
+        path_part_ = false;
         a_initial_ = o.a;                                              // optim.jl:92
         if (o.status != CGO_SUCCESS) { finish(n - 1, o.status); break; }  // optim.jl:93-104
         // Two-phase objective: g⁺ of the accepted step was not written during the line search.  Under the Gram form of L-BFGS
@@ -601,6 +622,9 @@ int Solver::iterate(int64_t iters, bool &finished) {
                 for (int j = 0; j < CTL_MAXP; ++j) cs.a[j] = pts[j < k ? j : k - 1];
                 cs.npts = k; cs.go = 1; cs.it = it_;
                 rc = be_->accept_dir_trial_ctl(cc, cs, budget, out);   // (the fused launch of the slice's last iteration included)
+            } else if (be_->path_rows() && k >= 6) {   // (a tree of fewer points runs on a narrower row: other bits)
+                k = path_points(a_xp, beta, pts, k);
+                rc = be_->accept_dir_trial_path(a_xp, beta, pts, k, out);
             } else {
                 rc = be_->accept_dir_trial(a_xp, beta, pts, k, out);
             }
@@ -613,6 +637,42 @@ int Solver::iterate(int64_t iters, bool &finished) {
     }
     finished = finished_;
     return CGO_OK;
+}
+
+// Predicted path (the formulas: cgo_path.hpp).  The step a* = a_xp of iteration k has just been accepted with the
+// sums `last_` at its point, dphi0_ is still dϕ₀ of u_k and β is decided.  Along u_{k+1} = −g⁺ + β·u_k, for a constant Hessian H:
+//   c_k       = (g⁺·u_k − dϕ₀_k) / a*                    (H u_k = y / a*)
+//   dϕ₀_{k+1} = −g⁺·g⁺ + β·g⁺·u_k
+//   c_{k+1}   = g⁺ᵀH g⁺ − 2β·y·g⁺/a* + β²·c_k
+// pts[0..k) holds the tree; the result is the launch's points: the steps of the predicted path as far as the tree holds them
+// (a step outside it is a trial launch with or without the prediction), or the whole tree where there is no valid model.  Either
+// way every point is one of the tree's, so the search sees the sums it would have seen.
+int Solver::path_points(double a_xp, double beta, double (&pts)[7], int k) {
+    ntree_ = k;
+    for (int j = 0; j < 7; ++j) tree_[j] = pts[j];
+    path_part_ = false;
+    int kp = 0;
+    double pp[7] = {0, 0, 0, 0, 0, 0, 0};
+    if (cfg_.beta.kind == CGO_BETA_POLAK_RIBIERE && !path_reset_ && std::isfinite(last_.curv) && std::isfinite(beta) &&
+        std::isfinite(a_xp) && a_xp > 0.0 && std::isfinite(dphi0_) && std::isfinite(last_.gtu) && std::isfinite(last_.gtgt) &&
+        std::isfinite(last_.ygt) && std::isfinite(f_x_)) {
+        const double c_k = (last_.gtu - dphi0_) / a_xp;
+        const double d1 = -last_.gtgt + beta * last_.gtu;
+        const double c1 = (last_.curv - 2.0 * beta * last_.ygt / a_xp + beta * beta * c_k) * path_skew_;
+        kp = ls_predicted_path(ls_, f_x_, d1, c1, a_initial_, pp);   // (0 unless every input is finite, c1 > 0 and d1 < 0)
+    }
+    int ka = 0;
+    for (int j = 0; j < kp; ++j) {
+        bool held = false;
+        for (int q = 0; q < k; ++q) held = held || std::memcmp(&pp[j], &tree_[q], sizeof(double)) == 0;
+        if (!held) break;
+        pp[ka++] = pp[j];
+    }
+    if (ka == 0 || std::memcmp(&pp[0], &tree_[0], sizeof(double)) != 0) { path_tree_++; return k; }
+    for (int j = 0; j < 7; ++j) pts[j] = j < ka ? pp[j] : 0.0;
+    path_part_ = ka < k;
+    path_pred_++;
+    return ka;
 }
 
 // ---- batched solves -----------------------------------------------------------------------------------------------------

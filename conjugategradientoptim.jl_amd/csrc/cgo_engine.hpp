@@ -18,6 +18,7 @@
 
 #include "../../include/cgo.h"
 #include "cgo_ctl.hpp"
+#include "cgo_path.hpp"
 #include "cgo_resident.hpp"
 
 namespace cgo {
@@ -35,6 +36,8 @@ struct Scal {
     // direction part, for the freshly updated u and the current g
     double gu = 0;    // dϕ₀ = g·u                    nocedal.jl:56, wolfe.jl:40
     double uu = 0;    // u·u                          wolfe.jl:240
+    // path launches only (predicted path): g⁺ᵀH g⁺ of the trial point; NaN: the launch carried no curvature
+    double curv = NAN;
 };
 
 enum KernelKind : int {
@@ -100,6 +103,11 @@ struct VecBackend {
     virtual int trial(const double *a, int k, Scal *out) = 0;
     // x += a_acc·u; g ← g⁺; u = −g + β·u → gu, uu (in out[0]); then the k trials as above
     virtual int accept_dir_trial(double a_acc, double beta, const double *a, int k, Scal *out) = 0;
+    // Predicted path.  path_rows(): this backend can run the accept + direction + trial launch of this solver as
+    // a path launch — the 7-point row with only the first k points evaluated, the same bits as the 7-point launch gives for them,
+    // and out[j].curv filled.  accept_dir_trial_path is that launch; k = 7 is the whole tree with its curvature sums.
+    virtual bool path_rows() const { return false; }
+    virtual int accept_dir_trial_path(double a_acc, double beta, const double *a, int k, Scal *out) { return accept_dir_trial(a_acc, beta, a, k, out); }
     // On-device controller (cgo_ctl.hpp).  ctl_depth() > 0: accept_dir_trial_ctl runs the launch
     // described by `s` like accept_dir_trial, and may run up to `rounds` − 1 FURTHER launches ahead
     // of the host, each armed by ctl_step() on the device from the previous launch's sums; later
@@ -233,6 +241,10 @@ class Solver {
     const cgo_cg_config &config() const { return cfg_; }
     const cgo_ls_config &linesearch() const { return ls_; }
     bool is_sys() const { return sys_; }
+    // Predicted path: launches that evaluated a predicted path / the whole tree on a path row, and line searches
+    // that asked for a step of the tree the launch had left out (answered by a trial launch of the tree).
+    void path_stats(int64_t &predicted, int64_t &tree, int64_t &misses) const { predicted = path_pred_; tree = path_tree_; misses = path_miss_; }
+    void set_path_skew(double f) { path_skew_ = f; }   // tests only: a factor on the model's curvature, to force wrong predictions
     // A solve a batched launch started and advanced by s.it > 0 iterations continues on this engine (its backend holds the
     // problem's x and u): in place of start().  evals: evalϕdϕ! calls of those iterations; recs: their s.it records.
     void resume(double f_x0, int64_t evals, const ResState &s, const ResRecord *recs);
@@ -297,6 +309,14 @@ class Solver {
     std::vector<int64_t> tr_e_;
     std::vector<TrialRecord> log_;
     bool log_on_ = false;
+    // predicted path: the tree of the launch in flight (what the launch would have evaluated without a prediction), whether the
+    // launch evaluated only a part of it, whether the line search reset its direction (the model's dϕ₀ is then void)
+    double tree_[7] = {};
+    int ntree_ = 0;
+    bool path_part_ = false, path_reset_ = false;
+    double path_skew_ = 1.0;
+    int64_t path_pred_ = 0, path_tree_ = 0, path_miss_ = 0;
+    int path_points(double a_xp, double beta, double (&pts)[7], int k);   // the launch's points: the predicted part of the tree, or the tree
 };
 
 // Batched solves: `batch` independent problems under ONE cfg and ls, a workgroup each (VecBackend::batch_launch), launched until

@@ -874,6 +874,19 @@ int HipBackend::accept_dir_trial(double a_acc, double beta, const double *a, int
     return CGO_OK;
 }
 
+// … as a path launch: the 7-point row whatever k, the curvature sums in the y·y slots (which a lean row leaves +0.0)
+int HipBackend::accept_dir_trial_path(double a_acc, double beta, const double *a, int k, Scal *out) {
+    if (!path_rows()) return accept_dir_trial(a_acc, beta, a, k, out);
+    double s[NR7];
+    path_nact_ = k <= 5 ? std::max(k, 1) : MAXP;   // the smallest row that holds k points (cgo_instances.def: 1 … 5, 7)
+    const int rc = accept_dir_trial_r(a_acc, beta, a, k, s);
+    path_nact_ = 0;
+    if (rc) return rc;
+    unpack_r(s, k, out, true, MAXP);
+    for (int j = 0; j < k; ++j) { out[j].curv = out[j].yy; out[j].yy = 0.0; }
+    return CGO_OK;
+}
+
 int HipBackend::accept_dir(double a_acc, double beta, Scal &out) {
     if (rmode_) {
         double s[NR7];

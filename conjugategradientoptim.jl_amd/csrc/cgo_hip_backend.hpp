@@ -267,6 +267,15 @@ class HipBackend : public VecBackend {
     void set_beta_unread(int bits) { lean_mask_ = bits; if (lean_bits_) lean_bits_ = bits; }
     void set_lean_sums(bool on) { lean_bits_ = on ? lean_mask_ : 0; }
     bool lean_sums() const { return lean_bits_ != 0; }
+    // Predicted path: where launches N and S would run their lean rows, they run as path launches (k_cg_path) —
+    // the first k trial points of the 7-point row and the curvature sums.  Objectives with a constant Hessian only (ObjCurv); the
+    // stored state is the same either way.
+    void set_path_prediction(bool on) { path_on_ = on; }
+    bool path_prediction() const { return path_on_; }
+    bool path_rows() const override;
+    int accept_dir_trial_path(double a_acc, double beta, const double *a, int k, Scal *out) override;
+    int64_t path_launches(int nact) const { return (nact >= 1 && nact <= 7) ? path_count_[nact] : 0; }
+    void set_probe_path(int nact) { probe_nact_ = nact; }   // the next probe_launch of a lean row runs as that path row (0: the lean row)
     std::string kernel_symbol(int kernel_kind) const;
     // Test entry point (cgo_solver_probe_launch): the vectors → this solver's device state, ONE launch of kind `kernel_kind`
     // with mode bits `variant` through the engine's own launch path, the whole reduced row and the vectors back.  The first
@@ -333,7 +342,7 @@ class HipBackend : public VecBackend {
     bool last_big_ = false;
     int probe_prepare();
     int probe_slack_intact();
-    std::string r_symbol(int mode, int npts, bool big) const;
+    std::string r_symbol(int mode, int npts, bool big, int nact = 0) const;
     std::string probe_syms_;   // probe_lbfgs: every instantiation its pass launched (probe_note)
     void probe_note(const double *row, int len, const char *fmt, ...);
     int probe_ring_slack_intact();
@@ -383,6 +392,12 @@ class HipBackend : public VecBackend {
     int materialize_lag();   // … and the replayed pair (x, u) likewise; clears u_lag_ and rep_n_
     int lean_mask_ = 0, lean_bits_ = 0;   // the flavour's R_NO… bits; those in force (0: full rows)
     int lean_for(int mode) const;         // … for this mode: lean_bits_ where a lean row exists, else 0
+    // predicted path: the switch; NACT of the path launch being issued (0: an ordinary launch) and of the last launch; the last
+    // path row launches N and S ran as; launches by NACT
+    bool path_on_ = false;
+    int path_nact_ = 0, last_nact_ = 0, probe_nact_ = 0;
+    int path_last_n_ = 0, path_last_s_ = 0;
+    int64_t path_count_[8] = {};
     int accept_dir_trial_r(double a_acc, double beta, const double *a, int k, double *s);
     int trial_r(const double *a, int k, double *s);
     int launch_r_kernel(int kk, int mode, double a_acc, double beta, const double *a, int k, int npts,

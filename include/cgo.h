@@ -771,6 +771,28 @@ typedef struct cgo_batch_probe_args {
 } cgo_batch_probe_args;
 int cgo_batch_probe(cgo_ctx *ctx, cgo_batch_probe_args *p);
 int64_t cgo_batch_probe_qn_bytes(void);                                           /* sizeof(QnState): what a mirror of it must measure */
+/* Predicted path.  For an objective with a constant Hessian the curvature along the NEXT direction is known
+ * before the launch that forms it — from sums the accepting launch returns plus one more, g⁺ᵀH g⁺ — and the line search run over
+ * the parabola ϕ(a) = f + a·dϕ₀ + ½a²·c lists the steps the real search will ask for.  With prediction on, launches N and S of the
+ * replay cycle run as path launches ("k_cg_path<Obj, mode, NACT, true>" in the reported symbol) wherever they would run their lean rows:
+ * the 7-point row with only the first NACT points evaluated — the steps of the predicted path that the seven-point tree holds —
+ * the other points' slots +0.0, g⁺ᵀH g⁺ in the slot of y·y.  An evaluated point has the bits the seven-point launch gives it and
+ * every decision is taken on sums a launch formed, so a solve returns what it returns with prediction off, bit for bit; a search
+ * that asks for a step of the tree the launch left out gets the whole tree from one trial launch (counted as a miss).  Kernel
+ * kinds and bytes per launch are unchanged.  It takes effect for the separable quadratic, Polak–Ribière and StrongWolfeBisection or
+ * WolfeBisection with the Wolfe conditions; any other solver keeps its rows whatever is asked.  Library policy: on exactly where
+ * lean sums are on by the library's own default; env CGO_PATH_PREDICT=0|1 forces the switch; this call has the last word for one
+ * solver and takes effect at the next launch. */
+int cgo_solver_set_path_prediction(cgo_solver *s, int32_t on);
+/* by_nact[8]: path launches by points evaluated (index 1 … 5, 7); predicted / tree: launches that evaluated a predicted path / the
+ * whole tree on a path row; misses: line searches answered by a trial launch of the tree.  Any pointer may be null. */
+int cgo_solver_path_stats(cgo_solver *s, int64_t *by_nact, int64_t *predicted, int64_t *tree, int64_t *misses);
+/* The NEXT cgo_solver_probe_launch of a lean row (launch N or S of the replay cycle, variant with the R_NO… bits) runs as its path
+ * twin k_cg_path<Obj, mode, nact, true> (cgo_solver_set_path_prediction): nact = 1 … 5 or 7 active points, at most nact trial steps.
+ * 0 takes the request back.  Asked once per launch. */
+int cgo_solver_probe_set_path(cgo_solver *s, int32_t nact);
+/* Tests only: a factor on the curvature of the predicted path's model (1.0: the model as it is), so that predictions go wrong. */
+int cgo_solver_debug_set_path_skew(cgo_solver *s, double factor);
 /* CGO_HOST_ONLY_END */
 /* The stop test at the top of iteration it + 1 (optim.jl:53-80,162-169) as a function of the loop state — the one rule the
  * engine and the problems a batch finishes on the device share: the terminal status (CGO_INCOMPLETE: the iteration runs) and
