@@ -1175,11 +1175,29 @@ class _BatchOut:
         return out
 
 
-def _batch_rows(name: str, v, shape) -> np.ndarray:
+def _batch_rows(name: str, v, shape, msg: Optional[str] = None) -> np.ndarray:
     a = np.ascontiguousarray(np.asarray(v, dtype=np.float64))
     if a.shape != tuple(shape):
-        raise ValueError(f"{name} must be {list(shape)}")
+        raise ValueError(msg or f"{name} must be {list(shape)}")
     return a
+
+
+def _batch_inputs(X0, params=None, n=None, none_ok=True):
+    """X0 as a contiguous [batch, n] array and `params` as the list of slot rows of its shape (an entry that is None stays None
+    where `none_ok`); `n`: the size X0's rows must have, a model's."""
+    X0 = np.ascontiguousarray(np.asarray(X0, dtype=np.float64))
+    if X0.ndim != 2:
+        raise ValueError("X0 must be [batch, n]")
+    if n is not None and X0.shape[1] != n:
+        raise ValueError(f"X0 must be [batch, {n}], the size of the model objective")
+    Pc = []
+    for j, v in enumerate(params if params is not None else []):
+        if v is None and not none_ok:
+            raise ValueError(f"params[{j}] is None: every slot needs its [batch, n] rows")
+        Pc.append(None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.float64)))
+        if Pc[-1] is not None and Pc[-1].shape != X0.shape:
+            raise ValueError(f"params[{j}] must have the shape of X0")
+    return X0, Pc
 
 
 def minimizeobjectivebatch(obj_or_kind, X0, config: CGConfig, linesearch_config: LineSearchConfig, D=None, params=None,
@@ -1203,9 +1221,7 @@ def minimizeobjectivebatch(obj_or_kind, X0, config: CGConfig, linesearch_config:
     model = obj_or_kind if isinstance(obj_or_kind, DeviceObjective) else None
     if model is None and obj_or_kind not in OBJ_KINDS:
         raise ValueError(f"unknown objective kind {obj_or_kind!r}")
-    X0 = np.ascontiguousarray(np.asarray(X0, dtype=np.float64))
-    if X0.ndim != 2:
-        raise ValueError("X0 must be [batch, n]")
+    X0, _ = _batch_inputs(X0)
     batch, n = X0.shape
     if scalars is not None and model is None:
         raise ValueError(f"scalars belongs to a run-time compiled objective: {obj_or_kind} reads no scalar")
@@ -1213,17 +1229,10 @@ def minimizeobjectivebatch(obj_or_kind, X0, config: CGConfig, linesearch_config:
     if D is not None:
         if model is not None:
             raise ValueError("D belongs to the built-in quadratic: an objective takes params, one array per slot")
-        Dc = np.ascontiguousarray(np.asarray(D, dtype=np.float64))
-        if Dc.shape != X0.shape:
-            raise ValueError("D must have the shape of X0")
-    Pc = []
-    if params is not None:
-        if model is None:
-            raise ValueError("params belongs to a run-time compiled objective: the built-in quadratic takes D")
-        for j, v in enumerate(params):
-            Pc.append(None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.float64)))
-            if Pc[-1] is not None and Pc[-1].shape != X0.shape:
-                raise ValueError(f"params[{j}] must have the shape of X0")
+        Dc = _batch_rows("D", D, X0.shape, "D must have the shape of X0")
+    if params is not None and model is None:
+        raise ValueError("params belongs to a run-time compiled objective: the built-in quadratic takes D")
+    _, Pc = _batch_inputs(X0, params)
     if model is not None:
         if n != model.n_global:
             raise ValueError(f"X0 must be [batch, {model.n_global}], the size of the model objective")
@@ -1443,15 +1452,9 @@ def minimizeobjectivebatch_lbfgs(kind: str, X0, config: CGConfig, linesearch_con
     if not isinstance(kind, str) or kind not in OBJ_KINDS:
         raise ValueError(f"unknown objective kind {kind!r} (a run-time compiled objective: minimizeobjectivebatch_lbfgs_obj)")
     pol = _batch_lbfgs_policy(rows)
-    X0 = np.ascontiguousarray(np.asarray(X0, dtype=np.float64))
-    if X0.ndim != 2:
-        raise ValueError("X0 must be [batch, n]")
+    X0, _ = _batch_inputs(X0)
     batch, n = X0.shape
-    Dc = None
-    if D is not None:
-        Dc = np.ascontiguousarray(np.asarray(D, dtype=np.float64))
-        if Dc.shape != X0.shape:
-            raise ValueError("D must have the shape of X0")
+    Dc = None if D is None else _batch_rows("D", D, X0.shape, "D must have the shape of X0")
     ctx = ctx or default_context()
     o = _BatchOut(batch, n, config)
     cfg, ls = config._c(), linesearch_config._c()
@@ -1506,19 +1509,8 @@ def minimizeobjectivebatch_lbfgs_obj(model: "DeviceObjective", X0, config: CGCon
     if not isinstance(model, DeviceObjective):
         raise ValueError("model must be a run-time compiled DeviceObjective (ElementwiseObjective); built-in kinds: minimizeobjectivebatch_lbfgs")
     pol = _batch_lbfgs_policy(rows)
-    X0 = np.ascontiguousarray(np.asarray(X0, dtype=np.float64))
-    if X0.ndim != 2:
-        raise ValueError("X0 must be [batch, n]")
+    X0, Pc = _batch_inputs(X0, params, n=model.n_global, none_ok=False)
     batch, n = X0.shape
-    if n != model.n_global:
-        raise ValueError(f"X0 must be [batch, {model.n_global}], the size of the model objective")
-    Pc = []
-    for j, v in enumerate(params if params is not None else []):
-        if v is None:
-            raise ValueError(f"params[{j}] is None: every slot needs its [batch, n] rows")
-        Pc.append(np.ascontiguousarray(np.asarray(v, dtype=np.float64)))
-        if Pc[-1].shape != X0.shape:
-            raise ValueError(f"params[{j}] must have the shape of X0")
     sc = None
     if scalars is not None:
         sc = _batch_rows("scalars", scalars, (batch,))
@@ -1549,19 +1541,31 @@ class Batch:
     only some of the problems.  rows: "lds" | "device" | "auto", as in minimizeobjectivebatch; `.rows` says which tier the open
     batch runs in.  A context manager; `close` frees the device rows."""
 
+    _NAME, _SOLVE = "Batch", "cgo_batch_solve"   # the class in messages, the C symbol of `solve`
+
     def __init__(self, model: DeviceObjective, params, batch: int, rows: str = "lds"):
         self._h = None
         pol = _batch_policy(rows)
+        polp = C.byref(pol) if pol is not None else None
+        self._open(model, params, batch, lambda c, mh, b, pr, k, h: _lib.lib().cgo_batch_open_ex(c, mh, b, pr, k, polp, h))
+
+    def _open(self, model, params, batch, open_call, m=None):
+        """What both kinds of handle check and do to open: `open_call(ctx, model, batch, slot rows, n_params, handle)` is the C call;
+        `m`: the ring depth of a BatchLBFGS (`.m`)."""
         if not isinstance(model, DeviceObjective) or model.kind != "user":
-            raise ValueError("Batch: the model must be a run-time compiled objective (ElementwiseObjective)")
+            raise ValueError(f"{self._NAME}: the model must be a run-time compiled objective (ElementwiseObjective)")
+        if m is not None and (not isinstance(m, (int, np.integer)) or isinstance(m, bool)):
+            raise ValueError(f"{self._NAME}: m must be an integer")
         self.model, self.batch, self.n = model, int(batch), int(model.n_global)
+        if m is not None:
+            self.m = int(m)
         if self.batch < 1:
-            raise ValueError("Batch: batch must be ≥ 1")
+            raise ValueError(f"{self._NAME}: batch must be ≥ 1")
         Pc = [_batch_rows(f"params[{j}]", v, (self.batch, self.n)) for j, v in enumerate(params or [])]
         prows = (dp * max(len(Pc), 1))(*[v.ctypes.data_as(dp) for v in Pc])
         h = C.c_void_p()
         ctx_h = model.ctx._h if model.ctx is not None else None
-        check(_lib.lib().cgo_batch_open_ex(ctx_h, model._h, self.batch, prows, len(Pc), C.byref(pol) if pol is not None else None, C.byref(h)))
+        check(open_call(ctx_h, model._h, self.batch, prows, len(Pc), C.byref(h)))
         self._h = h
         used = C.c_int32(0)
         check(_lib.lib().cgo_batch_rows(h, C.byref(used)))
@@ -1571,10 +1575,14 @@ class Batch:
     def solve(self, X0, config: CGConfig, linesearch_config: LineSearchConfig, scalars=None, active=None,
               slice_iters: int = 0) -> BatchResults:
         """One batched solve from X0 ([batch, n]).  scalars: [batch], every problem's own `s0` (None: the model's for all — then
-        every number is what minimizeobjectivebatch returns).  active: [batch] booleans, the problems that run (None: all); the
-        entry of an inactive problem in the returned list is None."""
+        every number is what the one-shot call returns).  active: [batch] booleans, the problems that run (None: all); the
+        entry of an inactive problem in the returned list is None.  On a `BatchLBFGS`: `config.β_config` is LBFGS(m) with m ≤ `.m`;
+        every ring starts empty with this solve's m, so nothing of an earlier solve is read, and every number has the bits of
+        minimizeobjectivebatch_lbfgs_obj with the same inputs, rows and m.  A problem the device loop does not finish is solved
+        again from its row of X0 by the ordinary engine, with the handle's slot rows and its own scalar, and counted in
+        `handed_back`."""
         if self._h is None:
-            raise ValueError("Batch: closed")
+            raise ValueError(f"{self._NAME}: closed")
         X0 = _batch_rows("X0", X0, (self.batch, self.n))
         sc = None if scalars is None else _batch_rows("scalars", scalars, (self.batch,))
         ac = None
@@ -1584,9 +1592,9 @@ class Batch:
                 raise ValueError(f"active must be [{self.batch}]")
         o = _BatchOut(self.batch, self.n, config)
         cfg, ls = config._c(), linesearch_config._c()
-        check(_lib.lib().cgo_batch_solve(self._h, X0.ctypes.data_as(dp), sc.ctypes.data_as(dp) if sc is not None else None,
-                                         ac.ctypes.data_as(C.POINTER(C.c_uint8)) if ac is not None else None, C.byref(cfg),
-                                         C.byref(ls), int(slice_iters), C.byref(o.c)))
+        check(getattr(_lib.lib(), self._SOLVE)(self._h, X0.ctypes.data_as(dp), sc.ctypes.data_as(dp) if sc is not None else None,
+                                               ac.ctypes.data_as(C.POINTER(C.c_uint8)) if ac is not None else None, C.byref(cfg),
+                                               C.byref(ls), int(slice_iters), C.byref(o.c)))
         return o.results(ac, rows_used=self._rows_used)
 
     def close(self):
@@ -1618,50 +1626,13 @@ class BatchLBFGS(Batch):
     the model's source is compiled here, so a solve never compiles.  `.rows` says which tier the handle runs in, `.m` the m it
     was opened with.  A context manager; `close` frees the device rows."""
 
+    _NAME, _SOLVE = "BatchLBFGS", "cgo_batch_lbfgs_solve"
+
     def __init__(self, model: DeviceObjective, params, batch: int, m: int, rows: str = "device"):
         self._h = None
         pol = _batch_lbfgs_policy(rows)
-        if not isinstance(model, DeviceObjective) or model.kind != "user":
-            raise ValueError("BatchLBFGS: the model must be a run-time compiled objective (ElementwiseObjective)")
-        if not isinstance(m, (int, np.integer)) or isinstance(m, bool):
-            raise ValueError("BatchLBFGS: m must be an integer")
-        self.model, self.batch, self.n, self.m = model, int(batch), int(model.n_global), int(m)
-        if self.batch < 1:
-            raise ValueError("BatchLBFGS: batch must be ≥ 1")
-        Pc = [_batch_rows(f"params[{j}]", v, (self.batch, self.n)) for j, v in enumerate(params or [])]
-        prows = (dp * max(len(Pc), 1))(*[v.ctypes.data_as(dp) for v in Pc])
-        h = C.c_void_p()
-        ctx_h = model.ctx._h if model.ctx is not None else None
-        check(_lib.lib().cgo_batch_lbfgs_open(ctx_h, model._h, self.batch, prows, len(Pc), self.m,
-                                              C.byref(pol) if pol is not None else None, C.byref(h)))
-        self._h = h
-        used = C.c_int32(0)
-        check(_lib.lib().cgo_batch_rows(h, C.byref(used)))
-        self._rows_used = int(used.value)
-        self.rows = _BATCH_ROWS_NAMES[self._rows_used]
-
-    def solve(self, X0, config: CGConfig, linesearch_config: LineSearchConfig, scalars=None, active=None,
-              slice_iters: int = 0) -> BatchResults:
-        """One batched L-BFGS solve from X0 ([batch, n]): `config.β_config` is LBFGS(m) with m ≤ `.m`; every ring starts empty
-        with this solve's m, so nothing of an earlier solve is read.  scalars, active and the returned list as `Batch.solve` has
-        them.  Every number has the bits of minimizeobjectivebatch_lbfgs_obj with the same inputs, rows and m.  A problem the
-        device loop does not finish is solved again from its row of X0 by the ordinary engine, with the handle's slot rows
-        and its own scalar, and counted in `handed_back`."""
-        if self._h is None:
-            raise ValueError("BatchLBFGS: closed")
-        X0 = _batch_rows("X0", X0, (self.batch, self.n))
-        sc = None if scalars is None else _batch_rows("scalars", scalars, (self.batch,))
-        ac = None
-        if active is not None:
-            ac = np.ascontiguousarray(np.asarray(active).astype(bool).astype(np.uint8))
-            if ac.shape != (self.batch,):
-                raise ValueError(f"active must be [{self.batch}]")
-        o = _BatchOut(self.batch, self.n, config)
-        cfg, ls = config._c(), linesearch_config._c()
-        check(_lib.lib().cgo_batch_lbfgs_solve(self._h, X0.ctypes.data_as(dp), sc.ctypes.data_as(dp) if sc is not None else None,
-                                               ac.ctypes.data_as(C.POINTER(C.c_uint8)) if ac is not None else None, C.byref(cfg),
-                                               C.byref(ls), int(slice_iters), C.byref(o.c)))
-        return o.results(ac, rows_used=self._rows_used)
+        polp = C.byref(pol) if pol is not None else None
+        self._open(model, params, batch, lambda c, mh, b, pr, k, h: _lib.lib().cgo_batch_lbfgs_open(c, mh, b, pr, k, self.m, polp, h), m=m)
 
 
 class UndefVarError(RuntimeError):

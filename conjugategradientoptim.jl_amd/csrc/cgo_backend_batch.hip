@@ -162,11 +162,6 @@ int HipBackend::batch_recs_reserve(int64_t stride) {
     return CGO_OK;
 }
 
-int HipBackend::batch_begin(int64_t batch, int64_t n, const double *x0, const double *const *params, int64_t max_iters, bool trace) {
-    if (int rc = batch_alloc(batch, n, params)) return rc;
-    return batch_reset(x0, nullptr, nullptr, max_iters, trace);
-}
-
 void HipBackend::batch_fill_params(BatchParams &B, const ResConfig &c, int64_t budget) const {
     B.x = xc_; B.u = uc_; B.p0 = obj_->p[0].p; B.p1 = obj_->p[1].p; B.p2 = obj_->p[2].p; B.p3 = obj_->p[3].p;
     B.st = bat_st_; B.recs = bat_recs_; B.f_x0 = bat_fx0_;
@@ -177,7 +172,7 @@ void HipBackend::batch_fill_params(BatchParams &B, const ResConfig &c, int64_t b
 }
 
 int HipBackend::batch_launch(const ResConfig &c, int64_t budget, std::vector<ResState> &st, std::vector<double> &f_x0) {
-    if (!bat_st_) { set_error("internal: batch_launch before batch_begin"); return CGO_ESTATE; }
+    if (!bat_st_) { set_error("internal: batch_launch before batch_alloc"); return CGO_ESTATE; }
     if (bat_m_ > 0) return batch_lbfgs_launch(c, budget, st, f_x0);   // a batched L-BFGS solve: k_batch_lbfgs (cgo_backend_batch_lbfgs.hip)
     HIPCHK(hipSetDevice(ctx_->device));
     if (budget < 1) budget = 1;

@@ -6,48 +6,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <new>
 #include <vector>
 
-#include "cgo_hip_backend.hpp"
-#include "cgo_qn.hpp"
+#include "cgo_capi_internal.hpp"
 #include "cgo_build_id.inc"
 
 using namespace cgo;
-
-// Lifetimes: an objective keeps its context alive and a solver keeps its objective alive, whatever order the host
-// destroys the handles in (a garbage-collected host — Python at interpreter exit, Julia finalizers — gives no order).
-// cgo_*_destroy drops the HOST's reference; the object goes when the last reference does.
-struct cgo_ctx { HipCtx c; int refs = 1; cgo_solver_policy defpol; bool has_defpol = false; };
-struct cgo_objective { HipObjective o; cgo_ctx *owner = nullptr; int refs = 1; };
-static void ctx_unref(cgo_ctx *c) { if (c && --c->refs == 0) delete c; }
-static void obj_unref(cgo_objective *o) {
-    if (o && --o->refs == 0) {
-        cgo_ctx *c = o->owner;
-        if (c) (void)hipSetDevice(c->c.device);
-        delete o;
-        ctx_unref(c);
-    }
-}
-struct cgo_solver {
-    cgo_ctx *ctx;
-    cgo_objective *obj;
-    HipBackend *be;
-    Solver *sv;
-    cgo_solver_policy pol;   // what it runs with (cgo_solver_get_policy)
-    ~cgo_solver() { delete sv; delete be; if (obj && obj->o.users > 0) obj->o.users--; }
-};
-
-#define API_GUARD_BEGIN try {
-#define API_GUARD_END                                                        \
-    } catch (const std::bad_alloc &) { set_error("out of host memory"); return CGO_ENOMEM; } \
-    catch (const std::exception &e) { set_error(std::string("internal: ") + e.what()); return CGO_EINVAL; } \
-    catch (...) { set_error("internal: unknown exception"); return CGO_EINVAL; }
-
-#define REQUIRE(cond, msg) do { if (!(cond)) { set_error(msg); return CGO_EINVAL; } } while (0)
-#define HIPCHK2(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { \
-    set_error(std::string("HIP error: ") + hipGetErrorString(e__) + " at " #expr); return CGO_EHIP; } } while (0)
 
 extern "C" {
 
@@ -384,7 +349,7 @@ static const int kReplayDepth = 8;   // 6 was the best median of 1, 2, 3, 4, 6, 
 static const bool kLeanSums = true;   // lean sums where replay's default is on: BASELINE.md, profiles/r07_lean_*
 static const bool kPathPredict = true;   // predicted path where lean sums' default is on: DESIGN.md §4
 static int env_tri(const char *name) { const char *e = getenv(name); return e ? (e[0] != '0' ? 1 : 0) : -1; }
-static int resolve_policy(cgo_ctx *ctx, const cgo_solver_policy *arg, cgo_solver_policy &r, std::string &why) {
+extern "C++" int resolve_policy(cgo_ctx *ctx, const cgo_solver_policy *arg, cgo_solver_policy &r, std::string &why) {
     cgo_solver_policy lib; cgo_solver_policy_init(&lib);
     const cgo_solver_policy *defp = ctx->has_defpol ? &ctx->defpol : nullptr;
     for (const cgo_solver_policy *p : {arg, defp})
@@ -468,7 +433,7 @@ static bool path_applies(const cgo_objective *obj, const cgo_cg_config *cfg, con
     return ls->kind == CGO_LS_WOLFE_BISECTION && ls->cond_kind == CGO_COND_WOLFE;
 }
 
-static int make_solver(cgo_ctx *ctx, cgo_objective *obj, const cgo_cg_config *cfg, const cgo_ls_config *ls,
+extern "C++" int make_solver(cgo_ctx *ctx, cgo_objective *obj, const cgo_cg_config *cfg, const cgo_ls_config *ls,
                        const cgo_lss_config *lss, const cgo_solver_policy *policy, cgo_solver **out) {
     *out = nullptr;
     REQUIRE(obj->o.ctx == &ctx->c, "objective belongs to another ctx");
@@ -1012,791 +977,6 @@ int cgo_minimize_rerun(cgo_ctx *ctx, cgo_objective *obj, const double *x0, const
     }
     *nouts = cnt;
     return CGO_OK;
-    API_GUARD_END
-}
-
-// ---- batched solves: many small problems in one launch, a workgroup each (k_batch) ----------------------------------------
-static bool batch_kind(int32_t k) { return k == CGO_OBJ_QUAD_DIAG || k == CGO_OBJ_ROSENBROCK_PAIRED || k == CGO_OBJ_BOOTH; }
-
-int64_t cgo_batch_max_n(cgo_ctx *ctx, int32_t obj_kind) {
-    if (!ctx || !batch_kind(obj_kind)) return 0;
-    const int64_t m = HipBackend::batch_max_n(&ctx->c, obj_kind);
-    return obj_kind == CGO_OBJ_BOOTH ? std::min<int64_t>(m, 2) : m;
-}
-
-int32_t cgo_stop_status(int64_t it, int64_t max_iters, double f_x, double grad_norm, double eps, double f_x0, int64_t *iters_ran) {
-    int64_t ran = 0;
-    const int st = stop_status(it, max_iters, f_x, grad_norm, eps, f_x0, ran);
-    if (iters_ran) *iters_ran = ran;
-    return st;
-}
-
-// What both entry points refuse alike: a config the device loop does not run, a multi-rank context, a batch, a slice or a size
-// out of range.
-static int check_batch_call(cgo_ctx *ctx, const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t n, int64_t batch, int64_t slice_iters) {
-    {
-        std::string why;
-        if (int rc = check_cg_config(cfg, why)) { set_error(why); return rc; }
-        if (int rc = check_ls_config(ls, why)) { set_error(why); return rc; }
-        if (int rc = check_batch_config(*cfg, *ls, why)) { set_error(why); return rc; }
-    }
-    REQUIRE(ctx->c.world() == 1, "batched solves: a multi-rank context is not supported (one rank only)");
-    REQUIRE(batch >= 1, "batched solves: batch must be ≥ 1");
-    REQUIRE(batch <= 0x7FFFFFFF, "batched solves: batch exceeds the largest grid");
-    REQUIRE(slice_iters >= 0, "batched solves: slice_iters must be ≥ 0 (0 = the library's policy)");
-    REQUIRE(n >= 1, "batched solves: n must be ≥ 1");
-    return CGO_OK;
-}
-
-// ---- where a batch's rows live (cgo_batch_policy): LDS (k_batch) or device memory (k_batch_rows) ---------------------------------
-void cgo_batch_policy_init(cgo_batch_policy *p) {
-    if (!p) return;
-    std::memset(p, 0, sizeof(*p));
-    p->size = (int32_t)sizeof(*p);
-    p->rows = CGO_BATCH_ROWS_LDS;
-}
-
-void cgo_batch_rows_shape(int32_t *block, int32_t *pairs_per_trip) {
-    if (block) *block = HipBackend::batch_rows_block();
-    if (pairs_per_trip) *pairs_per_trip = HipBackend::batch_rows_unroll();
-}
-
-// the rows a call asks for: a null policy is the call without one
-static int batch_rows_asked(const cgo_batch_policy *pol, int &rows) {
-    rows = CGO_BATCH_ROWS_LDS;
-    if (!pol) return CGO_OK;
-    REQUIRE(pol->size == (int32_t)sizeof(cgo_batch_policy), "cgo_batch_policy.size does not match this library (call cgo_batch_policy_init first)");
-    REQUIRE(pol->rows == CGO_BATCH_ROWS_LDS || pol->rows == CGO_BATCH_ROWS_DEVICE || pol->rows == CGO_BATCH_ROWS_AUTO,
-            "batched solves: cgo_batch_policy.rows must be CGO_BATCH_ROWS_LDS, CGO_BATCH_ROWS_DEVICE or CGO_BATCH_ROWS_AUTO");
-    rows = pol->rows;
-    return CGO_OK;
-}
-// … and the tier a batch of problems of size n then runs in.  lds_max: what one workgroup's LDS holds of this objective
-// (`lds_name` reports it); beyond the LDS tier the limits are the pass index and the device's free memory.
-static int batch_tier(cgo_ctx *ctx, int rows, int64_t n, int64_t batch, int nparams, int64_t lds_max, const char *lds_name, bool &device_rows) {
-    device_rows = rows == CGO_BATCH_ROWS_DEVICE || (rows == CGO_BATCH_ROWS_AUTO && n > lds_max);
-    if (!device_rows) {
-        if (n > lds_max) { set_error("batched solves: n = " + std::to_string(n) + " exceeds what one workgroup's LDS holds (" + lds_name + " = " + std::to_string(lds_max) + ")"); return CGO_EINVAL; }
-        return CGO_OK;
-    }
-    const int64_t max_n = HipBackend::batch_rows_max_n();
-    if (n > max_n) { set_error("batched solves: n = " + std::to_string(n) + " exceeds the index range of a pass over rows in device memory (cgo_batch_max_n_ex = " + std::to_string(max_n) + ")"); return CGO_EINVAL; }
-    size_t free_b = 0, total_b = 0;
-    HIPCHK2(hipMemGetInfo(&free_b, &total_b));
-    const double need = HipBackend::batch_rows_bytes(batch, n, nparams);
-    if (need > (double)free_b) {
-        char buf[256];
-        std::snprintf(buf, sizeof buf, "batched solves: the rows of %lld problems of n = %lld ask for %.0f bytes of device memory, %zu are free",
-                      (long long)batch, (long long)n, need, free_b);
-        set_error(buf);
-        return CGO_ENOMEM;
-    }
-    return CGO_OK;
-}
-
-// The concatenated problems: ONE objective `cat` (n_local = batch · ld, its parameter slots allocated) and backend whose x, u and
-// parameter slots are the [batch][ld] rows.  batch_backend_on makes the backend and uploads the slot rows; batch_solve_on starts
-// a solve on it — launched until every active problem is finished or handed back, then everything after the launch loop:
-// statuses from stop_status, traces, and the hand-back of the problems the device loop does not finish to ONE ordinary solver on
-// `make_hobj`'s objective of size n (created on the first hand-back), which takes the problem's own scalar where the call has them.
-static int batch_backend_on(cgo_ctx *ctx, HipObjective &cat, int64_t n, int64_t batch, const double *const *params, HipBackend &be, bool device_rows) {
-    cgo_solver_policy pol;
-    { std::string pw; if (int rc = resolve_policy(ctx, nullptr, pol, pw)) { set_error(pw); return rc; } }
-    be.set_policy(pol);
-    be.set_rmode(true);
-    if (int rc = be.alloc()) return rc;
-    return be.batch_alloc(batch, n, params, device_rows);
-}
-
-static int batch_solve_on(cgo_ctx *ctx, HipBackend &be, int64_t n, int64_t batch, const double *x0, const double *scalars,
-                          const unsigned char *active, const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters,
-                          cgo_batch_results *out, const std::function<int(cgo_objective **)> &make_hobj, bool qn = false,
-                          const double *const *qn_params = nullptr, int qn_nparams = 0, int qn_m = 0) {
-    // qn: a batched L-BFGS solve (cgo_minimize_batch_lbfgs[_obj]) — every ring empty at the start, and a handed-back problem is
-    // solved again by the host engine from its own x0 (the ring and Gram state of the device are not exported), with its row of the
-    // caller's x0 and of every slot of qn_params (a quasi-Newton solver keeps a stored gradient: not a backend batch_export_row serves).
-    // On a handle (cgo_batch_lbfgs_solve) qn_params is null — the caller's arrays were valid during open only — and the slot rows
-    // come from the batch's own device rows (batch_export_slots); qn_m: this solve's ring depth on a ring allocated for more.
-    auto on = [&](int64_t b) { return !active || active[b] != 0; };
-    if (int rc = be.batch_reset(x0, scalars, active, cfg->max_iters, cfg->trace_enabled != 0)) return rc;
-    if (qn) { if (int rc = be.batch_lbfgs_reset(qn_m)) return rc; }
-    BatchRun run;
-    if (int rc = run_batch(&be, *cfg, *ls, batch, slice_iters, run)) { if (rc == CGO_ESTATE) set_error("internal: a batched launch left a problem in a state the driver does not know"); return rc; }
-    out->launches = run.launches;
-    // finished on the device: the status follows from the state (stop_status); minimizer and gradient of EVERY row from one
-    // download — the rows the host engine finishes below are overwritten with its own
-    if (int rc = be.batch_results(out->minimizer, out->gradient, active)) return rc;
-    const bool trace = cfg->trace_enabled != 0;
-    const int64_t mi = cfg->max_iters;
-    std::vector<ResRecord> recs;
-    const bool want_trace = trace && (out->trace_objective || out->trace_grad_norm || out->trace_step_size || out->trace_objective_evals);
-    if (want_trace) { if (int rc = be.batch_records(-1, 1, recs)) return rc; }
-    const int64_t stride = be.batch_rec_stride();
-    for (int64_t b = 0; b < batch; ++b) {
-        const ResState &s = run.st[(size_t)b];
-        if (s.reason != RES_STOP || !on(b)) continue;
-        int64_t ran = 0;
-        const int st = stop_status(s.it, mi, s.f_x, s.norm, cfg->eps, run.f_x0[(size_t)b], ran);
-        if (st == CGO_INCOMPLETE) { set_error("internal: a batched problem stopped on the device in a state that does not stop"); return CGO_ESTATE; }
-        if (out->objective) out->objective[b] = s.f_x;
-        if (out->iters_ran) out->iters_ran[b] = ran;
-        if (out->status) out->status[b] = st;
-        if (out->total_fdf_evals) out->total_fdf_evals[b] = 1 + run.evals[(size_t)b];
-        if (want_trace)
-            for (int64_t i = 0; i < s.it; ++i) {
-                const ResRecord &r = recs[(size_t)(b * stride + i)];
-                if (out->trace_objective) out->trace_objective[b * mi + i] = r.f;
-                if (out->trace_grad_norm) out->trace_grad_norm[b * mi + i] = r.norm;
-                if (out->trace_step_size) out->trace_step_size[b * mi + i] = r.a;
-                if (out->trace_objective_evals) out->trace_objective_evals[b * mi + i] = r.evals;
-            }
-    }
-    // handed back: the iteration at st.it + 1 is the host engine's — ONE ordinary solver (no resident slices), reused
-    cgo_objective *hobj = nullptr;
-    cgo_solver *hs = nullptr;
-    int rc = CGO_OK;
-    for (int64_t b = 0; b < batch && !rc; ++b) {
-        const ResState &s = run.st[(size_t)b];
-        if (s.reason != RES_HOST || !on(b)) continue;
-        if (!hs) {
-            if ((rc = make_hobj(&hobj))) break;
-            cgo_solver_policy hp;
-            cgo_solver_policy_init(&hp);
-            hp.resident = 0;
-            if ((rc = make_solver(ctx, hobj, cfg, ls, nullptr, &hp, &hs))) break;
-        }
-        if (scalars) { if ((rc = cgo_objective_set_scalar(hobj, 0, scalars[b]))) break; }   // (the call's own objective, never the model)
-        if (qn) {          // the whole solve, from the problem's own x0 (the device's row of x has moved on)
-            if (!qn_params) rc = be.batch_export_slots(b, *hs->be);
-            for (int j = 0; qn_params && j < qn_nparams && !rc; ++j)
-                if (qn_params[j]) rc = cgo_objective_set_param_host(hobj, j, qn_params[j] + b * n);
-            if (rc) break;
-            if ((rc = hs->be->set_x0_host(x0 + b * n))) break;
-            if ((rc = hs->sv->start())) break;
-        } else if (s.it == 0) {   // nothing completed: the problem's own start, as a single solve has it
-            if ((rc = be.batch_export_row(b, *hs->be, false))) break;
-            if ((rc = hs->sv->start())) break;
-        } else {
-            if ((rc = be.batch_export_row(b, *hs->be, true))) break;
-            std::vector<ResRecord> prefix;
-            if ((rc = be.batch_records(b, s.it, prefix))) break;
-            hs->sv->resume(run.f_x0[(size_t)b], run.evals[(size_t)b], s, prefix.data());
-        }
-        bool fin = false;
-        while (!rc && !fin) rc = hs->sv->iterate(INT64_MAX / 2, fin);
-        if (rc) break;
-        cgo_results r{};
-        r.minimizer = out->minimizer ? out->minimizer + b * n : nullptr;
-        r.gradient = out->gradient ? out->gradient + b * n : nullptr;
-        r.trace_objective = out->trace_objective ? out->trace_objective + b * mi : nullptr;
-        r.trace_grad_norm = out->trace_grad_norm ? out->trace_grad_norm + b * mi : nullptr;
-        r.trace_step_size = out->trace_step_size ? out->trace_step_size + b * mi : nullptr;
-        r.trace_objective_evals = out->trace_objective_evals ? out->trace_objective_evals + b * mi : nullptr;
-        if ((rc = cgo_solver_results(hs, &r))) break;
-        if (out->objective) out->objective[b] = r.objective;
-        if (out->iters_ran) out->iters_ran[b] = r.iters_ran;
-        if (out->status) out->status[b] = r.status;
-        if (out->total_fdf_evals) out->total_fdf_evals[b] = r.total_fdf_evals;
-        out->handed_back++;
-    }
-    std::string keep = get_error();
-    if (hs) cgo_solver_destroy(hs);
-    if (hobj) cgo_objective_destroy(hobj);
-    if (rc) set_error(keep);
-    return rc;
-}
-
-static int run_batch_on(cgo_ctx *ctx, HipObjective &cat, int64_t n, int64_t batch, const double *x0, const double *const *params,
-                        const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out,
-                        const std::function<int(cgo_objective **)> &make_hobj, bool device_rows) {
-    HipBackend be(&ctx->c, &cat);
-    if (int rc = batch_backend_on(ctx, cat, n, batch, params, be, device_rows)) return rc;
-    return batch_solve_on(ctx, be, n, batch, x0, nullptr, nullptr, cfg, ls, slice_iters, out, make_hobj);
-}
-
-int cgo_minimize_batch(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
-                       const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out) {
-    return cgo_minimize_batch_ex(ctx, obj_kind, n, batch, x0, param0, cfg, ls, slice_iters, nullptr, out, nullptr);
-}
-
-int cgo_minimize_batch_ex(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
-                          const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, const cgo_batch_policy *policy,
-                          cgo_batch_results *out, int32_t *rows_used) {
-    API_GUARD_BEGIN
-    REQUIRE(ctx && x0 && cfg && ls && out, "null argument");
-    out->launches = 0; out->handed_back = 0;
-    int rows = 0;
-    if (int rc = batch_rows_asked(policy, rows)) return rc;
-    REQUIRE(batch_kind(obj_kind), "batched solves: the objective must be CGO_OBJ_QUAD_DIAG, CGO_OBJ_ROSENBROCK_PAIRED or CGO_OBJ_BOOTH");
-    if (int rc = check_batch_call(ctx, cfg, ls, n, batch, slice_iters)) return rc;
-    if (obj_kind == CGO_OBJ_ROSENBROCK_PAIRED) REQUIRE(n % 2 == 0, "batched solves: paired Rosenbrock needs an even n");
-    if (obj_kind == CGO_OBJ_BOOTH) REQUIRE(n == 2, "batched solves: Booth is 2-dimensional (n = 2)");
-    if (obj_kind == CGO_OBJ_QUAD_DIAG) REQUIRE(param0, "batched solves: the quadratic needs param0, the [batch*n] rows of D");
-    HIPCHK2(hipSetDevice(ctx->c.device));
-    bool device_rows = false;
-    if (int rc = batch_tier(ctx, rows, n, batch, obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0, cgo_batch_max_n(ctx, obj_kind), "cgo_batch_max_n", device_rows)) return rc;
-    if (rows_used) *rows_used = device_rows ? CGO_BATCH_ROWS_DEVICE : CGO_BATCH_ROWS_LDS;
-    const int64_t ld = n + (n & 1);
-    HipObjective cat;
-    cat.ctx = &ctx->c; cat.kind = obj_kind; cat.n_global = cat.n_local = batch * ld; cat.offset = 0;
-    if (cat.uses_param()) { if (int rc = cat.p[0].alloc((size_t)(batch * ld))) return rc; }
-    const double *params[1] = {param0};
-    return run_batch_on(ctx, cat, n, batch, x0, params, cfg, ls, slice_iters, out,
-                        [&](cgo_objective **h) { return cgo_objective_create(ctx, obj_kind, n, 0, n, h); }, device_rows);
-    API_GUARD_END
-}
-
-// ---- batched solves with β = LBFGS(m): k_batch_lbfgs, the ring of every problem in device memory (k_batch_lbfgs_lds: in LDS) -------------------------------------
-int32_t cgo_batch_lbfgs_max_m(void) { return QN_MAX_M; }
-
-void cgo_batch_lbfgs_shape(int32_t *block, int32_t *pairs_per_trip) {
-    if (block) *block = HipBackend::batch_lbfgs_block();
-    if (pairs_per_trip) *pairs_per_trip = HipBackend::batch_lbfgs_unroll();
-}
-
-int64_t cgo_batch_lbfgs_max_n(cgo_ctx *ctx, int32_t obj_kind) {
-    const int64_t lds = cgo_batch_max_n(ctx, obj_kind);   // (0: no context, no such kind, no device)
-    if (lds == 0) return 0;
-    return obj_kind == CGO_OBJ_BOOTH ? lds : HipBackend::batch_lbfgs_max_n();
-}
-
-// What a batched L-BFGS solve and its probe refuse of sizes alike: n beyond the pass index, and rows and rings the device's free
-// memory does not hold — (3 + K + 2(m+1)) · batch · ld · 8 bytes against what is free, before anything is allocated.
-static int batch_lbfgs_sizes_of(cgo_ctx *ctx, int64_t max_n, const char *max_name, int nparams, int64_t n, int64_t batch, int m) {
-    HIPCHK2(hipSetDevice(ctx->c.device));
-    if (n > max_n) { set_error("batched L-BFGS solves: n = " + std::to_string(n) + " exceeds the index range of a pass (" + max_name + " = " + std::to_string(max_n) + ")"); return CGO_EINVAL; }
-    size_t free_b = 0, total_b = 0;
-    HIPCHK2(hipMemGetInfo(&free_b, &total_b));
-    const double need = HipBackend::batch_lbfgs_bytes(batch, n, nparams, m);
-    if (need > (double)free_b) {
-        char buf[288];
-        std::snprintf(buf, sizeof buf, "batched L-BFGS solves: the rows and rings (m = %d) of %lld problems of n = %lld ask for %.0f bytes of device memory, %zu are free",
-                      m, (long long)batch, (long long)n, need, free_b);
-        set_error(buf);
-        return CGO_ENOMEM;
-    }
-    return CGO_OK;
-}
-static int batch_lbfgs_sizes(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, int m) {
-    return batch_lbfgs_sizes_of(ctx, cgo_batch_lbfgs_max_n(ctx, obj_kind), "cgo_batch_lbfgs_max_n", obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0, n, batch, m);
-}
-
-// What both entry points refuse of a config and a call alike; `cg_entry`: where a CG flavour belongs instead
-static int check_batch_lbfgs_call(cgo_ctx *ctx, const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t n, int64_t batch, int64_t slice_iters,
-                                  const char *cg_entry) {
-    {
-        std::string why;
-        if (int rc = check_cg_config(cfg, why)) { set_error(why); return rc; }
-        if (int rc = check_ls_config(ls, why)) { set_error(why); return rc; }
-    }
-    if (cfg->beta.kind != CGO_BETA_LBFGS) { set_error(std::string("batched L-BFGS solves: β must be LBFGS(m) (CG flavours: ") + cg_entry + "; the Broyden family has no batched form)"); return CGO_EINVAL; }
-    if (cfg->beta.lbfgs_m > QN_MAX_M) { set_error("batched L-BFGS solves: m = " + std::to_string(cfg->beta.lbfgs_m) + " exceeds cgo_batch_lbfgs_max_m = " + std::to_string(QN_MAX_M)); return CGO_EINVAL; }
-    REQUIRE(ls->kind != CGO_LS_BACKTRACKING, "batched L-BFGS solves: the Backtracking line search is not supported (StrongWolfeBisection or WolfeBisection)");
-    REQUIRE(ctx->c.world() == 1, "batched L-BFGS solves: a multi-rank context is not supported (one rank only)");
-    REQUIRE(batch >= 1, "batched L-BFGS solves: batch must be ≥ 1");
-    REQUIRE(batch <= 0x7FFFFFFF, "batched L-BFGS solves: batch exceeds the largest grid");
-    REQUIRE(slice_iters >= 0, "batched L-BFGS solves: slice_iters must be ≥ 0 (0 = the library's policy)");
-    REQUIRE(n >= 1, "batched L-BFGS solves: n must be ≥ 1");
-    return CGO_OK;
-}
-
-// ---- … and their LDS tier (k_batch_lbfgs_lds): the calls above with a policy.  A null policy is the call without one — device rows.
-static int batch_lbfgs_rows_asked(const cgo_batch_policy *pol, int &rows) {
-    rows = CGO_BATCH_ROWS_DEVICE;
-    if (!pol) return CGO_OK;
-    REQUIRE(pol->size == (int32_t)sizeof(cgo_batch_policy), "cgo_batch_policy.size does not match this library (call cgo_batch_policy_init first)");
-    REQUIRE(pol->rows == CGO_BATCH_ROWS_LDS || pol->rows == CGO_BATCH_ROWS_DEVICE || pol->rows == CGO_BATCH_ROWS_AUTO,
-            "batched L-BFGS solves: cgo_batch_policy.rows must be CGO_BATCH_ROWS_LDS, CGO_BATCH_ROWS_DEVICE or CGO_BATCH_ROWS_AUTO");
-    rows = pol->rows;
-    return CGO_OK;
-}
-// THE rule of CGO_BATCH_ROWS_AUTO for batched L-BFGS (stated in include/cgo.h): device rows.  "LDS where n fits" needed the LDS
-// tier's kernel time below the device tier's by more than that tier's own spread at EVERY measured shape, and at n = 1000, m = 5
-// it is not.  true: LDS where n fits for this m and slot count.
-static constexpr bool kBatchLbfgsAutoTakesLds = false;
-// the tier a batch of problems of size n runs in: lds_max = what one workgroup's LDS holds for this m and slot count
-static int batch_lbfgs_tier(int rows, int64_t n, int64_t lds_max, bool &lds, const char *lds_name = "cgo_batch_lbfgs_max_n_ex") {
-    lds = rows == CGO_BATCH_ROWS_LDS || (rows == CGO_BATCH_ROWS_AUTO && kBatchLbfgsAutoTakesLds && n <= lds_max);
-    if (lds && n > lds_max) {
-        set_error("batched L-BFGS solves: n = " + std::to_string(n) + " exceeds what one workgroup's LDS holds of a problem's rows and ring (" + lds_name + " = " + std::to_string(lds_max) + ")");
-        return CGO_EINVAL;
-    }
-    return CGO_OK;
-}
-
-int cgo_minimize_batch_lbfgs(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
-                             const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out) {
-    return cgo_minimize_batch_lbfgs_ex(ctx, obj_kind, n, batch, x0, param0, cfg, ls, slice_iters, nullptr, out, nullptr);
-}
-
-int32_t cgo_batch_lbfgs_lds_rows(int32_t n_params, int32_t m) { return HipBackend::batch_lbfgs_lds_rows(n_params, m); }
-
-void cgo_batch_lbfgs_lds_shape(int32_t n_params, int32_t *block, int32_t *pairs_per_trip) {
-    if (block) *block = HipBackend::batch_lbfgs_block();
-    if (pairs_per_trip) *pairs_per_trip = HipBackend::batch_lbfgs_lds_unroll_for(n_params);
-}
-
-// what one workgroup's LDS holds of a built-in problem's rows and ring (0: no context, kind or device, a bad m)
-static int64_t batch_lbfgs_lds_max_n(cgo_ctx *ctx, int32_t obj_kind, int32_t m) {
-    if (!ctx || !batch_kind(obj_kind)) return 0;
-    const int64_t ld = HipBackend::batch_lbfgs_lds_max_ld(&ctx->c, obj_kind, m);
-    return obj_kind == CGO_OBJ_BOOTH ? std::min<int64_t>(ld, 2) : ld;
-}
-
-int64_t cgo_batch_lbfgs_max_n_ex(cgo_ctx *ctx, int32_t obj_kind, int32_t m, const cgo_batch_policy *policy) {
-    try {
-        int rows = 0;
-        if (batch_lbfgs_rows_asked(policy, rows)) return 0;
-        if (m < 1 || m > QN_MAX_M) return 0;
-        if (rows == CGO_BATCH_ROWS_LDS) return batch_lbfgs_lds_max_n(ctx, obj_kind, m);
-        return cgo_batch_lbfgs_max_n(ctx, obj_kind);
-    } catch (...) { return 0; }
-}
-
-int cgo_minimize_batch_lbfgs_ex(cgo_ctx *ctx, int32_t obj_kind, int64_t n, int64_t batch, const double *x0, const double *param0,
-                                const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters, const cgo_batch_policy *policy,
-                                cgo_batch_results *out, int32_t *rows_used) {
-    API_GUARD_BEGIN
-    REQUIRE(ctx && x0 && cfg && ls && out, "null argument");
-    out->launches = 0; out->handed_back = 0;
-    int rows = 0;
-    if (int rc = batch_lbfgs_rows_asked(policy, rows)) return rc;
-    REQUIRE(batch_kind(obj_kind), "batched L-BFGS solves: the objective must be CGO_OBJ_QUAD_DIAG, CGO_OBJ_ROSENBROCK_PAIRED or CGO_OBJ_BOOTH");
-    if (int rc = check_batch_lbfgs_call(ctx, cfg, ls, n, batch, slice_iters, "cgo_minimize_batch")) return rc;
-    if (obj_kind == CGO_OBJ_ROSENBROCK_PAIRED) REQUIRE(n % 2 == 0, "batched L-BFGS solves: paired Rosenbrock needs an even n");
-    if (obj_kind == CGO_OBJ_BOOTH) REQUIRE(n == 2, "batched L-BFGS solves: Booth is 2-dimensional (n = 2)");
-    if (obj_kind == CGO_OBJ_QUAD_DIAG) REQUIRE(param0, "batched L-BFGS solves: the quadratic needs param0, the [batch*n] rows of D");
-    const int m = cfg->beta.lbfgs_m;
-    bool lds = false;
-    if (rows != CGO_BATCH_ROWS_DEVICE) {
-        HIPCHK2(hipSetDevice(ctx->c.device));
-        if (int rc = batch_lbfgs_tier(rows, n, batch_lbfgs_lds_max_n(ctx, obj_kind, m), lds)) return rc;
-    }
-    if (int rc = batch_lbfgs_sizes(ctx, obj_kind, n, batch, m)) return rc;
-    if (rows_used) *rows_used = lds ? CGO_BATCH_ROWS_LDS : CGO_BATCH_ROWS_DEVICE;
-    const int64_t ld = n + (n & 1);
-    HipObjective cat;
-    cat.ctx = &ctx->c; cat.kind = obj_kind; cat.n_global = cat.n_local = batch * ld; cat.offset = 0;
-    if (cat.uses_param()) { if (int rc = cat.p[0].alloc((size_t)(batch * ld))) return rc; }
-    const double *params[1] = {param0};
-    HipBackend be(&ctx->c, &cat);
-    if (int rc = batch_backend_on(ctx, cat, n, batch, params, be, true)) return rc;
-    if (int rc = be.batch_lbfgs_alloc(m, lds)) return rc;
-    return batch_solve_on(ctx, be, n, batch, x0, nullptr, nullptr, cfg, ls, slice_iters, out,
-                          [&](cgo_objective **h) { return cgo_objective_create(ctx, obj_kind, n, 0, n, h); }, true, params, 1);
-    API_GUARD_END
-}
-
-int64_t cgo_batch_max_n_ex(cgo_ctx *ctx, int32_t obj_kind, const cgo_batch_policy *policy) {
-    int rows = 0;
-    if (batch_rows_asked(policy, rows)) return 0;
-    const int64_t lds = cgo_batch_max_n(ctx, obj_kind);
-    if (rows == CGO_BATCH_ROWS_LDS || lds == 0) return lds;
-    return obj_kind == CGO_OBJ_BOOTH ? lds : HipBackend::batch_rows_max_n();
-}
-
-// The model's batch program (k_batch<UserObjective, …>, cgo_rtc_batch.hip): compiled on the first batched use of its module
-static int batch_program(cgo_objective *model) {
-    std::string log;
-    if (int rc = rtc_compile_batch(*model->o.rtc, log)) { set_error("user objective: the batch program did not compile:\n" + log); return rc; }
-    return CGO_OK;
-}
-// … and the program of the tier whose rows stay in device memory, on the first use of that tier
-static int batch_rows_program(cgo_objective *model) {
-    std::string log;
-    if (int rc = rtc_compile_batch_rows(*model->o.rtc, log)) { set_error("user objective: the program of the batched solves' device-rows tier did not compile:\n" + log); return rc; }
-    return CGO_OK;
-}
-static bool batch_model_whole(const cgo_objective *m) { return m->o.offset == 0 && m->o.n_local == m->o.n_global && m->o.ctx->world() == 1; }
-
-int64_t cgo_batch_max_n_obj(cgo_objective *model) {
-    try {
-        if (!model || model->o.kind != CGO_OBJ_USER || !model->o.rtc || !batch_model_whole(model)) return 0;
-        if (batch_program(model)) return 0;
-        return HipBackend::batch_max_n(model->o.ctx, CGO_OBJ_USER, model->o.rtc.get());
-    } catch (...) { return 0; }
-}
-
-int64_t cgo_batch_max_n_obj_ex(cgo_objective *model, const cgo_batch_policy *policy) {
-    try {
-        int rows = 0;
-        if (batch_rows_asked(policy, rows)) return 0;
-        if (rows == CGO_BATCH_ROWS_LDS) return cgo_batch_max_n_obj(model);
-        if (!model || model->o.kind != CGO_OBJ_USER || !model->o.rtc || !batch_model_whole(model)) return 0;
-        return HipBackend::batch_rows_max_n();   // (nothing is compiled for the answer)
-    } catch (...) { return 0; }
-}
-
-// What every entry point on a model refuses of it, and what it builds from it: the concatenated objective `cat` — it shares the
-// model's compiled module, its scalar and its cost class; the slots are its own [batch][ld] rows — and the objective of size n a
-// handed-back problem is finished on.
-static int check_batch_model(cgo_ctx *ctx, cgo_objective *model) {
-    REQUIRE(model->o.kind == CGO_OBJ_USER && model->o.rtc,
-            "batched solves: the model must be a run-time compiled objective (cgo_objective_create_from_source[_ex]); built-in objectives: cgo_minimize_batch");
-    REQUIRE(model->o.ctx == &ctx->c, "batched solves: the model belongs to another context");
-    REQUIRE(batch_model_whole(model), "batched solves: a sharded or multi-rank model is not supported (n_global = n_local = the size of ONE problem, one rank only)");
-    return CGO_OK;
-}
-static int check_batch_model_params(cgo_objective *model, const double *const *params, int32_t n_params) {
-    const int K = model->o.nparams();
-    if (n_params != K) { set_error("batched solves: n_params = " + std::to_string(n_params) + ", the model reads " + std::to_string(K) + " parameter slots"); return CGO_EINVAL; }
-    REQUIRE(K == 0 || params, "batched solves: params is null, the model reads parameter slots");
-    for (int j = 0; j < K; ++j)
-        if (!params[j]) { set_error("batched solves: params[" + std::to_string(j) + "] is null (the [batch*n] rows of slot " + std::to_string(j) + ")"); return CGO_EINVAL; }
-    return CGO_OK;
-}
-// the concatenated objective itself: the model's module, scalar and cost class, its own [batch][ld] slot rows
-static int batch_model_cat_rows(cgo_ctx *ctx, cgo_objective *model, int64_t batch, HipObjective &cat) {
-    const int64_t n = model->o.n_local, ld = n + (n & 1);
-    const int K = model->o.nparams();
-    cat.ctx = &ctx->c; cat.kind = CGO_OBJ_USER; cat.n_global = cat.n_local = batch * ld; cat.offset = 0;
-    cat.rtc = model->o.rtc; cat.user_nparams = K; cat.s0 = model->o.s0; cat.user_cheap = model->o.user_cheap;
-    for (int j = 0; j < K; ++j) { if (int rc = cat.p[j].alloc((size_t)(batch * ld))) return rc; }
-    return CGO_OK;
-}
-static int batch_model_cat(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *const *params, int32_t n_params, HipObjective &cat,
-                           int rows, bool &device_rows) {
-    const int64_t n = model->o.n_local;
-    const int K = model->o.nparams();
-    if (int rc = check_batch_model_params(model, params, n_params)) return rc;
-    HIPCHK2(hipSetDevice(ctx->c.device));
-    // (rows in device memory, asked for outright: the batch program — the LDS tier's kernel — is neither needed nor compiled)
-    int64_t lds_max = 0;
-    if (rows != CGO_BATCH_ROWS_DEVICE) {
-        if (int rc = batch_program(model)) return rc;
-        lds_max = HipBackend::batch_max_n(&ctx->c, CGO_OBJ_USER, model->o.rtc.get());
-    }
-    if (int rc = batch_tier(ctx, rows, n, batch, K, lds_max, "cgo_batch_max_n_obj", device_rows)) return rc;
-    if (device_rows) { if (int rc = batch_rows_program(model)) return rc; }
-    return batch_model_cat_rows(ctx, model, batch, cat);
-}
-static std::function<int(cgo_objective **)> batch_model_hobj(cgo_ctx *ctx, cgo_objective *model) {
-    return [ctx, model](cgo_objective **h) {
-        // (the module cache makes this free while the model lives: same device, text and n_params)
-        const int64_t n = model->o.n_local;
-        if (int rc = cgo_objective_create_from_source_ex(ctx, model->o.rtc->user_source.c_str(), model->o.nparams(), n, 0, n, h)) return rc;
-        (*h)->o.s0 = model->o.s0; (*h)->o.user_cheap = model->o.user_cheap;
-        return (int)CGO_OK;
-    };
-}
-
-int cgo_minimize_batch_obj(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *x0, const double *const *params,
-                           int32_t n_params, const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters,
-                           cgo_batch_results *out) {
-    return cgo_minimize_batch_obj_ex(ctx, model, batch, x0, params, n_params, cfg, ls, slice_iters, nullptr, out, nullptr);
-}
-
-int cgo_minimize_batch_obj_ex(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *x0, const double *const *params,
-                              int32_t n_params, const cgo_cg_config *cfg, const cgo_ls_config *ls, int64_t slice_iters,
-                              const cgo_batch_policy *policy, cgo_batch_results *out, int32_t *rows_used) {
-    API_GUARD_BEGIN
-    REQUIRE(ctx && model && x0 && cfg && ls && out, "null argument");
-    out->launches = 0; out->handed_back = 0;
-    int rows = 0;
-    if (int rc = batch_rows_asked(policy, rows)) return rc;
-    if (int rc = check_batch_model(ctx, model)) return rc;
-    const int64_t n = model->o.n_local;
-    if (int rc = check_batch_call(ctx, cfg, ls, n, batch, slice_iters)) return rc;
-    HipObjective cat;
-    bool device_rows = false;
-    if (int rc = batch_model_cat(ctx, model, batch, params, n_params, cat, rows, device_rows)) return rc;
-    if (rows_used) *rows_used = device_rows ? CGO_BATCH_ROWS_DEVICE : CGO_BATCH_ROWS_LDS;
-    return run_batch_on(ctx, cat, n, batch, x0, params, cfg, ls, slice_iters, out, batch_model_hobj(ctx, model), device_rows);
-    API_GUARD_END
-}
-
-// ---- batched L-BFGS solves on a run-time compiled objective: k_batch_lbfgs<UserObjective, 3>, the fifth program of its module ------
-// (cgo_rtc_batch_lbfgs.hip).  The model and params are checked as cgo_minimize_batch_obj checks them, the config as
-// cgo_minimize_batch_lbfgs checks it; the batch is the device-rows tier's with the ring beside it.
-void cgo_batch_lbfgs_shape_obj(int32_t n_params, int32_t *block, int32_t *pairs_per_trip) {
-    if (block) *block = HipBackend::batch_lbfgs_block();
-    if (pairs_per_trip) *pairs_per_trip = HipBackend::batch_lbfgs_unroll_for(n_params);
-}
-
-int64_t cgo_batch_lbfgs_max_n_obj(cgo_objective *model) {
-    try {
-        if (!model || model->o.kind != CGO_OBJ_USER || !model->o.rtc || !batch_model_whole(model)) return 0;
-        return HipBackend::batch_lbfgs_max_n();   // (nothing is compiled for the answer)
-    } catch (...) { return 0; }
-}
-
-int cgo_minimize_batch_lbfgs_obj(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *x0, const double *const *params,
-                                 int32_t n_params, const double *scalars, const cgo_cg_config *cfg, const cgo_ls_config *ls,
-                                 int64_t slice_iters, cgo_batch_results *out) {
-    return cgo_minimize_batch_lbfgs_obj_ex(ctx, model, batch, x0, params, n_params, scalars, cfg, ls, slice_iters, nullptr, out, nullptr);
-}
-
-// the model's program of the LDS tier (k_batch_lbfgs_lds<UserObjective, …>, cgo_rtc_batch_lbfgs_lds.hip): compiled on the first use of the tier
-static int batch_lbfgs_lds_program(cgo_objective *model) {
-    std::string log;
-    if (int rc = rtc_compile_batch_lbfgs_lds(*model->o.rtc, log)) { set_error("user objective: the program of the batched L-BFGS solves' LDS tier did not compile:\n" + log); return rc; }
-    return CGO_OK;
-}
-
-int64_t cgo_batch_lbfgs_max_n_obj_ex(cgo_objective *model, int32_t m, const cgo_batch_policy *policy) {
-    try {
-        int rows = 0;
-        if (batch_lbfgs_rows_asked(policy, rows)) return 0;
-        if (m < 1 || m > QN_MAX_M) return 0;
-        if (rows != CGO_BATCH_ROWS_LDS) return cgo_batch_lbfgs_max_n_obj(model);   // (nothing is compiled for the answer)
-        if (!model || model->o.kind != CGO_OBJ_USER || !model->o.rtc || !batch_model_whole(model)) return 0;
-        if (batch_lbfgs_lds_program(model)) return 0;   // (as cgo_batch_max_n_obj compiles the batch program: the limit follows from the kernel's static LDS)
-        return HipBackend::batch_lbfgs_lds_max_ld(model->o.ctx, CGO_OBJ_USER, m, model->o.rtc.get());
-    } catch (...) { return 0; }
-}
-
-int cgo_minimize_batch_lbfgs_obj_ex(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *x0, const double *const *params,
-                                    int32_t n_params, const double *scalars, const cgo_cg_config *cfg, const cgo_ls_config *ls,
-                                    int64_t slice_iters, const cgo_batch_policy *policy, cgo_batch_results *out, int32_t *rows_used) {
-    API_GUARD_BEGIN
-    REQUIRE(ctx && model && x0 && cfg && ls && out, "null argument");
-    out->launches = 0; out->handed_back = 0;
-    int rows = 0;
-    if (int rc = batch_lbfgs_rows_asked(policy, rows)) return rc;
-    if (int rc = check_batch_model(ctx, model)) return rc;
-    const int64_t n = model->o.n_local;
-    if (int rc = check_batch_lbfgs_call(ctx, cfg, ls, n, batch, slice_iters, "cgo_minimize_batch_obj")) return rc;
-    if (int rc = check_batch_model_params(model, params, n_params)) return rc;
-    if (scalars)
-        for (int64_t b = 0; b < batch; ++b)
-            if (!std::isfinite(scalars[b])) { set_error("batched L-BFGS solves: scalars[" + std::to_string(b) + "] is not finite"); return CGO_EINVAL; }
-    const int m = cfg->beta.lbfgs_m, K = model->o.nparams();
-    bool lds = false;
-    if (rows != CGO_BATCH_ROWS_DEVICE && (rows == CGO_BATCH_ROWS_LDS || kBatchLbfgsAutoTakesLds)) {   // the tier's program: its static LDS decides the limit
-        HIPCHK2(hipSetDevice(ctx->c.device));
-        if (int rc = batch_lbfgs_lds_program(model)) return rc;
-        if (int rc = batch_lbfgs_tier(rows, n, HipBackend::batch_lbfgs_lds_max_ld(&ctx->c, CGO_OBJ_USER, m, model->o.rtc.get()), lds)) return rc;
-    }
-    if (int rc = batch_lbfgs_sizes_of(ctx, cgo_batch_lbfgs_max_n_obj(model), "cgo_batch_lbfgs_max_n_obj", K, n, batch, m)) return rc;
-    if (!lds) {   // the model's batched L-BFGS program: compiled on the first such solve on its module
-        std::string log;
-        if (int rc = rtc_compile_batch_lbfgs(*model->o.rtc, log)) { set_error("user objective: the batched L-BFGS program did not compile:\n" + log); return rc; }
-    }
-    if (rows_used) *rows_used = lds ? CGO_BATCH_ROWS_LDS : CGO_BATCH_ROWS_DEVICE;
-    HipObjective cat;
-    if (int rc = batch_model_cat_rows(ctx, model, batch, cat)) return rc;
-    HipBackend be(&ctx->c, &cat);
-    if (int rc = batch_backend_on(ctx, cat, n, batch, params, be, true)) return rc;
-    if (int rc = be.batch_lbfgs_alloc(m, lds)) return rc;
-    return batch_solve_on(ctx, be, n, batch, x0, scalars, nullptr, cfg, ls, slice_iters, out, batch_model_hobj(ctx, model), true, params, K);
-    API_GUARD_END
-}
-
-// ---- a batch that stays on the device between solves ---------------------------------------------------------------------------
-// The concatenated objective, its backend and the uploaded slot rows of cgo_minimize_batch_obj, kept: every cgo_batch_solve is
-// then "reset for a solve" (HipBackend::batch_reset) and the launch loop, hand-backs and result assembly of the one-shot call.
-struct cgo_batch {
-    cgo_ctx *ctx = nullptr;
-    cgo_objective *model = nullptr;   // a reference is held: its scalar and cost class are read at every solve
-    int64_t n = 0, batch = 0;
-    int m_max = 0;                    // > 0: opened for L-BFGS (cgo_batch_lbfgs_open) with a ring of that depth per problem
-    HipObjective cat;
-    HipBackend *be = nullptr;
-    ~cgo_batch() { delete be; }
-};
-
-int cgo_batch_open(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *const *params, int32_t n_params, cgo_batch **handle) {
-    return cgo_batch_open_ex(ctx, model, batch, params, n_params, nullptr, handle);
-}
-
-int cgo_batch_rows(const cgo_batch *h, int32_t *rows_used) {
-    API_GUARD_BEGIN
-    REQUIRE(h && h->be && rows_used, "null argument");
-    if (h->m_max > 0) *rows_used = h->be->batch_lbfgs_in_lds() ? CGO_BATCH_ROWS_LDS : CGO_BATCH_ROWS_DEVICE;   // (its rows are device rows in both tiers)
-    else *rows_used = h->be->batch_device_rows() ? CGO_BATCH_ROWS_DEVICE : CGO_BATCH_ROWS_LDS;
-    return CGO_OK;
-    API_GUARD_END
-}
-
-int cgo_batch_open_ex(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *const *params, int32_t n_params,
-                      const cgo_batch_policy *policy, cgo_batch **handle) {
-    API_GUARD_BEGIN
-    REQUIRE(ctx && model && handle, "null argument");
-    *handle = nullptr;
-    int rows = 0;
-    if (int rc = batch_rows_asked(policy, rows)) return rc;
-    if (int rc = check_batch_model(ctx, model)) return rc;
-    const int64_t n = model->o.n_local;
-    REQUIRE(ctx->c.world() == 1, "batched solves: a multi-rank context is not supported (one rank only)");
-    REQUIRE(batch >= 1, "batched solves: batch must be ≥ 1");
-    REQUIRE(batch <= 0x7FFFFFFF, "batched solves: batch exceeds the largest grid");
-    REQUIRE(n >= 1, "batched solves: n must be ≥ 1");
-    std::unique_ptr<cgo_batch> h(new cgo_batch);
-    h->ctx = ctx; h->n = n; h->batch = batch;
-    bool device_rows = false;
-    if (int rc = batch_model_cat(ctx, model, batch, params, n_params, h->cat, rows, device_rows)) return rc;
-    h->be = new HipBackend(&ctx->c, &h->cat);
-    if (int rc = batch_backend_on(ctx, h->cat, n, batch, params, *h->be, device_rows)) return rc;
-    h->model = model; model->refs++;
-    *handle = h.release();
-    return CGO_OK;
-    API_GUARD_END
-}
-
-int cgo_batch_solve(cgo_batch *h, const double *x0, const double *scalars, const unsigned char *active, const cgo_cg_config *cfg,
-                    const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out) {
-    API_GUARD_BEGIN
-    REQUIRE(h && x0 && cfg && ls && out, "null argument");
-    out->launches = 0; out->handed_back = 0;
-    REQUIRE(h->m_max == 0, "batched solves: the handle was opened for L-BFGS: cgo_batch_lbfgs_solve");
-    if (int rc = check_batch_call(h->ctx, cfg, ls, h->n, h->batch, slice_iters)) return rc;
-    if (scalars)
-        for (int64_t b = 0; b < h->batch; ++b)
-            if (!std::isfinite(scalars[b])) { set_error("batched solves: scalars[" + std::to_string(b) + "] is not finite"); return CGO_EINVAL; }
-    if (active) {
-        bool any = false;
-        for (int64_t b = 0; b < h->batch && !any; ++b) any = active[b] != 0;
-        REQUIRE(any, "batched solves: active selects no problem");
-    }
-    HIPCHK2(hipSetDevice(h->ctx->c.device));
-    h->cat.s0 = h->model->o.s0; h->cat.user_cheap = h->model->o.user_cheap;
-    return batch_solve_on(h->ctx, *h->be, h->n, h->batch, x0, scalars, active, cfg, ls, slice_iters, out, batch_model_hobj(h->ctx, h->model));
-    API_GUARD_END
-}
-
-int cgo_batch_close(cgo_batch *h) {
-    API_GUARD_BEGIN
-    if (!h) return CGO_OK;
-    cgo_ctx *c = h->ctx;
-    cgo_objective *m = h->model;
-    if (c) (void)hipSetDevice(c->c.device);
-    delete h;            // (the backend before the model: its objective shares the model's module)
-    obj_unref(m);
-    return CGO_OK;
-    API_GUARD_END
-}
-
-// ---- … for β = LBFGS(m): the batch of cgo_minimize_batch_lbfgs_obj_ex, kept -----------------------------------------------------
-// The rows, the slot rows and a ring of m_max + 1 slots per problem stay allocated; every cgo_batch_lbfgs_solve resets the rows
-// and states (batch_reset), empties every ring with ITS m ≤ m_max (batch_lbfgs_reset(m): the kernels lay the ring out from the
-// QnState's own m, the stride between two problems' rings stays (m_max + 1) · ld) and is then the one-shot call.  A handed-back
-// problem takes its slot rows from the batch's device rows: the caller's params were valid during open only.
-int cgo_batch_lbfgs_open(cgo_ctx *ctx, cgo_objective *model, int64_t batch, const double *const *params, int32_t n_params,
-                         int32_t m_max, const cgo_batch_policy *policy, cgo_batch **handle) {
-    API_GUARD_BEGIN
-    REQUIRE(ctx && model && handle, "null argument");
-    *handle = nullptr;
-    int rows = 0;
-    if (int rc = batch_lbfgs_rows_asked(policy, rows)) return rc;
-    if (int rc = check_batch_model(ctx, model)) return rc;
-    const int64_t n = model->o.n_local;
-    if (m_max < 1 || m_max > QN_MAX_M) { set_error("batched L-BFGS solves: m_max = " + std::to_string(m_max) + " lies outside 1 … cgo_batch_lbfgs_max_m = " + std::to_string(QN_MAX_M)); return CGO_EINVAL; }
-    REQUIRE(ctx->c.world() == 1, "batched L-BFGS solves: a multi-rank context is not supported (one rank only)");
-    REQUIRE(batch >= 1, "batched L-BFGS solves: batch must be ≥ 1");
-    REQUIRE(batch <= 0x7FFFFFFF, "batched L-BFGS solves: batch exceeds the largest grid");
-    REQUIRE(n >= 1, "batched L-BFGS solves: n must be ≥ 1");
-    if (int rc = check_batch_model_params(model, params, n_params)) return rc;
-    const int K = model->o.nparams();
-    bool lds = false;
-    if (rows != CGO_BATCH_ROWS_DEVICE && (rows == CGO_BATCH_ROWS_LDS || kBatchLbfgsAutoTakesLds)) {   // the tier's program: its static LDS decides the limit
-        HIPCHK2(hipSetDevice(ctx->c.device));
-        if (int rc = batch_lbfgs_lds_program(model)) return rc;
-        if (int rc = batch_lbfgs_tier(rows, n, HipBackend::batch_lbfgs_lds_max_ld(&ctx->c, CGO_OBJ_USER, m_max, model->o.rtc.get()), lds, "cgo_batch_lbfgs_max_n_obj_ex")) return rc;
-    }
-    if (int rc = batch_lbfgs_sizes_of(ctx, cgo_batch_lbfgs_max_n_obj(model), "cgo_batch_lbfgs_max_n_obj", K, n, batch, m_max)) return rc;
-    if (!lds) {   // compiled here, so that a solve never compiles
-        std::string log;
-        if (int rc = rtc_compile_batch_lbfgs(*model->o.rtc, log)) { set_error("user objective: the batched L-BFGS program did not compile:\n" + log); return rc; }
-    }
-    std::unique_ptr<cgo_batch> h(new cgo_batch);
-    h->ctx = ctx; h->n = n; h->batch = batch; h->m_max = m_max;
-    if (int rc = batch_model_cat_rows(ctx, model, batch, h->cat)) return rc;
-    h->be = new HipBackend(&ctx->c, &h->cat);
-    if (int rc = batch_backend_on(ctx, h->cat, n, batch, params, *h->be, true)) return rc;
-    if (int rc = h->be->batch_lbfgs_alloc(m_max, lds)) return rc;
-    h->model = model; model->refs++;
-    *handle = h.release();
-    return CGO_OK;
-    API_GUARD_END
-}
-
-int cgo_batch_lbfgs_m(const cgo_batch *h, int32_t *m_max) {
-    API_GUARD_BEGIN
-    REQUIRE(h && h->be && m_max, "null argument");
-    *m_max = h->m_max;
-    return CGO_OK;
-    API_GUARD_END
-}
-
-int cgo_batch_lbfgs_solve(cgo_batch *h, const double *x0, const double *scalars, const unsigned char *active, const cgo_cg_config *cfg,
-                          const cgo_ls_config *ls, int64_t slice_iters, cgo_batch_results *out) {
-    API_GUARD_BEGIN
-    REQUIRE(h && x0 && cfg && ls && out, "null argument");
-    out->launches = 0; out->handed_back = 0;
-    REQUIRE(h->m_max > 0, "batched L-BFGS solves: the handle was opened for the CG flavours: cgo_batch_solve");
-    if (int rc = check_batch_lbfgs_call(h->ctx, cfg, ls, h->n, h->batch, slice_iters, "cgo_batch_solve")) return rc;
-    const int m = cfg->beta.lbfgs_m;
-    if (m > h->m_max) { set_error("batched L-BFGS solves: m = " + std::to_string(m) + " exceeds the m_max = " + std::to_string(h->m_max) + " the handle was opened with"); return CGO_EINVAL; }
-    if (scalars)
-        for (int64_t b = 0; b < h->batch; ++b)
-            if (!std::isfinite(scalars[b])) { set_error("batched solves: scalars[" + std::to_string(b) + "] is not finite"); return CGO_EINVAL; }
-    if (active) {
-        bool any = false;
-        for (int64_t b = 0; b < h->batch && !any; ++b) any = active[b] != 0;
-        REQUIRE(any, "batched solves: active selects no problem");
-    }
-    HIPCHK2(hipSetDevice(h->ctx->c.device));
-    h->cat.s0 = h->model->o.s0; h->cat.user_cheap = h->model->o.user_cheap;
-    return batch_solve_on(h->ctx, *h->be, h->n, h->batch, x0, scalars, active, cfg, ls, slice_iters, out, batch_model_hobj(h->ctx, h->model),
-                          true, nullptr, h->model->o.nparams(), m);
-    API_GUARD_END
-}
-
-// ---- cgo_batch_probe: a script of passes of a batched solve in one launch (cgo_backend_batch_probe.hip) ------------------------------
-// The batch is made as the solve of that tier makes it — the same refusals of objectives, shapes and sizes, the same concatenated
-// objective, batch_backend_on, batch_lbfgs_alloc — and lives for this one call.
-int64_t cgo_batch_probe_qn_bytes(void) { return (int64_t)sizeof(QnState); }
-
-int cgo_batch_probe(cgo_ctx *ctx, cgo_batch_probe_args *p) {
-    API_GUARD_BEGIN
-    REQUIRE(ctx && p, "null argument");
-    p->points = 0; p->ld = 0; p->symbol[0] = 0;
-    REQUIRE(p->tier >= 0 && p->tier <= 3, "batch probe: tier must be 0 (LDS), 1 (device rows), 2 (L-BFGS) or 3 (L-BFGS in LDS)");
-    REQUIRE(p->npass >= 1 && p->npass <= CGO_BATCH_PROBE_MAX_PASSES, "batch probe: 1 … 32 passes");
-    REQUIRE(ctx->c.world() == 1, "batch probe: a multi-rank context is not supported (one rank only)");
-    REQUIRE(p->batch >= 1 && p->batch <= 0x7FFFFFFF, "batch probe: 1 ≤ batch ≤ the largest grid");
-    REQUIRE(p->x && p->u, "batch probe: x and u are required");
-    const int64_t batch = p->batch;
-    const int rows = p->tier == 0 ? CGO_BATCH_ROWS_LDS : CGO_BATCH_ROWS_DEVICE;
-    bool device_rows = false;
-    HipObjective cat;
-    int64_t n = p->n;
-    if (p->model) {
-        REQUIRE(p->tier < 2, "batch probe: the batched L-BFGS kernels of a run-time compiled objective have no PROBE twin (tiers 0 and 1)");
-        if (int rc = check_batch_model(ctx, p->model)) return rc;
-        n = p->model->o.n_local;
-        REQUIRE(p->n == n, "batch probe: n is not the size of the model objective");
-        REQUIRE(n >= 1, "batch probe: n must be ≥ 1");
-        if (p->scalars)
-            for (int64_t b = 0; b < batch; ++b)
-                if (!std::isfinite(p->scalars[b])) { set_error("batch probe: scalars[" + std::to_string(b) + "] is not finite"); return CGO_EINVAL; }
-        if (int rc = batch_model_cat(ctx, p->model, batch, p->params, p->n_params, cat, rows, device_rows)) return rc;
-    } else {
-        const int32_t obj_kind = p->obj_kind;
-        REQUIRE(batch_kind(obj_kind), "batch probe: the objective must be CGO_OBJ_QUAD_DIAG, CGO_OBJ_ROSENBROCK_PAIRED, CGO_OBJ_BOOTH or a model");
-        REQUIRE(n >= 1, "batch probe: n must be ≥ 1");
-        REQUIRE(!p->scalars, "batch probe: scalars belong to a run-time compiled objective");
-        if (obj_kind == CGO_OBJ_ROSENBROCK_PAIRED) REQUIRE(n % 2 == 0, "batch probe: paired Rosenbrock needs an even n");
-        if (obj_kind == CGO_OBJ_BOOTH) REQUIRE(n == 2, "batch probe: Booth is 2-dimensional (n = 2)");
-        if (obj_kind == CGO_OBJ_QUAD_DIAG) REQUIRE(p->params[0], "batch probe: the quadratic needs params[0], the [batch*n] rows of D");
-        HIPCHK2(hipSetDevice(ctx->c.device));
-        if (p->tier >= 2) {
-            REQUIRE(p->m >= 1, "batch probe: m must be ≥ 1");
-            if (p->m > QN_MAX_M) { set_error("batch probe: m = " + std::to_string(p->m) + " exceeds cgo_batch_lbfgs_max_m = " + std::to_string(QN_MAX_M)); return CGO_EINVAL; }
-            if (p->tier == 3) { bool lds = false; if (int rc = batch_lbfgs_tier(CGO_BATCH_ROWS_LDS, n, batch_lbfgs_lds_max_n(ctx, obj_kind, p->m), lds)) return rc; }
-            if (int rc = batch_lbfgs_sizes(ctx, obj_kind, n, batch, p->m)) return rc;
-            device_rows = true;
-        } else {
-            if (int rc = batch_tier(ctx, rows, n, batch, obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0, cgo_batch_max_n(ctx, obj_kind), "cgo_batch_max_n", device_rows)) return rc;
-        }
-        const int64_t ld = n + (n & 1);
-        cat.ctx = &ctx->c; cat.kind = obj_kind; cat.n_global = cat.n_local = batch * ld; cat.offset = 0;
-        if (cat.uses_param()) { if (int rc = cat.p[0].alloc((size_t)(batch * ld))) return rc; }
-    }
-    HipBackend be(&ctx->c, &cat);
-    if (int rc = batch_backend_on(ctx, cat, n, batch, p->params, be, device_rows)) return rc;
-    if (p->tier >= 2) { if (int rc = be.batch_lbfgs_alloc(p->m, p->tier == 3)) return rc; }
-    return be.batch_probe(*p);
     API_GUARD_END
 }
 

@@ -163,7 +163,6 @@ class HipBackend : public VecBackend {
     // largest n one workgroup's LDS holds of x, u and the slots (res_plan's arithmetic); 0: no kernel.  CGO_OBJ_USER: `rtc` with its batch program
     static int64_t batch_max_n(HipCtx *ctx, int obj_kind, const RtcModule *rtc = nullptr);
     // params[j], j < nparams(): the [batch·n] rows of slot j
-    int batch_begin(int64_t batch, int64_t n, const double *x0, const double *const *params, int64_t max_iters, bool trace);
     // … in its two halves, for a batch that stays on the device between solves (cgo_batch_open / cgo_batch_solve): the slot rows
     // once; then per solve x0, the states, and optionally a scalar per problem (scalars, [batch]) and which problems run
     // (active, [batch] bytes; null: all — an inactive problem's workgroup returns at once)
