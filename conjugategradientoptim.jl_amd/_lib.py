@@ -207,6 +207,8 @@ SIGNATURES = {
     "cgo_solver_probe_set_path": (C.c_int, [_vp, C.c_int32]),
     "cgo_solver_debug_set_path_skew": (C.c_int, [_vp, C.c_double]),
     "cgo_solver_probe_set_replay": (C.c_int, [_vp, C.c_int32, dp, dp]),
+    "cgo_solver_probe_set_deep_trial": (C.c_int, [_vp, C.c_int32]),
+    "cgo_solver_replay_stats": (C.c_int, [_vp, i64p, i64p, i64p, i64p, i64p, i64p, C.POINTER(C.c_int32)]),
     "cgo_solver_kernel_symbol": (C.c_int, [_vp, C.c_int32, C.c_char_p, C.c_int32]),
     "cgo_evalwolfeconditions": (C.c_int, [C.POINTER(LSConfigC), C.c_double, C.c_double, C.c_double, C.c_double,
                                           C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

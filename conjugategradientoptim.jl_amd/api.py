@@ -786,10 +786,20 @@ class Solver:
         check(_lib.lib().cgo_solver_set_lazy_direction(self._h, int(bool(on))))
 
     def set_replay_depth(self, d: int):
-        """Replay depth of this solver, 1 … 8 (cgo_solver_set_replay_depth): on an eligible solver d − 1 of every d accept +
+        """Replay depth of this solver, 1 … 16 (cgo_solver_set_replay_depth): on an eligible solver d − 1 of every d accept +
         direction + trial launches store neither x nor u and the d-th replays them and stores both; 1 = the lazy direction's
-        alternation.  Mid-solve, outstanding steps are stored first."""
+        alternation.  Above 8 (deep replay) where the cycle runs as path launches; any other solver runs it as 8.  Mid-solve,
+        outstanding steps are stored first."""
         check(_lib.lib().cgo_solver_set_replay_depth(self._h, int(d)))
+
+    def replay_stats(self):
+        """dict(n=, s=, t=, m=, t_deep=, m_deep=, max_list=) of this solver (cgo_solver_replay_stats): launches N, S, T (a trial met
+        with steps outstanding) and materialise passes M so far, the T and M that met more than seven outstanding steps, and the
+        longest list a launch replayed."""
+        v = [C.c_int64(0) for _ in range(6)]
+        mx = C.c_int32(0)
+        check(_lib.lib().cgo_solver_replay_stats(self._h, *[C.byref(q) for q in v], C.byref(mx)))
+        return dict(zip(("n", "s", "t", "m", "t_deep", "m_deep"), (q.value for q in v)), max_list=mx.value)
 
     def set_lean_sums(self, on: bool):
         """Lean sums for this solver (cgo_solver_set_lean_sums): the replay cycle's launches N and S leave out the trial sums
@@ -816,7 +826,8 @@ class Solver:
         check(_lib.lib().cgo_solver_debug_set_path_skew(self._h, float(factor)))
 
     def probe_launch(self, kind_name: str, variant: int, a_acc: float, beta: float, a: Sequence[float], x, u=None, aux=None,
-                     beta_prev: Optional[float] = None, replay: Optional[Sequence] = None, path_nact: Optional[int] = None):
+                     beta_prev: Optional[float] = None, replay: Optional[Sequence] = None, path_nact: Optional[int] = None,
+                     deep_trial: bool = False):
         """ONE launch of kind `kind_name` with mode bits `variant` on this rank's host vectors (cgo_solver_probe_launch): returns
         dict(sums=the whole reduced row, x=, u=, g= the vectors after the launch, symbol=the instantiation).  A test entry point:
         the solver is for probing only from the first call on.
@@ -838,6 +849,8 @@ class Solver:
             check(L.cgo_solver_probe_set_replay(self._h, len(replay), ra.ctypes.data_as(dp), rb.ctypes.data_as(dp)))
         if path_nact is not None:   # a lean row as its path twin k_cg_path<…, path_nact, true> (this launch only)
             check(L.cgo_solver_probe_set_path(self._h, int(path_nact)))
+        if deep_trial:              # launch T (variant 4100) as k_cg_trial_deep whatever the list's length (this launch only)
+            check(L.cgo_solver_probe_set_deep_trial(self._h, 1))
         n = self.obj.n_local
         vec = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float64)
         x, u, aux = vec(x), vec(u), vec(aux)

@@ -59,9 +59,17 @@ static int launch_cg(int mode, int npts, const RParams &P, int grid, hipStream_t
 
 // the path rows of cgo_instances.def (k_cg_path: pure-HBM streaming, the 7-point row, `nact` points evaluated); -1: no such row
 template <class Obj>
-static int launch_cg_path(int mode, int nact, const RParams &P, int grid, hipStream_t st) {
-#define ROW(MODE, NACT) if (mode == (MODE) && nact == (NACT)) { k_cg_path<Obj, (MODE), (NACT), true><<<grid, BLOCK, 0, st>>>(P); return 0; }
+static int launch_cg_path(int mode, int nact, const RParams &P, const RDeep &Q, int grid, hipStream_t st) {
+#define ROW(MODE, NACT) if (mode == (MODE) && nact == (NACT)) { k_cg_path<Obj, (MODE), (NACT), true><<<grid, BLOCK, 0, st>>>(P, Q); return 0; }
     CGO_CG_PATH_ROWS(ROW)
+#undef ROW
+    return -1;
+}
+// the deep trial rows of cgo_instances.def (k_cg_trial_deep: launch T with more than RMAX steps outstanding); -1: no such row
+template <class Obj>
+static int launch_cg_deep_t(int npts, const RParams &P, const RDeep &Q, int grid, hipStream_t st) {
+#define ROW(NPTS) if (npts == (NPTS)) { k_cg_trial_deep<Obj, (NPTS), true><<<grid, BLOCK, 0, st>>>(P, Q); return 0; }
+    CGO_CG_DEEP_T_ROWS(ROW)
 #undef ROW
     return -1;
 }
@@ -79,6 +87,9 @@ static inline bool path_objective(int kind) {   // the objectives that declare a
 }
 // Predicted path: launches N and S of this solver run as path launches — where the switch is on, the replay
 // cycle runs, and both would otherwise run their lean rows.
+bool HipBackend::deep_trial(int mode) const {
+    return mode == (R_REPLAY | R_TRIAL) && !path_nact_ && path_objective(obj_->kind) && (rep_n_ > RMAX || deep_t_);
+}
 bool HipBackend::path_rows() const {
     if (!path_on_ || !path_objective(obj_->kind) || replay_depth_ < 2 || !lazy_eligible()) return false;
     const int mode_n = r_mode_of(KK_ACCEPT_TRIAL_NOSTORE), mode_s = R_REPLAY | R_ADT;
@@ -131,6 +142,9 @@ int HipBackend::launch_r(int kk, int mode, double a_acc, double beta, const doub
     // Steps outstanding (replay): x lags too, and every launch reads x — R_RESET and R_INIT included.  Any launch but N / S / T
     // gets both vectors stored first.
     if (rep_n_ > 0 && !(mode & R_REPLAY)) { if (int rc = materialize_lag()) return rc; }
+    // More steps outstanding than RParams holds (deep replay): a path launch and the deep trial launch take the rest in their second
+    // argument, every other replay launch gets the pair stored first and starts from an empty list.
+    if (rep_n_ > RMAX && (mode & R_REPLAY) && r_base(mode) != R_REPLAY && !path_nact_ && !deep_trial(mode)) { if (int rc = materialize_lag()) return rc; }
     RPlan plan;
     const int npts = path_nact_ ? MAXP : npts_for(k);   // a path launch fills the 7-point row whatever k
     if (int rc = launch_r_kernel(kk, mode, a_acc, beta, a, k, npts, nullptr, &plan)) return rc;
@@ -203,27 +217,37 @@ int HipBackend::materialize_u() {
 // materialize_u not a launch the solve asked for; the profile shows it under its own kind.
 int HipBackend::materialize_lag() {
     if (int rc = materialize_u()) return rc;
-    if (rep_n_ == 0) return CGO_OK;
     const int64_t asked = total_launches_;
     const int nact = path_nact_;
     path_nact_ = 0;
-    const int rc = launch_rk(KK_MATERIALIZE_XU, 0.0, 0.0, nullptr, 0, false, nullptr);
+    int rc = CGO_OK;
+    // the pass replays RMAX steps at most: a longer list (deep replay) goes in chunks — store the pair after the first RMAX steps,
+    // shift the list, again.  Rare (the end of a solve, a mode switch), so no kernel of its own.
+    while (rep_n_ > 0 && rc == CGO_OK) {
+        const int all = rep_n_, take = std::min(all, (int)RMAX);
+        rep_n_ = take;
+        rc = launch_rk(KK_MATERIALIZE_XU, 0.0, 0.0, nullptr, 0, false, nullptr);
+        rep_n_ = all;
+        if (rc) break;
+        rstats_.m++;
+        if (all > RMAX) rstats_.m_deep++;
+        for (int j = take; j < all; ++j) { rep_a_[j - take] = rep_a_[j]; rep_b_[j - take] = rep_b_[j]; }
+        rep_n_ = all - take;
+    }
     path_nact_ = nact;
     total_launches_ = asked;
-    if (rc) return rc;
-    rep_n_ = 0;
-    return CGO_OK;
+    return rc;
 }
 
 int HipBackend::set_replay_depth_now(int d) {
-    if (d < 1 || d > RMAX + 1) { set_error("replay depth: 1 … 8"); return CGO_EINVAL; }
+    if (d < 1 || d > RCAP + 1) { set_error("replay depth: 1 … 16"); return CGO_EINVAL; }
     if (d != replay_depth_) { if (int rc = materialize_lag()) return rc; }   // mid-solve: a cycle of the old depth ends first
     replay_depth_ = d;
     return CGO_OK;
 }
 
 void HipBackend::set_probe_replay(int nrep, const double *a, const double *beta) {
-    probe_rep_n_ = std::max(0, std::min(nrep, (int)RMAX));
+    probe_rep_n_ = std::max(0, std::min(nrep, (int)RCAP));   // (more than RMAX: path rows and the deep trial launch only — probe_launch refuses the others)
     for (int j = 0; j < probe_rep_n_; ++j) { probe_rep_a_[j] = a[j]; probe_rep_b_[j] = beta[j]; }
 }
 
@@ -233,11 +257,14 @@ int HipBackend::accept_dir_trial_r(double a_acc, double beta, const double *a, i
     if (!lazy_eligible()) return launch_rk(KK_ACCEPT_DIR_TRIAL, a_acc, beta, a, k, true, s);
     if (replay_depth_ >= 2) {
         if (int rc = materialize_u()) return rc;
-        if (rep_n_ < replay_depth_ - 1 && rep_n_ < RMAX) {   // launch N: the new pair in registers only
+        // launch N while the list is short of the depth and of what the launch about to run replays: a path launch takes RCAP steps
+        // (deep replay), any other RMAX — a solver without path rows runs a depth above 8 as depth 8
+        if (rep_n_ < replay_depth_ - 1 && rep_n_ < (path_nact_ ? RCAP : RMAX)) {   // launch N: the new pair in registers only
             const int mode_n = r_mode_of(KK_ACCEPT_TRIAL_NOSTORE);
             if (int rc = launch_r(KK_ACCEPT_TRIAL_NOSTORE, mode_n | lean_for(mode_n), a_acc, beta, a, k, true, s)) return rc;
             if (path_nact_) { path_last_n_ = path_nact_; path_count_[path_nact_]++; }
             rep_a_[rep_n_] = a_acc; rep_b_[rep_n_] = beta; rep_n_++;
+            rstats_.n++;
             return CGO_OK;
         }
         // launch S: replays the outstanding steps, then today's launch
@@ -245,6 +272,7 @@ int HipBackend::accept_dir_trial_r(double a_acc, double beta, const double *a, i
         if (int rc = launch_r(KK_ACCEPT_DIR_TRIAL, mode_s | lean_for(mode_s), a_acc, beta, a, k, true, s)) return rc;
         if (path_nact_) { path_last_s_ = path_nact_; path_count_[path_nact_]++; }
         rep_n_ = 0;
+        rstats_.s++;
         return CGO_OK;
     }
     if (!u_lag_) {   // launch A: x ← x + a·u, the new direction in registers only
@@ -258,7 +286,11 @@ int HipBackend::accept_dir_trial_r(double a_acc, double beta, const double *a, i
     return CGO_OK;
 }
 int HipBackend::trial_r(const double *a, int k, double *s) {
-    if (rep_n_ > 0 && lazy_eligible()) return launch_r(KK_TRIAL, R_REPLAY | R_TRIAL, 0, 0, a, k, true, s);   // 24 B: nothing stored, steps still outstanding
+    if (rep_n_ > 0 && lazy_eligible()) {   // launch T — 24 B: nothing stored, steps still outstanding
+        rstats_.t++;
+        if (rep_n_ > RMAX) rstats_.t_deep++;
+        return launch_r(KK_TRIAL, R_REPLAY | R_TRIAL, 0, 0, a, k, true, s);
+    }
     if (u_lag_ && lazy_eligible()) return launch_r(KK_TRIAL, R_ULAG | R_TRIAL, 0, 0, a, k, true, s);   // 24 B: nothing stored, still lagged
     return launch_rk(KK_TRIAL, 0, 0, a, k, true, s);
 }
@@ -298,7 +330,8 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
     const bool has_sums = r_has_sums(mode);
     const RPlan plan = *plan_out = r_plan(mode, npts);
     const bool big = plan.big; const int grid = plan.grid;
-    last_mode_ = mode; last_npts_ = plan.npts; last_big_ = big; last_nact_ = path_nact_;
+    const bool deep_t = deep_trial(mode);
+    last_mode_ = mode; last_npts_ = plan.npts; last_big_ = big; last_nact_ = deep_t ? -1 : path_nact_;
     if (path_nact_ && (chain() || !big || ctl || !path_row(mode, path_nact_) || !path_objective(obj_->kind))) { set_error("internal: not a path row"); return CGO_EINVAL; }
     if (chain()) {
         if (int rc = prof_begin(kk)) return rc;
@@ -310,8 +343,14 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
     P.xo = xc_; P.uo = uc_;
     P.a_acc = a_acc; P.beta = beta; P.s0 = obj_->s0; P.partials = ctx_->partials;
     P.beta_prev = beta_lag_;
-    P.nrep = (mode & R_REPLAY) ? rep_n_ : 0;
+    const int nrep = (mode & R_REPLAY) ? rep_n_ : 0;
+    if (nrep > RCAP || (nrep > RMAX && !path_nact_ && !deep_t)) { set_error("internal: more replayed steps than the launch takes"); return CGO_ESTATE; }
+    P.nrep = std::min(nrep, (int)RMAX);
     for (int j = 0; j < RMAX; ++j) { P.ra[j] = j < P.nrep ? rep_a_[j] : 0.0; P.rb[j] = j < P.nrep ? rep_b_[j] : 0.0; }
+    RDeep Q;   // the steps beyond RMAX (path launches and the deep trial launch)
+    Q.nrep2 = nrep - P.nrep;
+    for (int j = 0; j < RDEEP; ++j) { Q.ra2[j] = j < Q.nrep2 ? rep_a_[RMAX + j] : 0.0; Q.rb2[j] = j < Q.nrep2 ? rep_b_[RMAX + j] : 0.0; }
+    rstats_.max_list = std::max(rstats_.max_list, nrep);
     P.ctl = ctl;
     P.x2 = xn_;
     for (int j = 0; j < MAXP; ++j) P.a[j] = (a && j < k) ? a[j] : ((a && k > 0) ? a[k - 1] : 0.0);
@@ -336,7 +375,15 @@ int HipBackend::launch_r_kernel(int kk, int mode, double a_acc, double beta, con
     int r = -2;
     if (path_nact_) {
         switch (obj_->kind) {
-#define ROW(KIND, T) case KIND: r = launch_cg_path<T>(mode, path_nact_, P, grid, st); break;
+#define ROW(KIND, T) case KIND: r = launch_cg_path<T>(mode, path_nact_, P, Q, grid, st); break;
+        CGO_OBJ_CURV_ROWS(ROW)
+#undef ROW
+        default: break;
+        }
+    } else if (deep_t) {
+        if (!big) { set_error("internal: not a deep trial row"); return CGO_EINVAL; }
+        switch (obj_->kind) {
+#define ROW(KIND, T) case KIND: r = launch_cg_deep_t<T>(plan.npts, P, Q, grid, st); break;
         CGO_OBJ_CURV_ROWS(ROW)
 #undef ROW
         default: break;
@@ -397,6 +444,7 @@ int HipBackend::launch_chain_kernel(int mode, double a_acc, double beta, const d
 std::string HipBackend::r_symbol(int mode, int npts, bool big, int nact) const {
     char buf[160];
     if (chain()) snprintf(buf, sizeof buf, "k_chain<%d, %d, %s>", mode, npts, big ? "true" : "false");
+    else if (nact < 0) snprintf(buf, sizeof buf, "k_cg_trial_deep<%s, %d, true>", obj_tname(), npts);   // (nact −1: the deep trial launch)
     else if (nact) snprintf(buf, sizeof buf, "k_cg_path<%s, %d, %d, true>", obj_tname(), mode, nact);
     else snprintf(buf, sizeof buf, "k_cg<%s, %d, %d, %s>", obj_tname(), mode, npts, big ? "true" : "false");
     return buf;
@@ -420,12 +468,14 @@ std::string HipBackend::kernel_symbol(int kk) const {
     case KK_ACCEPT_TRIAL_NOSTORE: case KK_MATERIALIZE_XU: if (!lazy || replay_depth_ < 2) return ""; break;
     default: break;
     }
+    if (kk == KK_TRIAL && lazy && rep_n_ > RMAX) mode |= R_REPLAY;   // launch T with a deep list outstanding: what runs next
     const RPlan plan = r_plan(mode, rk->pts == PTS_ONE ? 1 : npts_for(rk->pts == PTS_MAX ? max_points() : std::min(max_points(), 3)));
     if ((mode & R_REPLAY) && (mode & R_ACCEPT)) mode |= lean_for(mode);   // N and S: the lean row where that is what runs
     if ((mode & R_REPLAY) && (mode & R_ACCEPT) && path_rows()) {   // … or the path row that last ran for the kind (none yet: the tree's)
         const int last = kk == KK_ACCEPT_TRIAL_NOSTORE ? path_last_n_ : path_last_s_;
         return r_symbol(mode, plan.npts, plan.big, last ? last : MAXP);
     }
+    if (kk == KK_TRIAL && deep_trial(mode)) return r_symbol(mode, plan.npts, plan.big, -1);
     return r_symbol(mode, plan.npts, plan.big);
 }
 
@@ -809,6 +859,8 @@ int HipBackend::probe_launch(int kk, int variant, double a_acc, double beta, con
     *sums_len = 0;
     const int want_nact = probe_nact_;   // a lean row as its path twin (cgo_solver_probe_set_path): asked once, for this call
     probe_nact_ = 0;
+    const bool want_deep = probe_deep_t_;   // launch T as the deep trial launch (cgo_solver_probe_set_deep_trial): asked once, for this call
+    probe_deep_t_ = false;
     const bool lse = obj_->two_phase();
     if (k < 0 || k > MAXP || (k > 0 && !a)) { set_error("probe: 0 ≤ k ≤ 7 trial steps"); return CGO_EINVAL; }
     if (!rmode_ && !lse) return probe_launch_stored(kk, variant, a_acc, beta, a, k, x, u, aux, sums, sums_cap, sums_len, x_out, u_out, g_out, symbol);
@@ -882,12 +934,18 @@ int HipBackend::probe_launch(int kk, int variant, double a_acc, double beta, con
         symbol = buf;
     } else {
         double s[64];
+        if (want_deep && (mode != (R_REPLAY | R_TRIAL) || want_nact || !path_objective(obj_->kind))) { rep_n_ = 0; set_error("probe: not a deep trial launch of this solver"); return CGO_EINVAL; }
+        if (rep_n_ > RMAX && !want_nact && !(mode == (R_REPLAY | R_TRIAL) && path_objective(obj_->kind))) {
+            rep_n_ = 0; set_error("probe: more than 7 replayed steps: path rows and the deep trial launch only"); return CGO_EINVAL;
+        }
+        deep_t_ = want_deep;
         if (want_nact) {
             if (!path_row(mode, want_nact) || !path_objective(obj_->kind) || k > want_nact) { rep_n_ = 0; set_error("probe: not a path row of this solver, or more steps than it evaluates"); return CGO_EINVAL; }
             path_nact_ = want_nact;
         }
         rc = launch_r(kk, mode, a_acc, beta, a, k, true, s);
         path_nact_ = 0;
+        deep_t_ = false;
         rep_n_ = 0;
         if (rc) return rc;
         symbol = r_symbol(last_mode_, last_npts_, last_big_, last_nact_);

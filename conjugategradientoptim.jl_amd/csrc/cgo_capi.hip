@@ -344,8 +344,10 @@ int cgo_ctx_set_default_policy(cgo_ctx *ctx, const cgo_solver_policy *policy) {
 }
 
 // explicit argument > context default > CGO_* experiment override > library policy, field by field
-static const int kReplayDepth = 8;   // 6 was the best median of 1, 2, 3, 4, 6, 8 on one MI355X at n = 1e8 (profiles/r06_replay_*) while a replayed
-                                     // step cost seven trial points of arithmetic; with the predicted path 8 is + 3.8 % over 6 (profiles/r09_path_*)
+static const int kReplayDepth = 12;  // 6 was the best median of 1, 2, 3, 4, 6, 8 on one MI355X at n = 1e8 (profiles/r06_replay_*) while a replayed
+                                     // step cost seven trial points of arithmetic; with the predicted path 8 was + 3.8 % over 6 (profiles/r09_path_*);
+                                     // with deep replay (path launches take up to 15 steps) 12 is the best median of 8, 10, 12, 16: + 1.65 % over 8, while
+                                     // 16 gives the gain back to the arithmetic of its long lists (profiles/r10_deep_*)
 static const bool kLeanSums = true;   // lean sums where replay's default is on: BASELINE.md, profiles/r07_lean_*
 static const bool kPathPredict = true;   // predicted path where lean sums' default is on: DESIGN.md §4
 static int env_tri(const char *name) { const char *e = getenv(name); return e ? (e[0] != '0' ? 1 : 0) : -1; }
@@ -523,11 +525,11 @@ extern "C++" int make_solver(cgo_ctx *ctx, cgo_objective *obj, const cgo_cg_conf
     // them and stores both — (24d + 16)/d B/element per iteration on the separable quadratic.  Library policy: kReplayDepth
     // for that objective where an accepting launch exceeds the library's OWN pure-HBM threshold (a threshold lowered through
     // hbm_stream_bytes does not lower this one: nothing has been measured at such sizes); 1 — the lazy direction's
-    // alternation — everywhere else.  CGO_REPLAY_DEPTH=1…8 forces it; cgo_solver_set_replay_depth has the last word.
+    // alternation — everywhere else.  CGO_REPLAY_DEPTH=1…16 forces it; cgo_solver_set_replay_depth has the last word.
     {
         int depth = 1;
         if (obj->o.kind == CGO_OBJ_QUAD_DIAG && 8.0 * (double)obj->o.n_local * 5.0 > 1.4e9) depth = kReplayDepth;
-        if (const char *e = getenv("CGO_REPLAY_DEPTH")) { const int v = atoi(e); if (v >= 1 && v <= 8) depth = v; }
+        if (const char *e = getenv("CGO_REPLAY_DEPTH")) { const int v = atoi(e); if (v >= 1 && v <= 16) depth = v; }
         s->be->set_replay_depth(depth);
     }
     // Lean sums: launches N and S of the replay cycle do not form the trial sums the β flavour never reads
@@ -772,8 +774,24 @@ int cgo_solver_set_lazy_direction(cgo_solver *s, int32_t on) {
 int cgo_solver_set_replay_depth(cgo_solver *s, int32_t d) {
     API_GUARD_BEGIN
     REQUIRE(s, "null argument");
-    REQUIRE(d >= 1 && d <= 8, "replay depth: 1 … 8");
+    REQUIRE(d >= 1 && d <= 16, "replay depth: 1 … 16");
     return s->be->set_replay_depth_now(d);
+    API_GUARD_END
+}
+
+int cgo_solver_replay_stats(cgo_solver *s, int64_t *n, int64_t *s_launches, int64_t *t, int64_t *m, int64_t *t_deep, int64_t *m_deep,
+                            int32_t *max_list) {
+    API_GUARD_BEGIN
+    REQUIRE(s, "null argument");
+    const auto &r = s->be->replay_stats();
+    if (n) *n = r.n;
+    if (s_launches) *s_launches = r.s;
+    if (t) *t = r.t;
+    if (m) *m = r.m;
+    if (t_deep) *t_deep = r.t_deep;
+    if (m_deep) *m_deep = r.m_deep;
+    if (max_list) *max_list = r.max_list;
+    return CGO_OK;
     API_GUARD_END
 }
 
@@ -828,8 +846,16 @@ int cgo_solver_probe_set_path(cgo_solver *s, int32_t nact) {
 int cgo_solver_probe_set_replay(cgo_solver *s, int32_t nrep, const double *a, const double *beta) {
     API_GUARD_BEGIN
     REQUIRE(s, "null argument");
-    REQUIRE(nrep >= 0 && nrep <= 7 && (nrep == 0 || (a && beta)), "probe replay list: 0 … 7 (a*, β) pairs");
+    REQUIRE(nrep >= 0 && nrep <= 15 && (nrep == 0 || (a && beta)), "probe replay list: 0 … 15 (a*, β) pairs (more than 7: path rows and the deep trial launch)");
     s->be->set_probe_replay(nrep, a, beta);
+    return CGO_OK;
+    API_GUARD_END
+}
+
+int cgo_solver_probe_set_deep_trial(cgo_solver *s, int32_t on) {
+    API_GUARD_BEGIN
+    REQUIRE(s, "null argument");
+    s->be->set_probe_deep_trial(on != 0);
     return CGO_OK;
     API_GUARD_END
 }

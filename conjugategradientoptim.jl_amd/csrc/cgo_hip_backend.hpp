@@ -257,10 +257,17 @@ class HipBackend : public VecBackend {
     void set_probe_beta_prev(double b) { probe_beta_prev_ = b; }
     // Replay: of every d accepting launches of an eligible solver d − 1 store nothing and the d-th stores x and u.
     // d = 1: the lazy direction's alternation.
-    void set_replay_depth(int d) { replay_depth_ = d < 1 ? 1 : (d > 8 ? 8 : d); }
+    // d ≤ 16 where launches N and S run as path launches, which take the steps beyond the seventh in a second kernel argument (deep
+    // replay); every other solver runs a larger request as depth 8.
+    void set_replay_depth(int d) { replay_depth_ = d < 1 ? 1 : (d > 16 ? 16 : d); }
     int replay_depth() const { return replay_depth_; }
     int set_replay_depth_now(int d);   // (mid-solve: outstanding steps are stored first)
     void set_probe_replay(int nrep, const double *a, const double *beta);
+    void set_probe_deep_trial(bool on) { probe_deep_t_ = on; }   // the next probe_launch of launch T runs as k_cg_trial_deep whatever its list
+    // launches N, S, T (a trial met with steps outstanding) and M (a materialise pass) so far; the T and M among them that met more
+    // than seven outstanding steps; the longest list a launch replayed
+    struct ReplayStats { int64_t n = 0, s = 0, t = 0, m = 0, t_deep = 0, m_deep = 0; int max_list = 0; };
+    const ReplayStats &replay_stats() const { return rstats_; }
     // Lean sums: launches N and S without the trial sums the solver's β flavour never reads (beta_unread_sums),
     // where cgo_instances.def has rows for that mask.  The stored state is the same either way: no pass is needed to switch.
     void set_beta_unread(int bits) { lean_mask_ = bits; if (lean_bits_) lean_bits_ = bits; }
@@ -387,7 +394,10 @@ class HipBackend : public VecBackend {
     int materialize_u();   // store the rebuilt direction for any reader but the lag launches; clears u_lag_
     // replay: memory holds (x_k, u_k); rep_a_[j], rep_b_[j] = (a*, β) of the rep_n_ steps accepted since, oldest first
     int replay_depth_ = 1, rep_n_ = 0, probe_rep_n_ = 0;
-    double rep_a_[7] = {}, rep_b_[7] = {}, probe_rep_a_[7] = {}, probe_rep_b_[7] = {};
+    double rep_a_[15] = {}, rep_b_[15] = {}, probe_rep_a_[15] = {}, probe_rep_b_[15] = {};
+    bool probe_deep_t_ = false, deep_t_ = false;   // deep T whatever the list: asked for by a probe; in force for the probe's launch
+    bool deep_trial(int mode) const;   // this launch runs as k_cg_trial_deep: launch T with more than seven steps outstanding (or the probe's request)
+    ReplayStats rstats_;
     int materialize_lag();   // … and the replayed pair (x, u) likewise; clears u_lag_ and rep_n_
     int lean_mask_ = 0, lean_bits_ = 0;   // the flavour's R_NO… bits; those in force (0: full rows)
     int lean_for(int mode) const;         // … for this mode: lean_bits_ where a lean row exists, else 0

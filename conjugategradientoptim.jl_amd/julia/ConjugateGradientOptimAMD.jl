@@ -347,7 +347,7 @@ end
 # ---- src/engine/optim.jl:6-171 ----------------------------------------------------------------
 # (The one-shot entry points build their solvers inside the library, so the per-solver setters — cgo_solver_set_lazy_direction,
 #  cgo_solver_set_replay_depth, cgo_solver_set_lean_sums, cgo_solver_set_path_prediction — have no handle here: ENV["CGO_LAZY_DIR"],
-#  ENV["CGO_REPLAY_DEPTH"] = "1" … "8", ENV["CGO_LEAN_SUMS"] = "0" | "1" and ENV["CGO_PATH_PREDICT"] = "0" | "1" reach them, INTEGRATION.md.)
+#  ENV["CGO_REPLAY_DEPTH"] = "1" … "16", ENV["CGO_LEAN_SUMS"] = "0" | "1" and ENV["CGO_PATH_PREDICT"] = "0" | "1" reach them, INTEGRATION.md.)
 function minimizeobjective(fdf!::DeviceObjective, x_initial::Vector{T}, config::CGConfig{T,BT,ET},
                            linesearch_config::LineSearchConfig) where {T<:AbstractFloat,BT<:βConfig,ET}
     T === Float64 || throw(MethodError(minimizeobjective, (fdf!, x_initial, config, linesearch_config)))  # reference is Float64-only (optim.jl:47)

@@ -429,10 +429,18 @@ int cgo_solver_set_lazy_direction(cgo_solver *s, int32_t on);
  * (a*, β) of the steps accepted since, and the d-th ("accept_dir_trial", R_REPLAY instantiation, 8n(2+p+2) bytes) stores both.
  * Any other reader of x or u gets both stored first ("materialize_xu", not counted in total_launches).  Results are those of
  * the plain launches bit for bit.  d = 1 is the lazy direction's alternation.  Library policy: d > 1 only for the separable
- * quadratic where an accepting launch exceeds the library's own pure-HBM threshold (1.4 GB); env CGO_REPLAY_DEPTH=1…8 forces
- * it; this call has the last word for one solver (1 ≤ d ≤ 8; mid-solve, outstanding steps are stored first).
+ * quadratic where an accepting launch exceeds the library's own pure-HBM threshold (1.4 GB); env CGO_REPLAY_DEPTH=1…16 forces
+ * it; this call has the last word for one solver (1 ≤ d ≤ 16; mid-solve, outstanding steps are stored first).
+ * Deep replay: d > 8 takes effect where launches N and S run as path launches (below), which take the steps beyond the seventh
+ * in a second kernel argument; a trial-only launch met with more than seven steps outstanding runs "k_cg_trial_deep<Obj, NPTS,
+ * true>", "materialize_xu" stores a longer list in passes of seven steps, and any other solver runs d > 8 as d = 8.
  * cgo_solver_set_lazy_direction(s, 0) and CGO_LAZY_DIR=0 switch all of it off. */
 int cgo_solver_set_replay_depth(cgo_solver *s, int32_t d);
+/* What the replay cycle of this solver has launched so far: launches N, S, T (a trial-only launch met with steps outstanding) and M
+ * ("materialize_xu" passes); how many of the T and of the M met more than seven outstanding steps; the longest list a launch
+ * replayed.  Any pointer may be null. */
+int cgo_solver_replay_stats(cgo_solver *s, int64_t *n, int64_t *s_launches, int64_t *t, int64_t *m, int64_t *t_deep, int64_t *m_deep,
+                            int32_t *max_list);
 /* Lean sums.  A β flavour reads only some of the seven sums a trial point delivers (Polak–Ribière: f, g⁺·u,
  * g⁺·g⁺ and y·g⁺); the seven-point launches are short of FP64 issue slots, not of bytes.  With lean sums on, launches N and S of
  * the replay cycle run instantiations that do not form the sums the solver's flavour never reads (R_NOGTG = 16384,
@@ -864,9 +872,12 @@ int cgo_solver_probe_set_beta_prev(cgo_solver *s, double beta_prev);
 /* The replay instantiations likewise (R_REPLAY = 4096, R_NOWX = 8192):
  *   accept_trial_nostore: 4096|7|2048|8192 = 14343   accept_dir_trial: 4096|7 = 4103   trial: 4096|4 = 4100   materialize_xu: 4096
  * R_REPLAY does, on load, for j < nrep: x ← x + a[j]·u ; u ← −∇f(x) + beta[j]·u.  The list is what this call set last (empty
- * until then; 0 ≤ nrep ≤ 7).
+ * until then; 0 ≤ nrep ≤ 15: more than 7 for a path row (cgo_solver_probe_set_path) and for "trial", which then runs as
+ * "k_cg_trial_deep<Obj, NPTS, true>" — cgo_solver_probe_launch refuses a longer list for any other launch).
+ * cgo_solver_probe_set_deep_trial(s, 1): the NEXT probe of "trial" with variant 4100 runs as k_cg_trial_deep whatever the list.
  * Lean N and S (Polak–Ribière's mask 16384|32768|65536 = 114688 or-ed in): accept_trial_nostore 129031, accept_dir_trial 118791. */
 int cgo_solver_probe_set_replay(cgo_solver *s, int32_t nrep, const double *a, const double *beta);
+int cgo_solver_probe_set_deep_trial(cgo_solver *s, int32_t on);
 int cgo_solver_probe_launch(cgo_solver *s, int32_t kernel_kind, int32_t variant, double a_acc, double beta,
                             const double *a, int32_t k,
                             const double *x, const double *u, const double *aux,
