@@ -1,11 +1,13 @@
-// cgo_backend_batch.hip — the host side of batched solves: many small problems in one launch, a workgroup each (k_batch,
-// cgo_kernels_batch.hip.hpp).  The backend's objective spans the concatenated problems (n_local = batch · ld), so x, u and every
-// parameter slot ARE the [batch][ld] rows; the loop over launches is the engine's (run_batch, cgo_engine.cpp), the hand-back
-// of a problem the device loop does not finish is the C API's (cgo_minimize_batch[_obj]), through batch_export_row below.
-// A run-time compiled objective (CGO_OBJ_USER) brings its own k_batch, the batch program of its module (cgo_rtc_batch.hip).
-// Two tiers share everything here but the kernel symbol and the dynamic LDS of the launch: rows in LDS (k_batch) and rows
-// streamed from device memory (k_batch_rows, batch_alloc's device_rows) — whose instantiations live in a translation unit of
-// their own (cgo_backend_batch_rows.hip), so that the device code of this one is what it was before that tier existed.
+// cgo_backend_batch.hip — the host side of batched solves: many small problems in one launch, a workgroup each.  The backend's
+// objective spans the concatenated problems (n_local = batch · ld), so x, u and every parameter slot ARE the [batch][ld] rows;
+// the loop over launches is the engine's (run_batch, cgo_engine.cpp), the hand-back of a problem the device loop does not
+// finish is the C API's (cgo_minimize_batch[_obj]), through batch_export_row below.
+// Four tiers (BatchTier) share everything here — allocation, reset, THE launch, records, hand-back, results.  What differs is one
+// row of batch_tier_of() below: the kernel family (ahead of time, or the program of a run-time compiled objective's module,
+// cgo_rtc_batch.hip), whether it is a quasi-Newton tier, and the rows a launch keeps in dynamic LDS.  The instantiations of
+// k_batch live here; those of every other tier in a translation unit of their own (cgo_backend_batch_rows.hip, _lbfgs.hip,
+// _lbfgs_lds.hip; the PROBE twins of all four in _probe.hip), so that the device code of each unit is what it was before the
+// next tier existed.
 #include "cgo_backend_internal.hpp"
 #include "cgo_kernels_batch.hip.hpp"
 
@@ -13,24 +15,53 @@ namespace cgo {
 
 using namespace dev;
 
-// The rows of cgo_instances.def: the last row with NPTS ≤ npts, the first row below that.
 template <class Obj>
-static const void *batch_kernel(int npts) {
-    const void *fn = nullptr;
-#define ROW(NPTS) if (!fn || npts >= NPTS) fn = (const void *)k_batch<Obj, NPTS>;
-    CGO_BATCH_ROWS(ROW)
+struct BatchRows {
+    static RowPick at(int npts) {
+        RowPick p;
+#define ROW(NPTS) p.row(npts, NPTS, (const void *)k_batch<Obj, NPTS>);
+        CGO_BATCH_ROWS(ROW)
 #undef ROW
-    return fn;
+        return p;
+    }
+};
+static RowPick batch_kernel_for(int obj_kind, int npts) { return row_pick_for<BatchRows>(obj_kind, npts); }
+
+static int batch_vecs(int nparams, int = 0) { return 2 + nparams; }   // x, u and the parameter slots
+// this tier's row of the table (batch_tier_of) (a table inside a function: a namespace-scope constant of a .hip unit is emitted for the device as well)
+const BatchTierRow &tier_row_lds() {
+    static const BatchTierRow row = {"k_batch", batch_kernel_for, RTC_BATCH, "batch:", RTC_BATCH_PROBE, "batch_probe:", false, [](int K, int) { return batch_vecs(K); },
+                                     "batched solves: no k_batch instantiation for this objective"};
+    return row;
 }
-static const void *batch_kernel_for(int obj_kind, int npts) {
-    switch (obj_kind) {
-#define ROW(KIND, T) case KIND: return batch_kernel<T>(npts);
-    CGO_OBJ_ROWS(ROW)
-#undef ROW
-    default: return nullptr;
+// THE table of tiers: each row stands in the translation unit of its tier, beside the instantiations it names
+const BatchTierRow &batch_tier_of(BatchTier tier) {
+    switch (tier) {
+    case BatchTier::LDS: return tier_row_lds();
+    case BatchTier::ROWS: return tier_row_rows();
+    case BatchTier::LBFGS: return tier_row_lbfgs();
+    default: return tier_row_lbfgs_lds();
     }
 }
-const void *batch_rows_kernel_for(int obj_kind, int npts);   // the same for the tier whose rows stay in device memory (cgo_backend_batch_rows.hip)
+
+hipFunction_t batch_tier_module_kernel(const BatchTierRow &t, const RtcModule *rtc, int npts, bool probe) {
+    if (!rtc || (probe && t.probe_prog == RTC_NONE)) return nullptr;
+    return probe ? rtc->kernel(t.probe_prog, t.probe_key, npts) : rtc->kernel(t.prog, t.key, npts);
+}
+
+bool kernel_static_lds(const void *fn, hipFunction_t mf, int64_t &bytes) {
+    if (fn) {
+        hipFuncAttributes fa;
+        if (hipFuncGetAttributes(&fa, fn) != hipSuccess) { (void)hipGetLastError(); return false; }
+        bytes = (int64_t)fa.sharedSizeBytes;
+    } else {
+        int v = 0;
+        if (hipFuncGetAttribute(&v, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, mf) != hipSuccess) { (void)hipGetLastError(); return false; }
+        bytes = v;
+    }
+    return true;
+}
+
 static const void *batch_grad_kernel_for(int obj_kind) {
     switch (obj_kind) {
 #define ROW(KIND, T) case KIND: return (const void *)k_batch_grad<T>;
@@ -39,33 +70,25 @@ static const void *batch_grad_kernel_for(int obj_kind) {
     default: return nullptr;
     }
 }
-static int batch_vecs(int nparams) { return 2 + nparams; }   // x, u and the parameter slots
-
 // res_plan's arithmetic for ONE workgroup that holds a whole problem: what the device gives a block, minus the kernel's static
-// LDS, minus the same 512 bytes of slack, over 8 bytes × the vectors, rounded down to an even count (ld is even).
-// `rtc`: the module of a CGO_OBJ_USER objective, its batch program loaded (rtc_compile_batch).
-int64_t HipBackend::batch_max_n(HipCtx *ctx, int obj_kind, const RtcModule *rtc) {
-    const void *fn = batch_kernel_for(obj_kind, 3);
-    const hipFunction_t mf = (obj_kind == CGO_OBJ_USER && rtc) ? rtc->batch(3) : nullptr;
+// LDS, minus the same 512 bytes of slack, over 8 bytes × the rows the tier keeps there, rounded down to an even count (ld is even)
+// — batch_lbfgs_lds_ld_of, for both LDS tiers.  (k_batch's limit was written out here before the tiers shared it: the same values,
+// a negative remainder gave 0 there by the last line and gives 0 here by the first.)
+// `rtc`: the module of a CGO_OBJ_USER objective, the tier's program loaded.  0: no kernel, no device, rows out of range.
+int64_t batch_tier_max_ld(HipCtx *ctx, BatchTier tier, int obj_kind, int m, const RtcModule *rtc) {
+    const BatchTierRow &t = batch_tier_of(tier);
+    const void *fn = t.aot(obj_kind, 3).fn;
+    const hipFunction_t mf = obj_kind == CGO_OBJ_USER ? batch_tier_module_kernel(t, rtc, 3) : nullptr;
     if (!fn && !mf) return 0;
     if (hipSetDevice(ctx->device) != hipSuccess) { (void)hipGetLastError(); return 0; }
     int max_lds = 0;
     if (hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess) { (void)hipGetLastError(); return 0; }
     int64_t static_lds = 0;
-    if (fn) {
-        hipFuncAttributes fa;
-        if (hipFuncGetAttributes(&fa, fn) != hipSuccess) { (void)hipGetLastError(); return 0; }
-        static_lds = (int64_t)fa.sharedSizeBytes;
-    } else {
-        int v = 0;
-        if (hipFuncGetAttribute(&v, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, mf) != hipSuccess) { (void)hipGetLastError(); return 0; }
-        static_lds = v;
-    }
+    if (!kernel_static_lds(fn, mf, static_lds)) return 0;
     const int nparams = fn ? (obj_kind == CGO_OBJ_QUAD_DIAG ? 1 : 0) : rtc->n_params;
-    const int64_t avail = (int64_t)max_lds - static_lds - 512;
-    const int64_t ld_max = (avail / (8 * batch_vecs(nparams))) & ~1LL;
-    return ld_max < 2 ? 0 : ld_max;
+    return HipBackend::batch_lbfgs_lds_ld_of(max_lds, static_lds, t.lds_rows(nparams, m));
 }
+int64_t HipBackend::batch_max_n(HipCtx *ctx, int obj_kind, const RtcModule *rtc) { return batch_tier_max_ld(ctx, BatchTier::LDS, obj_kind, 0, rtc); }
 
 // x, u, every slot and the results' gradient, [batch][ld] each; the states, f_x0 and a scalar per problem beside them
 double HipBackend::batch_rows_bytes(int64_t batch, int64_t n, int nparams) {
@@ -80,8 +103,9 @@ int HipBackend::batch_alloc(int64_t batch, int64_t n, const double *const *param
     if (batch < 1 || n < 1 || obj_->n_local != batch * ld || !rmode_ || bat_st_) { set_error("internal: batched solve on a backend of another shape"); return CGO_ESTATE; }
     HIPCHK(hipSetDevice(ctx_->device));
     bat_count_ = batch; bat_n_ = n; bat_ld_ = ld;
-    bat_rows_ = device_rows;
-    bat_lds_ = device_rows ? 0 : (size_t)ld * 8 * (size_t)batch_vecs(obj_->nparams());
+    bat_tier_ = device_rows ? BatchTier::ROWS : BatchTier::LDS;
+    const BatchTierRow &t = batch_tier_of(bat_tier_);
+    bat_lds_ = (size_t)ld * 8 * (size_t)t.lds_rows(obj_->nparams(), 0);
     if (device_rows && n > batch_rows_max_n()) { set_error("internal: a batch beyond the pass index of the device-rows tier"); return CGO_ESTATE; }
     // rows padded to ld.  No pass reads the padding element (the odd tail is the workgroup's own element n − 1); the ONE
     // gradient launch over the concatenated rows (batch_results) does evaluate it.  Built-in objectives: zero in x, u and the
@@ -100,12 +124,14 @@ int HipBackend::batch_alloc(int64_t batch, int64_t n, const double *const *param
     HIPCHK(hipMalloc((void **)&bat_st_, sizeof(ResState) * (size_t)batch));
     HIPCHK(hipMalloc((void **)&bat_fx0_, sizeof(double) * (size_t)batch));
     if (obj_->kind == CGO_OBJ_USER) {   // (a module's kernel takes its dynamic LDS as launched, as the resident solver's does)
-        // (rows in device memory: the device-rows program, or the batched L-BFGS program of a batch batch_lbfgs_alloc follows on)
-        if (!obj_->rtc || !(device_rows ? (obj_->rtc->batch_rows(3) || obj_->rtc->batch_lbfgs(3) || obj_->rtc->batch_lbfgs_lds(3)) : obj_->rtc->batch(3) != nullptr)) { set_error("internal: batched solve before the objective's batch program was compiled"); return CGO_ESTATE; }
+        // (rows in device memory: the program of any tier whose rows are — batch_lbfgs_alloc may follow on and make the batch that tier's)
+        bool compiled = false;
+        for (int r = (int)bat_tier_; r < (device_rows ? BATCH_TIERS : 1); ++r) compiled = compiled || batch_tier_module_kernel(batch_tier_of((BatchTier)r), obj_->rtc.get(), 3);
+        if (!compiled) { set_error("internal: batched solve before the objective's batch program was compiled"); return CGO_ESTATE; }
         return CGO_OK;
     }
-    const void *fn = device_rows ? batch_rows_kernel_for(obj_->kind, 3) : batch_kernel_for(obj_->kind, 3);
-    if (!fn) { set_error("batched solves: no k_batch instantiation for this objective"); return CGO_EINVAL; }
+    const void *fn = t.aot(obj_->kind, 3).fn;
+    if (!fn) { set_error(t.missing); return CGO_EINVAL; }
     if (bat_lds_ > 48 * 1024) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bat_lds_));
     return CGO_OK;
 }
@@ -171,26 +197,41 @@ void HipBackend::batch_fill_params(BatchParams &B, const ResConfig &c, int64_t b
     B.budget = budget;
 }
 
+// the fork every launch of a batch takes, a workgroup per problem
+int HipBackend::batch_launch_kernel(const void *fn, hipFunction_t mf, const char *missing, void **args, size_t lds) {
+    if (obj_->kind == CGO_OBJ_USER) {   // (a module's kernel takes its dynamic LDS as launched, as the resident solver's does)
+        if (!mf) { set_error("internal: kernel missing from the run-time compiled objective module"); return CGO_EINVAL; }
+        HIPCHK(hipModuleLaunchKernel(mf, (unsigned)bat_count_, 1, 1, BLOCK, 1, 1, (unsigned)lds, ctx_->stream, args, nullptr));
+    } else {
+        if (!fn) { set_error(missing); return CGO_EINVAL; }
+        HIPCHK(hipLaunchKernel(fn, dim3((unsigned)bat_count_), dim3(BLOCK), args, lds, ctx_->stream));
+    }
+    total_launches_++;
+    return CGO_OK;
+}
+
+// … of the tier's own kernel on its parameter block (BatchParams; BatchLbfgsParams for a quasi-Newton tier)
+int HipBackend::batch_launch_tier(void *params) {
+    const BatchTierRow &t = batch_tier_of(bat_tier_);
+    const bool user = obj_->kind == CGO_OBJ_USER;
+    void *args[] = {params};
+    return batch_launch_kernel(user ? nullptr : t.aot(obj_->kind, 3).fn, user ? batch_tier_module_kernel(t, obj_->rtc.get(), 3) : nullptr, t.missing, args, bat_lds_);
+}
+
 int HipBackend::batch_launch(const ResConfig &c, int64_t budget, std::vector<ResState> &st, std::vector<double> &f_x0) {
     if (!bat_st_) { set_error("internal: batch_launch before batch_alloc"); return CGO_ESTATE; }
-    if (bat_m_ > 0) return batch_lbfgs_launch(c, budget, st, f_x0);   // a batched L-BFGS solve: k_batch_lbfgs (cgo_backend_batch_lbfgs.hip)
     HIPCHK(hipSetDevice(ctx_->device));
     if (budget < 1) budget = 1;
     if (!bat_trace_) {   // nobody reads the records: the leader still writes one per completed iteration of the slice
         if (int rc = batch_recs_reserve(budget)) return rc;
     }
-    BatchParams B{};
-    batch_fill_params(B, c, budget);
-    void *args[] = {&B};
-    if (obj_->kind == CGO_OBJ_USER) {
-        const hipFunction_t mf = !obj_->rtc ? nullptr : bat_rows_ ? obj_->rtc->batch_rows(3) : obj_->rtc->batch(3);
-        if (!mf) { set_error("internal: kernel missing from the run-time compiled objective module"); return CGO_EINVAL; }
-        HIPCHK(hipModuleLaunchKernel(mf, (unsigned)bat_count_, 1, 1, BLOCK, 1, 1, (unsigned)bat_lds_, ctx_->stream, args, nullptr));
+    if (batch_tier_of(bat_tier_).qn) {   // the parameter block with the ring: cgo_backend_batch_lbfgs.hip
+        if (int rc = batch_lbfgs_launch_tier(c, budget)) return rc;
     } else {
-        const void *fn = bat_rows_ ? batch_rows_kernel_for(obj_->kind, 3) : batch_kernel_for(obj_->kind, 3);   // (bat_lds_ = 0 for the rows in device memory)
-        HIPCHK(hipLaunchKernel(fn, dim3((unsigned)bat_count_), dim3(BLOCK), args, bat_lds_, ctx_->stream));
+        BatchParams B{};
+        batch_fill_params(B, c, budget);
+        if (int rc = batch_launch_tier(&B)) return rc;
     }
-    total_launches_++;
     st.resize((size_t)bat_count_); f_x0.resize((size_t)bat_count_);
     HIPCHK(hipMemcpyAsync(st.data(), bat_st_, sizeof(ResState) * (size_t)bat_count_, hipMemcpyDeviceToHost, ctx_->stream));
     HIPCHK(hipMemcpyAsync(f_x0.data(), bat_fx0_, sizeof(double) * (size_t)bat_count_, hipMemcpyDeviceToHost, ctx_->stream));
@@ -240,21 +281,15 @@ int HipBackend::batch_grad_rows() {
     G.x = xc_; G.g = ga_.p; G.p0 = obj_->p[0].p; G.p1 = obj_->p[1].p; G.p2 = obj_->p[2].p; G.p3 = obj_->p[3].p;
     G.s0v = bat_s0v_; G.n = bat_n_; G.ld = bat_ld_;
     void *args[] = {&G};
-    if (obj_->kind == CGO_OBJ_USER) {
-        if (obj_->rtc && !obj_->rtc->batch_grad()) {   // (a batch opened on rows in device memory never compiled the batch program, where this kernel lives)
+    hipFunction_t mf = nullptr;
+    if (obj_->kind == CGO_OBJ_USER && obj_->rtc) {
+        if (!obj_->rtc->batch_grad()) {   // (a batch opened on rows in device memory never compiled the batch program, where this kernel lives)
             std::string log;
-            if (int rc = rtc_compile_batch(*obj_->rtc, log)) { set_error("user objective: the batch program did not compile:\n" + log); return rc; }
+            if (int rc = rtc_compile_program(*obj_->rtc, RTC_BATCH, log)) { set_error(std::string("user objective: ") + rtc_program_what(RTC_BATCH) + " did not compile:\n" + log); return rc; }
         }
-        const hipFunction_t mf = obj_->rtc ? obj_->rtc->batch_grad() : nullptr;
-        if (!mf) { set_error("internal: kernel missing from the run-time compiled objective module"); return CGO_EINVAL; }
-        HIPCHK(hipModuleLaunchKernel(mf, (unsigned)bat_count_, 1, 1, BLOCK, 1, 1, 0, ctx_->stream, args, nullptr));
-    } else {
-        const void *fn = batch_grad_kernel_for(obj_->kind);
-        if (!fn) { set_error("batched solves: no k_batch_grad instantiation for this objective"); return CGO_EINVAL; }
-        HIPCHK(hipLaunchKernel(fn, dim3((unsigned)bat_count_), dim3(BLOCK), args, 0, ctx_->stream));
+        mf = obj_->rtc->batch_grad();
     }
-    total_launches_++;
-    return CGO_OK;
+    return batch_launch_kernel(batch_grad_kernel_for(obj_->kind), mf, "batched solves: no k_batch_grad instantiation for this objective", args, 0);
 }
 
 int HipBackend::batch_results(double *x, double *g, const unsigned char *active) {

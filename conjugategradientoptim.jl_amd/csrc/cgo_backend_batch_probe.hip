@@ -1,7 +1,8 @@
 // cgo_backend_batch_probe.hip — cgo_batch_probe: the PROBE twins of k_batch, k_batch_rows, k_batch_lbfgs and k_batch_lbfgs_lds (the rows of
 // cgo_instances.def × the objectives, each with the template's PROBE flag set) and the host side of a probe.  A translation unit
 // of its own, for the reason cgo_backend_batch_rows.hip and cgo_backend_batch_lbfgs.hip exist: the device code of the product
-// units is what it was before the probe.
+// units is what it was before the probe.  Which twin a batch takes, what the probe calls it and whether a run-time compiled
+// objective has one is the batch's row of batch_tier_of() (cgo_backend_batch.hip).
 //
 // A probe runs on a batch that batch_alloc (and batch_lbfgs_alloc) made, and its launch arguments are batch_fill_params' /
 // batch_lbfgs_fill_params' — the product's ld, slot pointers, s0 / s0v, ring stride and record stride.  What the probe replaces
@@ -17,45 +18,28 @@ using namespace dev;
 static_assert(sizeof(BatchProbePass) == sizeof(cgo_batch_pass) && sizeof(BatchProbeOut) == sizeof(cgo_batch_pass_out), "C ABI twins");
 static_assert(BATCH_PROBE_MAX_PASSES == CGO_BATCH_PROBE_MAX_PASSES && BATCH_PROBE_ROW == 64 && RES_MAXP == 7 && QN_MAX_M == 10, "include/cgo.h states them");
 
-// The rows of cgo_instances.def: the last row with NPTS ≤ npts, the first row below that — as the product's dispatch.
+// The PROBE twins of every tier's rows, picked as the product's dispatch picks (RowPick).  One expansion per objective holds
+// all four tiers, in tier order: the order the kernels were instantiated in before the tiers had a table.
 template <class Obj>
-static const void *batch_probe_kernel(int tier, int npts, int &picked) {
-    const void *fn = nullptr;
-    if (tier == 0) {
-#define ROW(NPTS) if (!fn || npts >= NPTS) { fn = (const void *)k_batch<Obj, NPTS, true>; picked = NPTS; }
+struct ProbeRows {
+    static RowPick at(int npts, BatchTier tier) {
+        RowPick p[BATCH_TIERS];
+#define ROW(NPTS) p[(int)BatchTier::LDS].row(npts, NPTS, (const void *)k_batch<Obj, NPTS, true>);
         CGO_BATCH_ROWS(ROW)
 #undef ROW
-    } else if (tier == 1) {
-#define ROW(NPTS) if (!fn || npts >= NPTS) { fn = (const void *)k_batch_rows<Obj, NPTS, true>; picked = NPTS; }
+#define ROW(NPTS) p[(int)BatchTier::ROWS].row(npts, NPTS, (const void *)k_batch_rows<Obj, NPTS, true>);
         CGO_BATCH_DEVROWS_ROWS(ROW)
 #undef ROW
-    } else if (tier == 2) {
-#define ROW(NPTS) if (!fn || npts >= NPTS) { fn = (const void *)k_batch_lbfgs<Obj, NPTS, true>; picked = NPTS; }
+#define ROW(NPTS) p[(int)BatchTier::LBFGS].row(npts, NPTS, (const void *)k_batch_lbfgs<Obj, NPTS, true>);
         CGO_BATCH_LBFGS_ROWS(ROW)
 #undef ROW
-    } else {
-#define ROW(NPTS) if (!fn || npts >= NPTS) { fn = (const void *)k_batch_lbfgs_lds<Obj, NPTS, true>; picked = NPTS; }
+#define ROW(NPTS) p[(int)BatchTier::LBFGS_LDS].row(npts, NPTS, (const void *)k_batch_lbfgs_lds<Obj, NPTS, true>);
         CGO_BATCH_LBFGS_LDS_ROWS(ROW)
 #undef ROW
+        return p[(int)tier];
     }
-    return fn;
-}
-static const void *batch_probe_kernel_for(int tier, int obj_kind, int npts, int &picked) {
-    switch (obj_kind) {
-#define ROW(KIND, T) case KIND: return batch_probe_kernel<T>(tier, npts, picked);
-    CGO_OBJ_ROWS(ROW)
-#undef ROW
-    default: return nullptr;
-    }
-}
-static int batch_probe_points(int tier, bool user) {   // the points of the instantiation a solve of this tier launches (npts = 3)
-    int picked = 0;
-    if (!user) { (void)batch_probe_kernel_for(tier, CGO_OBJ_QUAD_DIAG, 3, picked); return picked; }
-#define ROW(NPTS) if (!picked || 3 >= NPTS) picked = NPTS;
-    if (tier == 0) { CGO_BATCH_ROWS(ROW) } else { CGO_BATCH_DEVROWS_ROWS(ROW) }
-#undef ROW
-    return picked;
-}
+};
+RowPick batch_probe_kernel_for(BatchTier tier, int obj_kind, int npts) { return row_pick_for<ProbeRows>(obj_kind, npts, tier); }
 
 namespace {
 // a device buffer of `used` bytes with one 128-B line of the NaN pattern behind it
@@ -88,10 +72,13 @@ int HipBackend::batch_probe(cgo_batch_probe_args &p) {
     const bool user = obj_->kind == CGO_OBJ_USER;
     const int64_t batch = bat_count_, n = bat_n_, ld = bat_ld_;
     const int m = bat_m_, K = obj_->nparams();
-    const bool qnt = tier >= 2;   // the two tiers of batched L-BFGS: the ring in device memory (2) or, with the rows, in LDS (3)
-    if ((tier == 0) != !bat_rows_ || qnt != (m > 0) || (tier == 3) != bat_qn_lds_) { set_error("internal: batch_probe on a batch of another tier"); return CGO_ESTATE; }
-    // ---- the script: what this tier's loop issues, for the points of its instantiation
-    const int npts = batch_probe_points(tier, user), nt = npts < 3 ? npts : 3;
+    if (tier != (int)bat_tier_) { set_error("internal: batch_probe on a batch of another tier"); return CGO_ESTATE; }
+    const BatchTierRow &t = batch_tier_of(bat_tier_);
+    const bool qnt = t.qn;   // the two tiers of batched L-BFGS: the ring in device memory (2) or, with the rows, in LDS (3)
+    // ---- the script: what this tier's loop issues, for the points of the instantiation a solve of this tier launches (npts = 3)
+    // (a module's rows are the table's: the points the built-in dispatch picks)
+    const RowPick twin = user ? RowPick{nullptr, t.aot(CGO_OBJ_QUAD_DIAG, 3).points} : batch_probe_kernel_for(bat_tier_, obj_->kind, 3);
+    const int picked = twin.points, npts = picked, nt = npts < 3 ? npts : 3;
     if (p.npass < 1 || p.npass > CGO_BATCH_PROBE_MAX_PASSES) { set_error("batch probe: 1 … 32 passes"); return CGO_EINVAL; }
     std::vector<BatchProbePass> script((size_t)p.npass);
     bool pushed = false;
@@ -139,25 +126,23 @@ int HipBackend::batch_probe(cgo_batch_probe_args &p) {
     } else if (p.scalars && !user) { set_error("batch probe: scalars belong to a run-time compiled objective"); return CGO_EINVAL; }
     if (qnt && p.scalars) { set_error("batch probe: the batched L-BFGS solves take no scalar per problem"); return CGO_EINVAL; }
 
-    // ---- the kernel
-    int picked = 0;
-    const void *fn = user ? nullptr : batch_probe_kernel_for(tier, obj_->kind, 3, picked);
+    // ---- the kernel: the PROBE twin
+    const void *fn = twin.fn;
     hipFunction_t mf = nullptr;
-    if (user) {
+    if (user && t.probe_prog != RTC_NONE) {
         if (!obj_->rtc) { set_error("internal: a run-time compiled objective without its module"); return CGO_ESTATE; }
         std::string log;
-        if (int rc = rtc_compile_batch_probe(*obj_->rtc, log)) { set_error("batch probe: the probe program of the objective did not compile:\n" + log); return rc; }
-        mf = obj_->rtc->batch_probe(tier == 1, 3);
-        picked = npts;
+        if (int rc = rtc_compile_program(*obj_->rtc, t.probe_prog, log)) { set_error(std::string("batch probe: ") + rtc_program_what(t.probe_prog) + " did not compile:\n" + log); return rc; }
+        mf = batch_tier_module_kernel(t, obj_->rtc.get(), 3, true);
     }
     if (!fn && !mf) { set_error("batch probe: no PROBE instantiation for this objective"); return CGO_EINVAL; }
     HIPCHK(hipSetDevice(ctx_->device));
     hipStream_t st = ctx_->stream;
     {   // the batch was sized for the product instantiation: the twin must fit the same launch
-        int max_lds = 0, static_lds = 0;
+        int max_lds = 0;
+        int64_t static_lds = 0;
         HIPCHK(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx_->device));
-        if (fn) { hipFuncAttributes fa; HIPCHK(hipFuncGetAttributes(&fa, fn)); static_lds = (int)fa.sharedSizeBytes; }
-        else HIPCHK(hipFuncGetAttribute(&static_lds, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, mf));
+        if (!kernel_static_lds(fn, mf, static_lds)) { set_error("batch probe: the static LDS of the PROBE instantiation cannot be read"); return CGO_EHIP; }
         if ((size_t)static_lds + bat_lds_ > (size_t)max_lds) { set_error("batch probe: the PROBE instantiation does not fit the launch of the batch"); return CGO_ESTATE; }
         if (fn && bat_lds_ > 48 * 1024) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bat_lds_));
     }
@@ -231,14 +216,11 @@ int HipBackend::batch_probe(cgo_batch_probe_args &p) {
     BatchProbeParams A{};
     BatchLbfgsProbeParams AL{};
     void *args[1];
-    const char *family = tier == 0 ? "k_batch" : tier == 1 ? "k_batch_rows" : tier == 2 ? "k_batch_lbfgs" : "k_batch_lbfgs_lds";
     if (qnt) { batch_lbfgs_fill_params(AL, cfg, 1); AL.pr = pr; args[0] = &AL; }
     else { batch_fill_params(A, cfg, 1); A.pr = pr; args[0] = &A; }
     p.points = picked; p.ld = ld;
-    snprintf(p.symbol, sizeof p.symbol, "%s<%s, %d, true>", family, obj_tname(), picked);
-    if (fn) HIPCHK(hipLaunchKernel(fn, dim3((unsigned)batch), dim3(BLOCK), args, bat_lds_, st));
-    else HIPCHK(hipModuleLaunchKernel(mf, (unsigned)batch, 1, 1, BLOCK, 1, 1, (unsigned)bat_lds_, st, args, nullptr));
-    total_launches_++;
+    snprintf(p.symbol, sizeof p.symbol, "%s<%s, %d, true>", t.family, obj_tname(), picked);
+    if (int rc = batch_launch_kernel(fn, mf, "batch probe: no PROBE instantiation for this objective", args, bat_lds_)) return rc;
     HIPCHK(hipStreamSynchronize(st));
 
     // ---- what it left

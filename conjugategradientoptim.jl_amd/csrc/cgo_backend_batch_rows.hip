@@ -1,7 +1,7 @@
 // cgo_backend_batch_rows.hip — the ahead-of-time instantiations of k_batch_rows (cgo_kernels_batch_rows.hip.hpp), the batched
-// solves' tier whose problem rows stay in device memory, and the facts of its streaming loop.  Everything else of a batched
-// solve — allocation, reset, the launch, records, hand-back, results — is cgo_backend_batch.hip's for both tiers; this file
-// exists so that k_batch's translation unit compiles to what it compiled to before this tier.
+// solves' tier whose problem rows stay in device memory (BatchTier::ROWS), and the facts of its streaming loop.  Everything else
+// of a batched solve is cgo_backend_batch.hip's for every tier; this file exists so that k_batch's translation unit compiles to
+// what it compiled to before this tier.
 #include "cgo_backend_internal.hpp"
 #include "cgo_kernels_batch_rows.hip.hpp"
 
@@ -9,22 +9,22 @@ namespace cgo {
 
 using namespace dev;
 
-// The rows of cgo_instances.def: the last row with NPTS ≤ npts, the first row below that.
 template <class Obj>
-static const void *batch_rows_kernel(int npts) {
-    const void *fn = nullptr;
-#define ROW(NPTS) if (!fn || npts >= NPTS) fn = (const void *)k_batch_rows<Obj, NPTS>;
-    CGO_BATCH_DEVROWS_ROWS(ROW)
+struct BatchDevRows {
+    static RowPick at(int npts) {
+        RowPick p;
+#define ROW(NPTS) p.row(npts, NPTS, (const void *)k_batch_rows<Obj, NPTS>);
+        CGO_BATCH_DEVROWS_ROWS(ROW)
 #undef ROW
-    return fn;
-}
-const void *batch_rows_kernel_for(int obj_kind, int npts) {
-    switch (obj_kind) {
-#define ROW(KIND, T) case KIND: return batch_rows_kernel<T>(npts);
-    CGO_OBJ_ROWS(ROW)
-#undef ROW
-    default: return nullptr;
+        return p;
     }
+};
+static RowPick batch_rows_kernel_for(int obj_kind, int npts) { return row_pick_for<BatchDevRows>(obj_kind, npts); }
+// this tier's row of the table (batch_tier_of): no dynamic LDS
+const BatchTierRow &tier_row_rows() {
+    static const BatchTierRow row = {"k_batch_rows", batch_rows_kernel_for, RTC_BATCH_ROWS, "batch_rows:", RTC_BATCH_PROBE, "batch_rows_probe:", false, [](int, int) { return 0; },
+                                     "batched solves: no k_batch instantiation for this objective"};
+    return row;
 }
 
 int64_t HipBackend::batch_rows_max_n() { return (int64_t)BATCH_ROWS_MAX_N; }

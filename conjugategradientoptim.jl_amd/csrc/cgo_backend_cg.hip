@@ -1425,7 +1425,7 @@ int HipBackend::probe_resident(const cgo_cg_config &cfg, const cgo_ls_config &ls
     hipFunction_t mf = nullptr;
     if (!fn && obj_->kind == CGO_OBJ_USER && obj_->rtc && obj_->rtc->resident(res_npts_)) {   // compiled on the first probe, not with the objective
         std::string log;
-        if (int rc = rtc_compile_resident_probe(*obj_->rtc, log)) { set_error("probe: " + log); return rc; }
+        if (int rc = rtc_compile_program(*obj_->rtc, RTC_RESIDENT_PROBE, log)) { set_error("probe: " + log); return rc; }
         mf = obj_->rtc->resident_probe(res_npts_);
     }
     if (!fn && !mf) { set_error("probe: no PROBE instantiation of this solver's resident kernel"); return CGO_EINVAL; }

@@ -129,18 +129,10 @@ static int check_batch_model_params(cgo_objective *model, const double *const *p
     return CGO_OK;
 }
 
-// The batched programs of a model's module, each compiled on the first use of its tier on the module: the batch program
-// (k_batch<UserObjective, …>, cgo_rtc_batch.hip), the device-rows tier's, the batched L-BFGS program (cgo_rtc_batch_lbfgs.hip) and
-// its LDS tier's (cgo_rtc_batch_lbfgs_lds.hip)
-enum BatchProgram { PROG_BATCH, PROG_BATCH_ROWS, PROG_BATCH_LBFGS, PROG_BATCH_LBFGS_LDS };
-static int batch_program(cgo_objective *model, BatchProgram which) {
-    static const struct { int (*compile)(RtcModule &, std::string &); const char *what; } kPrograms[] = {
-        {rtc_compile_batch, "the batch program"},
-        {rtc_compile_batch_rows, "the program of the batched solves' device-rows tier"},
-        {rtc_compile_batch_lbfgs, "the batched L-BFGS program"},
-        {rtc_compile_batch_lbfgs_lds, "the program of the batched L-BFGS solves' LDS tier"}};
+// A batched program of a model's module (RtcProgram, cgo_rtc.hpp), compiled on the first use of its tier on the module
+static int batch_program(cgo_objective *model, RtcProgram which) {
     std::string log;
-    if (int rc = kPrograms[which].compile(*model->o.rtc, log)) return refuse(rc, std::string("user objective: ") + kPrograms[which].what + " did not compile:\n" + log);
+    if (int rc = rtc_compile_program(*model->o.rtc, which, log)) return refuse(rc, std::string("user objective: ") + rtc_program_what(which) + " did not compile:\n" + log);
     return CGO_OK;
 }
 
@@ -190,7 +182,7 @@ int64_t cgo_batch_max_n_ex(cgo_ctx *ctx, int32_t obj_kind, const cgo_batch_polic
 
 int64_t cgo_batch_max_n_obj(cgo_objective *model) {
     try {
-        if (!batch_model_ok(model) || batch_program(model, PROG_BATCH)) return 0;
+        if (!batch_model_ok(model) || batch_program(model, RTC_BATCH)) return 0;
         return HipBackend::batch_max_n(model->o.ctx, CGO_OBJ_USER, model->o.rtc.get());
     } catch (...) { return 0; }
 }
@@ -245,7 +237,7 @@ int64_t cgo_batch_lbfgs_max_n_obj_ex(cgo_objective *model, int32_t m, const cgo_
         if (m < 1 || m > QN_MAX_M) return 0;
         if (rows != CGO_BATCH_ROWS_LDS) return cgo_batch_lbfgs_max_n_obj(model);   // (nothing is compiled for the answer)
         // (as cgo_batch_max_n_obj compiles the batch program: the limit follows from the kernel's static LDS)
-        if (!batch_model_ok(model) || batch_program(model, PROG_BATCH_LBFGS_LDS)) return 0;
+        if (!batch_model_ok(model) || batch_program(model, RTC_BATCH_LBFGS_LDS)) return 0;
         return HipBackend::batch_lbfgs_lds_max_ld(model->o.ctx, CGO_OBJ_USER, m, model->o.rtc.get());
     } catch (...) { return 0; }
 }
@@ -294,11 +286,11 @@ static int batch_lbfgs_model_plan(cgo_ctx *ctx, cgo_objective *model, int rows, 
     lds = false;
     if (rows != CGO_BATCH_ROWS_DEVICE && (rows == CGO_BATCH_ROWS_LDS || kBatchLbfgsAutoTakesLds)) {
         HIPCHK2(hipSetDevice(ctx->c.device));
-        if (int rc = batch_program(model, PROG_BATCH_LBFGS_LDS)) return rc;
+        if (int rc = batch_program(model, RTC_BATCH_LBFGS_LDS)) return rc;
         if (int rc = batch_lbfgs_tier(rows, n, HipBackend::batch_lbfgs_lds_max_ld(&ctx->c, CGO_OBJ_USER, m, model->o.rtc.get()), lds, lds_name)) return rc;
     }
     if (int rc = batch_lbfgs_sizes_of(ctx, cgo_batch_lbfgs_max_n_obj(model), "cgo_batch_lbfgs_max_n_obj", model->o.nparams(), n, batch, m)) return rc;
-    return lds ? CGO_OK : batch_program(model, PROG_BATCH_LBFGS);
+    return lds ? CGO_OK : batch_program(model, RTC_BATCH_LBFGS);
 }
 
 // ---- the batch itself ------------------------------------------------------------------------------------------------------------
@@ -321,11 +313,11 @@ static int batch_model_cat(cgo_ctx *ctx, cgo_objective *model, int64_t batch, co
     // (rows in device memory, asked for outright: the batch program — the LDS tier's kernel — is neither needed nor compiled)
     int64_t lds_max = 0;
     if (rows != CGO_BATCH_ROWS_DEVICE) {
-        if (int rc = batch_program(model, PROG_BATCH)) return rc;
+        if (int rc = batch_program(model, RTC_BATCH)) return rc;
         lds_max = HipBackend::batch_max_n(&ctx->c, CGO_OBJ_USER, model->o.rtc.get());
     }
     if (int rc = batch_tier(rows, model->o.n_local, batch, model->o.nparams(), lds_max, "cgo_batch_max_n_obj", device_rows)) return rc;
-    if (device_rows) { if (int rc = batch_program(model, PROG_BATCH_ROWS)) return rc; }
+    if (device_rows) { if (int rc = batch_program(model, RTC_BATCH_ROWS)) return rc; }
     return batch_model_cat_rows(ctx, model, batch, cat);
 }
 // the objective of size n a handed-back problem of a model is finished on

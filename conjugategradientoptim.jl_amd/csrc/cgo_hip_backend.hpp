@@ -14,6 +14,12 @@
 
 namespace cgo {
 
+// Where a batch's rows (and ring) live during a launch, and which solver runs on them: the kernel family of its launches.  The
+// numbers are the C ABI's cgo_batch_probe_args.tier (include/cgo.h); one row each in batch_tier_of() (cgo_backend_internal.hpp).
+enum class BatchTier : int { LDS = 0, ROWS = 1, LBFGS = 2, LBFGS_LDS = 3 };
+constexpr int BATCH_TIERS = 4;
+struct BatchTierRow;
+
 namespace dev { struct CtlArgs; struct Tail; struct LoopParams; struct ResParams; struct BatchParams; struct BatchLbfgsParams; }
 
 void set_error(const std::string &msg);
@@ -173,7 +179,7 @@ class HipBackend : public VecBackend {
     static int batch_rows_unroll();            // pairs per lane and trip of its streaming loop
     static int batch_rows_block();             // lanes of its workgroup
     static double batch_rows_bytes(int64_t batch, int64_t n, int nparams);   // device bytes a batch of that shape asks for
-    bool batch_device_rows() const { return bat_rows_; }
+    bool batch_device_rows() const { return bat_tier_ != BatchTier::LDS; }   // (the L-BFGS tiers' rows are device rows too)
     int batch_reset(const double *x0, const double *scalars, const unsigned char *active, int64_t max_iters, bool trace);
     int batch_launch(const ResConfig &c, int64_t budget, std::vector<ResState> &st, std::vector<double> &f_x0) override;
     int batch_records(int64_t b, int64_t count, std::vector<ResRecord> &out);     // the trace records of problem b's first `count` iterations (b < 0: every row)
@@ -186,7 +192,7 @@ class HipBackend : public VecBackend {
     // Batched solves with β = LBFGS(m) (cgo_backend_batch_lbfgs.hip; k_batch_lbfgs, cgo_kernels_batch_lbfgs.hip.hpp): a batch
     // allocated with device_rows gets a ring of 2(m+1) rows and a QnState per problem beside its rows; batch_launch then runs
     // k_batch_lbfgs.  batch_lbfgs_reset after every batch_reset: every problem's ring empty.  A run-time compiled objective runs
-    // the kernel of its module's batched L-BFGS program (cgo_rtc_batch_lbfgs.hip), which the caller compiles first.
+    // the kernel of its module's batched L-BFGS program (RTC_BATCH_LBFGS), which the caller compiles first.
     int batch_lbfgs_alloc(int m, bool lds = false);
     int batch_lbfgs_reset(int m = 0);          // m: this solve's ring depth, 1 … the allocated one (0: the allocated one) — the ring keeps its stride
     int batch_lbfgs_m() const { return bat_m_; }   // the ring depth allocated (0: not a batched L-BFGS batch)
@@ -198,13 +204,13 @@ class HipBackend : public VecBackend {
     // … with the problem's rows and ring in LDS during a launch (cgo_backend_batch_lbfgs_lds.hip; k_batch_lbfgs_lds,
     // cgo_kernels_batch_lbfgs_lds.hip.hpp): batch_lbfgs_alloc(m, true) — the same allocation, the launches take
     // 8 · ld · batch_lbfgs_lds_rows(K, m) bytes of dynamic LDS.  A run-time compiled objective runs the kernel of its module's
-    // program of this tier (cgo_rtc_batch_lbfgs_lds.hip), which the caller compiles first.
+    // program of this tier (RTC_BATCH_LBFGS_LDS), which the caller compiles first.
     static int batch_lbfgs_lds_rows(int nparams, int m);        // 2 + K + 2(m+1); 0: K or m out of range
     static int batch_lbfgs_lds_unroll_for(int nparams);         // pairs per lane and trip of the two ring passes over LDS
     static int64_t batch_lbfgs_lds_ld_of(int64_t max_lds, int64_t static_lds, int rows);   // the size arithmetic alone
     // largest ld (even) one workgroup's LDS holds of a problem's rows and ring; 0: none.  CGO_OBJ_USER: `rtc` with that program
     static int64_t batch_lbfgs_lds_max_ld(HipCtx *ctx, int obj_kind, int m, const RtcModule *rtc = nullptr);
-    bool batch_lbfgs_in_lds() const { return bat_qn_lds_; }
+    bool batch_lbfgs_in_lds() const { return bat_tier_ == BatchTier::LBFGS_LDS; }
     // Test entry point (cgo_batch_probe, cgo_backend_batch_probe.hip): a script of passes in ONE launch of the PROBE twin of this
     // batch's kernel, on host vectors; the batch is one batch_alloc (and batch_lbfgs_alloc) made, the launch arguments are
     // batch_fill_params' / batch_lbfgs_fill_params'.  Every buffer of the batch gets NaN slack: a probed batch is for probing only.
@@ -474,7 +480,7 @@ class HipBackend : public VecBackend {
     int64_t bat_count_ = 0, bat_n_ = 0, bat_ld_ = 0, bat_rec_stride_ = 0;
     bool bat_trace_ = false;
     size_t bat_lds_ = 0;
-    bool bat_rows_ = false;                  // the tier: rows in LDS (k_batch) or streamed from device memory (k_batch_rows)
+    BatchTier bat_tier_ = BatchTier::LDS;    // batch_alloc: LDS or ROWS; batch_lbfgs_alloc turns ROWS into LBFGS or LBFGS_LDS
     ResState *bat_st_ = nullptr;             // device [batch]
     ResRecord *bat_recs_ = nullptr;          // device [batch][bat_rec_stride_]
     double *bat_fx0_ = nullptr;              // device [batch]
@@ -484,16 +490,17 @@ class HipBackend : public VecBackend {
     void batch_fill_rows(std::vector<double> &rows, const double *src) const;
     int batch_recs_reserve(int64_t stride);
     int batch_grad_rows();
+    // ONE launch of a batch's kernel, a workgroup per problem: the ahead-of-time instantiation `fn`, or for a run-time compiled
+    // objective its module's `mf`; `missing`: the refusal where a built-in objective has no instantiation
+    int batch_launch_kernel(const void *fn, hipFunction_t mf, const char *missing, void **args, size_t lds);
+    int batch_launch_tier(void *params);                               // … of this batch's tier on its parameter block
+    int batch_lbfgs_launch_tier(const ResConfig &c, int64_t budget);   // … a quasi-Newton tier's: batch_lbfgs_fill_params, then that
     // what a launch reads of the batch — ld, the slot pointers, s0 / s0v, the record stride: batch_launch's and the probe's alike
     void batch_fill_params(dev::BatchParams &B, const ResConfig &c, int64_t budget) const;
     void batch_lbfgs_fill_params(dev::BatchLbfgsParams &L, const ResConfig &c, int64_t budget) const;   // … and the ring, its stride, the states
     int bat_m_ = 0;                          // > 0: a batched L-BFGS solve of that ring depth (batch_lbfgs_alloc)
     double *bat_S_ = nullptr, *bat_Y_ = nullptr;   // device [batch][m+1][ld]
     QnState *bat_qn_ = nullptr;             // device [batch]
-    int batch_lbfgs_launch(const ResConfig &c, int64_t budget, std::vector<ResState> &st, std::vector<double> &f_x0);
-    bool bat_qn_lds_ = false;                // … whose launches keep the rows and the ring in LDS (batch_lbfgs_lds_on)
-    int batch_lbfgs_lds_on();
-    int batch_lbfgs_lds_launch(const dev::BatchLbfgsParams &L);
     bool prof_on_ = false;
     struct ProfSlot { hipEvent_t e0 = nullptr, e1 = nullptr; int kk = -1; double bytes = 0; };
     std::vector<ProfSlot> ring_;

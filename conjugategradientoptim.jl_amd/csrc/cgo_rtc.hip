@@ -24,13 +24,8 @@ namespace cgo {
 using namespace dev;
 
 RtcModule::~RtcModule() {
-    if (mod) (void)hipModuleUnload(mod);
-    if (probe_mod) (void)hipModuleUnload(probe_mod);
-    if (batch_mod) (void)hipModuleUnload(batch_mod);
-    if (rows_mod) (void)hipModuleUnload(rows_mod);
-    if (batch_probe_mod) (void)hipModuleUnload(batch_probe_mod);
-    if (batch_lbfgs_mod) (void)hipModuleUnload(batch_lbfgs_mod);
-    if (batch_lbfgs_lds_mod) (void)hipModuleUnload(batch_lbfgs_lds_mod);
+    for (hipModule_t m : mods)
+        if (m) (void)hipModuleUnload(m);
 }
 
 static std::string key_cg(int mode, int npts, bool big) {
@@ -47,10 +42,6 @@ hipFunction_t RtcModule::resident(int npts) const {
     auto it = fn.find("res:" + std::to_string(npts));
     return it == fn.end() ? nullptr : it->second;
 }
-hipFunction_t RtcModule::resident_probe(int npts) const {
-    auto it = fn.find("resprobe:" + std::to_string(npts));
-    return it == fn.end() ? nullptr : it->second;
-}
 hipFunction_t RtcModule::spec(bool big, bool push) const {
     auto it = fn.find(std::string("spec:") + (big ? "1" : "0") + (push ? "1" : "0"));
     return it == fn.end() ? nullptr : it->second;
@@ -63,7 +54,7 @@ hipFunction_t RtcModule::fused(int mode, bool big) const {
     auto it = fn.find(key_fused(mode, big));
     return it == fn.end() ? nullptr : it->second;
 }
-hipFunction_t RtcModule::row_kernel(const std::string &prefix, std::initializer_list<int> rows, int npts) const {
+hipFunction_t RtcModule::row_kernel(const std::string &prefix, const std::vector<int> &rows, int npts) const {
     hipFunction_t f = nullptr;
     for (int r : rows) {
         if (!f || npts >= r) { auto it = fn.find(prefix + std::to_string(r)); if (it != fn.end()) f = it->second; }
@@ -159,22 +150,11 @@ int rtc_build(const std::string &src, const char *name, const std::vector<Want> 
     return CGO_OK;
 }
 
-int rtc_compile_objective(int device, const std::string &source, int n_params,
-                          std::shared_ptr<RtcModule> &out, std::string &log) {
-    if (hipSetDevice(device) != hipSuccess) { log = "hipSetDevice failed"; return CGO_EHIP; }
-    // A module depends on (device, source, n_params) only, not on the objective's length, and is never changed once loaded: while
-    // an objective still holds the module of the same text, the next one shares it instead of compiling for seconds again
-    // (the barrier method's two objectives per call, a sweep over sizes).  Not owned here: the last objective unloads it.
-    static std::mutex mu;
-    static std::map<std::tuple<int, int, std::string>, std::weak_ptr<RtcModule>> live;
-    const auto key = std::make_tuple(device, n_params, source);
-    std::lock_guard<std::mutex> lock(mu);
-    if (auto it = live.find(key); it != live.end()) {
-        if (auto m = it->second.lock()) { out = m; return CGO_OK; }
-        live.erase(it);
-    }
+// the name expressions of the program every objective compiles at creation (RTC_CREATE): every per-objective row of
+// cgo_instances.def for UserObjective
+std::vector<Want> rtc_create_wants() {
     std::vector<Want> wants;
-    // every per-objective row of cgo_instances.def for UserObjective, in both streaming policies
+    // k_cg and k_fused in both streaming policies
     const std::string uo = "<cgo::dev::UserObjective, ";
     auto tf = [](int b) { return b ? "true" : "false"; };
     for (int big = 0; big < 2; ++big) {
@@ -202,22 +182,31 @@ int rtc_compile_objective(int device, const std::string &source, int n_params,
 #define ROW(NPTS) wants.push_back({"res:" #NPTS, "cgo::dev::k_resident" + uo + #NPTS ">"});
     CGO_RTC_RESIDENT_ROWS(ROW)
 #undef ROW
+    return wants;
+}
+
+int rtc_compile_objective(int device, const std::string &source, int n_params,
+                          std::shared_ptr<RtcModule> &out, std::string &log) {
+    if (hipSetDevice(device) != hipSuccess) { log = "hipSetDevice failed"; return CGO_EHIP; }
+    // A module depends on (device, source, n_params) only, not on the objective's length, and its first program is never changed
+    // once loaded: while an objective still holds the module of the same text, the next one shares it instead of compiling for
+    // seconds again (the barrier method's two objectives per call, a sweep over sizes).  Not owned here: the last objective
+    // unloads it.  (The further programs: rtc_compile_program, under the module's own mutex.)
+    static std::mutex mu;
+    static std::map<std::tuple<int, int, std::string>, std::weak_ptr<RtcModule>> live;
+    const auto key = std::make_tuple(device, n_params, source);
+    std::lock_guard<std::mutex> lock(mu);
+    if (auto it = live.find(key); it != live.end()) {
+        if (auto m = it->second.lock()) { out = m; return CGO_OK; }
+        live.erase(it);
+    }
     auto mod = std::make_shared<RtcModule>();
-    if (int rc = rtc_build(rtc_program_source(source, n_params), "cgo_user_objective.hip", wants, mod->mod, mod->fn, log)) return rc;
+    const RtcPlan plan = rtc_program_plan(RTC_CREATE, source, n_params);
+    if (int rc = rtc_build(plan.src, plan.name, plan.wants, mod->mods[RTC_CREATE], mod->fn, log)) return rc;
     mod->user_source = source; mod->n_params = n_params; mod->device = device;
     live[key] = mod;
     out = mod;
     return CGO_OK;
-}
-
-int rtc_compile_resident_probe(RtcModule &m, std::string &log) {
-    if (m.probe_mod) return CGO_OK;
-    if (hipSetDevice(m.device) != hipSuccess) { log = "hipSetDevice failed"; return CGO_EHIP; }
-    std::vector<Want> wants;   // the PROBE form of the module's resident kernel
-#define ROW(NPTS) wants.push_back({"resprobe:" #NPTS, "cgo::dev::k_resident<cgo::dev::UserObjective, " #NPTS ", true>"});
-    CGO_RTC_RESIDENT_ROWS(ROW)
-#undef ROW
-    return rtc_build(rtc_program_source(m.user_source, m.n_params), "cgo_user_objective_probe.hip", wants, m.probe_mod, m.fn, log);
 }
 
 }  // namespace cgo

@@ -35,3 +35,32 @@ def stray_uses():
     text = "\n".join(open(p).read() for p in sorted(glob.glob(os.path.join(CSRC, "*.hip")))).replace("\\\n", " ")
     code = [re.sub(r'"(?:\\.|[^"\\])*"', '""', line).split("//")[0] for line in text.split("\n")]
     return [c.strip() for c in code if re.search(r"\bk_(cg|cg_armed|chain|fused|resident|resident_chain|batch|batch_rows|batch_lbfgs|batch_grad)<", c) and not c.startswith("#define ROW(")]
+
+
+def rtc_programs():
+    """the programs of a run-time compiled objective's module, in file order: {RtcProgram: (file name, wording, text layers)}"""
+    return {r[0]: r[1:] for r in rows("RTC_PROGRAM")}
+
+
+def rtc_program_kernels(prog):
+    """the name expressions of a further program of the module, in order and without `cgo::dev::`: its rows of RTC_KERNEL (one
+    per NPTS of the row macro they name, `, true` for a PROBE twin), then its rows of RTC_EXTRA"""
+    out = []
+    for p, _prefix, kernel, macro, probe in rows("RTC_KERNEL"):
+        if p == prog:
+            family = re.match(r"CGO_(\w+)_ROWS$", macro).group(1)
+            out += ["%s<UserObjective, %d%s>" % (kernel, npts, ", true" if probe else "") for (npts,) in rows(family)]
+    return out + ["%s<UserObjective>" % kernel for p, _key, kernel in rows("RTC_EXTRA") if p == prog]
+
+
+def rtc_compile_program_body():
+    """the code of rtc_compile_program (cgo_rtc_batch.hip), THE function that compiles every further program"""
+    text = open(os.path.join(CSRC, "cgo_rtc_batch.hip")).read()
+    return re.search(r"^int rtc_compile_program\(RtcModule &m, RtcProgram prog, std::string &log\) \{\n.*?^}", text, re.M | re.S).group(0)
+
+
+def every_program_module_is_unloaded():
+    """RtcModule holds one handle per program, and its destructor unloads every one of them"""
+    return ("hipModule_t mods[RTC_PROGRAMS] = {};" in open(os.path.join(CSRC, "cgo_rtc.hpp")).read()
+            and re.search(r"RtcModule::~RtcModule\(\) \{\s*for \(hipModule_t m : mods\)\s*if \(m\) \(void\)hipModuleUnload\(m\);\s*\}",
+                          open(os.path.join(CSRC, "cgo_rtc.hip")).read()) is not None)

@@ -635,9 +635,11 @@ def test_the_entry_point_is_declared_host_only_and_refuses_without_a_device(cgo)
         cgo.batch_probe("lds", "quad_diag", np.ones((1, 4)), np.ones((1, 4)), [("reset",)], params=[np.ones((1, 4))])
     mk = open(os.path.join(I.CSRC, "Makefile")).read()
     assert "cgo_backend_batch_probe.hip" in mk
-    rtc = open(os.path.join(I.CSRC, "cgo_rtc_batch.hip")).read()
-    body = rtc[rtc.index("int rtc_compile_batch(RtcModule"):rtc.index("hipFunction_t RtcModule::batch_rows")]
-    assert ", true>" not in body and "k_batch" not in open(os.path.join(I.CSRC, "cgo_rtc.hip")).read()   # a program of its own
+    # a program of its own: exactly the twins of tiers 0 and 1, and no product program lists a twin
+    assert I.rtc_program_kernels("RTC_BATCH_PROBE") == ["k_batch<UserObjective, 3, true>", "k_batch_rows<UserObjective, 3, true>"]
+    for prog in ("RTC_BATCH", "RTC_BATCH_ROWS", "RTC_BATCH_LBFGS", "RTC_BATCH_LBFGS_LDS"):
+        assert not [k for k in I.rtc_program_kernels(prog) if ", true>" in k], prog
+    assert "k_batch" not in open(os.path.join(I.CSRC, "cgo_rtc.hip")).read()
 
 
 # ---- GPU tier ----------------------------------------------------------------------------------------------------------------

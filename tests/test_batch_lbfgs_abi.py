@@ -53,10 +53,15 @@ def test_the_table_row_and_the_translation_units():
     assert I.rows("BATCH_LBFGS") == [(3,)]
     assert I.rows("BATCH") == [(3,)] and I.rows("BATCH_DEVROWS") == [(3,)]   # as they were
     tu = open(os.path.join(I.CSRC, "cgo_backend_batch_lbfgs.hip")).read()
-    assert "CGO_BATCH_LBFGS_ROWS(ROW)" in tu and "CGO_OBJ_ROWS(ROW)" in tu and "k_batch_lbfgs<Obj, NPTS>" in tu
-    for other in ("cgo_backend_batch.hip", "cgo_backend_batch_rows.hip", "cgo_rtc.hip", "cgo_rtc_batch.hip"):
+    assert "CGO_BATCH_LBFGS_ROWS(ROW)" in tu and "k_batch_lbfgs<Obj, NPTS>" in tu
+    assert "row_pick_for<BatchLbfgsRows>(obj_kind, npts)" in tu and "CGO_OBJ_ROWS(ROW)" in open(os.path.join(I.CSRC, "cgo_backend_internal.hpp")).read()   # (the switch over the objectives: once, for every tier)
+    for other in ("cgo_backend_batch.hip", "cgo_backend_batch_rows.hip", "cgo_rtc.hip"):
         text = open(os.path.join(I.CSRC, other)).read()
         assert "cgo_kernels_batch_lbfgs.hip.hpp" not in text and "k_batch_lbfgs<" not in text, other
+    # (the one unit of the module's further programs holds this tier's program too: no OTHER program lists the kernel)
+    assert "k_batch_lbfgs<" not in open(os.path.join(I.CSRC, "cgo_rtc_batch.hip")).read()
+    for prog in ("RTC_RESIDENT_PROBE", "RTC_BATCH", "RTC_BATCH_ROWS", "RTC_BATCH_PROBE"):
+        assert not [k for k in I.rtc_program_kernels(prog) if k.startswith("k_batch_lbfgs")] and I.rtc_programs()[prog][2] == "RTC_TEXT_BASE", prog
     # the loop lives in a header of its own: the text of the run-time compiled modules does not carry it
     assert "res_iterate_qn" not in open(os.path.join(I.CSRC, "cgo_resident.hpp")).read()
     gen = open(os.path.join(I.CSRC, "gen_rtc_sources.py")).read()

@@ -104,14 +104,21 @@ def test_the_table_row_and_the_translation_units():
     assert I.rows("BATCH_LBFGS") == [(3,)] and I.rows("BATCH") == [(3,)] and I.rows("BATCH_DEVROWS") == [(3,)]   # as they were
     assert I.stray_uses() == []
     tu = open(os.path.join(I.CSRC, "cgo_backend_batch_lbfgs_lds.hip")).read()
-    assert "CGO_BATCH_LBFGS_LDS_ROWS(ROW)" in tu and "CGO_OBJ_ROWS(ROW)" in tu and "k_batch_lbfgs_lds<Obj, NPTS>" in tu
-    assert "hipDeviceAttributeMaxSharedMemoryPerBlock" in tu and "hipFuncAttributeMaxDynamicSharedMemorySize" in tu and "- 512" in tu
+    assert "CGO_BATCH_LBFGS_LDS_ROWS(ROW)" in tu and "k_batch_lbfgs_lds<Obj, NPTS>" in tu
+    assert "row_pick_for<BatchLbfgsLdsRows>(obj_kind, npts)" in tu and "CGO_OBJ_ROWS(ROW)" in open(os.path.join(I.CSRC, "cgo_backend_internal.hpp")).read()   # (the switch over the objectives: once, for every tier)
+    # the size arithmetic is the tier's; what the device gives a block and the kernel's static LDS are read once for both LDS
+    # tiers (cgo_backend_batch.hip), the launch's dynamic LDS is allowed where the ring is allocated (cgo_backend_batch_lbfgs.hip)
+    assert "- 512" in tu and "batch_tier_max_ld(ctx, BatchTier::LBFGS_LDS, obj_kind, m, rtc)" in tu
+    shared = open(os.path.join(I.CSRC, "cgo_backend_batch.hip")).read()
+    assert "hipDeviceAttributeMaxSharedMemoryPerBlock" in shared and "HipBackend::batch_lbfgs_lds_ld_of(max_lds, static_lds, t.lds_rows(nparams, m))" in shared
+    assert "hipFuncAttributeMaxDynamicSharedMemorySize" in open(os.path.join(I.CSRC, "cgo_backend_batch_lbfgs.hip")).read()
     mk = open(os.path.join(I.CSRC, "Makefile")).read()
-    for f in ("cgo_backend_batch_lbfgs_lds.hip", "cgo_rtc_batch_lbfgs_lds.hip", "cgo_kernels_batch_lbfgs_lds.hip.hpp", "gen_rtc_lbfgs_lds_sources.py $@"):
+    for f in ("cgo_backend_batch_lbfgs_lds.hip", "cgo_rtc_batch.hip", "cgo_kernels_batch_lbfgs_lds.hip.hpp",
+              "gen_rtc_sources.py $@ kRtcLbfgsLdsSourceChunks cgo_kernels_batch_lbfgs_lds.hip.hpp"):
         assert f in mk, f
     # the kernel is instantiated in its own unit, in the run-time compiled objectives' unit of the tier (by name) and, as PROBE
     # twins, in the probe unit: no other translation unit names it, and none of them includes its header
-    own = {"cgo_backend_batch_lbfgs_lds.hip", "cgo_rtc_batch_lbfgs_lds.hip", "cgo_backend_batch_probe.hip"}
+    own = {"cgo_backend_batch_lbfgs_lds.hip", "cgo_rtc_batch.hip", "cgo_backend_batch_probe.hip"}
     for name in sorted(os.listdir(I.CSRC)):
         if not (name.endswith(".hip") or name.endswith(".cpp")) or name in own:
             continue
@@ -128,15 +135,22 @@ def test_the_table_row_and_the_translation_units():
     assert re.search(r"using LbfgsDev = LbfgsRing<[^;]*\bbatch_lbfgs_u<Obj>\(\)[^;]*>;", dev)
     assert ring_pass_definitions(ring_template_body()) == dict.fromkeys(RING_PASSES, 1)
     assert ring_pass_definitions(dev + _code("cgo_kernels_batch_lbfgs_lds.hip.hpp")) == dict.fromkeys(RING_PASSES, 1)
-    rtc = open(os.path.join(I.CSRC, "cgo_rtc_batch_lbfgs_lds.hip")).read()
-    assert "k_batch_lbfgs_lds<cgo::dev::UserObjective, " in rtc and "std::mutex" in rtc and "batch_lbfgs_lds_mod" in rtc
-    assert "k_batch_grad" not in re.sub(r"//.*", "", rtc) and "k_batch_lbfgs<" not in rtc      # that one kernel and nothing else
-    assert "batch_lbfgs_lds_mod" in open(os.path.join(I.CSRC, "cgo_rtc.hip")).read()            # unloaded in the destructor
+    assert I.rtc_program_kernels("RTC_BATCH_LBFGS_LDS") == ["k_batch_lbfgs_lds<UserObjective, 3>"]   # that one kernel and nothing else
+    assert I.rtc_programs()["RTC_BATCH_LBFGS_LDS"][2] == "RTC_TEXT_LBFGS_LDS"
+    assert "std::lock_guard<std::mutex> lock(m.mu);" in I.rtc_compile_program_body() and "m.mods[prog]" in I.rtc_compile_program_body()
+    assert I.every_program_module_is_unloaded()
 
 
 # ---- 3. the generated texts --------------------------------------------------------------------------------------------------------
+GENERATED = {   # the three texts, by the name each went by when a script of its own wrote it: the arguments of the one generator (the Makefile's rules)
+    "gen_rtc_sources.py": (),
+    "gen_rtc_lbfgs_sources.py": ("kRtcLbfgsSourceChunks", "cgo_qn.hpp", "cgo_resident_qn.hpp", "cgo_kernels_batch_lbfgs.hip.hpp"),
+    "gen_rtc_lbfgs_lds_sources.py": ("kRtcLbfgsLdsSourceChunks", "cgo_kernels_batch_lbfgs_lds.hip.hpp"),
+}
+
+
 def _generate(csrc, name, out):
-    subprocess.run([sys.executable, os.path.join(csrc, name), str(out)], check=True)
+    subprocess.run([sys.executable, os.path.join(csrc, "gen_rtc_sources.py"), str(out), *GENERATED[name]], check=True)
     return out.read_text(encoding="utf-8")
 
 

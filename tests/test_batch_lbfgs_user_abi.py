@@ -67,7 +67,8 @@ def test_the_shape_needs_no_device_and_follows_the_slot_count(cgo):
 # ---- 2. the fifth program's text ---------------------------------------------------------------------------------------------------
 def test_the_new_generator_embeds_the_kernel_and_the_old_one_does_not(tmp_path):
     new, old = tmp_path / "cgo_rtc_lbfgs_sources.inc", tmp_path / "cgo_rtc_sources.inc"
-    subprocess.run([sys.executable, os.path.join(I.CSRC, "gen_rtc_lbfgs_sources.py"), str(new)], check=True)
+    subprocess.run([sys.executable, os.path.join(I.CSRC, "gen_rtc_sources.py"), str(new), "kRtcLbfgsSourceChunks",
+                    "cgo_qn.hpp", "cgo_resident_qn.hpp", "cgo_kernels_batch_lbfgs.hip.hpp"], check=True)   # (the Makefile's rule)
     subprocess.run([sys.executable, os.path.join(I.CSRC, "gen_rtc_sources.py"), str(old)], check=True)
     text, was = new.read_text(encoding="utf-8"), old.read_text(encoding="utf-8")
     def code(t):   # (comments of the existing text name the kernel: its CODE must not carry it)
@@ -77,12 +78,16 @@ def test_the_new_generator_embeds_the_kernel_and_the_old_one_does_not(tmp_path):
     assert "qn_update" not in was and "k_batch_lbfgs<" not in was
     # stripped as the existing generator strips: no include survives, and nothing host-only
     assert "#include" not in text and "#pragma once" not in text and "CGO_HOST_ONLY" not in text and "std::" not in re.sub(r"//.*", "", text)
-    tu = open(os.path.join(I.CSRC, "cgo_rtc_batch_lbfgs.hip")).read()
-    assert "CGO_BATCH_LBFGS_ROWS(ROW)" in tu and "k_batch_lbfgs<cgo::dev::UserObjective, " in tu and "k_batch_grad<cgo::dev::UserObjective>" in tu
-    assert "cgo_rtc_lbfgs_sources.inc" in tu and "std::mutex" in tu and "batch_lbfgs_mod" in tu
+    assert I.rtc_program_kernels("RTC_BATCH_LBFGS") == ["k_batch_lbfgs<UserObjective, 3>", "k_batch_grad<UserObjective>"]
+    assert ("RTC_BATCH_LBFGS", "batch_qn:", "k_batch_lbfgs", "CGO_BATCH_LBFGS_ROWS", 0) in I.rows("RTC_KERNEL")
+    assert I.rtc_programs()["RTC_BATCH_LBFGS"][2] == "RTC_TEXT_LBFGS"
+    tu = open(os.path.join(I.CSRC, "cgo_rtc_batch.hip")).read()
+    assert "cgo_rtc_lbfgs_sources.inc" in tu and "kRtcLbfgsSourceChunks" in tu
+    assert "std::lock_guard<std::mutex> lock(m.mu);" in I.rtc_compile_program_body() and "m.mods[prog]" in I.rtc_compile_program_body()
     mk = open(os.path.join(I.CSRC, "Makefile")).read()
-    assert "cgo_rtc_batch_lbfgs.hip" in mk and "gen_rtc_lbfgs_sources.py $@" in mk
-    assert "batch_lbfgs_mod" in open(os.path.join(I.CSRC, "cgo_rtc.hip")).read()   # unloaded in the destructor
+    assert "cgo_rtc_batch.hip" in mk and "gen_rtc_sources.py $@ kRtcLbfgsSourceChunks cgo_qn.hpp cgo_resident_qn.hpp cgo_kernels_batch_lbfgs.hip.hpp" in mk
+    assert new.read_text(encoding="utf-8").startswith("// generated by gen_rtc_sources.py") and "static const char *const kRtcLbfgsSourceChunks[] = {" in text
+    assert I.every_program_module_is_unloaded()
 
 
 # ---- 3. Python argument checks ------------------------------------------------------------------------------------------------------

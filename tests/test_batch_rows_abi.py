@@ -104,16 +104,17 @@ def test_python_rows_argument_is_checked_before_any_library_call(cgo, monkeypatc
 def test_the_table_row_and_the_translation_units():
     assert I.rows("BATCH_DEVROWS") == [(3,)] and I.rows("BATCH") == [(3,)]
     rows_tu = open(os.path.join(I.CSRC, "cgo_backend_batch_rows.hip")).read()
-    assert "CGO_BATCH_DEVROWS_ROWS(ROW)" in rows_tu and "CGO_OBJ_ROWS(ROW)" in rows_tu and "k_batch_rows<Obj, NPTS>" in rows_tu
+    assert "CGO_BATCH_DEVROWS_ROWS(ROW)" in rows_tu and "k_batch_rows<Obj, NPTS>" in rows_tu
+    assert "row_pick_for<BatchDevRows>(obj_kind, npts)" in rows_tu and "CGO_OBJ_ROWS(ROW)" in open(os.path.join(I.CSRC, "cgo_backend_internal.hpp")).read()   # (the switch over the objectives: once, for every tier)
     # k_batch's translation unit does not see the new kernel (its device code stays what it was), nor does the program every
     # objective compiles at creation or the batch program's kernel list
     batch_tu = open(os.path.join(I.CSRC, "cgo_backend_batch.hip")).read()
     assert "cgo_kernels_batch_rows.hip.hpp" not in batch_tu and "k_batch_rows<" not in batch_tu
     assert "k_batch" not in open(os.path.join(I.CSRC, "cgo_rtc.hip")).read()
-    rtc = open(os.path.join(I.CSRC, "cgo_rtc_batch.hip")).read()
-    assert "k_batch_rows<cgo::dev::UserObjective, " in rtc and "m.rows_mod" in rtc
-    body = rtc[rtc.index("int rtc_compile_batch(RtcModule"):rtc.index("hipFunction_t RtcModule::batch_rows")]
-    assert "k_batch_rows" not in body   # a third program: the batch program compiles what it compiled
+    # a program of its own, with a module handle of its own: the batch program compiles what it compiled
+    assert I.rtc_program_kernels("RTC_BATCH_ROWS") == ["k_batch_rows<UserObjective, 3>"]
+    assert '"<cgo::dev::UserObjective, "' in open(os.path.join(I.CSRC, "cgo_rtc_batch.hip")).read() and "m.mods[prog]" in I.rtc_compile_program_body()
+    assert I.rtc_program_kernels("RTC_BATCH") == ["k_batch<UserObjective, 3>", "k_batch_grad<UserObjective>"]
     mk = open(os.path.join(I.CSRC, "Makefile")).read()
     assert "cgo_backend_batch_rows.hip" in mk and mk.count("cgo_kernels_batch_rows.hip.hpp") == 2
 

@@ -79,8 +79,8 @@ def test_the_gradient_kernel_is_built_ahead_of_time_and_in_the_batch_program(tmp
     assert I.rows("BATCH") == [(3,)] and len(I.rows("OBJ")) == 3
     backend = open(os.path.join(I.CSRC, "cgo_backend_batch.hip")).read()
     assert re.search(r"#define ROW\(KIND, T\) case KIND: return \(const void \*\)k_batch_grad<T>;\s*CGO_OBJ_ROWS\(ROW\)", backend)
-    batch = open(os.path.join(I.CSRC, "cgo_rtc_batch.hip")).read()
-    assert "k_batch_grad<cgo::dev::UserObjective>" in batch
+    assert ("RTC_BATCH", "batch:grad", "k_batch_grad") in I.rows("RTC_EXTRA") and "k_batch_grad<UserObjective>" in I.rtc_program_kernels("RTC_BATCH")
+    assert "CGO_RTC_EXTRA_ROWS(ROW)" in open(os.path.join(I.CSRC, "cgo_rtc_batch.hip")).read()
     assert "k_batch_grad" not in open(os.path.join(I.CSRC, "cgo_rtc.hip")).read()   # not in the program every objective compiles at creation
     assert I.stray_uses() == []
     out = tmp_path / "cgo_rtc_sources.inc"

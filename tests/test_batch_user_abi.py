@@ -83,8 +83,8 @@ def test_the_batch_row_is_as_it_was_and_the_module_builds_it_in_a_program_of_its
     assert I.rows("BATCH") == [(3,)]
     assert I.rows("RTC_RESIDENT") == [(3,)] and I.rows("OBJ") == [("CGO_OBJ_QUAD_DIAG", "ObjQuadDiag"), ("CGO_OBJ_ROSENBROCK_PAIRED", "ObjRosenPaired"),
                                                                   ("CGO_OBJ_BOOTH", "ObjBooth")]
-    batch = open(os.path.join(I.CSRC, "cgo_rtc_batch.hip")).read()
-    assert "CGO_BATCH_ROWS(ROW)" in batch and "k_batch<cgo::dev::UserObjective, " in batch
+    assert ("RTC_BATCH", "batch:", "k_batch", "CGO_BATCH_ROWS", 0) in I.rows("RTC_KERNEL") and "k_batch<UserObjective, 3>" in I.rtc_program_kernels("RTC_BATCH")
+    assert "CGO_RTC_KERNEL_ROWS(ROW)" in open(os.path.join(I.CSRC, "cgo_rtc_batch.hip")).read()
     assert "k_batch" not in open(os.path.join(I.CSRC, "cgo_rtc.hip")).read()      # not in the program every objective compiles at creation
     assert "cgo_rtc_batch.hip" in open(os.path.join(I.CSRC, "Makefile")).read()
     assert I.stray_uses() == []
